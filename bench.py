@@ -13,6 +13,7 @@ source, tile ownership, species key groups, one-hot indices) is rebuilt inside t
 a batch is never seen twice.  ``per_batch_prep_ms`` reports that part on its own.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs      (+ the last timed step's outputs as .npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -38,6 +39,7 @@ for _p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -80,7 +82,18 @@ def parse():
                          "(rounds 3-4's default; reported under config.launch_auto)")
     ap.add_argument("--eager", action="store_true", help="the eager multi-stream step (rounds 1-5's default for config_energy)")
     ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU work for the baseline leg")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0): the loss, the "
+                         "predictions (a padded batch's ghost graph dropped), the parameters, their gradients and the EMA shadow "
+                         "(model.named_parameters() order), at most 64 MB in all (a fixed, seeded sample of the largest arrays "
+                         "beyond that).  The inputs are seeded: two builds run with the same arguments can be compared output "
+                         "for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.launch == "auto":
+        ap.error("--dump-outputs needs --launch fixed: the auto mode takes a timing-dependent number of trial steps first")
+    return args
 
 
 def _cpu_model_times(tree, batch, target, reps_fwd, reps_bwd, budget_s):
@@ -142,6 +155,27 @@ def cpu_baseline(budget_s):
         "forward_only_value": round(n_mol / f3, 4),
         "lmax2_forward_only_value": round(n_mol / f2, 4),
     }
+
+
+DUMP_BUDGET_BYTES = 63_000_000      # array data: with the .npy headers the files stay under 64 MB
+
+
+def write_outputs(arrays, dirname):
+    """``arrays`` as ``dirname/<name>.npy``; {name: shape written}.  Beyond DUMP_BUDGET_BYTES in all, the budget is shared out
+    smallest array first and an array larger than its share is cut to a fixed, seeded sample of its entries (flattened: the
+    same entries from run to run)."""
+    os.makedirs(dirname, exist_ok=True)
+    left, names, shapes = DUMP_BUDGET_BYTES, sorted(arrays, key=lambda k: arrays[k].nbytes), {}
+    for i, name in enumerate(names):
+        a = arrays[name]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def _knots_now():
@@ -311,17 +345,31 @@ def main():
             b.attrs["forces_target"] = ("node", "1x1o")
     sde = VPSDE({"pos": 3}) if cfg_kind == "diffusion" else (VPSDE({"CA": 3}) if cfg_kind == "diffusion_CA" else None)
 
+    def keep_outputs(loss, batch, graph=None, node=None, other=None):
+        """--dump-outputs: the step's outputs ride on the loss tensor it returns (a replayed step returns its capture's loss tensor,
+        so these are the captured buffers, which every replay rewrites).  ``graph`` / ``node``: per-graph / per-node outputs -- the
+        rows of a padded batch's ghost graph (loss weight 0) are dropped when they are written."""
+        gw = batch["_graph_weight"] if "_graph_weight" in batch else None
+        nw = batch["_node_weight"] if "_node_weight" in batch else None
+        loss._bench_outputs = ([(k, v, gw) for k, v in (graph or {}).items()] + [(k, v, nw) for k, v in (node or {}).items()]
+                               + [(k, v, None) for k, v in (other or {}).items()])
+        return loss
+
     def loss_of(batch):
         if cfg_kind == "energy":
             target = batch["total_energy"]          # the model writes its prediction under the same key of the same Batch
-            return ops.sq_error(model(batch)["total_energy"], target, None, 1e3)      # (= 1e3 * mse_loss: loss + gradient in one launch)
+            pred = model(batch)["total_energy"]
+            # (= 1e3 * mse_loss: loss + gradient in one launch)
+            return keep_outputs(ops.sq_error(pred, target, None, 1e3), batch, graph={"total_energy": pred})
         if cfg_kind == "energy_force":                  # config_energy_force.py:18 loss_coeffs
             # (the model writes its graph energy under "energy", config_energy_force.py:73; the synthetic target travels as
             #  "total_energy" -- until round 5 this line compared the target with itself: the energy term was identically zero)
             e_t, f_t = batch["total_energy"], batch["forces_target"]
             out = model(batch)
-            return ops.sq_error(out["energy"], e_t, None, 1e3) + ops.sq_error(out["forces"], f_t, None, 3e4)
-        return sde_loss(sde, model, batch, generator=gen)[0]
+            return keep_outputs(ops.sq_error(out["energy"], e_t, None, 1e3) + ops.sq_error(out["forces"], f_t, None, 3e4), batch,
+                                graph={"energy": out["energy"]}, node={"forces": out["forces"]})
+        loss, terms = sde_loss(sde, model, batch, generator=gen)
+        return keep_outputs(loss, batch, other={f"loss_{k}": v for k, v in terms.items() if k != "total"})
 
     # setup, not a step of the workload: libe3k.so is loaded, the TP plans are created and the code objects of every
     # kernel on the path are paged in by one forward/backward over a SMALL batch (no optimizer step, gradients zeroed
@@ -388,7 +436,8 @@ def main():
             if pending[0] is None:
                 pending[0] = noised_and_prepared()
             pert, misc = pending[0]
-            loss = sde_loss_of(sde, model, pert, misc)[0]
+            loss, terms = sde_loss_of(sde, model, pert, misc)
+            keep_outputs(loss, pert, other={f"loss_{k}": v for k, v in terms.items() if k != "total"})
             pending[0] = noised_and_prepared()
             flat.zero()
             backward_parameters(loss, opt.params)
@@ -431,19 +480,22 @@ def main():
 
         def gradients_of(batch):
             if cfg_kind == "diffusion":       # VP-SDE denoising loss: a mean over the REAL nodes
-                loss = sde_loss(sde, model, batch, generator=gen, node_weight=batch["_node_weight"])[0]
+                loss, terms = sde_loss(sde, model, batch, generator=gen, node_weight=batch["_node_weight"])
+                keep_outputs(loss, batch, other={f"loss_{k}": v for k, v in terms.items() if k != "total"})
                 flat.zero()
                 backward_parameters(loss, opt.params)
                 return loss
             target, weight = batch["total_energy"], batch["_graph_weight"]      # weight: 1 / G for the real graphs, 0 for the ghost
             if cfg_kind == "energy":
-                loss = ops.sq_error(model(batch)["total_energy"], target, weight, 1e3)
+                pred = model(batch)["total_energy"]
+                loss = keep_outputs(ops.sq_error(pred, target, weight, 1e3), batch, graph={"total_energy": pred})
                 flat.zero()
                 loss.backward(gradient=ops.unit_gradient(loss))
             else:      # config_energy_force.py:18 loss_coeffs; the force term is a mean over the REAL nodes' components
                 f_t, wn = batch["forces_target"], batch["_node_weight"]
                 out = model(batch)
                 loss = ops.sq_error(out["energy"], target, weight, 1e3) + ops.sq_error(out["forces"], f_t, wn, 3e4 / 3.0)
+                keep_outputs(loss, batch, graph={"energy": out["energy"]}, node={"forces": out["forces"]})
                 flat.zero()
                 backward_parameters(loss, opt.params)
             return loss
@@ -688,7 +740,26 @@ def main():
             recs = native_records(recs)
         return max_over_ranks(seconds), recs, out
 
+    def outputs_of(loss):
+        """--dump-outputs: host copies of what the step that returned ``loss`` computed, and of the parameters, gradients and
+        EMA shadow it left (gathered from the flat vectors in ``model.named_parameters()`` order, not the optimizer's layout)."""
+        arrays = {"loss": loss}
+        for name, t, w in getattr(loss, "_bench_outputs", ()):
+            arrays[name] = t if w is None else t[w.reshape(-1) > 0]
+        pos = {n: i for i, (n, _) in enumerate(model.named_parameters())}
+        spans = sorted(((o, k, n) for o, k, _, n in opt.layout()), key=lambda s: pos[s[2]])
+        for name, vec in (("parameters", opt.flat), ("gradients", opt.grads.buffer), ("ema_parameters", opt.ema)):
+            if vec is not None:
+                arrays[name] = torch.cat([vec[o:o + k] for o, k, _ in spans])
+        out = {}
+        for name, t in arrays.items():
+            a = t.detach().cpu().numpy()
+            out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        return out
+
     elapsed, records, loss = timed_region()
+    # what the K-th timed step computed, copied to the host before anything else runs (a retimed region trains K steps more)
+    dumped = outputs_of(loss) if (args.dump_outputs is not None and rank == 0) else None
     check_replicas(f"after the timed region's step {args.steps}")
     retimed = None
     if ref_step is not None and elapsed / args.steps > 3.0 * ref_step:
@@ -939,6 +1010,9 @@ def main():
             cb = cpu_baseline(args.cpu_budget)
             result["cpu_baseline"] = cb
             result["gpu_vs_cpu_forward"] = round(result["gpu_forward_only_molecules_per_s"] / cb["lmax2_forward_only_value"], 1)
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "after_step": f"timed step {args.steps} of the first timed region",
+                                        "arrays": write_outputs(dumped, args.dump_outputs)}
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()
