@@ -123,7 +123,9 @@ def poll_capture_flags(device=None) -> None:
 
 _PERSISTENT_MSG = ("a batch held node ids outside [0, num_nodes) in its edge_index (such edges were attached to node 0), row keys "
                    "outside [0, n_keys) (such rows were dropped from the keyed self-connection), a type index outside [0, num_types) "
-                   "(OneHotEncoding: an all-zero row where the reference's one_hot raises) or an edge key outside the keyed radial tables")
+                   "(OneHotEncoding: an all-zero row where the reference's one_hot raises), an edge key outside the keyed radial tables, or a "
+                   "collated batch (data/device_store.py) held a graph id outside its store or did not fit its bucket (it was collated "
+                   "as empty graphs)")
 
 
 def persistent_flag(device) -> torch.Tensor:

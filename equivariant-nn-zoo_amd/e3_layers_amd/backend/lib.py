@@ -117,6 +117,11 @@ class MlpNet(C.Structure):
                 ("g_weights", C.c_void_p * 4), ("g_x", C.c_void_p)]
 
 
+class CollateField(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("ghost", C.c_int32), ("row_bytes", C.c_int64), ("src", C.c_void_p), ("dst", C.c_void_p),
+                ("table", C.c_void_p), ("src_ld", C.c_int64), ("dst_ld", C.c_int64)]
+
+
 class LayerFwdArgs(C.Structure):
     _fields_ = ([("N", C.c_int64), ("E", C.c_int64)]
                 + [(k, C.c_int32) for k in ("in_cf", "out_cf", "keep", "fork", "has_w", "n_keys", "have_m", "_pad")]
@@ -225,6 +230,9 @@ SIGNATURES = {
     "e3k_tp_bwd_x": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "e3k_csr_workspace_ints": (C.c_int64, [_I64, _I64]),
     "e3k_csr_build": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "e3k_collate_work_ints": (C.c_int64, [_I32]),
+    "e3k_collate_plan": (C.c_int, [_P, _I32, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "e3k_collate_gather": (C.c_int, [C.POINTER(CollateField), _I32, _I32, _I64, _I64, _P, _P]),
     "e3k_group_rows": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P]),
     "e3k_rtable_bins_workspace_ints": (C.c_int64, [_I64, _I32]),
     "e3k_rtable_bins": (C.c_int, [_P, _I64, _F, _I32, _P, _P, _P, _P, _P, _P, _P]),

@@ -190,6 +190,23 @@ class DataLoader(torch.utils.data.DataLoader):
 # ---------------------------------------------------------------------------------------------------------------------
 # the loader that keeps up
 # ---------------------------------------------------------------------------------------------------------------------
+def id_batches(n: int, batch_size: int, shuffle: bool = True, seed: int = 0, drop_last: bool = True,
+               epochs: Optional[int] = 1) -> Iterator[List[int]]:
+    """The graph ids of every batch drawn from ``n`` graphs, in order: per epoch a fresh ``torch.randperm`` from one
+    ``torch.Generator`` seeded with ``seed`` (``shuffle``) or ``0 .. n-1``, cut into batches of ``batch_size`` (``drop_last``:
+    without the short tail).  ``epochs=None``: endless.  The id sequence of ``PrefetchLoader`` and
+    ``device_store.DeviceLoader``."""
+    gen = torch.Generator()
+    gen.manual_seed(seed)
+    epoch = 0
+    while epochs is None or epoch < epochs:
+        order = torch.randperm(n, generator=gen) if shuffle else torch.arange(n)
+        stop = n - batch_size + 1 if drop_last else n
+        for a in range(0, stop, batch_size):
+            yield order[a:a + batch_size].tolist()
+        epoch += 1
+
+
 class PrefetchLoader:
     """Batches of ``batch_size`` graphs drawn from a condensed store, assembled ahead of the consumer.
 
@@ -228,15 +245,7 @@ class PrefetchLoader:
 
     def id_batches(self) -> Iterator[List[int]]:
         """The graph ids of every batch, in order (what the worker consumes; exposed for the parity test)."""
-        gen = torch.Generator()
-        gen.manual_seed(self.seed)
-        epoch = 0
-        while self.epochs is None or epoch < self.epochs:
-            order = torch.randperm(self.n, generator=gen) if self.shuffle else torch.arange(self.n)
-            stop = self.n - self.batch_size + 1 if self.drop_last else self.n
-            for a in range(0, stop, self.batch_size):
-                yield order[a:a + self.batch_size].tolist()
-            epoch += 1
+        return id_batches(self.n, self.batch_size, self.shuffle, self.seed, self.drop_last, self.epochs)
 
     def assemble(self, ids: Sequence[int]) -> Batch:
         """One batch on the host (the worker's first half; also the oracle-free reference point of the tests)."""

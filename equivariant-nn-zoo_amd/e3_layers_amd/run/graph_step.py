@@ -19,6 +19,7 @@ from __future__ import annotations
 import os
 from typing import Any, Callable
 
+import numpy as np
 import torch
 
 
@@ -119,6 +120,17 @@ class CapturedStep:
 # equals the un-padded batch's up to the order of the sums.  All host-side decisions of the model (knot table, stacks,
 # streams, keyed self-connection) depend on sizes only, which the bucket fixes.
 # ---------------------------------------------------------------------------------------------------------------------
+def ghost_positions(n_nodes: int, dtype=torch.float32) -> torch.Tensor:
+    """The ghost graph's node positions [n_nodes, 3]: collinear, neighbour distances spread over [1.0, 3.5) A (golden-ratio
+    sequence): ghost edges must not pile up in ONE knot bin of the radial table (a bin's edges are walked by one wave, its CSR row
+    is ranked in O(len^2 / 64)).  Row k depends on k alone (a float64 running sum), so the rows of a longer table are those of a
+    shorter one: ``data/device_store.py`` copies ghost positions from one table per node capacity."""
+    gaps = 1.0 + 2.5 * torch.frac(0.6180339887 * torch.arange(n_nodes, dtype=torch.float64))
+    pos = torch.zeros(n_nodes, 3, dtype=dtype)
+    pos[:, 0] = (torch.cumsum(gaps, 0) - gaps[0]).to(dtype)
+    return pos
+
+
 def ghost_sample(like, n_nodes: int, n_edges: int):
     """A sample with ``n_nodes`` (>= 2 when it has edges) collinear nodes and ``n_edges`` nearest-neighbour edges, with the
     keys of ``like`` (a ``Data`` sample on the host: ``pos``, ``species``, ``edge_index``, per-graph targets)."""
@@ -126,11 +138,7 @@ def ghost_sample(like, n_nodes: int, n_edges: int):
 
     if n_nodes < (2 if n_edges else 1):
         raise ValueError(f"a ghost graph with {n_edges} edges needs at least two nodes (got {n_nodes}): raise the node capacity")
-    # neighbour distances spread over [1.0, 3.5) A (golden-ratio sequence): ghost edges must not pile up in ONE knot bin of
-    # the radial table (a bin's edges are walked by one wave, its CSR row is ranked in O(len^2 / 64))
-    gaps = 1.0 + 2.5 * torch.frac(0.6180339887 * torch.arange(n_nodes, dtype=torch.float64))
-    pos = torch.zeros(n_nodes, 3, dtype=like["pos"].dtype)
-    pos[:, 0] = (torch.cumsum(gaps, 0) - gaps[0]).to(like["pos"].dtype)
+    pos = ghost_positions(n_nodes, like["pos"].dtype)
     k = torch.arange(n_edges, dtype=torch.int64)
     a = k % max(n_nodes - 1, 1)
     flip = (k // max(n_nodes - 1, 1)) % 2 == 1
@@ -427,4 +435,166 @@ class PipelinedBucketedStep:
                 self.ev_prep[o].record(self.prep_stream)
         if self.tail is not None:
             self.tail()
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Replay fed from a dataset in HBM: the preparation graph of a buffer collates the batch itself, from its graph ids.
+# ---------------------------------------------------------------------------------------------------------------------
+class _IdsRing:
+    """Pinned host buffers the graph ids of a batch travel to the device from, each guarded by the event of the copy last issued
+    from it: the host never rewrites a buffer whose copy may still be in flight."""
+
+    def __init__(self, n: int, depth: int = 4):
+        self.bufs = [torch.zeros(n, dtype=torch.int32).pin_memory() for _ in range(depth)]
+        self.events = [None] * depth
+        self.turn = 0
+
+    def __call__(self, ids, dst: torch.Tensor) -> None:
+        """On the CURRENT stream: ``dst`` (device int32) <- ``ids`` (host int32)."""
+        k = self.turn % len(self.bufs)
+        self.turn += 1
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        buf = self.bufs[k][:ids.shape[0]]
+        np.copyto(buf.numpy(), ids)
+        dst.copy_(buf, non_blocking=True)
+        if self.events[k] is None:
+            self.events[k] = torch.cuda.Event()
+        self.events[k].record()
+
+
+class _CollatedBuffers(PipelinedBucketedStep):
+    """``PipelinedBucketedStep`` for one bucket of a ``DeviceLoader``, whose preparation graphs collate their batch:
+
+        P[b]  = collate(ids[b] -> static[b]) + ``prepare(static[b])``      (csrc/e3k_collate.hip: two launches)
+
+    The only input of buffer b is its ids tensor (int32 [G]); ``_enqueue_prepare`` copies the next batch's ids into it from a
+    pinned buffer and replays P[b].  ``__call__`` and the two-buffer schedule are the parent's."""
+
+    def __init__(self, ds, item, prepare, fn, warmup: int, generators, tail, ring: _IdsRing):
+        from ..backend.graph import capture_flag
+
+        self.tail = tail
+        self.prepare = prepare
+        self.dev = ds.device
+        self.ring = ring
+        self.prep_stream = stream_beside(torch.cuda.current_stream(self.dev))
+        self.collations = [ds.collation(item.G, *item.capacity) for _ in range(2)]
+        self.static = [c.batch for c in self.collations]
+        self.prep_graphs, self.steps = [], []
+        self.ev_prep = [torch.cuda.Event() for _ in range(2)]
+        self.ev_step = [torch.cuda.Event() for _ in range(2)]
+        self._holds = [None, None]
+        self._held_by = [None, None]        # the last batch each buffer was prepared for (CollatedStep.last_static)
+        self._step_ran = [False, False]
+        self.keys = list(self.static[0].keys())
+        self._given = []                    # (everything in a buffer is regenerated from its ids)
+        capture_flag(self.dev)
+        ids = torch.from_numpy(item.ids)
+        for b, c in enumerate(self.collations):
+            c.ids.copy_(ids)
+            c()                             # eagerly first (see PipelinedBucketedStep.__init__), then recorded with the preparation
+            if b == 0:
+                warm = c.batch.clone()
+                prepare(warm)
+                torch.cuda.synchronize(self.dev)
+                del warm
+            torch.cuda.synchronize(self.dev)
+            self.prep_graphs.append(self._record_prepare(b))
+            self._held_by[b] = item
+            self.steps.append(CapturedStep((lambda s=c.batch: fn(s.view())), warmup=warmup if b == 0 else 1, generators=generators))
+        self.captured = self.steps[0]
+
+    def _record_prepare(self, b: int):
+        c = self.collations[b]
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            c()
+            self.prepare(c.batch)
+        g.replay()                          # (a capture records, it does not run: the step's recording reads these results)
+        torch.cuda.synchronize(self.dev)
+        return g
+
+    def _record_again(self, b: int) -> None:
+        """As ``PipelinedBucketedStep._record_again``: the preparation graph is recorded again first, on NEW output tensors (no
+        per-tensor memo knows them), collating the ids the buffer holds."""
+        torch.cuda.synchronize(self.dev)
+        c = self.collations[b]
+        self.prep_graphs[b] = None          # (its pool holds the old bins)
+        c.renew()
+        c.batch._e3k_done = None
+        forget_batch_memos()
+        c()
+        warm = c.batch.clone()
+        self.prepare(warm)                  # (eagerly first: see __init__)
+        torch.cuda.synchronize(self.dev)
+        del warm
+        self.prep_graphs[b] = self._record_prepare(b)
+
+    def _enqueue_prepare(self, b: int, item) -> None:
+        """On the CURRENT stream: the batch's ids into buffer b, then its preparation graph (collation + preparation)."""
+        self.ring(item.ids, self.collations[b].ids)
+        self.prep_graphs[b].replay()
+        self._holds[b] = item
+        self._held_by[b] = item
+
+
+class CollatedStep:
+    """A training step replayed on batches drawn from a ``DeviceLoader`` (``data/device_store.py``): ``step()`` draws the next
+    batch's graph ids, announces the batch after it (prepared beside this step when both share a bucket) and replays.
+
+        ds = DeviceDataset(store, device=dev)
+        loader = DeviceLoader(ds, batch_size=256, shuffle=True, seed=rank)
+        step = CollatedStep(loader, prepare=model.prepare_data, fn=train_on, warmup=3, generators=gens)
+        for _ in range(n_steps):
+            loss = step()
+
+    Per bucket one pair of buffers (``PipelinedBucketedStep``'s schedule), whose preparation graphs collate the batch on the
+    device from its ids: the host's part of a step is the ids (1 KB) and two graph launches.  The first batch's bucket is
+    recorded here; a bucket a later batch opens is recorded when that batch comes -- its warm-up runs of ``fn`` take optimizer
+    steps on that batch, as those of the first bucket's do on the first batch (callers that care rewind after construction).
+    ``tail`` as ``BucketedStep``'s (several ranks).  A loader with a finite number of epochs raises ``StopIteration`` when it is
+    exhausted."""
+
+    def __init__(self, loader, prepare: Callable[[Any], Any], fn: Callable[[Any], Any], warmup: int = 3, generators=(),
+                 tail: Callable[[], Any] = None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("CollatedStep needs a HIP device: there is no CPU fallback for graph replay")
+        self.loader, self.ds = loader, loader.ds
+        self.prepare, self.fn, self.warmup, self.generators, self.tail = prepare, fn, warmup, tuple(generators), tail
+        self._ring = _IdsRing(loader.batch_size)
+        self._buffers = {}
+        self._it = iter(loader)
+        self._next = next(self._it, None)
+        if self._next is None:
+            raise ValueError("the loader yields no batch")
+        self.last_static = None
+        self._buffers_for(self._next)
+
+    def _buffers_for(self, item) -> _CollatedBuffers:
+        buf = self._buffers.get(item.key)
+        if buf is None:
+            buf = self._buffers[item.key] = _CollatedBuffers(self.ds, item, self.prepare, self.fn, self.warmup, self.generators,
+                                                             self.tail, self._ring)
+        return buf
+
+    @property
+    def n_buckets(self) -> int:
+        """Buckets recorded so far."""
+        return len(self._buffers)
+
+    @property
+    def recaptures(self) -> int:
+        return sum(b.recaptures for b in self._buffers.values())
+
+    def __call__(self):
+        cur = self._next
+        if cur is None:
+            raise StopIteration
+        nxt = next(self._it, None)
+        buf = self._buffers_for(cur)
+        out = buf(cur, nxt=nxt if nxt is not None and nxt.key == cur.key else None)
+        self.last_static = buf.static[buf._held_by.index(cur)]
+        self._next = nxt
         return out

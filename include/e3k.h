@@ -338,6 +338,47 @@ int e3k_group_rows(const int64_t* key, int64_t R, int32_t K, int32_t* perm, int3
                    int32_t* bad_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Padded collation on the device (csrc/e3k_collate.hip; data/device_store.py).
+ * Replaces, per batch, the reference's collate (Batch.from_data_list over Data objects, e3_layers/data/dataloader.py:30-45)
+ * followed by run/graph_step.pad_batch: G graphs chosen by `ids` are gathered from a device-resident store (graph s owns node
+ * rows [node_off[s], node_off[s+1]) and edge rows [edge_off[s], edge_off[s+1]), edge_index sample-local int32 [2, E_store])
+ * and padded with ONE ghost graph to exactly n_cap nodes and e_cap edges -- bit for bit what pad_batch(store.index_select(ids),
+ * n_cap, e_cap) builds on the host.  Two launches, fixed shapes per (G, n_cap, e_cap), no host read-back, no memset:
+ *   e3k_collate_plan    one workgroup (G <= 1024): exclusive scans of the chosen graphs' counts into `work`
+ *                       (e3k_collate_work_ints(G) int64), n_nodes / n_edges [G+1] (the ghost's last), graph_weight [G+1]
+ *                       (1/G, ghost 0).  An id outside [0, S), n + 2 > n_cap or e > e_cap ORs bit 4 (16) into *flag (a
+ *                       persistent flag: never cleared here) and collates the batch as G EMPTY graphs plus a ghost that fills
+ *                       the capacities -- nothing is read through a bad id, nothing is written past a capacity.
+ *   e3k_collate_gather  one wave per (graph slot, field): the fields below, ghost rows included.
+ * ------------------------------------------------------------------------------------------ */
+#define E3K_COLLATE_NODE 0         /* row copy: node rows (ghost: see `ghost`) */
+#define E3K_COLLATE_EDGE 1         /* row copy: edge rows (ghost: see `ghost`) */
+#define E3K_COLLATE_GRAPH 2        /* row copy: one row per graph (ghost: zeros) */
+#define E3K_COLLATE_EDGE_INDEX 3   /* src int32 [2, src_ld] sample-local -> dst int64 [2, dst_ld] + the graph's first node */
+#define E3K_COLLATE_NODE_SEGMENT 4 /* dst int64 [n_cap]: graph slot of every node */
+#define E3K_COLLATE_EDGE_SEGMENT 5 /* dst int64 [e_cap]: graph slot of every edge */
+#define E3K_COLLATE_NODE_WEIGHT 6  /* dst float [n_cap]: (float)(1.0 / n) on the real nodes, 0 on the ghost's */
+#define E3K_COLLATE_GHOST_FIRST 0  /* ghost rows = the first real graph's first row (zeros when it has none) */
+#define E3K_COLLATE_GHOST_TABLE 1  /* ghost row k = row k of `table` (>= n_cap rows; ghost positions) */
+#define E3K_COLLATE_MAX_FIELDS 16
+typedef struct {
+  int32_t kind;       /* E3K_COLLATE_* */
+  int32_t ghost;      /* node / edge rows: E3K_COLLATE_GHOST_* */
+  int64_t row_bytes;  /* row copies: bytes per row, a multiple of 4 */
+  const void* src;    /* the store's tensor (row copies, edge_index) */
+  void* dst;          /* the batch's tensor */
+  const void* table;  /* E3K_COLLATE_GHOST_TABLE */
+  int64_t src_ld;     /* edge_index: elements between the store's two rows (E_store) */
+  int64_t dst_ld;     /* edge_index: elements between the batch's two rows (e_cap) */
+} e3k_collate_field;
+int64_t e3k_collate_work_ints(int32_t G);
+int e3k_collate_plan(const int32_t* ids, int32_t G, const int64_t* node_off, const int64_t* edge_off, int64_t S, int64_t n_cap,
+                     int64_t e_cap, int64_t* work, int64_t* n_nodes, int64_t* n_edges, float* graph_weight, int32_t* flag,
+                     void* stream);
+int e3k_collate_gather(const e3k_collate_field* fields, int32_t n_fields, int32_t G, int64_t n_cap, int64_t e_cap,
+                       const int64_t* work, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Radial weights through a knot table (csrc/e3k_rtable.hip).
  * Replaces weight = fc(edge_radial) (nn/message_passing.py:74-79,93) evaluated per edge when edge_radial is
  * RadialBasisEncoding(edge_length) (nn/embedding.py:210-219): the MLP is evaluated on the K + 1 knots j * r_max / K
