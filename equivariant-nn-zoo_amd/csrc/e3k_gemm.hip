@@ -17,10 +17,6 @@
 //                       fragment (lane -> row l&31, k l>>5) is bank-conflict free; B tile [k][n].  Global
 //                       loads are 16 B/lane into registers one K-step ahead of the MFMAs (issue early,
 //                       write LDS late).  dgrad (dA = dC . B^T) = same kernel, b_k / b_n swapped.
-//   gemm_smallk_kernel  K <= 64 (radial MLP, 64-channel node Linears): the A tile (128 x K) stays in LDS
-//                       while the block walks up to 8 column tiles, so A is read once per 512 columns and
-//                       the stores of one column tile drain under the MFMAs of the next: this GEMM is
-//                       bound by its output stream (E x W floats), not by the matrix pipe.
 //   gemm_outer_kernel   self-connection: Aeff[(r1,r2), u*V+v] = X[(r1,r2),u] * attrs[r1,v]; X and attrs
 //                       tiles sit in LDS for the whole K loop, the product is formed when the fragment is
 //                       read, so x (x) node_attrs (N x 1280 x (2l+1)) is never materialised.
@@ -31,7 +27,6 @@
 // Descriptors: up to 20 problems per launch, passed by value (3.85 KB of kernel arguments); keyed and plain problems mix; every
 // workgroup finds its problem and pulls it into scalar registers with s_load (the batch is wave-uniform).
 #include <algorithm>
-#include <cstdlib>
 
 #include "e3k_common.h"
 
@@ -42,14 +37,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // 20 x 168 B of descriptors + tables = 3.85 KB of the 4 KB kernel-argument segment (round 6: 16 -> 20 -- the three weight gradients of a
 // layer are 7 + 7 + 6 problems: with 16 per launch linear_1's last four went out as a second, 23 us launch of their own)
 constexpr int GEMM_MAXP = 20;
-static_assert(true, "");
 struct GemmBatch {
   int n;
   int reps[GEMM_MAXP];              // > 1: the problem stands for `reps` key groups (its tile range is reps equal sub-ranges);
   long long key_stride[GEMM_MAXP];  //      key t uses B + t*key_stride and the device pair group_dev + 2*t
   int tile_start[GEMM_MAXP + 1];
   int flags[GEMM_MAXP];  // bit0: A float4-loadable, bits1-2: B mode (0 scalar, 1 n-contiguous vec, 2 k-contiguous vec), bit3: G float4-loadable (wgrad)
-  int aux[GEMM_MAXP];    // wgrad: row splits; smallk: column tiles per block
+  int aux[GEMM_MAXP];    // wgrad: row splits (compact keyed grid: rows per split)
   e3k_gemm_problem p[GEMM_MAXP];
 };
 static_assert(sizeof(GemmBatch) % 4 == 0 && sizeof(e3k_gemm_problem) % 4 == 0, "word-copyable descriptors");
@@ -62,32 +56,6 @@ constexpr int XU = 64;          // outer mode: channels of X kept per super-step
 constexpr int LDX = XU + 1;
 constexpr int VMAX = 32;        // outer mode: max attrs width
 constexpr int LDV = VMAX + 1;
-constexpr int SK_KMAX = 64;     // small-K kernel: max K
-constexpr int SK_LDA = SK_KMAX + 1;
-constexpr int SK_CT = 8;        // small-K kernel: column tiles per block
-
-#ifdef E3K_STAMPS
-__device__ unsigned long long e3k_dbg_buf[1 << 20];
-#define STAMP_DECL unsigned long long st_last = __builtin_readcyclecounter(), st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define STAMP(i)                                                  \
-  do {                                                            \
-    const unsigned long long now_ = __builtin_readcyclecounter(); \
-    st_acc[i] += now_ - st_last;                                  \
-    st_last = now_;                                               \
-  } while (0)
-#define STAMP_FLUSH()                                                                             \
-  do {                                                                                            \
-    if ((threadIdx.x & 63) == 0) {                                                                \
-      const size_t slot = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;                      \
-      if (slot + 8 <= (1u << 20))                                                                 \
-        for (int i_ = 0; i_ < 8; ++i_) e3k_dbg_buf[slot + i_] = st_acc[i_];                       \
-    }                                                                                             \
-  } while (0)
-#else
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_FLUSH()
-#endif
 
 struct BlockProblem {
   e3k_gemm_problem P;
@@ -95,7 +63,7 @@ struct BlockProblem {
   int pi, key;      // index of the problem in the batch; key group of a keyed problem (0 otherwise): what a K-chain's followers reuse
 };
 
-// COMPACT keyed grids (round 6; flags bit 6, gemm_kernel and gemm_smallk_kernel): a keyed problem used to get `reps` x the tiles of its
+// COMPACT keyed grids (round 6; flags bit 6, gemm_kernel and gemm_wgrad2_kernel): a keyed problem used to get `reps` x the tiles of its
 // row bound M1 -- every key a full-size grid, the workgroups past a key's last row exit after reading their descriptor: 8 377
 // workgroups for ~1 300 tiles of work in a layer's linear_1 + self-connection launch, nine rounds of empty workgroups through the
 // CUs.  The key groups PARTITION the rows, so sum_k ceil(count_k M2 / bm) <= ceil(M1 M2 / bm) + reps row tiles suffice: a workgroup
@@ -389,9 +357,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmBatch gb) {
   const float* ap = As + (wm * 32 + (lane & 31)) * LDA + (lane >> 5);
   const float* bp = Bs + (lane >> 5) * LDB + wn * (BN / WN) + (lane & 31);
   auto mfma_tile = [&]() {
-#ifdef E3K_DEBUG_KNOBS
-    if (flags & 16) return;    // timing only: no MFMAs
-#endif
 #pragma unroll
     for (int kk = 0; kk < BK; kk += 2) {
       const float a = ap[kk];
@@ -468,15 +433,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmBatch gb) {
     }
   }
   }
-#ifdef E3K_DEBUG_KNOBS
-  if (bp_.flags & 32) return;      // timing only: no stores
-#endif
   store_acc<NT>(P, acc, rowC, wm * 32, n0 + wn * (BN / WN));
 }
-
-#ifdef E3K_DEBUG_KNOBS
-#include "../../tools/experiments/gemm_persist_kernel.inc"      // (debug build only: the persistent work-list experiment)
-#endif  // E3K_DEBUG_KNOBS
 
 // ---------------------------------------------------------------------------------------
 // few rows, long K (the radial MLP's dgrad on the knot table: 4097 x 64 outputs, K ~ 2000): a 64-row tile grid would
@@ -565,141 +523,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_kernel(const GemmBatch gb) {
 // instead of eight 32x32x2 f32 ones -- was built and measured in round 1: 2.7x cheaper on the matrix pipe and as accurate,
 // but +12 % at best (K = N = 1024) and -12 % on the radial shapes: the split costs VALU per staged element and these GEMMs
 // are not matrix-pipe-bound.  Removed in round 2)
-
-// ---------------------------------------------------------------------------------------
-// small-K forward (K <= 64, A k-contiguous, B n-contiguous): A tile resident, walk column tiles
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gemm_smallk_kernel(const GemmBatch gb) {
-  constexpr int BM_ = 128;
-  __shared__ float As[BM_ * SK_LDA];
-  __shared__ __attribute__((aligned(16))) float Bs[SK_KMAX * LDB];
-  __shared__ long long rowA[BM_];
-  __shared__ long long rowC[BM_];
-  STAMP_DECL
-  const BlockProblem bp_ = fetch_problem(gb, BM_, [](const e3k_gemm_problem& Q, int aux) {
-    const int tn = (Q.N + BN - 1) / BN;
-    return (tn + aux - 1) / aux;
-  });
-  if (bp_.local < 0) return;      // (block-uniform: surplus workgroup of a compact keyed grid)
-  STAMP(0);
-  const e3k_gemm_problem& P = bp_.P;
-  const int local = bp_.local, ct = bp_.aux;
-  const int M = P.M1 * P.M2, K = P.K;
-  const int tiles_n = (P.N + BN - 1) / BN;
-  const int col_groups = (tiles_n + ct - 1) / ct;
-  const int row0 = (local / col_groups) * BM_;
-  if (row0 >= M) return;  // block-uniform: surplus workgroup of a device-sized group
-  const int tile_beg = (local % col_groups) * ct;
-  const int tile_end = (tile_beg + ct < tiles_n) ? tile_beg + ct : tiles_n;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int kpad = (K + 3) & ~3;  // K % 4 == 0 is a precondition of this kernel (float4 rows)
-
-  fill_row_tables<BM_>(P, row0, M, rowA, rowC);
-  __syncthreads();
-  // ---- A tile: 2 threads per row, each up to 8 float4
-  {
-    const long long off = rowA[t >> 1];
-    const float* arow = off >= 0 ? P.A + off : nullptr;
-    float* d = As + (t >> 1) * SK_LDA;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = ((t & 1) * 8 + j) * 4;
-      if (k < kpad) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (arow && k < K) v = *reinterpret_cast<const float4*>(arow + k);
-        d[k] = v.x; d[k + 1] = v.y; d[k + 2] = v.z; d[k + 3] = v.w;
-      }
-    }
-  }
-  // ---- B tile registers: K x 64 floats = up to 4 float4 per thread
-  float4 rb[4];
-  auto gload_b = [&](int n0) {
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-      const int k = (t >> 4) + 16 * pass, nq = (t & 15) * 4;
-      rb[pass] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (k < K && n0 + nq < P.N) rb[pass] = *reinterpret_cast<const float4*>(P.B + (int64_t)k * P.b_k + (n0 + nq));
-    }
-  };
-  const float* ap = As + (w * 32 + (lane & 31)) * SK_LDA + (lane >> 5);
-  const float* bp = Bs + (lane >> 5) * LDB + (lane & 31);
-  gload_b(tile_beg * BN);
-  STAMP(1);
-  for (int tile = tile_beg; tile < tile_end; ++tile) {
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-      const int k = (t >> 4) + 16 * pass, nq = (t & 15) * 4;
-      if (k < kpad) *reinterpret_cast<float4*>(Bs + k * LDB + nq) = rb[pass];
-    }
-    STAMP(2);
-    __syncthreads();
-    STAMP(3);
-    if (tile + 1 < tile_end) gload_b((tile + 1) * BN);
-    // The MFMA is issued with the operands EXCHANGED (weights as the row operand, activations as the column operand):
-    // the accumulator then holds C^T — lane = output row (edge), four consecutive registers = four consecutive
-    // output columns — so every lane stores 16 contiguous bytes straight from its registers.  (The natural
-    // orientation gives a lane one column and 16 scattered rows: 4-byte stores, or a trip through LDS, which
-    // measured as long as the MFMAs of the tile.)
-    f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
-    int kk = 0;
-    for (; kk + 16 <= kpad; kk += 16) {  // 16 MFMAs per trip, all fragment reads issued up front
-      float a[8], b0[8], b1[8];
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        a[s] = ap[kk + 2 * s];
-        b0[s] = bp[(kk + 2 * s) * LDB];
-        b1[s] = bp[(kk + 2 * s) * LDB + 32];
-      }
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0[s], a[s], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b1[s], a[s], acc[1], 0, 0, 0);
-      }
-    }
-    for (; kk < kpad; kk += 2) {
-      const float a = ap[kk];
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bp[kk * LDB], a, acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bp[kk * LDB + 32], a, acc[1], 0, 0, 0);
-    }
-    STAMP(4);
-    {
-      const long long off = rowC[w * 32 + (lane & 31)];
-      if (off >= 0) {
-        float* crow = P.C + off;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int n = tile * BN + 32 * j + 8 * q + 4 * (lane >> 5);
-            if (n < P.N) {
-              float4 o = make_float4(P.alpha * acc[j][4 * q], P.alpha * acc[j][4 * q + 1], P.alpha * acc[j][4 * q + 2],
-                                     P.alpha * acc[j][4 * q + 3]);
-              if (P.bias) {
-                const float4 b4 = *reinterpret_cast<const float4*>(P.bias + n);
-                o.x += b4.x; o.y += b4.y; o.z += b4.z; o.w += b4.w;
-              }
-              float4* dst = reinterpret_cast<float4*>(crow + n);
-              if (P.accumulate) {
-                const float4 old = *dst;
-                o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
-              }
-              o.x = epilogue_act(P, o.x); o.y = epilogue_act(P, o.y); o.z = epilogue_act(P, o.z); o.w = epilogue_act(P, o.w);
-              *dst = o;
-            }
-          }
-        }
-      }
-    }
-    STAMP(5);
-    __syncthreads();
-    STAMP(6);
-  }
-  STAMP_FLUSH();
-}
 
 // ---------------------------------------------------------------------------------------
 // outer-mode forward:  Aeff[(r1,r2), u*V+v] = X[(r1,r2),u] * attrs[r1,v]
@@ -1140,12 +963,7 @@ __device__ __forceinline__ void gemm_wgrad2_body(const BlockProblem& bp_, float*
   for (int c = 0; c < n_chunks; ++c) {
     const int st = c & 1;
     if (c + 1 < n_chunks) lstore(st ^ 1);
-#ifdef E3K_DEBUG_KNOBS
-    if (c + 2 < n_chunks && !(bp_.flags & 32)) gload();
-    if (bp_.flags & 16) { __syncthreads(); continue; }
-#else
     if (c + 2 < n_chunks) gload();
-#endif
     const float* ap = &As[st][aoff];
     const float* gp = &Gs[st][goff];
 #pragma unroll
@@ -1185,10 +1003,6 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad2_kernel(const GemmBatch gb)
     else gemm_wgrad2_body<2, false>(bp_, As, Gs);
   }
 }
-
-#ifdef E3K_DEBUG_KNOBS
-#include "../../tools/experiments/gemm_wgrad3_kernel.inc"       // (debug build only: the LDS-ring weight-gradient experiment)
-#endif  // E3K_DEBUG_KNOBS
 
 // ---------------------------------------------------------------------------------------
 // small helpers: column sums and the self-connection backward reduction
@@ -1356,9 +1170,8 @@ int cu_count() {      // compute units of the current device (launches sized to 
 }
 
 template <class K>
-int launch_batch(K kernel, const e3k::GemmBatch& gb, int blocks, hipStream_t st) {
+void launch_batch(K kernel, const e3k::GemmBatch& gb, int blocks, hipStream_t st) {
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, gb);
-  return E3K_OK;
 }
 
 int validate(const e3k_gemm_problem& P, bool wgrad) {
@@ -1382,17 +1195,14 @@ bool follows(const e3k_gemm_problem& H, const e3k_gemm_problem& F) {
 bool a_vec(const e3k_gemm_problem& P) {
   return P.V == 0 && P.a_k == 1 && P.K % 4 == 0 && P.a_r1 % 4 == 0 && (P.M2 == 1 || P.a_r2 % 4 == 0) && aligned16(P.A);
 }
-bool c_vec(const e3k_gemm_problem& P) {
-  return P.c_n == 1 && P.N % 4 == 0 && P.c_r1 % 4 == 0 && (P.M2 == 1 || P.c_r2 % 4 == 0) && aligned16(P.C) &&
-         (!P.bias || aligned16(P.bias));
-}
 int b_mode(const e3k_gemm_problem& P) {
   if (P.b_n == 1 && P.N % 4 == 0 && P.b_k % 4 == 0 && aligned16(P.B)) return 1;
   if (P.b_k == 1 && P.K % 4 == 0 && P.b_n % 4 == 0 && aligned16(P.B)) return 2;
   return 0;
 }
 
-enum FwdKind { FWD_PLAIN = 0, FWD_SMALLK, FWD_OUTER, FWD_SPLITK, FWD_PERSIST, FWD_KINDS, FWD_FOLLOWER };      // (a follower rides with its head)
+// The batched kinds launch in this order; the one-column problems (gemm_n1_kernel) before them, a K-chain's followers with their head
+enum FwdKind { FWD_PLAIN = 0, FWD_OUTER, FWD_SPLITK, FWD_KINDS, FWD_N1, FWD_FOLLOWER };
 
 struct Batcher {
   e3k::GemmBatch gb{};
@@ -1405,25 +1215,113 @@ struct Batcher {
   }
 };
 constexpr int MAX_CALL = 64;   // problems per C-ABI call
+
+// 64-row tiles (gemm_kernel<2>) unless the launch holds at least kSmallGrid 128-row tiles.  Round 3 switched to 128-row
+// tiles from three per CU; re-measured in round 4 (tools/ab_bench.py, 2-3 interleaved rounds): the 64-row form wins at
+// every size met -- trailing Linear forward 56 vs 62 us (twice the tiles: the unequal-K problems of a launch spread more
+// evenly over the CUs), 256 molecules 4.65 vs 4.69 ms, l_max 3 7.03 vs 7.16, the protein net 8.99 vs 9.09 -- so the
+// threshold now sits above anything a layer issues and gemm_kernel<4> is the form kept for launches beyond it.
+constexpr int64_t kSmallGrid = 1 << 20;
+
+// a forward call, planned: every problem's kind and the order in which the batches take them
+struct FwdPlan {
+  const e3k_gemm_problem* problems;
+  const int* reps;
+  const long long* key_stride;
+  int n;
+  bool small_grid;
+  int kind[MAX_CALL];
+  int order[MAX_CALL];
+};
+
+// The batches of kind k, filled in plan order: launched, or with launch == false only sized (the plan's dry run).  Both runs go
+// through this one loop, so the dry run meets every check the launching run would.
+int fwd_batches(const FwdPlan& pl, int k, bool launch, hipStream_t st) {
+  Batcher b;
+  auto flush = [&]() {
+    if (launch && b.blocks) {
+      b.gb.tile_start[b.gb.n] = b.blocks;
+      switch (k) {
+        case FWD_PLAIN:
+          if (b.chained)
+            pl.small_grid ? launch_batch(e3k::gemm_kernel<2, true>, b.gb, b.blocks, st) : launch_batch(e3k::gemm_kernel<4, true>, b.gb, b.blocks, st);
+          else
+            pl.small_grid ? launch_batch(e3k::gemm_kernel<2, false>, b.gb, b.blocks, st) : launch_batch(e3k::gemm_kernel<4, false>, b.gb, b.blocks, st);
+          break;
+        case FWD_SPLITK: launch_batch(e3k::gemm_splitk_kernel, b.gb, b.blocks, st); break;
+        default: launch_batch(e3k::gemm_outer_kernel, b.gb, b.blocks, st); break;
+      }
+    }
+    b.reset();
+  };
+  for (int oi = 0; oi < pl.n; ++oi) {
+    const int i = pl.order[oi];
+    if (pl.kind[i] != k) continue;
+    const e3k_gemm_problem& P = pl.problems[i];
+    const int64_t M = (int64_t)P.M1 * P.M2;
+    if (M == 0) continue;
+    if (P.chain > 0 && b.gb.n + 1 + P.chain > e3k::GEMM_MAXP) flush();      // a chain does not straddle two launches
+    const int rp = pl.reps && pl.reps[i] > 1 ? pl.reps[i] : 1;
+    const int tiles_n = (P.N + e3k::BN - 1) / e3k::BN;
+    int64_t blocks;
+    if (k == FWD_SPLITK) blocks = ((M + 31) / 32) * ((P.N + 31) / 32);
+    else if (k == FWD_PLAIN && pl.small_grid) blocks = ((M + 63) / 64) * tiles_n;
+    else blocks = ((M + 127) / 128) * tiles_n;
+    const bool compact = rp > 1 && P.group_dev && P.row_index && k == FWD_PLAIN;
+    if (compact) {
+      // (blocks = row tiles x workgroups per row tile: the key groups partition the rows, see fetch_problem)
+      const int64_t bm = pl.small_grid ? 64 : 128;
+      const int64_t row_tiles = (M + bm - 1) / bm, per_row = blocks / row_tiles;
+      blocks = (row_tiles + rp) * per_row;
+    } else {
+      blocks *= rp;
+    }
+    if (b.blocks + blocks > 0x7fffffffLL) return E3K_ERR_INVALID;
+    e3k::GemmBatch& gb = b.gb;
+    gb.p[gb.n] = P;
+    gb.reps[gb.n] = rp;
+    gb.key_stride[gb.n] = rp > 1 ? pl.key_stride[i] : 0;
+    gb.flags[gb.n] = (a_vec(P) ? 1 : 0) | (b_mode(P) << 1) | (compact ? 64 : 0);
+    gb.aux[gb.n] = 0;
+    gb.tile_start[gb.n] = b.blocks;
+    b.blocks += (int)blocks;
+    ++gb.n;
+    if (P.chain > 0) b.chained = true;
+    for (int j = 1; j <= P.chain; ++j) {      // the followers: right behind their head, no tiles of their own
+      const e3k_gemm_problem& F = pl.problems[i + j];
+      gb.p[gb.n] = F;
+      gb.p[gb.n].accumulate = P.accumulate;      // (the last link's descriptor runs the epilogue)
+      gb.p[gb.n].bias = P.bias;
+      gb.p[gb.n].act = P.act;
+      gb.p[gb.n].act_cst = P.act_cst;
+      gb.reps[gb.n] = rp;
+      gb.key_stride[gb.n] = rp > 1 ? pl.key_stride[i + j] : 0;
+      gb.flags[gb.n] = (a_vec(F) ? 1 : 0) | (b_mode(F) << 1);
+      gb.aux[gb.n] = 0;
+      gb.tile_start[gb.n] = b.blocks;
+      ++gb.n;
+    }
+    if (gb.n == e3k::GEMM_MAXP) flush();
+  }
+  flush();
+  return E3K_OK;
+}
 }  // namespace
 
 // reps[i] > 1: problem i is a keyed template (row_index = the key-sorted permutation, group_dev = the pair of key 0,
-// B of key t at B + t * key_stride[i]); reps == nullptr: all plain
+// B of key t at B + t * key_stride[i]); reps == nullptr: all plain.
+// Plan, then launch: every problem is validated and classified and every batch sized before the first launch, so a call that
+// fails has written nothing (a retry with `accumulate` set would otherwise apply the problems that went out twice).
 static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const int* reps, const long long* key_stride,
                          void* stream) {
-  if (n_problems < 0 || (n_problems && !problems)) return E3K_ERR_INVALID;
-  if (n_problems > MAX_CALL) return E3K_ERR_INVALID;
+  if (n_problems < 0 || n_problems > MAX_CALL || (n_problems && !problems)) return E3K_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  int kind[MAX_CALL];
-  int64_t plain_tiles128 = 0;
-  // The resident-A small-K kernel (gemm_smallk_kernel) is OFF since round 6: with the plain kernel back at five waves per SIMD and the
-  // keyed grids compact, every workload measured runs faster with its K <= 64 problems on gemm_kernel<2> -- 256 molecules 3.88 -> 3.82 ms
-  // (debug library), l_max 3 6.39 -> 6.28, 32 molecules 1.52 -> 1.47, force training 5.40 -> 5.33, config_diffusion (per-edge radial MLPs, the
-  // kernel's original customer) 3.34 -> 3.29, config_diffusion_CA 8.03 -> 7.76.  Its 51 KB of LDS and 152 registers leave three workgroups per
-  // CU where a launch has two rounds of them.  E3K_SK_MIN_ROWS=1024 (debug library) routes rows x K <= 64 problems to it again.
-  E3K_KNOB_INT(sk_min_rows, "E3K_SK_MIN_ROWS", 1LL << 40);
-  E3K_KNOB_INT(splitk_on, "E3K_SPLITK", 1);
-  E3K_KNOB_INT(keyed_compact, "E3K_KEYED_COMPACT", 1);
+  FwdPlan pl;
+  pl.problems = problems;
+  pl.reps = reps;
+  pl.key_stride = key_stride;
+  pl.n = n_problems;
+  int* const kind = pl.kind;
   int follower_of[MAX_CALL];
   for (int i = 0; i < n_problems; ++i) follower_of[i] = -1;
   for (int i = 0; i < n_problems; ++i) {
@@ -1440,6 +1338,12 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
       }
     }
   }
+  // (The resident-A small-K kernel of rounds 2-5 was switched off in round 6 and later removed: with the plain kernel back at five
+  // waves per SIMD and the keyed grids compact, every workload measured ran faster with its K <= 64 problems on gemm_kernel<2> --
+  // 256 molecules 3.88 -> 3.82 ms, l_max 3 6.39 -> 6.28, 32 molecules 1.52 -> 1.47, force training 5.40 -> 5.33, config_diffusion
+  // 3.34 -> 3.29, config_diffusion_CA 8.03 -> 7.76.  Its 51 KB of LDS and 152 registers left three workgroups per CU where a launch
+  // has two rounds of them.)
+  int64_t plain_tiles128 = 0;
   for (int i = 0; i < n_problems; ++i) {
     const e3k_gemm_problem& P = problems[i];
     const int64_t M = (int64_t)P.M1 * P.M2;
@@ -1447,11 +1351,8 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
       kind[i] = FWD_FOLLOWER;
       continue;
     }
-    if (P.N == 1 && P.V == 0 && P.chain == 0 && !P.row_index && !(reps && reps[i] > 1)) {      // one output column: gemm_n1_kernel, at once
-      if (M > 0)
-        hipLaunchKernelGGL(e3k::gemm_n1_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, P.A, P.B, (int64_t)P.M1, P.M2, P.K, P.a_r1, P.a_r2,
-                           P.a_k, P.b_k, P.c_r1, P.c_r2, P.alpha, P.bias, P.accumulate, P.act, P.act_cst, P.C);
-      kind[i] = FWD_FOLLOWER;      // (nothing left for the batched kernels)
+    if (P.N == 1 && P.V == 0 && P.chain == 0 && !P.row_index && !(reps && reps[i] > 1)) {      // one output column: gemm_n1_kernel
+      kind[i] = FWD_N1;
       continue;
     }
     if (P.chain > 0) {
@@ -1460,8 +1361,7 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
       continue;
     }
     if (P.V > 0) kind[i] = FWD_OUTER;
-    else if (P.K <= e3k::SK_KMAX && a_vec(P) && b_mode(P) == 1 && c_vec(P) && M >= sk_min_rows) kind[i] = FWD_SMALLK;
-    else if (splitk_on && a_vec(P) && b_mode(P) == 2 && P.K >= 256 && P.K % 64 == 0 && ((M + 63) / 64) * ((P.N + e3k::BN - 1) / e3k::BN) < 128)
+    else if (a_vec(P) && b_mode(P) == 2 && P.K >= 256 && P.K % 64 == 0 && ((M + 63) / 64) * ((P.N + e3k::BN - 1) / e3k::BN) < 128)
       kind[i] = FWD_SPLITK;
     else {
       kind[i] = FWD_PLAIN;
@@ -1488,7 +1388,7 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
   {
     bool any_splitk = false;
     for (int i = 0; i < n_problems; ++i) any_splitk = any_splitk || kind[i] == FWD_SPLITK;
-    if (any_splitk && splitk_on)
+    if (any_splitk)
       for (int i = 0; i < n_problems; ++i) {
         const e3k_gemm_problem& P = problems[i];
         const int64_t M = (int64_t)P.M1 * P.M2;
@@ -1499,149 +1399,30 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
         }
       }
   }
-  // plain problems with vector-loadable operands: the persistent kernel when the launch holds enough tiles for every
-  // workgroup slot to walk a sequence of them (below that the one-tile-per-workgroup kernels start sooner)
-#ifdef E3K_DEBUG_KNOBS
-  E3K_KNOB_INT(kPersist, "E3K_GEMM_PERSIST", 0);
-  E3K_KNOB_INT(kPersistMin, "E3K_GEMM_PERSIST_MIN_TILES", 1024);
-  const int n_cu = cu_count();
-  if (kPersist) {
-    int64_t ptiles = 0;
-    auto persistable = [&](int i) {
-      const e3k_gemm_problem& P = problems[i];
-      return kind[i] == FWD_PLAIN && a_vec(P) && b_mode(P) != 0 && !(reps && reps[i] > 1) && !P.row_index && (int64_t)P.M1 * P.M2 > 0;
-    };
-    for (int i = 0; i < n_problems; ++i)
-      if (persistable(i)) ptiles += (((int64_t)problems[i].M1 * problems[i].M2 + 127) / 128) * ((problems[i].N + e3k::BN - 1) / e3k::BN);
-    if (ptiles >= kPersistMin)
-      for (int i = 0; i < n_problems; ++i)
-        if (persistable(i)) {
-          kind[i] = FWD_PERSIST;
-          plain_tiles128 -= (((int64_t)problems[i].M1 * problems[i].M2 + 127) / 128) * ((problems[i].N + e3k::BN - 1) / e3k::BN);
-        }
-  }
-#endif
-  // 64-row tiles (gemm_kernel<2>) unless the launch holds at least kSmallGrid 128-row tiles.  Round 3 switched to 128-row
-  // tiles from three per CU; re-measured in round 4 (tools/ab_bench.py, 2-3 interleaved rounds): the 64-row form wins at
-  // every size met -- trailing Linear forward 56 vs 62 us (twice the tiles: the unequal-K problems of a launch spread more
-  // evenly over the CUs), 256 molecules 4.65 vs 4.69 ms, l_max 3 7.03 vs 7.16, the protein net 8.99 vs 9.09 -- so the
-  // threshold now sits above anything a layer issues and gemm_kernel<4> is the form kept for launches beyond it.
-  E3K_KNOB_INT(kSmallGrid, "E3K_GEMM_SMALL_GRID_TILES", 1 << 20);
-  const bool small_grid = plain_tiles128 < kSmallGrid;
-  for (int k = 0; k < FWD_KINDS; ++k) {
-    Batcher b;
-    auto flush = [&]() -> int {
-      if (!b.blocks) {
-        b.reset();
-        return E3K_OK;
-      }
-      b.gb.tile_start[b.gb.n] = b.blocks;
-      int rc = E3K_OK;
-      switch (k) {
-        case FWD_PLAIN:
-          if (b.chained)
-            rc = small_grid ? launch_batch(e3k::gemm_kernel<2, true>, b.gb, b.blocks, st) : launch_batch(e3k::gemm_kernel<4, true>, b.gb, b.blocks, st);
-          else
-            rc = small_grid ? launch_batch(e3k::gemm_kernel<2, false>, b.gb, b.blocks, st) : launch_batch(e3k::gemm_kernel<4, false>, b.gb, b.blocks, st);
-          break;
-        case FWD_SMALLK: rc = launch_batch(e3k::gemm_smallk_kernel, b.gb, b.blocks, st); break;
-        case FWD_SPLITK: rc = launch_batch(e3k::gemm_splitk_kernel, b.gb, b.blocks, st); break;
-#ifdef E3K_DEBUG_KNOBS
-        case FWD_PERSIST: {
-          E3K_KNOB_INT(kPersistOcc, "E3K_GEMM_PERSIST_WG_PER_CU", 2);
-          const int grid = b.blocks < (int)kPersistOcc * n_cu ? b.blocks : (int)kPersistOcc * n_cu;
-          hipLaunchKernelGGL(e3k::gemm_persist_kernel, dim3(grid), dim3(256), 0, st, b.gb, b.blocks);
-          break;
-        }
-#endif
-        default: rc = launch_batch(e3k::gemm_outer_kernel, b.gb, b.blocks, st); break;
-      }
-      b.reset();
-      return rc;
-    };
-    // longest-processing-time-first: workgroups are dispatched in blockIdx order, so the problems with the longest
-    // K loops go first and the short ones fill the tail of the launch
-    int order[MAX_CALL];
-    for (int i = 0; i < n_problems; ++i) order[i] = i;
-    auto k_total = [&](int a) {
-      int kt = problems[a].K;
-      for (int j = 1; j <= problems[a].chain; ++j) kt += problems[a + j].K;
-      return kt;
-    };
-    std::stable_sort(order, order + n_problems, [&](int a, int b) { return k_total(a) > k_total(b); });
-    for (int oi = 0; oi < n_problems; ++oi) {
-      const int i = order[oi];
-      if (kind[i] != k) continue;
-      const e3k_gemm_problem& P = problems[i];
-      const int64_t M = (int64_t)P.M1 * P.M2;
-      if (M == 0) continue;
-      if (P.chain > 0 && b.gb.n + 1 + P.chain > e3k::GEMM_MAXP) {      // a chain does not straddle two launches
-        const int rc = flush();
-        if (rc != E3K_OK) return rc;
-      }
-      const int rp = reps && reps[i] > 1 ? reps[i] : 1;
-      const int tiles_n = (P.N + e3k::BN - 1) / e3k::BN;
-      int64_t blocks;
-      int aux = 0;
-      if (k == FWD_SMALLK) {
-        E3K_KNOB_INT(sk_ct, "E3K_SK_CT", e3k::SK_CT);
-        // a block keeps its A tile and walks `aux` column tiles -- unless the problem has too few tiles to fill the chip
-        // that way (the radial MLP's last layer on the knot table: 33 row tiles): then fewer columns per block
-        const int64_t fill = ((M + 127) / 128) * tiles_n / 1024;
-        aux = tiles_n < sk_ct ? tiles_n : sk_ct;
-        if (fill < aux) aux = fill < 1 ? 1 : (int)fill;
-        blocks = ((M + 127) / 128) * ((tiles_n + aux - 1) / aux);
-      } else if (k == FWD_SPLITK) {
-        blocks = ((M + 31) / 32) * ((P.N + 31) / 32);
-      } else if (k == FWD_PLAIN && small_grid) {
-        blocks = ((M + 63) / 64) * tiles_n;
-      } else {
-        blocks = ((M + 127) / 128) * tiles_n;
-      }
-      bool compact = false;
-      if (rp > 1 && keyed_compact && P.group_dev && P.row_index && (k == FWD_SMALLK || (k == FWD_PLAIN))) {
-        // (blocks = row tiles x workgroups per row tile for both kernels: the key groups partition the rows, see fetch_problem)
-        const int64_t bm = k == FWD_SMALLK ? 128 : (small_grid ? 64 : 128);
-        const int64_t row_tiles = (M + bm - 1) / bm, per_row = blocks / row_tiles;
-        blocks = (row_tiles + rp) * per_row;
-        compact = true;
-      } else {
-        blocks *= rp;
-      }
-      if (b.blocks + blocks > 0x7fffffffLL) return E3K_ERR_INVALID;
-      e3k::GemmBatch& gb = b.gb;
-      gb.p[gb.n] = P;
-      gb.reps[gb.n] = rp;
-      gb.key_stride[gb.n] = rp > 1 ? key_stride[i] : 0;
-      E3K_KNOB_INT(kAblF, "E3K_GEMM_ABLATE", 0);
-      gb.flags[gb.n] = (a_vec(P) ? 1 : 0) | (b_mode(P) << 1) | (int)kAblF | (compact ? 64 : 0);
-      gb.aux[gb.n] = aux;
-      gb.tile_start[gb.n] = b.blocks;
-      b.blocks += (int)blocks;
-      ++gb.n;
-      if (P.chain > 0) b.chained = true;
-      for (int j = 1; j <= P.chain; ++j) {      // the followers: right behind their head, no tiles of their own
-        const e3k_gemm_problem& F = problems[i + j];
-        gb.p[gb.n] = F;
-        gb.p[gb.n].accumulate = P.accumulate;      // (the last link's descriptor runs the epilogue)
-        gb.p[gb.n].bias = P.bias;
-        gb.p[gb.n].act = P.act;
-        gb.p[gb.n].act_cst = P.act_cst;
-        gb.reps[gb.n] = rp;
-        gb.key_stride[gb.n] = rp > 1 ? key_stride[i + j] : 0;
-        gb.flags[gb.n] = (a_vec(F) ? 1 : 0) | (b_mode(F) << 1) | (int)kAblF;
-        gb.aux[gb.n] = 0;
-        gb.tile_start[gb.n] = b.blocks;
-        ++gb.n;
-      }
-      if (gb.n == e3k::GEMM_MAXP) {
-        const int rc = flush();
-        if (rc != E3K_OK) return rc;
-      }
-    }
-    const int rc = flush();
+  pl.small_grid = plain_tiles128 < kSmallGrid;
+  // longest-processing-time-first: workgroups are dispatched in blockIdx order, so the problems with the longest
+  // K loops go first and the short ones fill the tail of the launch
+  for (int i = 0; i < n_problems; ++i) pl.order[i] = i;
+  auto k_total = [&](int a) {
+    int kt = problems[a].K;
+    for (int j = 1; j <= problems[a].chain; ++j) kt += problems[a + j].K;
+    return kt;
+  };
+  std::stable_sort(pl.order, pl.order + n_problems, [&](int a, int b) { return k_total(a) > k_total(b); });
+  for (int k = 0; k < FWD_KINDS; ++k) {      // the dry run: every batch sized as it will launch
+    const int rc = fwd_batches(pl, k, false, st);
     if (rc != E3K_OK) return rc;
   }
+
+  // launch: the one-column problems in problem order, then the batches kind by kind
+  for (int i = 0; i < n_problems; ++i) {
+    const e3k_gemm_problem& P = problems[i];
+    const int64_t M = (int64_t)P.M1 * P.M2;
+    if (kind[i] == FWD_N1 && M > 0)
+      hipLaunchKernelGGL(e3k::gemm_n1_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, P.A, P.B, (int64_t)P.M1, P.M2, P.K, P.a_r1, P.a_r2,
+                         P.a_k, P.b_k, P.c_r1, P.c_r2, P.alpha, P.bias, P.accumulate, P.act, P.act_cst, P.C);
+  }
+  for (int k = 0; k < FWD_KINDS; ++k) (void)fwd_batches(pl, k, true, st);      // (passed the dry run: cannot fail)
   E3K_CHECK_LAUNCH();
   return E3K_OK;
 }
@@ -1652,23 +1433,13 @@ extern "C" int e3k_gemm(const e3k_gemm_problem* problems, int n_problems, void* 
 
 static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, const int* reps, const long long* key_stride,
                            void* stream) {
-  if (n_problems < 0 || (n_problems && !problems)) return E3K_ERR_INVALID;
+  if (n_problems < 0 || n_problems > MAX_CALL || (n_problems && !problems)) return E3K_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_problems; ++i) {
     const int rc = validate(problems[i], true);
     if (rc != E3K_OK) return rc;
   }
-  // Problems with 16-byte-loadable operands (plain and keyed; not the outer-product form): the pipelined kernel, ONE launch
-  // sized to one round of workgroups (three per CU), every workgroup the same number of rows -- splits proportional to a
-  // problem's rows.  A keyed problem's key groups partition its M1 rows: it counts once, every key gets the splits of the
-  // whole, and the workgroups past a key's last row exit.
-  E3K_KNOB_INT(kV2, "E3K_WGRAD2", 1);
-  E3K_KNOB_INT(kBlocks, "E3K_WGRAD2_BLOCKS", 0);
-  E3K_KNOB_INT(kMinChunks, "E3K_WGRAD2_MIN_CHUNKS", 2);
-  E3K_KNOB_INT(kAbl, "E3K_WGRAD2_ABLATE", 0);
-  E3K_KNOB_INT(kCompact, "E3K_KEYED_COMPACT", 1);
   bool taken[MAX_CALL] = {};
-  if (n_problems > MAX_CALL) return E3K_ERR_INVALID;
   // one output column, plain rows: a weighted column sum (wgrad_n1_kernel)
   for (int i = 0; i < n_problems; ++i) {
     const e3k_gemm_problem& P = problems[i];
@@ -1684,24 +1455,28 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
     return P.c_n == 1 && P.N % 4 == 0 && P.c_r1 % 4 == 0 && (P.M2 == 1 || P.c_r2 % 4 == 0) && aligned16(P.C);
   };
   auto tiles_of = [](const e3k_gemm_problem& P) { return ((P.K + (P.K > 64 ? 127 : 63)) / (P.K > 64 ? 128 : 64)) * ((P.N + 63) / 64); };
-  // launch(gb, blocks) for every batch of up to GEMM_MAXP eligible problems, `target` workgroups in total, `chunk` rows per
-  // pipeline stage; gathered: keyed / row-indexed problems are eligible too
-  auto equal_rows = [&](auto launch, double target, int chunk, bool gathered) -> int {
+  const int n_cu = cu_count();
+  // Problems with 16-byte-loadable operands (plain and keyed; not the outer-product form): the pipelined kernel, ONE launch
+  // sized to one round of workgroups (three per CU), every workgroup the same number of rows -- splits proportional to a
+  // problem's rows, at least kMinChunks chunks of W2R rows each.  A keyed problem's key groups partition its M1 rows: it counts
+  // once, every key gets the splits of the whole, and the workgroups past a key's last row exit.
+  {
+    constexpr int kMinChunks = 2;
+    const double target = 3.0 * n_cu;
     auto eligible = [&](int i) {
       const e3k_gemm_problem& P = problems[i];
-      if (!gathered && ((reps && reps[i] > 1) || P.row_index)) return false;
       return P.V == 0 && (int64_t)P.M1 * P.M2 > 0 && a_vec(P) && g_vec(P);
     };
     double total = 0;      // rows x tiles over the problems of this launch
     for (int i = 0; i < n_problems; ++i)
       if (eligible(i)) total += (double)problems[i].M1 * problems[i].M2 * tiles_of(problems[i]);
     Batcher b;
-    auto flush = [&]() -> int {
-      if (!b.blocks) { b.reset(); return E3K_OK; }
-      b.gb.tile_start[b.gb.n] = b.blocks;
-      const int rc = launch(b.gb, b.blocks);
+    auto flush = [&]() {
+      if (b.blocks) {
+        b.gb.tile_start[b.gb.n] = b.blocks;
+        launch_batch(e3k::gemm_wgrad2_kernel, b.gb, b.blocks, st);
+      }
       b.reset();
-      return rc;
     };
     for (int i = 0; i < n_problems && total > 0; ++i) {
       if (!eligible(i)) continue;
@@ -1710,69 +1485,46 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
       const int rp = reps && reps[i] > 1 ? reps[i] : 1;
       taken[i] = true;
       int64_t splits = (int64_t)(target * (double)M / total);      // rounded down: the launch stays within one round
-      const int64_t max_splits = (M + kMinChunks * chunk - 1) / (kMinChunks * chunk);
+      const int64_t max_splits = (M + kMinChunks * e3k::W2R - 1) / (kMinChunks * e3k::W2R);
       if (splits > max_splits) splits = max_splits;
       if (splits < 1) splits = 1;
       e3k::GemmBatch& gb = b.gb;
       gb.p[gb.n] = P;
       gb.reps[gb.n] = rp;
       gb.key_stride[gb.n] = rp > 1 ? key_stride[i] : 0;
-      gb.flags[gb.n] = 9 | (int)kAbl;
+      gb.flags[gb.n] = 9;
       gb.aux[gb.n] = (int)splits;
       gb.tile_start[gb.n] = b.blocks;
-      if (rp > 1 && kCompact && P.group_dev && P.row_index) {
+      if (rp > 1 && P.group_dev && P.row_index) {
         // the key groups partition the M rows: `splits` splits of the whole (+ one per key for the remainders) instead of `splits` per key
-        const int64_t rows = ((M + splits - 1) / splits + chunk - 1) / chunk * chunk;
+        const int64_t rows = ((M + splits - 1) / splits + e3k::W2R - 1) / e3k::W2R * e3k::W2R;
         gb.flags[gb.n] |= 64;
         gb.aux[gb.n] = (int)rows;
         b.blocks += tiles_of(P) * (int)((M + rows - 1) / rows + rp);
       } else {
         b.blocks += tiles_of(P) * (int)splits * rp;
       }
-      if (++gb.n == e3k::GEMM_MAXP) {
-        const int rc = flush();
-        if (rc != E3K_OK) return rc;
-      }
+      if (++gb.n == e3k::GEMM_MAXP) flush();
     }
-    return flush();
-  };
-  const int n_cu = cu_count();
-#ifdef E3K_DEBUG_KNOBS
-  if (kV2 == 2) {      // experiment: the LDS-direct ring kernel (plain problems only)
-    E3K_KNOB_INT(kBlocks3, "E3K_WGRAD3_BLOCKS", 0);
-    E3K_KNOB_INT(kCfg3, "E3K_WGRAD3_CFG", 0);
-    const int rc = equal_rows(
-        [&](const e3k::GemmBatch& gb, int blocks) {
-          return kCfg3 == 1   ? launch_batch(e3k::gemm_wgrad3_kernel<64, 3, 1>, gb, blocks, st)
-                 : kCfg3 == 2 ? launch_batch(e3k::gemm_wgrad3_kernel<32, 3, 2>, gb, blocks, st)
-                              : launch_batch(e3k::gemm_wgrad3_kernel<32, 4, 1>, gb, blocks, st);
-        },
-        kBlocks3 > 0 ? (double)kBlocks3 : (double)n_cu * (kCfg3 == 2 ? 2 : 1), kCfg3 == 1 ? 64 : 32, false);
-    if (rc != E3K_OK) return rc;
+    flush();
   }
-#endif
-  if (kV2 == 1) {
-    const int rc = equal_rows([&](const e3k::GemmBatch& gb, int blocks) { return launch_batch(e3k::gemm_wgrad2_kernel, gb, blocks, st); },
-                              kBlocks > 0 ? (double)kBlocks : 3.0 * n_cu, e3k::W2R, true);
-    if (rc != E3K_OK) return rc;
-  }
+  // the rest (outer-product form, operands that are not 16-byte-loadable) on gemm_wgrad_kernel: about kTarget workgroups per problem,
+  // kChunks chunks of WR rows per workgroup
+  constexpr int64_t kTarget = 1024;
+  constexpr int kChunks = 4;
   for (int mode = 0; mode < 4; ++mode) {  // (outer: x (x) attrs formed on the fly?, 128-wide output tile?)
     const bool outer = mode & 1;
     const int tn = (mode & 2) ? 2 : 1;
     Batcher b;
-    auto flush = [&]() -> int {
-      if (!b.blocks) {
-        b.reset();
-        return E3K_OK;
+    auto flush = [&]() {
+      if (b.blocks) {
+        b.gb.tile_start[b.gb.n] = b.blocks;
+        if (!outer) tn == 2 ? launch_batch(e3k::gemm_wgrad_kernel<false, 2>, b.gb, b.blocks, st)
+                            : launch_batch(e3k::gemm_wgrad_kernel<false, 1>, b.gb, b.blocks, st);
+        else tn == 2 ? launch_batch(e3k::gemm_wgrad_kernel<true, 2>, b.gb, b.blocks, st)
+                     : launch_batch(e3k::gemm_wgrad_kernel<true, 1>, b.gb, b.blocks, st);
       }
-      b.gb.tile_start[b.gb.n] = b.blocks;
-      int rc;
-      if (!outer) rc = tn == 2 ? launch_batch(e3k::gemm_wgrad_kernel<false, 2>, b.gb, b.blocks, st)
-                               : launch_batch(e3k::gemm_wgrad_kernel<false, 1>, b.gb, b.blocks, st);
-      else rc = tn == 2 ? launch_batch(e3k::gemm_wgrad_kernel<true, 2>, b.gb, b.blocks, st)
-                        : launch_batch(e3k::gemm_wgrad_kernel<true, 1>, b.gb, b.blocks, st);
       b.reset();
-      return rc;
     };
     for (int i = 0; i < n_problems; ++i) {
       const e3k_gemm_problem& P = problems[i];
@@ -1783,11 +1535,9 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
       if (M == 0) continue;
       const int rp = reps && reps[i] > 1 ? reps[i] : 1;
       int f = a_vec(P) ? 1 : 0;
-      if (P.c_n == 1 && P.N % 4 == 0 && P.c_r1 % 4 == 0 && (P.M2 == 1 || P.c_r2 % 4 == 0) && aligned16(P.C)) f |= 8;
+      if (g_vec(P)) f |= 8;
       const int wn = 64 * tn;
       const int tiles = ((P.K + e3k::WK - 1) / e3k::WK) * ((P.N + wn - 1) / wn);
-      E3K_KNOB_INT(kTarget, "E3K_WGRAD_TARGET", 1024);
-      E3K_KNOB_INT(kChunks, "E3K_WGRAD_CHUNKS", 4);
       int64_t splits = (kTarget + tiles - 1) / tiles;
       // rows per workgroup: kChunks chunks of WR rows -- unless that leaves most of the chip idle (round 6: the one-hot embeddings'
       // and the energy head's weight gradients are ONE tile over 4 600 rows: 18 workgroups walking four chunks each took 17-22 us
@@ -1805,25 +1555,13 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
       gb.aux[gb.n] = (int)splits;
       gb.tile_start[gb.n] = b.blocks;
       b.blocks += tiles * (int)splits * rp;
-      if (++gb.n == e3k::GEMM_MAXP) {
-        const int rc = flush();
-        if (rc != E3K_OK) return rc;
-      }
+      if (++gb.n == e3k::GEMM_MAXP) flush();
     }
-    const int rc = flush();
-    if (rc != E3K_OK) return rc;
+    flush();
   }
   E3K_CHECK_LAUNCH();
   return E3K_OK;
 }
-
-#ifdef E3K_STAMPS
-extern "C" int e3k_debug_stamps(unsigned long long* out, int n) {
-  if (hipDeviceSynchronize() != hipSuccess) return E3K_ERR_LAUNCH;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(e3k::e3k_dbg_buf), sizeof(unsigned long long) * n) != hipSuccess) return E3K_ERR_LAUNCH;
-  return E3K_OK;
-}
-#endif
 
 extern "C" int e3k_gemm_wgrad(const e3k_gemm_problem* problems, int n_problems, void* stream) {
   return gemm_wgrad_impl(problems, n_problems, nullptr, nullptr, stream);

@@ -96,18 +96,10 @@ struct Timed {   // records an event pair around one launch when the layer is be
 
 namespace {
 
-// timing-only ablation (tools/ablate.sh): E3K_ABLATE is a bitmask of launches to SKIP -- the results are wrong with any
-// bit set; it answers "what would the step gain if this kernel family were free" before anyone optimises it.
-// 1: keyed-weight kernels (fwd + bwd), 2: weight-gradient GEMMs, 4: gate fwd + bwd, 8: table interpolation fwd + bwd,
-// 16: radial MLP hidden chain + last layer (fwd + bwd), 32: tp_bwd_x, 64: input-gradient GEMMs
-// (debug build only -- see e3k_common.h: in the product library ABLATE is the constant 0 and every `ABLATE & bit` below folds away)
-E3K_KNOB_INT(ABLATE, "E3K_ABLATE", 0);
 // where the backward's side work runs (re-measured in round 4 after the GEMM kernels got shorter, tools/ab_bench.py, 2-3
-// interleaved rounds per variant): tp_bwd_w on the radial stream + the weight gradients beside tp_bwd_x (1 / 0) against
-// tp_bwd_w on the main stream + the weight gradients behind tp_bwd_x (0 / 1, round 3's choice): 256 molecules eager 4.815 vs
+// interleaved rounds per variant): tp_bwd_w on the radial stream + the weight gradients beside tp_bwd_x (kept) against
+// tp_bwd_w on the main stream + the weight gradients behind tp_bwd_x (round 3's choice): 256 molecules eager 4.815 vs
 // 4.846 ms, l_max 3 7.32 vs 7.51, config_diffusion_CA 9.12 vs 9.60, config_diffusion and the replayed steps within noise
-E3K_KNOB_INT(BWDW_SIDE, "E3K_BWDW_SIDE", 1);
-E3K_KNOB_INT(WGRAD_LATE, "E3K_WGRAD_LATE", 0);
 // the tensor-product kernels interpolate the path weights from the knot table themselves (no w[E, W])
 static inline bool in_kernel_table(const e3k_layer_desc& d, const e3k_layer_radial& r) { return r.use_table && r.in_kernel; }
 
@@ -182,22 +174,21 @@ int radial_fwd(const e3k_layer* L, const e3k_layer_radial& r, void* st) {
   const e3k_layer_desc& d = L->d;
   if (r.R == 0 || r.E == 0) return E3K_OK;
   if (r.have_rows) {      // the stack computed T (table) or w (per edge) already
-    if (r.use_table && !(ABLATE & 8) && !in_kernel_table(d, r)) {
+    if (r.use_table && !in_kernel_table(d, r)) {
       Timed t(L, E3K_PROF_RTABLE_FWD, st, r.R, r.E);
       E3K_TRY(e3k_rtable_interp_fwd(r.T, r.bin_perm, r.bin, r.bin_coef, r.E, r.knots, d.W, r.w, st));
     }
     return pack_table(L, r, st);
   }
   float* zs[4] = {r.z[0], r.z[1], r.z[2], r.z[3]};
-  if (!(ABLATE & 16))
-    E3K_TRY(e3k_mlp_hidden_fwd(r.radial, r.R, d.k0, d.h, d.n_hidden, r.w_hidden, d.alphas, d.act, d.cst, r.keep ? zs : nullptr, r.h, st));
-  if (!(ABLATE & 16)) {
+  E3K_TRY(e3k_mlp_hidden_fwd(r.radial, r.R, d.k0, d.h, d.n_hidden, r.w_hidden, d.alphas, d.act, d.cst, r.keep ? zs : nullptr, r.h, st));
+  {
     Timed t(L, E3K_PROF_RADIAL_LAST_FWD, st, r.R, r.E);
     Seg g;
     g.add(L, LAST_FWD, r.h, r.w_last, r.use_table ? r.T : r.w, r.R);
     E3K_TRY(g.run(0, st));
   }
-  if (r.use_table && !(ABLATE & 8) && !in_kernel_table(d, r)) {
+  if (r.use_table && !in_kernel_table(d, r)) {
     Timed t(L, E3K_PROF_RTABLE_FWD, st, r.R, r.E);
     E3K_TRY(e3k_rtable_interp_fwd(r.T, r.bin_perm, r.bin, r.bin_coef, r.E, r.knots, d.W, r.w, st));
   }
@@ -331,8 +322,7 @@ extern "C" int e3k_layer_fwd(const e3k_layer* L, const e3k_layer_fwd_args* a) {
       const int tot = a->n_keys * d.V;
       hipLaunchKernelGGL(e3k::gather_rows_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)side2, a->node_attrs, a->reps,
                          a->n_keys, d.V, a->a_rep);
-      if (!(ABLATE & 1))
-        E3K_TRY(e3k_keyed_weights_fwd(a->a_rep, a->w_sc, L->kw.data(), (int32_t)L->kw.size(), a->n_keys, d.V, d.ld_m, a->m, side2));
+      E3K_TRY(e3k_keyed_weights_fwd(a->a_rep, a->w_sc, L->kw.data(), (int32_t)L->kw.size(), a->n_keys, d.V, d.ld_m, a->m, side2));
     }
     if (!d.sc_out_covered && e3k::zero_fill(a->conv, sizeof(float) * a->N * d.d_conv, (hipStream_t)side2))
       return E3K_ERR_LAUNCH;
@@ -373,8 +363,7 @@ extern "C" int e3k_layer_fwd(const e3k_layer* L, const e3k_layer_fwd_args* a) {
     g.add(L, POST_FWD, a->mid, a->w_post, a->conv, a->N);
     E3K_TRY(g.run(0, main));
   }
-  if (!(ABLATE & 4))
-    E3K_TRY(e3k_gate_fwd(a->conv, a->N, d.d_conv, d.d_out, L->gate.data(), (int32_t)L->gate.size(), a->out_cf, a->y, main));
+  E3K_TRY(e3k_gate_fwd(a->conv, a->N, d.d_conv, d.d_out, L->gate.data(), (int32_t)L->gate.size(), a->out_cf, a->y, main));
   if (hipGetLastError() != hipSuccess) return E3K_ERR_LAUNCH;
   return E3K_OK;
 }
@@ -401,9 +390,8 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   if (!a->gy || !a->g_conv || !a->g_mid || !a->conv) return E3K_ERR_INVALID;
 
   // gate' -> gradient of the convolution output; both readers of it in one call
-  if (!(ABLATE & 4))
-    E3K_TRY(e3k_gate_bwd(a->conv, a->gy, nullptr, a->N, d.d_conv, d.d_out, L->gate.data(), (int32_t)L->gate.size(), a->out_cf,
-                         a->g_conv, main));
+  E3K_TRY(e3k_gate_bwd(a->conv, a->gy, nullptr, a->N, d.d_conv, d.d_out, L->gate.data(), (int32_t)L->gate.size(), a->out_cf,
+                       a->g_conv, main));
   if (!d.post_in_covered && e3k::zero_fill(a->g_mid, sizeof(float) * a->N * d.d_mid, (hipStream_t)main))
     return E3K_ERR_LAUNCH;
   {
@@ -415,16 +403,15 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       if (!covered && e3k::zero_fill(a->g_xcf, sizeof(float) * a->N * d.d_in, (hipStream_t)main)) return E3K_ERR_LAUNCH;
       if (has_sc) g.add_keyed(L, SC_DGRAD, a->g_conv, a->m, a->g_xcf, a->N, a->perm, a->bounds, a->n_keys);
     }
-    if (!(ABLATE & 64)) E3K_TRY(g.run(0, main));
+    E3K_TRY(g.run(0, main));
   }
   // weight gradients that only need g_conv: off the critical path (forked) or together with linear_1's below
   auto keyed_weight_grads = [&]() -> int {
     E3K_TRY(edge(L, 1, side3, side2));
     if (a->have_m) return E3K_OK;
     if (a->need_attrs && e3k::zero_fill(a->ga, sizeof(float) * a->n_keys * d.V, (hipStream_t)side2)) return E3K_ERR_LAUNCH;
-    if (!(ABLATE & 1))
-      E3K_TRY(e3k_keyed_weights_bwd(a->a_rep, a->w_sc, a->gm, L->kw.data(), (int32_t)L->kw.size(), a->n_keys, d.V, d.ld_m,
-                                    a->need_attrs ? a->ga : nullptr, a->gb_sc, a->acc_sc, a->kw_ws, side2));
+    E3K_TRY(e3k_keyed_weights_bwd(a->a_rep, a->w_sc, a->gm, L->kw.data(), (int32_t)L->kw.size(), a->n_keys, d.V, d.ld_m,
+                                  a->need_attrs ? a->ga : nullptr, a->gb_sc, a->acc_sc, a->kw_ws, side2));
     if (a->need_attrs) {
       if (e3k::zero_fill(a->g_attrs, sizeof(float) * a->N * d.V, (hipStream_t)side2)) return E3K_ERR_LAUNCH;
       const int tot = a->n_keys * d.V;
@@ -442,15 +429,12 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       g.add_keyed(L, SC_WGRAD, a->x_cf, a->gm, const_cast<float*>(a->g_conv), a->N, a->perm, a->bounds, a->n_keys);
     }
     if (with_lin1 && need_lin1) g.add(L, LIN1_WGRAD, a->x_cf, a->gb_lin1, a->g_x1, a->N);
-    if (ABLATE & 2) return E3K_OK;
     return g.run(1, st);
   };
-  // WGRAD_LATE: the weight-gradient GEMMs start BEHIND tp_bwd_x (all three Linears in one call) instead of beside it: the
-  // gather-bound tp_bwd_x then runs alone, the MFMA-bound weight gradients beside the HBM-bound tp_bwd_w (256 molecules
-  // 5.34 -> 5.30 ms, 192: 4.51 -> 4.47, one launch less per layer in round 3; with round 4's kernels the early start wins
-  // again -- see the knobs' comment at the top -- and is the default)
-  const bool wgrad_late = WGRAD_LATE && side3 != main && need_x1;
-  if (side3 != main && (need_post || want_sc) && !wgrad_late) {
+  // the weight gradients that need only g_conv start BESIDE tp_bwd_x.  (Starting all three Linears' behind it, in one call, won in
+  // round 3 -- 256 molecules 5.34 -> 5.30 ms, 192: 4.51 -> 4.47 --; with round 4's kernels the early start wins again, see the
+  // stream placement note at the top.)
+  if (side3 != main && (need_post || want_sc)) {
     E3K_TRY(edge(L, 0, main, side3));
     E3K_TRY(weight_grads(true, false, side3));
     if (want_sc) E3K_TRY(keyed_weight_grads());
@@ -459,19 +443,18 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   // packed table + both gradients wanted: ONE walk of the source CSR forms g_x1 and g_w [E, W] (csrc/e3k_tp.hip, MODE 5): the
   // weight-gradient pass re-gathered sh, x[src] and g_mid[dst] of every edge for a dot product with sums the input gradient
   // already holds (layer 3 of config_energy at 256 molecules: 213 + 104 us -> 258 us isolated; 217 + 169 -> 261 in the replayed step)
-  const bool fused_xw = a->fuse_xw && need_x1 && in_kernel_table(d, r) && r.P && need_radial_side && a->E > 0 && a->g_w && a->x1 && !(ABLATE & 32);
+  const bool fused_xw = a->fuse_xw && need_x1 && in_kernel_table(d, r) && r.P && need_radial_side && a->E > 0 && a->g_w && a->x1;
   // ... the same for layers whose weights are streamed from w [E, W] (per-edge radial MLP, 32-channel plans), where the replayed /
   // one-stream step gains what the packed layers gain; with the backward forked over streams the separate weight-gradient pass
   // already runs beside the main stream's GEMMs, and stays
   const bool fused_xw_s = a->fuse_xw && !fused_xw && need_x1 && !in_kernel_table(d, r) && need_radial_side && a->E > 0 && a->g_w && a->x1 &&
-                          r.w && side == main && !(ABLATE & 32);
+                          r.w && side == main;
   if (need_x1) {
     if (!a->g_x1) return E3K_ERR_INVALID;
     if (!d.tp_bwd_x_overwrites && e3k::zero_fill(a->g_x1, sizeof(float) * a->N * d.d_x1, (hipStream_t)main))
       return E3K_ERR_LAUNCH;
     Timed t(L, E3K_PROF_TP_BWD_X, main, a->N, a->E);
-    if (ABLATE & 32) {
-    } else if (fused_xw) {      // ... and the per-edge weight gradient in the same walk: no tp_bwd_w pass below
+    if (fused_xw) {      // ... and the per-edge weight gradient in the same walk: no tp_bwd_w pass below
       E3K_TRY(e3k_tp_bwd_xw_ptable(d.tp, a->x1, r.P, r.erec_src, a->g_mid, a->src_ptr, a->N, a->E, a->g_x1, a->g_w, main));
     } else if (fused_xw_s) {
       E3K_TRY(e3k_tp_bwd_xw(d.tp, a->x1, a->sh, r.w, a->g_mid, a->dst, a->src_ptr, a->src_perm, a->N, a->E, a->g_x1, a->g_w, main));
@@ -483,11 +466,6 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       E3K_TRY(e3k_tp_bwd_x(d.tp, a->sh, r.w, a->g_mid, a->dst, a->src_ptr, a->src_perm, a->N, a->E, a->g_x1, main));
     }
   }
-  if (wgrad_late && (need_post || want_sc || need_lin1)) {
-    E3K_TRY(edge(L, 0, main, side3));
-    E3K_TRY(weight_grads(true, true, side3));
-    if (want_sc) E3K_TRY(keyed_weight_grads());
-  }
   if (need_radial_side && a->E > 0) {
     if (!a->g_w) return E3K_ERR_INVALID;
     const float* g_rows = a->g_w;                 // gradient of the MLP's output rows: per edge, or per knot behind the table
@@ -495,7 +473,7 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
     // the weight-gradient pass: on the radial stream BEHIND tp_bwd_x (both are memory streams: side by side they only
     // stretch each other), where it runs beside the GEMMs that follow on the main stream (this layer's linear_1 dgrad, the
     // previous layer's gate' and post-TP dgrad) -- nothing on the main stream waits for it
-    void* wst = (BWDW_SIDE && side != main && !fused_xw) ? side : main;
+    void* wst = (side != main && !fused_xw) ? side : main;
     if (wst != main) E3K_TRY(edge(L, 2, main, side));
     if (!fused_xw && !fused_xw_s) {
       Timed t(L, E3K_PROF_TP_BWD_W, wst, a->N, a->E);
@@ -504,18 +482,17 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
     if (wst == main) E3K_TRY(edge(L, 2, main, side));
     if (r.use_table) {
       Timed t(L, E3K_PROF_RTABLE_BWD, side, r.R, r.E);
-      if (!(ABLATE & 8))
-        E3K_TRY(e3k_rtable_interp_bwd(a->g_w, r.bin_coef, nullptr, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, d.W, a->table_ws,
-                                      a->g_T, 0, side));
+      E3K_TRY(e3k_rtable_interp_bwd(a->g_w, r.bin_coef, nullptr, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, d.W, a->table_ws,
+                                    a->g_T, 0, side));
       g_rows = a->g_T;
     }
     }
-    if (need_last && !(ABLATE & 16) && !r.have_rows) {
+    if (need_last && !r.have_rows) {
       Seg g;
       g.add(L, LAST_WGRAD, r.h, a->gb_last, const_cast<float*>(g_rows), r.R);
       E3K_TRY(g.run(1, side));
     }
-    if ((need_hidden || a->need_radial) && !(ABLATE & 16) && !r.have_rows) {
+    if ((need_hidden || a->need_radial) && !r.have_rows) {
       Seg g;
       g.add(L, LAST_DGRAD, g_rows, r.w_last, a->g_h, r.R);
       E3K_TRY(g.run(0, side));
@@ -529,14 +506,13 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   if (a->need_x) {
     Seg g;
     g.add(L, has_sc ? LIN1_DGRAD_ACC : LIN1_DGRAD, a->g_x1, a->w_lin1, a->g_xcf, a->N);
-    if (!(ABLATE & 64)) E3K_TRY(g.run(0, main));
+    E3K_TRY(g.run(0, main));
     if (!a->in_cf && !L->in_blocks.empty()) {
       if (!a->g_x) return E3K_ERR_INVALID;
       E3K_TRY(e3k_relayout(a->g_xcf, a->N, d.d_in, L->in_blocks.data(), (int32_t)L->in_blocks.size(), 0, a->g_x, main));
     }
   }
-  if (wgrad_late) {
-  } else if (side3 != main) {
+  if (side3 != main) {
     if (need_lin1) {
       E3K_TRY(edge(L, 3, main, side3));
       E3K_TRY(weight_grads(false, true, side3));
@@ -570,31 +546,29 @@ extern "C" int e3k_radial_stack_fwd(const e3k_layer* const* layers, const e3k_la
     nets[i] = nt;
   }
   if (rads[0].R == 0) return E3K_OK;
-  if (!(ABLATE & 16)) {
-    E3K_TRY(e3k_mlp_hidden_fwd_multi(nets, n, rads[0].radial, rads[0].R, d0.k0, d0.h, d0.n_hidden, d0.alphas, d0.act, d0.cst, stream));
-    for (int base = 0; base < n; base += SEG_MAX) {      // last layers: one e3k_gemm_multi call per SEG_MAX layers
-      Seg g;
-      for (int i = base; i < n && i < base + SEG_MAX; ++i) {
-        const e3k_layer_radial& r = rads[i];
-        g.add(layers[i], LAST_FWD, r.h, r.w_last, r.use_table ? r.T : r.w, r.R);
-      }
-      Timed t(layers[base], E3K_PROF_RADIAL_LAST_FWD, stream, rads[0].R, rads[0].E);
-      E3K_TRY(g.run(0, stream));
+  E3K_TRY(e3k_mlp_hidden_fwd_multi(nets, n, rads[0].radial, rads[0].R, d0.k0, d0.h, d0.n_hidden, d0.alphas, d0.act, d0.cst, stream));
+  for (int base = 0; base < n; base += SEG_MAX) {      // last layers: one e3k_gemm_multi call per SEG_MAX layers
+    Seg g;
+    for (int i = base; i < n && i < base + SEG_MAX; ++i) {
+      const e3k_layer_radial& r = rads[i];
+      g.add(layers[i], LAST_FWD, r.h, r.w_last, r.use_table ? r.T : r.w, r.R);
     }
-    // the tables the tensor-product kernels will read packed (rads with in_kernel and P): all of them in one launch, behind the
-    // last layers (round 6: five launches of 5-8 us in front of the five layers' forward otherwise)
-    const float* tabs[16];
-    void* packs[16];
-    int32_t widths[16];
-    int np = 0;
-    for (int i = 0; i < n; ++i)
-      if (rads[i].use_table && rads[i].in_kernel && rads[i].P && rads[i].T) {
-        tabs[np] = rads[i].T;
-        packs[np] = rads[i].P;
-        widths[np++] = layers[i]->d.W;
-      }
-    if (np) E3K_TRY(e3k_rtable_pack_multi(tabs, (int32_t)(rads[0].R - 1), widths, packs, np, stream));
+    Timed t(layers[base], E3K_PROF_RADIAL_LAST_FWD, stream, rads[0].R, rads[0].E);
+    E3K_TRY(g.run(0, stream));
   }
+  // the tables the tensor-product kernels will read packed (rads with in_kernel and P): all of them in one launch, behind the
+  // last layers (round 6: five launches of 5-8 us in front of the five layers' forward otherwise)
+  const float* tabs[16];
+  void* packs[16];
+  int32_t widths[16];
+  int np = 0;
+  for (int i = 0; i < n; ++i)
+    if (rads[i].use_table && rads[i].in_kernel && rads[i].P && rads[i].T) {
+      tabs[np] = rads[i].T;
+      packs[np] = rads[i].P;
+      widths[np++] = layers[i]->d.W;
+    }
+  if (np) E3K_TRY(e3k_rtable_pack_multi(tabs, (int32_t)(rads[0].R - 1), widths, packs, np, stream));
   if (hipGetLastError() != hipSuccess) return E3K_ERR_LAUNCH;
   return E3K_OK;
 }
@@ -632,7 +606,6 @@ extern "C" int e3k_radial_stack_bwd(const e3k_layer* const* layers, const e3k_ra
   const e3k_layer_desc& d0 = layers[0]->d;
   const int64_t R = items[0].rad.R;
   if (R == 0) return E3K_OK;
-  if (ABLATE & 16) return E3K_OK;
   e3k_mlp_net nets[16];
   int n_nets = 0;
   for (int base = 0; base < n; base += SEG_MAX) {        // weight gradients of the last layers
@@ -706,7 +679,7 @@ extern "C" int e3k_kw_stack_fwd(const e3k_layer* const* layers, const e3k_kw_sta
   const int tot = n_keys * V;
   hipLaunchKernelGGL(e3k::gather_rows_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, node_attrs, reps, n_keys, V,
                      a_rep);
-  if (!(ABLATE & 1)) E3K_TRY(e3k_keyed_weights_fwd_multi(mi, n, a_rep, n_keys, stream));
+  E3K_TRY(e3k_keyed_weights_fwd_multi(mi, n, a_rep, n_keys, stream));
   if (hipGetLastError() != hipSuccess) return E3K_ERR_LAUNCH;
   return E3K_OK;
 }
@@ -739,7 +712,7 @@ extern "C" int e3k_kw_stack_bwd(const e3k_layer* const* layers, const e3k_kw_sta
   // (ga directly in front of g_attrs in one allocation -- what the Python side hands over --: ONE fill for both)
   const bool together = ga && g_attrs == ga + (int64_t)n_keys * V;
   if (ga && e3k::zero_fill(ga, sizeof(float) * ((int64_t)n_keys * V + (together ? N * V : 0)), st)) return E3K_ERR_LAUNCH;
-  if (!(ABLATE & 1)) E3K_TRY(e3k_keyed_weights_bwd_multi(mi, n, a_rep, n_keys, ga, workspace, stream));
+  E3K_TRY(e3k_keyed_weights_bwd_multi(mi, n, a_rep, n_keys, ga, workspace, stream));
   if (g_attrs) {
     if (!together && e3k::zero_fill(g_attrs, sizeof(float) * N * V, st)) return E3K_ERR_LAUNCH;
     const int tot = n_keys * V;

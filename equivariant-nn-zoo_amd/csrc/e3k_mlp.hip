@@ -3,7 +3,7 @@
 //
 // Replaces (paths relative to /root/reference) the hidden layers of
 //   e3nn.nn.FullyConnectedNet([n_radial, H, ..., H, weight_numel], act)   e3_layers/nn/message_passing.py:74-79,93
-// (the last, linear layer H -> weight_numel stays a GEMM: e3k_gemm small-K kernel).  Unfused, every hidden layer is
+// (the last, linear layer H -> weight_numel stays a GEMM: e3k_gemm).  Unfused, every hidden layer is
 // a [E,64]x[64,64] GEMM + an activation pass forward and dgrad + wgrad + activation-backward passes backward:
 // ~20 launches per convolution that each stream [E,H] through HBM twice.  Here a 64-edge tile stays in LDS through
 // the whole chain; only the pre-activations z_l (needed by the backward) and the final h touch HBM, once.
@@ -289,8 +289,8 @@ int launch_fwd(const e3k::MlpBatch& mb, int64_t E, hipStream_t st) {
 int launch_bwd(const e3k::MlpBatch& mb, int64_t E, int n_layers, hipStream_t st) {
   const int64_t tiles = (E + e3k::MLP_BM - 1) / e3k::MLP_BM;
   if (tiles > 0x7fffffffLL) return E3K_ERR_INVALID;
-  E3K_KNOB_INT(max_blocks, "E3K_MLP_BLOCKS", 768);
-  int64_t blocks = max_blocks / mb.n;      // persistent: two to three workgroups per CU share the weight-gradient atomics
+  constexpr int kMaxBlocks = 768;
+  int64_t blocks = kMaxBlocks / mb.n;      // persistent: two to three workgroups per CU share the weight-gradient atomics
   if (blocks < 1) blocks = 1;
   if (tiles < blocks) blocks = tiles;
   const dim3 grid((unsigned)blocks, (unsigned)mb.n);

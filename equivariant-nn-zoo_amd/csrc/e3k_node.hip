@@ -1024,14 +1024,14 @@ extern "C" int e3k_gate_bwd(const float* x, const float* g_y, const float* g_y2,
   if (rows == 0) return E3K_OK;
   if (!x || !g_y || !g_x) return E3K_ERR_INVALID;
   // rows per wave of the float4 form (isolated, 4 608 rows: scalar form 30.9 us; 1 / 2 / 4 / 8 rows per wave 26.4 / 23.2 / 25.3 / 31.8)
-  E3K_KNOB_INT(gate4, "E3K_GATE4", 2);
+  constexpr int kGateRows = 2;
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  bool vec = gate4 > 0 && out_cf && in_dim % 4 == 0 && out_dim % 4 == 0 && al16(x) && al16(g_y) && al16(g_x) && (!g_y2 || al16(g_y2));
+  bool vec = out_cf && in_dim % 4 == 0 && out_dim % 4 == 0 && al16(x) && al16(g_y) && al16(g_x) && (!g_y2 || al16(g_y2));
   for (int k = 0; k < n_segs && vec; ++k)
     vec = segs[k].in_off % 4 == 0 && segs[k].out_off % 4 == 0 && segs[k].mul % 4 == 0 && (segs[k].kind == 0 || segs[k].gate_off % 4 == 0);
   if (vec) {
     const int gx = (in_dim / 4 + 63) / 64;
-    int64_t gy = (rows + 4 * gate4 - 1) / (4 * gate4);      // gate4 rows per wave
+    int64_t gy = (rows + 4 * kGateRows - 1) / (4 * kGateRows);      // kGateRows rows per wave
     if (gy < 1) gy = 1;
     hipLaunchKernelGGL(e3k::gate_bwd4_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, x, g_y, g_y2, rows,
                        in_dim, out_dim, ga, g_x);

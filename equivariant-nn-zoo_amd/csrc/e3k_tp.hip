@@ -113,10 +113,6 @@ __device__ __forceinline__ float knot_mix(float c0, float c1, float c2, float c3
   return fmaf(c3, vd, fmaf(c2, vc, fmaf(c1, vb, c0 * va)));
 }
 
-#ifdef E3K_DEBUG_KNOBS
-static int g_tp_ablate_host = 0;      // timing-only ablation mask of the packed-table forward (tools/tp_table_bench.py --ablate): 1 no table
-                                      // loads, 2 no x row loads, 4 no CG arithmetic -- wrong results by design; travels in TpArgs.ablate
-#endif
 // MODE 4 (packed table, round 5): the same cubic from 12 bytes per (knot, weight) in ONE table row -- {d0, d1: f32; d2 * 2^10,
 // d3 * 2^16: f16}, the Taylor coefficients about the middle of the knot interval (e3k_rtable_pack; a row = its W (d0, d1) pairs, then
 // its W f16 pairs) -- one dwordx2 + one dword load per slot instead of four dword loads out of four rows: 23 instead of 31 KB of
@@ -166,14 +162,7 @@ __device__ __forceinline__ KnotPacked knot_packed_rec(const TpArgs& a, const Edg
   return k;
 }
 // slot at weight offset woff4 (bytes of a 4-byte column) of the row, lane channel u4 = 4 u; pk_base = 8 W (bytes)
-__device__ __forceinline__ PackedRec buf_ld_rec(__amdgpu_buffer_rsrc_t r, int u4, int woff4, int pk_base, int ablate = 0) {
-#ifdef E3K_DEBUG_KNOBS
-  if (ablate & 1) {      // timing only: no table loads
-    PackedRec p;
-    p.d0 = __int_as_float(u4 + woff4); p.d1 = 1.f; p.pk = (unsigned)pk_base;
-    return p;
-  }
-#endif
+__device__ __forceinline__ PackedRec buf_ld_rec(__amdgpu_buffer_rsrc_t r, int u4, int woff4, int pk_base) {
   const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, u4 * 2, woff4 * 2, 0);
   PackedRec p;
   p.d0 = __uint_as_float(v[0]);
@@ -227,12 +216,6 @@ __device__ __forceinline__ void tp_fwd_body_full(const TpArgs& a, const e3k_tp_g
     if constexpr (JVP) load_y_full(y2, a.sh2 + (int64_t)e * a.d_sh);
     const __amdgpu_buffer_rsrc_t rx = row_rsrc(a.x + (int64_t)s * a.d_in, row_x);
     float xc[D1], x2c[JVP ? D1 : 1], wc[S::NQ], w2[JVP ? S::NQ : 1];
-#ifdef E3K_DEBUG_KNOBS
-    if (PACKED && (a.ablate & 2)) {
-#pragma unroll
-      for (int i = 0; i < D1; ++i) xc[i] = __int_as_float(s + i);
-    } else
-#endif
 #pragma unroll
     for (int i = 0; i < D1; ++i) xc[i] = buf_ld(rx, u4, xoff4 + i * mul4);
     if constexpr (JVP) {
@@ -245,7 +228,7 @@ __device__ __forceinline__ void tp_fwd_body_full(const TpArgs& a, const e3k_tp_g
       PackedRec rec[S::NQ];
       slot_for_part<S, L1, L3MAX, PART>([&](auto qc) {
         constexpr int Q = decltype(qc)::value;
-        rec[Q] = buf_ld_rec(kp.r, u4, woff4[Q], row_w * 2, a.ablate);
+        rec[Q] = buf_ld_rec(kp.r, u4, woff4[Q], row_w * 2);
       });
       slot_for_part<S, L1, L3MAX, PART>([&](auto qc) {
         constexpr int Q = decltype(qc)::value;
@@ -294,12 +277,6 @@ __device__ __forceinline__ void tp_fwd_body_full(const TpArgs& a, const e3k_tp_g
       constexpr int L2 = S::L2[Q], L3 = S::L3[Q], OFF = S::OFF[Q];
       const float wv = wc[Q] * cf[Q];
       float tt[2 * L3 + 1];
-#ifdef E3K_DEBUG_KNOBS
-      if (PACKED && (a.ablate & 4)) {
-#pragma unroll
-        for (int k = 0; k < 2 * L3 + 1; ++k) tt[k] = xc[k % D1] + yc.y0[0];
-      } else
-#endif
       CG<L1, L2, L3>::xy(xc, yref<L2>(yc), tt);
       if constexpr (JVP) {
         // d/d(eps) [ w(r + eps s2) * xy(x + eps x2, y + eps y2) ] at eps = 0
@@ -758,9 +735,6 @@ __device__ __forceinline__ void tp_bwd_x_body_full(const TpArgs& a, const e3k_tp
       nxt = load_rec(a.erec, t + 1 < end ? t + 1 : t);
       e = cur.e;
       d = cur.nbr;
-#ifdef E3K_DEBUG_KNOBS
-      if (a.ablate & 8) d = node;      // timing only: every edge reads the walker's own gradient rows (an L1 hit) instead of g[dst]
-#endif
       rec_y(yc, cur);
     } else {
       e = uniform(a.perm[t]);
@@ -792,7 +766,7 @@ __device__ __forceinline__ void tp_bwd_x_body_full(const TpArgs& a, const e3k_tp
 #pragma unroll
         for (int k = 0; k < 2 * L3 + 1; ++k)
           gn[OFF + k] = buf_ld(rg, u4, goff4[Q] + k * gstr4[Q]);
-        rec[Q] = buf_ld_rec(kp.r, u4, woff4[Q], row_w * 2, a.ablate);
+        rec[Q] = buf_ld_rec(kp.r, u4, woff4[Q], row_w * 2);
       });
       __builtin_amdgcn_sched_barrier(0);
       slot_for_part<S, L1, L3MAX, PART>([&](auto qc) {
@@ -1101,11 +1075,7 @@ __device__ __forceinline__ void tp_bwd_w_dual_body(const TpArgs& a, const e3k_tp
 // form's second-order (JVP / DUAL) variant -- FULL plans only for 1 and 2
 // (packed form, l_max <= 2 plans: 67 VGPRs as the compiler first allocates them -- one step over the 64 of eight waves per SIMD; asked
 //  for eight, it fits without spilling)
-#ifdef E3K_DEBUG_KNOBS
-#define E3K_TP_FWD_WAVES(MODE, MAXL, L3MAX) 1      // (the debug build's ablation branches do not fit 64 registers)
-#else
 #define E3K_TP_FWD_WAVES(MODE, MAXL, L3MAX) ((MODE == 4 && MAXL <= 2 && L3MAX <= 2) ? 8 : 1)
-#endif
 template <int MAXL, int L3MAX, bool SPLIT, bool FULL, int MODE = 0>
 __global__ __launch_bounds__(256, E3K_TP_FWD_WAVES(MODE, MAXL, L3MAX)) void tp_fwd_kernel(TpArgs a, const e3k_tp_group* __restrict__ groups,
                                                      const int2* __restrict__ gc, int n_gc) {
@@ -1120,14 +1090,7 @@ __global__ __launch_bounds__(256) void tp_bwd_w_kernel(TpArgs a, const e3k_tp_gr
   E3K_TP_DISPATCH(tp_bwd_w_body, WITH_SH, L3MAX)
 }
 
-#ifndef E3K_TP_XW_WAVES
-#define E3K_TP_XW_WAVES 8
-#endif
-#ifdef E3K_DEBUG_KNOBS
-#define E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX) 1
-#else
-#define E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX) ((MODE == 5 && MAXL <= 2 && L3MAX <= 2) ? E3K_TP_XW_WAVES : 1)
-#endif
+#define E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX) ((MODE == 5 && MAXL <= 2 && L3MAX <= 2) ? 8 : 1)
 template <int MAXL, int L3MAX, bool SPLIT, bool FULL, int MODE = 0>
 __global__ __launch_bounds__(256, E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX)) void tp_bwd_x_kernel(TpArgs a, const e3k_tp_group* __restrict__ groups,
                                                        const int2* __restrict__ gc, int n_gc) {
@@ -1284,8 +1247,8 @@ extern "C" int e3k_tp_plan_create(const e3k_tp_group* groups, int32_t n_groups, 
   }
   {
     // work list: (group, 64-channel chunk | part << 16).  A group whose enabled slots hold more than
-    // E3K_TP_SPLIT_ACC accumulators (l_max = 3 models) is walked by two waves, one per slot part.
-    E3K_KNOB_INT(split_acc, "E3K_TP_SPLIT_ACC", 24);
+    // kSplitAcc accumulators (l_max = 3 models) is walked by two waves, one per slot part.
+    constexpr int kSplitAcc = 24;
     int64_t cap = 0;
     for (int i = 0; i < n_groups; ++i) cap += 2 * ((groups[i].mul + 63) / 64);
     if (cap > (1 << 20)) {   // the work item index packs (chunk | part << 16): far beyond any irreps this path serves
@@ -1298,7 +1261,7 @@ extern "C" int e3k_tp_plan_create(const e3k_tp_group* groups, int32_t n_groups, 
     for (int i = 0; i < n_groups; ++i) {
       int n_acc = 0, lo = 0, hi = 0;
       plan_slot_counts(groups[i], n_acc, lo, hi);
-      if (groups[i].l1 >= 1 && n_acc > split_acc) any = true;
+      if (groups[i].l1 >= 1 && n_acc > kSplitAcc) any = true;
       if ((groups[i].mul + 63) / 64 > 0xffff) {
         delete[] host;
         e3k_tp_plan_destroy(p);
@@ -1355,13 +1318,6 @@ extern "C" int e3k_tp_plan_create(const e3k_tp_group* groups, int32_t n_groups, 
   return E3K_OK;
 }
 
-#ifdef E3K_DEBUG_KNOBS
-extern "C" int e3k_dbg_tp_ablate(int mask) {
-  e3k::g_tp_ablate_host = mask;
-  return 0;
-}
-#endif
-
 extern "C" int e3k_tp_bwd_x_overwrites(const e3k_tp_plan* p) {
   // every element of g_x is stored exactly once: one group per input block, all of [0, d_in) covered, single-wave groups
   return (p && !p->split && !p->x_shared && p->x_cols == p->d_in) ? 1 : 0;
@@ -1387,11 +1343,7 @@ int launch_all(TpKind kind, const e3k::TpArgs& a, const e3k_tp_plan* p, int64_t 
   int64_t blocks = (args.n_items + 3) / 4;
   // (packed table, layer 3 of config_energy at 256 molecules, isolated: forward 163 -> 151 us, input gradient 221 -> 215; inside the
   //  step 124 -> 118 and 194 -> 187; the four-row form, whose 3.9 MB table stays in L2 either way, gains nothing: 187 / 188 us)
-  E3K_KNOB_INT(tp_order, "E3K_TP_ORDER", 1);
-  args.order = (tp_order && (kind == TP_FWD_PACKED || kind == TP_BWD_X_PACKED || kind == TP_BWD_XW_PACKED) && N >= 64) ? 1 : 0;
-#ifdef E3K_DEBUG_KNOBS
-  args.ablate = e3k::g_tp_ablate_host;
-#endif
+  args.order = ((kind == TP_FWD_PACKED || kind == TP_BWD_X_PACKED || kind == TP_BWD_XW_PACKED) && N >= 64) ? 1 : 0;
   if (args.order) blocks = 8 * ((((N + 7) / 8) * n_gc + 3) / 4);      // eight equal sub-grids, one per XCD (blocks b, b + 8, .. share one)
   if (blocks > 0x7fffffffLL) return E3K_ERR_INVALID;
   dim3 grid((unsigned)blocks), block(256);

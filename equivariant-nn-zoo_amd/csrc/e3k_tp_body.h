@@ -57,7 +57,8 @@ struct TpArgs {
   const int32_t* erec; // FULL kernels, optional: the walk's edge records [E, 16] (e3k_edge_records) -- perm, nbr, bin, coef, sh are then unused
   int32_t d_in, d_sh, W, d_mid;
   int32_t x_shared;    // bwd_x: some input block is read by more than one group => accumulate g_x with atomics
-  int32_t ablate;      // debug build only: timing-only ablation mask (0 in the product library)
+  int32_t _pad;        // (holds order and e_store at their offsets: next to x_shared, order is fetched with it in one load and the
+                       //  compiler schedules the tensor-product kernels differently)
   int32_t order;       // work order of the launch (E3K_TP_PROLOGUE): 0 node-major, 1 group-major inside an XCD's node slice
   int32_t e_store;     // edge gradients (g_sh, g_r): 0 = float atomics into [E, .]; 1 = every work item STORES its share into its own
                        // slice of [n_gc, E, .] (g_sh / g_r point at the slices' base, e_edges = E): summed in a fixed order afterwards

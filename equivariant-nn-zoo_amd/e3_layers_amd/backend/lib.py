@@ -17,7 +17,7 @@ from .tuning import knob as _knob
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc"))
-LIB_PATH = _knob("E3K_LIB") or os.path.join(CSRC_DIR, "libe3k.so")  # E3K_LIB: debug builds only
+LIB_PATH = _knob("E3K_LIB") or os.path.join(CSRC_DIR, "libe3k.so")  # E3K_LIB: another build, for A/B runs
 
 TP_MAXQ = 8
 

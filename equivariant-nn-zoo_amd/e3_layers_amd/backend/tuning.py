@@ -2,8 +2,8 @@
 
 VERDICT r3 counted 46 ``E3K_*`` environment reads scattered over eight modules and the C library.  Now:
 
-* the C library reads NO environment variable in the product build (``csrc/e3k_common.h``: compile-time constants; ``make dbg``
-  builds ``libe3k_dbg.so`` with the experiment knobs and the timing-only ablation mask, loaded only through ``E3K_LIB``);
+* the C library reads NO environment variable: its tuning constants are compile-time constants in ``csrc/``, and there is one
+  build of it (``E3K_LIB`` loads another build instead, for A/B runs of two of them);
 * the Python modules ask ``knob(name)`` -- this module is the only one that touches ``os.environ``; ``table()`` lists every knob
   with its value, default and meaning (``python -m e3_layers_amd.backend.tuning``).  Modules keep their values as module-level
   constants (tests monkeypatch those), so the table is what the PROCESS started with.
@@ -65,7 +65,7 @@ KNOBS: Dict[str, Tuple[object, str, str]] = {
     "E3K_RADIAL_TABLE_COL_FLOOR": (2.0 ** -7, "accuracy", "the guard's bound is relative to each weight column's own scale, floored at this fraction of the table's largest entry"),
     # ---- debug ----
     "E3K_HOST_TIMING": (0, "debug", "host seconds inside the layer functions (tools/host_split.py)"),
-    "E3K_LIB": ("", "debug", "path of the shared library to load instead of csrc/libe3k.so (make dbg: libe3k_dbg.so)"),
+    "E3K_LIB": ("", "debug", "path of the shared library to load instead of csrc/libe3k.so (A/B runs of two builds)"),
 }
 
 _SEEN: Dict[str, object] = {}

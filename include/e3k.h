@@ -122,7 +122,10 @@ int e3k_gemm_multi(const e3k_gemm_segment* segments, int32_t n_segments, int32_t
 /* Grouped launch over key groups: every template problem is expanded into n_keys problems, one per
  * key t, with  B += t * b_key_stride,  row_index = perm,  group_dev = groups_dev + 2*t  and M1 kept as the
  * (host-known) upper bound of the group size.  wgrad != 0 runs e3k_gemm_wgrad semantics (B accumulated).
- * Used by the keyed self-connection: rows = nodes sorted by the key of their attribute row. */
+ * Used by the keyed self-connection: rows = nodes sorted by the key of their attribute row.
+ * The key groups must PARTITION the problem's M1 rows (counts summing to at most M1, as a stable sort by key gives):
+ * the grid is sized for M1 rows plus one partial tile per key, not n_keys times M1 (compact keyed grids), and
+ * with groups that overlap or over-count, the rows past that budget are not computed.  Nothing checks this at run time. */
 int e3k_gemm_grouped(const e3k_gemm_problem* templates, int n_templates, const int32_t* perm,
                      const int32_t* groups_dev, int32_t n_keys, int64_t b_key_stride, int32_t wgrad, void* stream);
 

@@ -92,10 +92,9 @@ def test_product_path_has_no_oracle_import():
                 assert "/root/reference" not in text, os.path.join(base, f)
 
 
-def test_switches_live_in_one_table_and_the_product_library_reads_no_environment():
-    """the C library's tuning constants are compile-time in the product build (getenv only behind
-    E3K_DEBUG_KNOBS: `make dbg`), and the Python package reads the environment in backend/tuning.py only -- every knob it reads is
-    documented there."""
+def test_switches_live_in_one_table_and_the_library_has_no_environment_knobs():
+    """the C library's tuning constants are compile-time constants (one build, no environment read, no debug-knob
+    switch), and the Python package reads the environment in backend/tuning.py only -- every knob it reads is documented there."""
     import re
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,10 +103,8 @@ def test_switches_live_in_one_table_and_the_product_library_reads_no_environment
         if not fn.endswith((".hip", ".h")):
             continue
         text = open(os.path.join(csrc, fn)).read()
-        if fn == "e3k_common.h":
-            assert text.count("getenv") >= 1 and "#ifdef E3K_DEBUG_KNOBS" in text
-            continue
-        assert "getenv" not in text, fn
+        for word in ("getenv", "E3K_DEBUG_KNOBS", "E3K_KNOB_INT"):
+            assert word not in text, (fn, word)
     pkg = os.path.join(root, "equivariant-nn-zoo_amd", "e3_layers_amd")
     used = set()
     for dirpath, _, files in os.walk(pkg):

@@ -252,6 +252,38 @@ def test_gemm_k_chain_through_the_c_abi(dev, m1, m2, n, ks, accumulate, bias, kd
     assert L.load().e3k_gemm(arr, len(probs), L.stream_ptr()) != 0
 
 
+def test_gemm_call_that_fails_sizing_writes_nothing(dev):
+    """e3k_gemm plans the whole call before its first launch: a problem that passes the argument checks but is too large for one
+    launch ((2^31 - 1) x 1024 rows: ~2^34 tiles) fails the call, and the one-column problem in front of it has not written its C
+    (a retry with `accumulate` set would otherwise add it twice).  The large problem never reaches a kernel: its sizing check
+    precedes its launch."""
+    from e3_layers_amd.backend import lib as L
+
+    torch.manual_seed(3)
+    a, b = torch.randn(100, 64, device=dev), torch.randn(64, 1, device=dev)
+    c = torch.full((100, 1), 7.0, device=dev)
+    before = c.clone()
+    p = L.GemmProblem()
+    p.A, p.A2, p.B, p.C, p.bias, p.row_index, p.group_dev = a.data_ptr(), None, b.data_ptr(), c.data_ptr(), None, None, None
+    p.M1, p.M2, p.N, p.K, p.V, p.accumulate = 100, 1, 1, 64, 0, 0
+    p.a_r1, p.a_r2, p.a_k, p.b_k, p.b_n, p.c_r1, p.c_r2, p.c_n = 64, 64, 1, 1, 1, 1, 1, 1
+    p.alpha, p.act, p.act_cst, p.chain = 1.0, 0, 1.0, 0
+    small = torch.zeros(64, 64, device=dev)
+    q = L.GemmProblem()
+    q.A, q.A2, q.B, q.C, q.bias, q.row_index, q.group_dev = small.data_ptr(), None, small.data_ptr(), small.data_ptr(), None, None, None
+    q.M1, q.M2, q.N, q.K, q.V, q.accumulate = 2 ** 31 - 1, 1024, 64, 64, 0, 0
+    q.a_r1, q.a_r2, q.a_k, q.b_k, q.b_n, q.c_r1, q.c_r2, q.c_n = 64, 64, 1, 64, 1, 64, 64, 1
+    q.alpha, q.act, q.act_cst, q.chain = 1.0, 0, 1.0, 0
+    arr = (L.GemmProblem * 2)(p, q)
+    assert L.load().e3k_gemm(arr, 2, L.stream_ptr()) != 0
+    torch.cuda.synchronize()
+    assert torch.equal(c, before)
+    # alone, the first problem does write C
+    L.check(L.load().e3k_gemm((L.GemmProblem * 1)(p), 1, L.stream_ptr()), "e3k_gemm")
+    torch.cuda.synchronize()
+    assert rel_err(c, a.double() @ b.double()) < 2e-6
+
+
 @pytest.mark.parametrize("rows,width", [(4097, 1920), (700, 960), (33, 260)])
 def test_fully_connected_net_few_rows_wide_output(dev, rows, width):
     """The radial MLP on the knot table: few rows, a wide last layer -- its dgrad is the split-K kernel (K = width),

@@ -35,10 +35,9 @@ bash tools/collect_lines_r05.sh > $OUT/lines.log 2>&1
 # 6. measured errors of the model-level parity tests (tests/util.py: record_measured)
 rm -f $OUT/parity_measured.jsonl
 E3K_PARITY_LOG=$PWD/$OUT/parity_measured.jsonl python3 -m pytest tests/test_gpu_model.py tests/test_gpu_double_backward.py -q -m gpu -k "protein or diffusion or bench_path or guard or backbone or force_block or threshold or shipped_config or position_gradient" > $OUT/parity_tests.log 2>&1
-# 7. round-5 probes: the packed-table kernels in isolation (+ the debug library's timing-only ablation of the packed forward), the
+# 7. round-5 probes: the packed-table kernels in isolation, the
 #    knot-order walk that would replace the g_w round trip (emulated), the guard's ratios at random init, the host's share of a step
 python3 tools/tp_table_bench.py 512 > $OUT/tp_table_bench.txt 2>&1
-E3K_LIB=$PWD/equivariant-nn-zoo_amd/csrc/libe3k_dbg.so python3 tools/tp_table_bench.py --ablate >> $OUT/tp_table_bench.txt 2>&1
 python3 tools/tp_table_bench.py --knot-order > $OUT/knot_order_walk.txt 2>&1
 python3 tools/guard_probe.py > $OUT/guard_probe.txt 2>&1
 E3K_HOST_TIMING=1 python3 tools/host_split.py 256 --layer-timing > $OUT/host_split.txt 2>&1

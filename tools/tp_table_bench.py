@@ -82,22 +82,6 @@ if "--knot-order" in sys.argv:
     print(f"knot-order walk ({n_seg} segments of <= 64 edges; gathers g_mid[dst] + one 7.7 KB row per edge): {t_k:7.1f} us")
     print(f"what it would replace: tp_bwd_w {t_w:7.1f} us + table transpose {t_t:7.1f} us = {t_w + t_t:7.1f} us   (tp_bwd_x in source order, same gather volume: {t_x:7.1f} us)")
     sys.exit(0)
-if "--ablate" in sys.argv:      # dbg library only (E3K_LIB=.../libe3k_dbg.so): timing-only masks of the packed forward
-    import ctypes
-    from e3_layers_amd.backend import lib as L
-    lib = ctypes.CDLL(os.environ["E3K_LIB"])
-    bins = radial_table.build_bins(r, 4.0, 512)
-    T = torch.randn(bins.knots + 1, tp.w_numel, device=dev) * 1e-3
-    P = radial_table.pack_raw(T, bins.knots)
-    for mask, what in ((0, "full"), (1, "no table loads"), (2, "no x loads"), (3, "no table, no x loads"), (4, "no CG arithmetic"), (7, "loop skeleton")):
-        assert lib.e3k_dbg_tp_ablate(mask) == 0
-        print(f"packed tp_fwd, {what:22s}: {timeit(lambda: conv_force._tp_fwd_ptable(x, sh, P, bins, topo, tp)):7.1f} us")
-    for mask, what in ((0, "full"), (8, "g[dst] rows from the walker's own node (L1 hits)"), (1, "no table loads"), (9, "neither")):
-        assert lib.e3k_dbg_tp_ablate(mask) == 0
-        print(f"packed tp_bwd_x, {what:50s}: {timeit(lambda: conv_force._tp_bwd_x_ptable(sh, P, bins, g, topo, tp)):7.1f} us   "
-              f"with g_w: {timeit(lambda: conv_force._tp_bwd_xw_ptable(x, sh, P, bins, g, topo, tp)):7.1f} us")
-    lib.e3k_dbg_tp_ablate(0)
-    sys.exit(0)
 print(f"streamed  tp_fwd {timeit(lambda: ops._tp_fwd_raw(x, sh, w, topo, tp)):7.1f} us   tp_bwd_x {timeit(lambda: ops._tp_bwd_x_raw(sh, w, g, topo, tp)):7.1f} us"
       f"   tp_bwd_w {timeit(lambda: ops._tp_bwd_w_raw(x, sh, None, g, topo, tp, False, True)):7.1f} us")
 gw, _ = ops._tp_bwd_w_raw(x, sh, None, g, topo, tp, False, True)
