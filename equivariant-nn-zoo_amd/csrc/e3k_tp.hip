@@ -20,7 +20,9 @@
 // Backward: bwd_w has the forward's shape (per destination node; writes grad_w[e] rows,
 // optionally reduces grad_sh[e] over lanes), bwd_x walks the out-edges of a source node
 // (CSR by source) and accumulates grad_x in registers.
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "e3k_tp_body.h"
 
@@ -1210,6 +1212,13 @@ unsigned plan_full_mask(int l1, int l3max) {
     default: return full_mask_of<3>(l3max);
   }
 }
+// A group whose enabled slots hold more than kSplitAcc accumulators (l_max = 3 models) is walked by two waves, one per slot part.
+constexpr int kSplitAcc = 24;
+// Every slot up to output degree 3 of an input degree l1 >= 1 is more than that (Slots<L1>::TOTAL: 27, 36, 34).  A channel-complete
+// plan enables every slot up to its instantiation's L3MAX in every group, so a channel-complete plan with L3MAX == 3 and an l1 >= 1
+// group is always split: launch_all has no FULL && !SPLIT && L3MAX == 3 && MAXL >= 1 instantiation.
+static_assert(e3k::Slots<1>::TOTAL > kSplitAcc && e3k::Slots<2>::TOTAL > kSplitAcc && e3k::Slots<3>::TOTAL > kSplitAcc,
+              "launch_all omits the unsplit channel-complete l3 <= 3 kernels of l1 >= 1 because no plan reaches them");
 int plan_max_l3(const e3k_tp_group& g) {
   switch (g.l1) {
     case 0: return max_l3_of<0>(g.mask);
@@ -1246,9 +1255,7 @@ extern "C" int e3k_tp_plan_create(const e3k_tp_group* groups, int32_t n_groups, 
     return E3K_ERR_LAUNCH;
   }
   {
-    // work list: (group, 64-channel chunk | part << 16).  A group whose enabled slots hold more than
-    // kSplitAcc accumulators (l_max = 3 models) is walked by two waves, one per slot part.
-    constexpr int kSplitAcc = 24;
+    // work list: (group, 64-channel chunk | part << 16); a group over kSplitAcc accumulators goes by parts
     int64_t cap = 0;
     for (int i = 0; i < n_groups; ++i) cap += 2 * ((groups[i].mul + 63) / 64);
     if (cap > (1 << 20)) {   // the work item index packs (chunk | part << 16): far beyond any irreps this path serves
@@ -1331,6 +1338,25 @@ extern "C" void e3k_tp_plan_destroy(e3k_tp_plan* p) {
 }
 
 namespace {
+// the instantiation of the calling thread's most recent TP launch, as the launch site spells it: "(e3k::tp_..._kernel<...>)"
+thread_local const char* tp_route = nullptr;
+thread_local char tp_route_buf[128];
+}  // namespace
+#define E3K_TP_GO(K, ...)                   \
+  do {                                      \
+    tp_route = #K;                          \
+    hipLaunchKernelGGL(K, __VA_ARGS__);     \
+  } while (0)
+
+extern "C" const char* e3k_tp_last_route(void) {
+  if (!tp_route) return nullptr;
+  const char* s = tp_route + (sizeof("(e3k::") - 1);
+  const int n = (int)strlen(s) - 1;      // (without the closing parenthesis)
+  snprintf(tp_route_buf, sizeof(tp_route_buf), "%.*s", n, s);
+  return tp_route_buf;
+}
+
+namespace {
 enum TpKind { TP_FWD, TP_BWD_W, TP_BWD_W_SH, TP_BWD_X, TP_FWD_TABLE, TP_BWD_X_TABLE, TP_FWD_JVP, TP_BWD_X_DUAL, TP_BWD_E, TP_BWD_W_DUAL,
               TP_FWD_PACKED, TP_BWD_X_PACKED, TP_BWD_XW_PACKED, TP_BWD_XW, TP_BWD_XW_DUAL, TP_BWD_XE };
 
@@ -1358,12 +1384,12 @@ int launch_all(TpKind kind, const e3k::TpArgs& a, const e3k_tp_plan* p, int64_t 
       if (!streamed) return E3K_ERR_UNSUPPORTED;
 #define E3K_TP_LAUNCH_2S(ML)                                                                                                            \
   switch (kind) {                                                                                                                       \
-    case TP_FWD_JVP: hipLaunchKernelGGL((e3k::tp_fwd_kernel<ML, 3, true, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;      \
-    case TP_BWD_X_DUAL: hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, 3, true, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    case TP_BWD_XW_DUAL: hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, 3, true, true, 7>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    case TP_BWD_XE: hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, 3, true, true, 8>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    case TP_BWD_E: hipLaunchKernelGGL((e3k::tp_bwd_e_kernel<ML, 3, true, true>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;         \
-    default: hipLaunchKernelGGL((e3k::tp_bwd_w_dual_kernel<ML, 3, true>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;                \
+    case TP_FWD_JVP: E3K_TP_GO((e3k::tp_fwd_kernel<ML, 3, true, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;      \
+    case TP_BWD_X_DUAL: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, 3, true, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
+    case TP_BWD_XW_DUAL: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, 3, true, true, 7>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
+    case TP_BWD_XE: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, 3, true, true, 8>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
+    case TP_BWD_E: E3K_TP_GO((e3k::tp_bwd_e_kernel<ML, 3, true, true>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;         \
+    default: E3K_TP_GO((e3k::tp_bwd_w_dual_kernel<ML, 3, true>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;                \
   }
       switch (p->max_l1) {
         case 1: E3K_TP_LAUNCH_2S(1) break;
@@ -1377,30 +1403,31 @@ int launch_all(TpKind kind, const e3k::TpArgs& a, const e3k_tp_plan* p, int64_t 
 #define E3K_TP_LAUNCH_2(ML, L3)                                                                                                         \
   switch (kind) {                                                                                                                       \
     case TP_FWD_JVP:                                                                                                                    \
-      if (streamed) hipLaunchKernelGGL((e3k::tp_fwd_kernel<ML, L3, false, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);   \
-      else hipLaunchKernelGGL((e3k::tp_fwd_kernel<ML, L3, false, true, 2>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
+      if (streamed) E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, false, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);   \
+      else E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, false, true, 2>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
       break;                                                                                                                            \
     case TP_BWD_X_DUAL:                                                                                                                 \
-      if (streamed) hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, false, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); \
-      else hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, false, true, 2>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);          \
+      if (streamed) E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); \
+      else E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 2>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);          \
       break;                                                                                                                            \
     case TP_BWD_XW_DUAL:                                                                                                                \
-      hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, false, true, 7>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);         \
+      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 7>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);         \
       break;                                                                                                                            \
     case TP_BWD_XE:                                                                                                                     \
-      hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, false, true, 8>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);         \
+      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 8>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);         \
       break;                                                                                                                            \
     case TP_BWD_E:                                                                                                                      \
-      if (streamed) hipLaunchKernelGGL((e3k::tp_bwd_e_kernel<ML, L3, true>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);           \
-      else hipLaunchKernelGGL((e3k::tp_bwd_e_kernel<ML, L3, false>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);                   \
+      if (streamed) E3K_TP_GO((e3k::tp_bwd_e_kernel<ML, L3, true, false>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);           \
+      else E3K_TP_GO((e3k::tp_bwd_e_kernel<ML, L3, false, false>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);                   \
       break;                                                                                                                            \
-    default: hipLaunchKernelGGL((e3k::tp_bwd_w_dual_kernel<ML, L3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;      \
+    default: E3K_TP_GO((e3k::tp_bwd_w_dual_kernel<ML, L3, false>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;      \
   }
+    // (l1 >= 1 with outputs up to 3 is split: see kSplitAcc)
     switch (p->max_l1) {
       case 0: if (lo) { E3K_TP_LAUNCH_2(0, 0) } else { E3K_TP_LAUNCH_2(0, 3) } break;
-      case 1: if (lo) { E3K_TP_LAUNCH_2(1, 1) } else { E3K_TP_LAUNCH_2(1, 3) } break;
-      case 2: if (lo) { E3K_TP_LAUNCH_2(2, 2) } else { E3K_TP_LAUNCH_2(2, 3) } break;
-      default: E3K_TP_LAUNCH_2(3, 3) break;
+      case 1: if (!lo) return E3K_ERR_UNSUPPORTED; E3K_TP_LAUNCH_2(1, 1) break;
+      case 2: if (!lo) return E3K_ERR_UNSUPPORTED; E3K_TP_LAUNCH_2(2, 2) break;
+      default: return E3K_ERR_UNSUPPORTED;
     }
 #undef E3K_TP_LAUNCH_2
     E3K_CHECK_LAUNCH();
@@ -1412,21 +1439,22 @@ int launch_all(TpKind kind, const e3k::TpArgs& a, const e3k_tp_plan* p, int64_t 
 #define E3K_TP_LAUNCH_T(ML, L3, SP)                                                                                                     \
   {                                                                                                                                     \
     if (kind == TP_FWD_TABLE)                                                                                                           \
-      hipLaunchKernelGGL((e3k::tp_fwd_kernel<ML, L3, SP, true, 1>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);              \
+      E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, SP, true, 1>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);              \
     else if (kind == TP_FWD_PACKED)                                                                                                     \
-      hipLaunchKernelGGL((e3k::tp_fwd_kernel<ML, L3, SP, true, 4>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);              \
+      E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, SP, true, 4>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);              \
     else if (kind == TP_BWD_X_PACKED)                                                                                                   \
-      hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 4>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
+      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 4>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
     else if (kind == TP_BWD_XW_PACKED)                                                                                                  \
-      hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 5>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
+      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 5>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
     else                                                                                                                                \
-      hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 1>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
+      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 1>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
   }
+    // (l1 >= 1 with outputs up to 3 is split: see kSplitAcc)
     switch (p->max_l1) {
       case 0: if (lo) E3K_TP_LAUNCH_T(0, 0, false) else E3K_TP_LAUNCH_T(0, 3, false) break;
-      case 1: if (lo && !spl) E3K_TP_LAUNCH_T(1, 1, false) else if (!spl) E3K_TP_LAUNCH_T(1, 3, false) else E3K_TP_LAUNCH_T(1, 3, true) break;
-      case 2: if (lo && !spl) E3K_TP_LAUNCH_T(2, 2, false) else if (!spl) E3K_TP_LAUNCH_T(2, 3, false) else E3K_TP_LAUNCH_T(2, 3, true) break;
-      default: if (!spl) E3K_TP_LAUNCH_T(3, 3, false) else E3K_TP_LAUNCH_T(3, 3, true) break;
+      case 1: if (!spl && !lo) return E3K_ERR_UNSUPPORTED; if (!spl) E3K_TP_LAUNCH_T(1, 1, false) else E3K_TP_LAUNCH_T(1, 3, true) break;
+      case 2: if (!spl && !lo) return E3K_ERR_UNSUPPORTED; if (!spl) E3K_TP_LAUNCH_T(2, 2, false) else E3K_TP_LAUNCH_T(2, 3, true) break;
+      default: if (!spl) return E3K_ERR_UNSUPPORTED; E3K_TP_LAUNCH_T(3, 3, true) break;
     }
 #undef E3K_TP_LAUNCH_T
     E3K_CHECK_LAUNCH();
@@ -1435,31 +1463,35 @@ int launch_all(TpKind kind, const e3k::TpArgs& a, const e3k_tp_plan* p, int64_t 
 #define E3K_TP_LAUNCH_F(ML, L3, SP, FU)                                                                                      \
   switch (kind) {                                                                                                   \
     case TP_BWD_XW:                                                                                                 \
-      hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, SP, FU, 6>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); \
+      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, FU, 6>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); \
       break;                                                                                                        \
-    case TP_FWD: hipLaunchKernelGGL((e3k::tp_fwd_kernel<ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
+    case TP_FWD: E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, SP, FU, 0>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
     case TP_BWD_W:                                                                                                  \
-      hipLaunchKernelGGL((e3k::tp_bwd_w_kernel<false, ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);  \
+      E3K_TP_GO((e3k::tp_bwd_w_kernel<false, ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);  \
       break;                                                                                                        \
     case TP_BWD_W_SH:                                                                                               \
-      hipLaunchKernelGGL((e3k::tp_bwd_w_kernel<true, ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);   \
+      E3K_TP_GO((e3k::tp_bwd_w_kernel<true, ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);   \
       break;                                                                                                        \
-    case TP_BWD_X: hipLaunchKernelGGL((e3k::tp_bwd_x_kernel<ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
+    case TP_BWD_X: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, FU, 0>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
     default: break;                                                                                                 \
   }
 #define E3K_TP_LAUNCH(ML, L3, SP)                  \
   if (p->full64) { E3K_TP_LAUNCH_F(ML, L3, SP, true) } \
   else { E3K_TP_LAUNCH_F(ML, L3, SP, false) }
+#define E3K_TP_LAUNCH_NF(ML, L3, SP)               \
+  if (p->full64) return E3K_ERR_UNSUPPORTED;       \
+  E3K_TP_LAUNCH_F(ML, L3, SP, false)
   // instantiations per input degree: outputs up to the same degree (l_max-limited models) or up to 3, the latter
-  // also in the split form (two waves per group)
+  // also in the split form (two waves per group); unsplit with outputs up to 3 and l1 >= 1: never channel-complete (see kSplitAcc)
   const bool low = p->max_l3 <= p->max_l1;
   const bool sp = p->split != 0;
   switch (p->max_l1) {
     case 0: if (low) { E3K_TP_LAUNCH(0, 0, false) } else { E3K_TP_LAUNCH(0, 3, false) } break;
-    case 1: if (low && !sp) { E3K_TP_LAUNCH(1, 1, false) } else if (!sp) { E3K_TP_LAUNCH(1, 3, false) } else { E3K_TP_LAUNCH(1, 3, true) } break;
-    case 2: if (low && !sp) { E3K_TP_LAUNCH(2, 2, false) } else if (!sp) { E3K_TP_LAUNCH(2, 3, false) } else { E3K_TP_LAUNCH(2, 3, true) } break;
-    default: if (!sp) { E3K_TP_LAUNCH(3, 3, false) } else { E3K_TP_LAUNCH(3, 3, true) } break;
+    case 1: if (low && !sp) { E3K_TP_LAUNCH(1, 1, false) } else if (!sp) { E3K_TP_LAUNCH_NF(1, 3, false) } else { E3K_TP_LAUNCH(1, 3, true) } break;
+    case 2: if (low && !sp) { E3K_TP_LAUNCH(2, 2, false) } else if (!sp) { E3K_TP_LAUNCH_NF(2, 3, false) } else { E3K_TP_LAUNCH(2, 3, true) } break;
+    default: if (!sp) { E3K_TP_LAUNCH_NF(3, 3, false) } else { E3K_TP_LAUNCH(3, 3, true) } break;
   }
+#undef E3K_TP_LAUNCH_NF
 #undef E3K_TP_LAUNCH
 #undef E3K_TP_LAUNCH_F
   E3K_CHECK_LAUNCH();

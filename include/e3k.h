@@ -227,6 +227,10 @@ int e3k_tp_bwd_w(const e3k_tp_plan* plan, const float* x, const float* sh, const
  * CSR by source (src_ptr, src_perm), dst [E]. */
 /* 1 when e3k_tp_bwd_x stores every element of g_x (no zero-fill needed): single-wave groups that tile [0, d_in). */
 int e3k_tp_bwd_x_overwrites(const e3k_tp_plan* plan);
+/* The kernel instantiation of the calling thread's most recent tensor-product launch, e.g. "tp_bwd_x_kernel<2, 3, true, true, 5>"
+ * (template arguments as in e3k_tp.hip), or NULL before the first.  For tests: which form a plan and a call kind reached.  The
+ * string stays valid until the thread's next call of this function. */
+const char* e3k_tp_last_route(void);
 
 /* The forward and the node-feature backward with the per-edge path weights interpolated INSIDE the kernel from the radial
  * knot table (the weights `self.fc(edge_radial)` of nn/message_passing.py:93, never materialised as [E, W]):
