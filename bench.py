@@ -10,20 +10,25 @@ n_dim 64, 5 layers, 256 molecules per GPU (weak scaling: graph-parallel data par
 Every step sees a NEW batch object: four distinct batches are resident in HBM and each step works on a fresh device
 copy of the next one's tensors, so everything the framework derives per batch (CSR topology by destination and by
 source, tile ownership, species key groups, one-hot indices) is rebuilt inside the timed step, as in training, where
-a batch is never seen twice.  ``per_batch_prep_ms`` reports that part on its own.
+a batch is never seen twice.  ``per_batch_prep_ms`` (--full) reports that part on its own.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs      (+ the last timed step's outputs as .npy)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                            (+ everything below the headline)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line carrying the metric plus
+Rank 0 prints ONE JSON line carrying the metric (molecules/s over the K timed steps, ms_per_step, the run's configuration).  A
+plain run does only that: set-up, W warm-up steps, the K timed steps, --dump-outputs, the line.  ``--full`` adds, measured behind
+the timed steps,
+  ms_per_step_repeats — the K-step region four more times back to back;
   roofline     — the fused TP+reduce forward kernel (e3k::tp_fwd_kernel): algorithmic bytes (SURVEY.md §8d variant A)
                  / HIP-event time of its launches inside the timed region, vs 8 TB/s; ``kernels`` lists the other
                  edge kernels and the radial GEMM the same way (the step's weakest kernel is in there, not hidden);
   cpu_baseline — the oracle (unfused PyTorch restatement, kind "port") on the host cores at BASELINE configs[0]
                  (config_energy as shipped: l_max 3, 32 molecules): warm-up + median, forward and forward+backward
-                 (rank 0, N=1 only).
+                 (rank 0, N=1 only);
+  gpu_forward_only_ms, per_batch_prep_ms — the forward alone and the per-batch preparation alone (config_energy).
 """
 from __future__ import annotations
 
@@ -66,7 +71,12 @@ def parse():
     ap.add_argument("--loader", action="store_true",
                     help="feed the step from the prefetching loader (data/loader.py: collate of fresh samples on a worker thread, "
                          "pinned buffers, async H2D) instead of HBM-resident batches; reported beside the resident figure")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the result line's headline does not need: the K-step region four "
+                         "more times (ms_per_step_repeats), the per-kernel roofline block from an eager pass, the forward and the "
+                         "per-batch preparation alone, and the CPU baseline of the oracle (config_energy); off: set up, warm up, time "
+                         "the K steps, write --dump-outputs, print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--graph-fresh", action="store_true",
                     help="HIP-graph replay with a NEW batch every step: the resident batches are padded to one size bucket with a "
                          "ghost graph (run/graph_step.py), each step copies the next one into the captured tensors and replays")
@@ -81,7 +91,7 @@ def parse():
                          "auto: time the eager layouts (and the replay when the host is the limit) on this box and keep the fastest "
                          "(rounds 3-4's default; reported under config.launch_auto)")
     ap.add_argument("--eager", action="store_true", help="the eager multi-stream step (rounds 1-5's default for config_energy)")
-    ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU work for the baseline leg")
+    ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU work for the baseline leg (--full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0): the loss, the "
                          "predictions (a padded batch's ghost graph dropped), the parameters, their gradients and the EMA shadow "
@@ -188,8 +198,8 @@ def launch_ranks(args) -> int:
     """``python bench.py --gpus N`` as given (no torchrun around it): this process touches no GPU -- it starts N FRESH rank
     processes through ``python -m torch.distributed.run`` (one per GPU, rendezvous on 127.0.0.1, the reference's
     ``torch.multiprocessing.spawn`` of ``train.py:272,280-304``), relays their output, and prints rank 0's JSON line ONCE, with
-    the CPU baseline of the same run (measured here, after the ranks have finished, so that it does not disturb their hosts'
-    launch rates) added to it.  A rank that fails makes the elastic agent end its siblings; the agent's exit code is ours."""
+    (--full) the CPU baseline of the same run (measured here, after the ranks have finished, so that it does not disturb their
+    hosts' launch rates) added to it.  A rank that fails makes the elastic agent end its siblings; the agent's exit code is ours."""
     import subprocess
 
     env = dict(os.environ)
@@ -220,7 +230,7 @@ def launch_ranks(args) -> int:
               file=sys.stderr, flush=True)
         return rc if rc != 0 else 1
     result = json.loads(line)
-    if not args.no_cpu_baseline and args.config == "energy" and os.environ.get("E3K_BENCH_DRY_RUN") is None:
+    if args.full and not args.no_cpu_baseline and args.config == "energy" and os.environ.get("E3K_BENCH_DRY_RUN") is None:
         result["cpu_baseline"] = cpu_baseline(args.cpu_budget)
     result.setdefault("config", {})["launcher"] = f"bench.py started {args.gpus} rank processes itself (torch.distributed.run, c10d rendezvous on 127.0.0.1)"
     print(json.dumps(result), flush=True)
@@ -766,184 +776,200 @@ def main():
         # exactly K steps are timed again, once; the line reports the repeat and the discarded figure
         retimed = {"first_ms_per_step": round(1e3 * elapsed / args.steps, 3), "warmup_ms_per_step": round(1e3 * ref_step, 3)}
         elapsed, records, loss = timed_region()
-    # the K-step region four more times (0.1 s is a short window on a shared box): reported as extra keys, `value` stays the first
-    # region's (the contract: exactly K timed steps)
-    repeats = [elapsed / args.steps]
-    for _ in range(4):
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            run()
-        fence()
-        repeats.append(max_over_ranks(time.perf_counter() - t0) / args.steps)
-    # eager pass for the roofline block: every kernel kind when the step was a replayed graph (per-kernel events cannot be
-    # read back from a replay), the secondary kinds otherwise (the dominant kernel keeps the timed region's records)
-    live = {k: v for k, v in (records or {}).items() if k in DOMINANT} if graph is None else {}
-    ops.PROFILE = {}
-    for nl in conv_native._LAYERS:
-        nl.profile(16)
-    from e3_layers_amd.nn import message_passing as _mp_
 
-    forked_ = (_mp_.FORK_MIN_EDGES, _mp_.FORK_MIN_EDGES_TABLE)
-    if graph is not None:
-        # A replayed step is ONE in-order queue.  Event pairs cannot bracket a kernel inside a graph on this runtime (the HIP 7.0
-        # runtime torch ships rejects hipEventRecordWithFlags(hipEventRecordExternal) under a capture -- tools/micro/ext_event_torch.py;
-        # ROCm 7.2's own accepts it: tools/micro/ext_event.hip), so the kernels' durations are taken from eager steps laid out like
-        # the replay: one stream, every kernel alone on the chip.  profiles/r06_bench_kernel_stats.csv (rocprofv3 over this very
-        # command: it does see the replayed kernels) carries the in-graph durations to compare with.
-        _mp_.FORK_MIN_EDGES = _mp_.FORK_MIN_EDGES_TABLE = 10 ** 12
-    for _ in range(min(args.steps, 5) + (2 if graph is not None else 0)):
-        step()
-    torch.cuda.synchronize()
-    _mp_.FORK_MIN_EDGES, _mp_.FORK_MIN_EDGES_TABLE = forked_
-    records, ops.PROFILE = ops.PROFILE, None
-    records = native_records(records)
-    records.update(live)
+    def full_measurements(records):
+        """--full: what the headline figure does not need, measured behind the timed region -- the K-step region four more
+        times, the per-kernel roofline block (``records``: the timed region's event pairs) from a short eager pass, the forward
+        alone and the per-batch preparation alone.  Every rank runs it (the repeats are maxima over the ranks); {result key:
+        value} of what it measured."""
+        # the K-step region four more times (0.1 s is a short window on a shared box): reported as extra keys, `value` stays the first
+        # region's (the contract: exactly K timed steps)
+        repeats = [elapsed / args.steps]
+        for _ in range(4):
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                run()
+            fence()
+            repeats.append(max_over_ranks(time.perf_counter() - t0) / args.steps)
+        # eager pass for the roofline block: every kernel kind when the step was a replayed graph (per-kernel events cannot be
+        # read back from a replay), the secondary kinds otherwise (the dominant kernel keeps the timed region's records)
+        live = {k: v for k, v in (records or {}).items() if k in DOMINANT} if graph is None else {}
+        ops.PROFILE = {}
+        for nl in conv_native._LAYERS:
+            nl.profile(16)
+        from e3_layers_amd.nn import message_passing as _mp_
 
-    # ---- outside the timed region: the pieces of a step on their own (rank 0 reports them) -------------------------
-    def event_ms(fn, n):
+        forked_ = (_mp_.FORK_MIN_EDGES, _mp_.FORK_MIN_EDGES_TABLE)
+        if graph is not None:
+            # A replayed step is ONE in-order queue.  Event pairs cannot bracket a kernel inside a graph on this runtime (the HIP 7.0
+            # runtime torch ships rejects hipEventRecordWithFlags(hipEventRecordExternal) under a capture -- tools/micro/ext_event_torch.py;
+            # ROCm 7.2's own accepts it: tools/micro/ext_event.hip), so the kernels' durations are taken from eager steps laid out like
+            # the replay: one stream, every kernel alone on the chip.  profiles/r06_bench_kernel_stats.csv (rocprofv3 over this very
+            # command: it does see the replayed kernels) carries the in-graph durations to compare with.
+            _mp_.FORK_MIN_EDGES = _mp_.FORK_MIN_EDGES_TABLE = 10 ** 12
+        for _ in range(min(args.steps, 5) + (2 if graph is not None else 0)):
+            step()
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        torch.cuda.synchronize()
-        return 1e3 * (time.perf_counter() - t0) / n
+        _mp_.FORK_MIN_EDGES, _mp_.FORK_MIN_EDGES_TABLE = forked_
+        records, ops.PROFILE = ops.PROFILE, None
+        records = native_records(records)
+        records.update(live)
 
-    def forward_only():
-        with torch.no_grad():
-            model(next_batch())
+        # ---- outside the timed region: the pieces of a step on their own (rank 0 reports them) -------------------------
+        def event_ms(fn, n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                fn()
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / n
 
-    def prep_only():
-        b = next_batch()
-        build_topology(b["edge_index"], b["pos"].shape[0])
+        def forward_only():
+            with torch.no_grad():
+                model(next_batch())
 
-    fwd_ms = prep_ms = None
-    if cfg_kind == "energy":      # (the other configurations' forward needs the loss wrapper's inputs: t, noise)
-        forward_only()
-        fwd_ms = event_ms(forward_only, 10)
-        prep_only()
-        prep_ms = event_ms(prep_only, 10)
+        def prep_only():
+            b = next_batch()
+            build_topology(b["edge_index"], b["pos"].shape[0])
 
+        fwd_ms = prep_ms = None
+        if cfg_kind == "energy":      # (the other configurations' forward needs the loss wrapper's inputs: t, noise)
+            forward_only()
+            fwd_ms = event_ms(forward_only, 10)
+            prep_only()
+            prep_ms = event_ms(prep_only, 10)
+
+        # ---- roofline blocks (rank 0's launches in the timed region) ---------------------------------------------------
+        table_rows = radial_table.layout(float(getattr(tree, "r_max", 4.0)), radial_table.KNOTS)[0] + 1      # rows of a layer's knot table
+
+        def in_kernel(e, plan):
+            """This launch interpolated its path weights from the knot table inside the kernel (csrc/e3k_tp.hip TABLE forms)."""
+            return bool(conv_native.TP_TABLE and radial_table.ENABLED and getattr(plan, "_e3k_table_form", False)
+                        and e >= radial_table.MIN_EDGES_PER_KNOT * table_rows)
+
+        def fused_bwd(e, plan):
+            """This input-gradient launch also wrote the per-edge weight gradient (csrc/e3k_tp.hip MODE 5: packed-table layers)."""
+            return bool(in_kernel(e, plan) and conv_native.TP_TABLE_PACKED and conv_native.TP_BWD_FUSED and conv_native.ENABLED)
+
+        def tp_bytes(kind, n, e, plan, variant="A"):
+            """Algorithmic bytes of one launch.  Variant A = the module-API operation
+            tp(x[src], sh, w) + scatter with the per-edge weights supplied (E x W streamed); variant B = the radial-fused
+            operation (weights produced in the kernel: here interpolated from the (K + 1) x W knot table, counted once)."""
+            w_term = 4 * plan.w_numel
+            extra = 0
+            if variant == "B" and kind != "tp_bwd_w":
+                # knot (4 B) + four interpolation weights (16 B) per edge; the table once -- 12-byte records when the kernels read it packed
+                w_term, extra = 20, (12 if conv_native.TP_TABLE_PACKED else 4) * table_rows * plan.w_numel
+            if kind == "tp_fwd":        # x[src] gather + sh + w + out rows
+                return e * (4 * plan.d_in + 4 * plan.d_sh + w_term + 16) + n * 4 * plan.d_mid + extra
+            if kind == "tp_bwd_w":      # x[src] gather + sh + g_w stream + g_mid rows
+                return e * (4 * plan.d_in + 4 * plan.d_sh + 4 * plan.w_numel + 16) + n * 4 * plan.d_mid
+            if kind == "tp_bwd_x":      # compulsory: w + sh + g_mid once + g_x rows (the g_mid[dst] gather is not counted)
+                fused = e * 4 * plan.w_numel + n * 4 * plan.d_in if (variant == "B" and fused_bwd(e, plan)) else 0      # + g_w [E, W] out, x rows in
+                return e * (4 * plan.d_sh + w_term + 16) + n * 4 * (plan.d_mid + plan.d_in) + extra + fused
+            raise KeyError(kind)
+
+        def summarise(kind):
+            recs = (records or {}).get(kind, [])
+            tot_b = sum(tp_bytes(kind, *meta) for _, _, meta in recs)
+            tot_ms = sum(ev0.elapsed_time(ev1) for ev0, ev1, _ in recs)
+            n = max(len(recs), 1)
+            ach = tot_b / (tot_ms * 1e-3) / 1e9 if tot_ms > 0 else 0.0
+            out = {"kernel": f"e3k::{kind}_kernel", "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                   "frac": round(ach / HBM_PEAK_GBS, 4), "launches": len(recs), "avg_launch_us": round(1e3 * tot_ms / n, 2),
+                   "avg_launch_algorithmic_MB": round(tot_b / n / 1e6, 2)}
+            n_tab = sum(1 for _, _, (nn, e, plan) in recs if in_kernel(e, plan))
+            if n_tab and kind != "tp_bwd_w" and tot_ms > 0:
+                # These launches never read w[E, W] from HBM: they gather four rows of the L2-resident knot table per edge.  A kernel
+                # that produces its own weights is SURVEY 8d's variant B: `achieved` / `frac` count the bytes this form must move
+                # (x[src], sh, knot + four weights per edge, the output rows, the table once); variant A (the module-API operation's
+                # bytes, E x W streamed: what rounds 1-3 led with) stays as a secondary key for comparison with the earlier rounds.
+                tot_bb = sum(tp_bytes(kind, *meta, variant="B" if in_kernel(meta[1], meta[2]) else "A") for _, _, meta in recs)
+                ach_b = tot_bb / (tot_ms * 1e-3) / 1e9
+                out.update({"variant_A_achieved": out["achieved"], "variant_A_frac": out["frac"],
+                            "variant_A_avg_launch_algorithmic_MB": out["avg_launch_algorithmic_MB"]})
+                out.update({"achieved": round(ach_b, 1), "frac": round(ach_b / HBM_PEAK_GBS, 4),
+                            "avg_launch_algorithmic_MB": round(tot_bb / n / 1e6, 2), "launches_with_in_kernel_table": n_tab,
+                            "bytes_model": "SURVEY 8d variant B (weights produced in the kernel from the knot table)",
+                            "note": "in-kernel knot-table form: E x W is not streamed from HBM (L2 / Infinity-Cache gathers of a "
+                                    f"<= {(12 if conv_native.TP_TABLE_PACKED else 4) * table_rows * max(m[2].w_numel for _, _, m in recs) / 1e6:.1f} MB "
+                                    + ("packed table (one 12-byte record per knot and weight) per layer" if conv_native.TP_TABLE_PACKED else "table per layer")
+                                    + "); frac = the bytes "
+                                    "this form must move / time / 8 TB/s; variant_A_frac = the module-API operation's bytes (E x W streamed) "
+                                    "/ time, as reported in rounds 1-3"})
+            return out
+
+        traffic = {}
+        TRAFFIC_FILE = TRAFFIC_FILES.get(args.lmax, "")
+        tfile = os.path.join(ROOT, TRAFFIC_FILE)
+        if TRAFFIC_FILE and os.path.exists(tfile) and cfg_kind == "energy" and args.batch == 256:
+            try:
+                traffic = json.load(open(tfile))
+            except Exception:
+                traffic = {}
+        main_k = summarise("tp_fwd")
+        roofline = {k: main_k[k] for k in ("bound", "achieved", "peak", "unit", "frac")}
+        t_fwd = traffic.get("tp_fwd", {}).get("traffic_bytes_per_launch")
+        roofline["traffic"] = round(t_fwd) if t_fwd else None
+        roofline["traffic_source"] = (f"{TRAFFIC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this command, "
+                                      "NOT this run; the counters sit on the L2's fabric side: Infinity-Cache hits -- the knot-table "
+                                      "rows and the gathered node rows that miss an XCD's L2 -- are counted with the HBM bytes, so this "
+                                      "is an upper bound on DRAM traffic)") if t_fwd else None
+        if t_fwd and main_k["avg_launch_us"] > 0:   # DRAM-side rate: counter bytes / this run's launch time / peak
+            roofline["dram_frac"] = round(t_fwd / (main_k["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+        roofline.update({k: main_k[k] for k in main_k if k not in roofline})
+        kernels = []
+        for kind in ("tp_bwd_x", "tp_bwd_w"):
+            k = summarise(kind)
+            if kind == "tp_bwd_w" and not k["launches"]:
+                continue      # (every layer formed its weight gradient inside the input-gradient walk)
+            if kind == "tp_bwd_x":
+                n_f = sum(1 for _, _, (nn, e, plan) in (records or {}).get(kind, []) if fused_bwd(e, plan))
+                if n_f:
+                    k["launches_with_fused_weight_gradient"] = n_f
+                    k["kernel"] += " (MODE 5: the per-edge weight gradient g_w [E, W] written in the same walk -- its bytes are in the model)"
+            t_k = traffic.get(kind, {}).get("traffic_bytes_per_launch")
+            k["traffic"] = round(t_k) if t_k else None
+            if t_k and k["avg_launch_us"] > 0:
+                k["dram_frac"] = round(t_k / (k["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+            kernels.append(k)
+        for kind, label in (("rtable_fwd", "interpolation of the radial knot table, forward: E x W written + the table"),
+                            ("rtable_bwd", "its transpose: E x W read + per-knot partial sums written and combined")):
+            recs = (records or {}).get(kind, [])
+            if not recs:
+                continue
+            nbytes = sum((4.0 * e * w + 4.0 * (k + 1) * w * (1 if kind == "rtable_fwd" else 7)) for _, _, (e, k, w) in recs)
+            ms = sum(ev0.elapsed_time(ev1) for ev0, ev1, _ in recs)
+            ach = nbytes / (ms * 1e-3) / 1e9
+            kernels.append({"kernel": f"e3k::{kind.replace('rtable_', 'rtable_interp_')}_kernel ({label})", "bound": "hbm",
+                            "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                            "launches": len(recs), "avg_launch_us": round(1e3 * ms / len(recs), 2),
+                            "avg_launch_algorithmic_MB": round(nbytes / len(recs) / 1e6, 2)})
+        recs = (records or {}).get("radial_last_fwd", [])
+        if recs:
+            flops = sum(2.0 * e * k * w for _, _, (e, k, w) in recs)
+            ms = sum(ev0.elapsed_time(ev1) for ev0, ev1, _ in recs)
+            rows = sorted({e for _, _, (e, k, w) in recs})
+            kernels.append({"kernel": "e3k::gemm_kernel<2, false> (radial MLP last layer, forward; rows per launch: "
+                                      + ("the knot table" if max(rows) < 10000 else "one per edge") + ")", "bound": "mfma",
+                            "achieved": round(flops / (ms * 1e-3) / 1e12, 1), "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
+                            "frac": round(flops / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF, 4), "launches": len(recs),
+                            "avg_launch_us": round(1e3 * ms / len(recs), 2)})
+        roofline["kernels"] = kernels
+        extra = {"ms_per_step_median": round(1e3 * statistics.median(repeats), 3),
+                 "ms_per_step_repeats": {"regions": len(repeats), "min": round(1e3 * min(repeats), 3),
+                                         "median": round(1e3 * statistics.median(repeats), 3), "max": round(1e3 * max(repeats), 3),
+                                         "note": "the K-step region timed five times back to back; value / ms_per_step are the first region's"},
+                 "roofline": roofline}
+        if fwd_ms is not None:
+            extra.update({"per_batch_prep_ms": round(prep_ms, 3), "gpu_forward_only_ms": round(fwd_ms, 3),
+                          "gpu_forward_only_molecules_per_s": round(args.batch / (fwd_ms * 1e-3), 1)})
+        return extra
+
+    extra = full_measurements(records) if args.full else {}
     if loader is not None:
         loader.close()
-
-    # ---- roofline blocks (rank 0's launches in the timed region) ---------------------------------------------------
-    table_rows = radial_table.layout(float(getattr(tree, "r_max", 4.0)), radial_table.KNOTS)[0] + 1      # rows of a layer's knot table
-
-    def in_kernel(e, plan):
-        """This launch interpolated its path weights from the knot table inside the kernel (csrc/e3k_tp.hip TABLE forms)."""
-        return bool(conv_native.TP_TABLE and radial_table.ENABLED and getattr(plan, "_e3k_table_form", False)
-                    and e >= radial_table.MIN_EDGES_PER_KNOT * table_rows)
-
-    def fused_bwd(e, plan):
-        """This input-gradient launch also wrote the per-edge weight gradient (csrc/e3k_tp.hip MODE 5: packed-table layers)."""
-        return bool(in_kernel(e, plan) and conv_native.TP_TABLE_PACKED and conv_native.TP_BWD_FUSED and conv_native.ENABLED)
-
-    def tp_bytes(kind, n, e, plan, variant="A"):
-        """Algorithmic bytes of one launch.  Variant A = the module-API operation
-        tp(x[src], sh, w) + scatter with the per-edge weights supplied (E x W streamed); variant B = the radial-fused
-        operation (weights produced in the kernel: here interpolated from the (K + 1) x W knot table, counted once)."""
-        w_term = 4 * plan.w_numel
-        extra = 0
-        if variant == "B" and kind != "tp_bwd_w":
-            # knot (4 B) + four interpolation weights (16 B) per edge; the table once -- 12-byte records when the kernels read it packed
-            w_term, extra = 20, (12 if conv_native.TP_TABLE_PACKED else 4) * table_rows * plan.w_numel
-        if kind == "tp_fwd":        # x[src] gather + sh + w + out rows
-            return e * (4 * plan.d_in + 4 * plan.d_sh + w_term + 16) + n * 4 * plan.d_mid + extra
-        if kind == "tp_bwd_w":      # x[src] gather + sh + g_w stream + g_mid rows
-            return e * (4 * plan.d_in + 4 * plan.d_sh + 4 * plan.w_numel + 16) + n * 4 * plan.d_mid
-        if kind == "tp_bwd_x":      # compulsory: w + sh + g_mid once + g_x rows (the g_mid[dst] gather is not counted)
-            fused = e * 4 * plan.w_numel + n * 4 * plan.d_in if (variant == "B" and fused_bwd(e, plan)) else 0      # + g_w [E, W] out, x rows in
-            return e * (4 * plan.d_sh + w_term + 16) + n * 4 * (plan.d_mid + plan.d_in) + extra + fused
-        raise KeyError(kind)
-
-    def summarise(kind):
-        recs = (records or {}).get(kind, [])
-        tot_b = sum(tp_bytes(kind, *meta) for _, _, meta in recs)
-        tot_ms = sum(ev0.elapsed_time(ev1) for ev0, ev1, _ in recs)
-        n = max(len(recs), 1)
-        ach = tot_b / (tot_ms * 1e-3) / 1e9 if tot_ms > 0 else 0.0
-        out = {"kernel": f"e3k::{kind}_kernel", "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-               "frac": round(ach / HBM_PEAK_GBS, 4), "launches": len(recs), "avg_launch_us": round(1e3 * tot_ms / n, 2),
-               "avg_launch_algorithmic_MB": round(tot_b / n / 1e6, 2)}
-        n_tab = sum(1 for _, _, (nn, e, plan) in recs if in_kernel(e, plan))
-        if n_tab and kind != "tp_bwd_w" and tot_ms > 0:
-            # These launches never read w[E, W] from HBM: they gather four rows of the L2-resident knot table per edge.  A kernel
-            # that produces its own weights is SURVEY 8d's variant B: `achieved` / `frac` count the bytes this form must move
-            # (x[src], sh, knot + four weights per edge, the output rows, the table once); variant A (the module-API operation's
-            # bytes, E x W streamed: what rounds 1-3 led with) stays as a secondary key for comparison with the earlier rounds.
-            tot_bb = sum(tp_bytes(kind, *meta, variant="B" if in_kernel(meta[1], meta[2]) else "A") for _, _, meta in recs)
-            ach_b = tot_bb / (tot_ms * 1e-3) / 1e9
-            out.update({"variant_A_achieved": out["achieved"], "variant_A_frac": out["frac"],
-                        "variant_A_avg_launch_algorithmic_MB": out["avg_launch_algorithmic_MB"]})
-            out.update({"achieved": round(ach_b, 1), "frac": round(ach_b / HBM_PEAK_GBS, 4),
-                        "avg_launch_algorithmic_MB": round(tot_bb / n / 1e6, 2), "launches_with_in_kernel_table": n_tab,
-                        "bytes_model": "SURVEY 8d variant B (weights produced in the kernel from the knot table)",
-                        "note": "in-kernel knot-table form: E x W is not streamed from HBM (L2 / Infinity-Cache gathers of a "
-                                f"<= {(12 if conv_native.TP_TABLE_PACKED else 4) * table_rows * max(m[2].w_numel for _, _, m in recs) / 1e6:.1f} MB "
-                                + ("packed table (one 12-byte record per knot and weight) per layer" if conv_native.TP_TABLE_PACKED else "table per layer")
-                                + "); frac = the bytes "
-                                "this form must move / time / 8 TB/s; variant_A_frac = the module-API operation's bytes (E x W streamed) "
-                                "/ time, as reported in rounds 1-3"})
-        return out
-
-    traffic = {}
-    TRAFFIC_FILE = TRAFFIC_FILES.get(args.lmax, "")
-    tfile = os.path.join(ROOT, TRAFFIC_FILE)
-    if TRAFFIC_FILE and os.path.exists(tfile) and cfg_kind == "energy" and args.batch == 256:
-        try:
-            traffic = json.load(open(tfile))
-        except Exception:
-            traffic = {}
-    main_k = summarise("tp_fwd")
-    roofline = {k: main_k[k] for k in ("bound", "achieved", "peak", "unit", "frac")}
-    t_fwd = traffic.get("tp_fwd", {}).get("traffic_bytes_per_launch")
-    roofline["traffic"] = round(t_fwd) if t_fwd else None
-    roofline["traffic_source"] = (f"{TRAFFIC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this command, "
-                                  "NOT this run; the counters sit on the L2's fabric side: Infinity-Cache hits -- the knot-table "
-                                  "rows and the gathered node rows that miss an XCD's L2 -- are counted with the HBM bytes, so this "
-                                  "is an upper bound on DRAM traffic)") if t_fwd else None
-    if t_fwd and main_k["avg_launch_us"] > 0:   # DRAM-side rate: counter bytes / this run's launch time / peak
-        roofline["dram_frac"] = round(t_fwd / (main_k["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
-    roofline.update({k: main_k[k] for k in main_k if k not in roofline})
-    kernels = []
-    for kind in ("tp_bwd_x", "tp_bwd_w"):
-        k = summarise(kind)
-        if kind == "tp_bwd_w" and not k["launches"]:
-            continue      # (every layer formed its weight gradient inside the input-gradient walk)
-        if kind == "tp_bwd_x":
-            n_f = sum(1 for _, _, (nn, e, plan) in (records or {}).get(kind, []) if fused_bwd(e, plan))
-            if n_f:
-                k["launches_with_fused_weight_gradient"] = n_f
-                k["kernel"] += " (MODE 5: the per-edge weight gradient g_w [E, W] written in the same walk -- its bytes are in the model)"
-        t_k = traffic.get(kind, {}).get("traffic_bytes_per_launch")
-        k["traffic"] = round(t_k) if t_k else None
-        if t_k and k["avg_launch_us"] > 0:
-            k["dram_frac"] = round(t_k / (k["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
-        kernels.append(k)
-    for kind, label in (("rtable_fwd", "interpolation of the radial knot table, forward: E x W written + the table"),
-                        ("rtable_bwd", "its transpose: E x W read + per-knot partial sums written and combined")):
-        recs = (records or {}).get(kind, [])
-        if not recs:
-            continue
-        nbytes = sum((4.0 * e * w + 4.0 * (k + 1) * w * (1 if kind == "rtable_fwd" else 7)) for _, _, (e, k, w) in recs)
-        ms = sum(ev0.elapsed_time(ev1) for ev0, ev1, _ in recs)
-        ach = nbytes / (ms * 1e-3) / 1e9
-        kernels.append({"kernel": f"e3k::{kind.replace('rtable_', 'rtable_interp_')}_kernel ({label})", "bound": "hbm",
-                        "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                        "launches": len(recs), "avg_launch_us": round(1e3 * ms / len(recs), 2),
-                        "avg_launch_algorithmic_MB": round(nbytes / len(recs) / 1e6, 2)})
-    recs = (records or {}).get("radial_last_fwd", [])
-    if recs:
-        flops = sum(2.0 * e * k * w for _, _, (e, k, w) in recs)
-        ms = sum(ev0.elapsed_time(ev1) for ev0, ev1, _ in recs)
-        rows = sorted({e for _, _, (e, k, w) in recs})
-        kernels.append({"kernel": "e3k::gemm_kernel<2, false> (radial MLP last layer, forward; rows per launch: "
-                                  + ("the knot table" if max(rows) < 10000 else "one per edge") + ")", "bound": "mfma",
-                        "achieved": round(flops / (ms * 1e-3) / 1e12, 1), "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
-                        "frac": round(flops / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF, 4), "launches": len(recs),
-                        "avg_launch_us": round(1e3 * ms / len(recs), 2)})
-    roofline["kernels"] = kernels
 
     if rank == 0:
         workloads = {
@@ -962,10 +988,6 @@ def main():
             "unit": f"{unit}/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "ms_per_step_median": round(1e3 * statistics.median(repeats), 3),
-            "ms_per_step_repeats": {"regions": len(repeats), "min": round(1e3 * min(repeats), 3),
-                                    "median": round(1e3 * statistics.median(repeats), 3), "max": round(1e3 * max(repeats), 3),
-                                    "note": "the K-step region timed five times back to back; value / ms_per_step are the first region's"},
             "host_busy_ms_per_step": round(1e3 * host_enqueue[0] / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
@@ -1001,12 +1023,9 @@ def main():
                 "parameters": countParameters(model), "final_loss": round(float(loss.detach()), 4),
                 "retimed_after_stall": retimed,
             },
-            "roofline": roofline,
         }
-        if fwd_ms is not None:
-            result.update({"per_batch_prep_ms": round(prep_ms, 3), "gpu_forward_only_ms": round(fwd_ms, 3),
-                           "gpu_forward_only_molecules_per_s": round(args.batch / (fwd_ms * 1e-3), 1)})
-        if world == 1 and not args.no_cpu_baseline and cfg_kind == "energy":
+        result.update(extra)
+        if args.full and world == 1 and not args.no_cpu_baseline and cfg_kind == "energy":
             cb = cpu_baseline(args.cpu_budget)
             result["cpu_baseline"] = cb
             result["gpu_vs_cpu_forward"] = round(result["gpu_forward_only_molecules_per_s"] / cb["lmax2_forward_only_value"], 1)

@@ -4,9 +4,9 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/r05
 mkdir -p $OUT
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 uptime > $OUT/lines_uptime.txt
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
 $B --lmax 3 > $OUT/bench_lmax3.json 2>/dev/null
 for b in 32 64 128; do $B --batch $b > $OUT/bench_b$b.json 2>/dev/null; done      # (eager: the fixed mode of this workload)
 $B --batch 512 > $OUT/bench_b512.json 2>/dev/null

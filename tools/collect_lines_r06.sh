@@ -4,9 +4,9 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/r06
 mkdir -p $OUT
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 uptime > $OUT/lines_uptime.txt
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
 $B --lmax 3 > $OUT/bench_lmax3.json 2>/dev/null
 for b in 32 64 128; do $B --batch $b > $OUT/bench_b$b.json 2>/dev/null; done      # (replayed, pipelined preparation: the fixed mode of this workload)
 $B --eager > $OUT/bench_eager.json 2>/dev/null                                       # rounds 1-5's default: the eager four-stream step

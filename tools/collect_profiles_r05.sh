@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/r05
 rm -rf $OUT; mkdir -p $OUT
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 # 1. default workload: kernel stats + one step's launch sequence, PMC traffic, calibration probe
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $B --steps 10 --warmup 3 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 python3 tools/step_kernels.py $(ls -t $OUT/stats/*kernel_trace.csv | head -1) $OUT/step_kernels.txt

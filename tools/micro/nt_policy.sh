@@ -5,6 +5,6 @@ C=$PWD/equivariant-nn-zoo_amd/csrc
 for round in 1 2; do
 for v in "" _x_pp _x_pn _x_np; do
   echo -n "libe3k$v: "
-  E3K_LIB=$C/libe3k$v.so python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['ms_per_step_repeats']['min'], d['ms_per_step_repeats']['max'])"
+  E3K_LIB=$C/libe3k$v.so python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['ms_per_step_repeats']['min'], d['ms_per_step_repeats']['max'])"
 done
 done
