@@ -11,9 +11,8 @@
 // serve the e3nn layout ([mul][2l+1]) and the channel-fastest layout ([2l+1][mul]).
 //
 // Kernels (256 threads = 4 waves, 32x32x2 f32 MFMA accumulators):
-//   gemm_kernel<WM>     forward / dgrad.  Tile (32*WM) x 64 x 32: WM=4 -> 128x64 (wave = 32 rows x 64 cols,
-//                       two accumulators), WM=2 -> 64x64 (wave = 32 x 32) for launches that would not fill
-//                       the chip with 128-row tiles.  A tile in LDS at an odd row stride (33): the MFMA A
+//   gemm_kernel<WM>     forward / dgrad.  Tile (32*WM) x 64 x 32; the library ships WM=2 only: 64x64 (wave = 32 x 32;
+//                       the 128-row form WM=4 lost to it at every size measured and was removed).  A tile in LDS at an odd row stride (33): the MFMA A
 //                       fragment (lane -> row l&31, k l>>5) is bank-conflict free; B tile [k][n].  Global
 //                       loads are 16 B/lane into registers one K-step ahead of the MFMAs (issue early,
 //                       write LDS late).  dgrad (dA = dC . B^T) = same kernel, b_k / b_n swapped.
@@ -27,6 +26,8 @@
 // Descriptors: up to 20 problems per launch, passed by value (3.85 KB of kernel arguments); keyed and plain problems mix; every
 // workgroup finds its problem and pulls it into scalar registers with s_load (the batch is wave-uniform).
 #include <algorithm>
+#include <cstdio>
+#include <cstring>
 
 #include "e3k_common.h"
 
@@ -675,89 +676,42 @@ __device__ __forceinline__ void gemm_wgrad_body(const BlockProblem& bp_, float* 
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
 
-  const bool avec = flags & 1;
   const bool gvec = flags & 8;
   const float* gp = Gs + (lane >> 5) * LDWG + wn * (32 * TN) + (lane & 31);
 
   if constexpr (!OUTER) {
-    if (avec && gvec) {
-      // fast path: both operands by 16-byte loads, one chunk ahead
-      RowCursor cur[4];
+    // (scalar staging only: a problem whose A and G are both 16-byte-loadable goes to gemm_wgrad2_kernel -- gemm_wgrad_impl)
+    RowCursor cur;
+    cur.init(rbeg + (t >> 2), M2);
+    const int cb = (t & 3) * 16;
+    const float* ap = As + (lane >> 5) * LDWA + wk * 32 + (lane & 31);
+    for (int r0 = rbeg; r0 < rend; r0 += WR) {
+      const bool ok = cur.R < rend;
+      const int n1 = (ok && P.row_index) ? P.row_index[cur.r1] : cur.r1;
+      const float* sa = P.A + (int64_t)n1 * P.a_r1 + (int64_t)cur.r2 * P.a_r2;
+      const float* sg = P.C + (int64_t)n1 * P.c_r1 + (int64_t)cur.r2 * P.c_r2;
 #pragma unroll
-      for (int pass = 0; pass < 4; ++pass) cur[pass].init(rbeg + (t >> 4) + 16 * pass, M2);
-      const int cq = (t & 15) * 4;
-      float4 ra[4], rg[4 * TN];
-      auto gload = [&]() {
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-          ra[pass] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-          for (int j = 0; j < TN; ++j) rg[pass * TN + j] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (cur[pass].R < rend) {
-            const int n1 = P.row_index ? P.row_index[cur[pass].r1] : cur[pass].r1;
-            if (k0 + cq < P.K)
-              ra[pass] = *reinterpret_cast<const float4*>(P.A + (int64_t)n1 * P.a_r1 + (int64_t)cur[pass].r2 * P.a_r2 + k0 + cq);
-            const float* grow = P.C + (int64_t)n1 * P.c_r1 + (int64_t)cur[pass].r2 * P.c_r2 + n0 + cq;
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              if (n0 + cq + 64 * j < P.N) rg[pass * TN + j] = *reinterpret_cast<const float4*>(grow + 64 * j);
-          }
-          cur[pass].advance(q64, rem64, M2);
-        }
-      };
-      const float* ap = As + (lane >> 5) * LDWA + wk * 32 + (lane & 31);
-      gload();
-      for (int r0 = rbeg; r0 < rend; r0 += WR) {
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-          const int r = (t >> 4) + 16 * pass;
-          *reinterpret_cast<float4*>(As + r * LDWA + cq) = ra[pass];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) *reinterpret_cast<float4*>(Gs + r * LDWG + cq + 64 * j) = rg[pass * TN + j];
-        }
-        __syncthreads();
-        if (r0 + WR < rend) gload();
-#pragma unroll 8
-        for (int rr = 0; rr < WR; rr += 2) {
-          const float a = ap[rr * LDWA];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, gp[rr * LDWG + 32 * j], acc[j], 0, 0, 0);
-        }
-        __syncthreads();
+      for (int j = 0; j < 16; ++j) {
+        float va = 0.f;
+        if (ok && k0 + cb + j < P.K) va = sa[(int64_t)(k0 + cb + j) * P.a_k];
+        As[(t >> 2) * LDWA + cb + j] = va;
       }
-    } else {
-      RowCursor cur;
-      cur.init(rbeg + (t >> 2), M2);
-      const int cb = (t & 3) * 16;
-      const float* ap = As + (lane >> 5) * LDWA + wk * 32 + (lane & 31);
-      for (int r0 = rbeg; r0 < rend; r0 += WR) {
-        const bool ok = cur.R < rend;
-        const int n1 = (ok && P.row_index) ? P.row_index[cur.r1] : cur.r1;
-        const float* sa = P.A + (int64_t)n1 * P.a_r1 + (int64_t)cur.r2 * P.a_r2;
-        const float* sg = P.C + (int64_t)n1 * P.c_r1 + (int64_t)cur.r2 * P.c_r2;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          float va = 0.f;
-          if (ok && k0 + cb + j < P.K) va = sa[(int64_t)(k0 + cb + j) * P.a_k];
-          As[(t >> 2) * LDWA + cb + j] = va;
-        }
-#pragma unroll
-        for (int j = 0; j < 16 * TN; ++j) {
-          float vg = 0.f;
-          const int c = (t & 3) * 16 * TN + j;
-          if (ok && n0 + c < P.N) vg = sg[(int64_t)(n0 + c) * P.c_n];
-          Gs[(t >> 2) * LDWG + c] = vg;
-        }
-        cur.advance(q64, rem64, M2);
-        __syncthreads();
-#pragma unroll 8
-        for (int rr = 0; rr < WR; rr += 2) {
-          const float a = ap[rr * LDWA];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, gp[rr * LDWG + 32 * j], acc[j], 0, 0, 0);
-        }
-        __syncthreads();
+      for (int j = 0; j < 16 * TN; ++j) {
+        float vg = 0.f;
+        const int c = (t & 3) * 16 * TN + j;
+        if (ok && n0 + c < P.N) vg = sg[(int64_t)(n0 + c) * P.c_n];
+        Gs[(t >> 2) * LDWG + c] = vg;
       }
+      cur.advance(q64, rem64, M2);
+      __syncthreads();
+#pragma unroll 8
+      for (int rr = 0; rr < WR; rr += 2) {
+        const float a = ap[rr * LDWA];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, gp[rr * LDWG + 32 * j], acc[j], 0, 0, 0);
+      }
+      __syncthreads();
     }
   } else {
     // outer mode: this lane's k index -> (u, v), fixed for the whole loop
@@ -1169,13 +1123,40 @@ int cu_count() {      // compute units of the current device (launches sized to 
   return n;
 }
 
-template <class K>
-void launch_batch(K kernel, const e3k::GemmBatch& gb, int blocks, hipStream_t st) {
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, gb);
+// The launches of the calling thread's most recent GEMM-family call (e3k_gemm_last_routes): each launch site records the kernel
+// as it spells it, "(e3k::gemm_kernel<2, false>)", and the batched kernels their number of problems.  Every entry point clears the
+// record on entry and again when it fails.
+thread_local char gemm_routes[4096];
+thread_local int gemm_routes_len = 0;
+void routes_clear() {
+  gemm_routes_len = 0;
+  gemm_routes[0] = 0;
 }
+void routes_add(const char* spelled, int n_problems) {
+  const char* s = spelled + (sizeof("(e3k::") - 1);
+  const int len = (int)strlen(s) - 1;      // (without the closing parenthesis)
+  const int room = (int)sizeof(gemm_routes) - gemm_routes_len;
+  const int w = n_problems > 0 ? snprintf(gemm_routes + gemm_routes_len, room, "%s%.*s[%d]", gemm_routes_len ? ";" : "", len, s, n_problems)
+                               : snprintf(gemm_routes + gemm_routes_len, room, "%s%.*s", gemm_routes_len ? ";" : "", len, s);
+  gemm_routes_len = w < room ? gemm_routes_len + w : (int)sizeof(gemm_routes) - 1;
+}
+int routes_kept(int rc) {      // an entry point's return: a call that fails leaves no record
+  if (rc != E3K_OK) routes_clear();
+  return rc;
+}
+}  // namespace
+// K: the kernel in parentheses (template arguments hold commas); n: problems of a batched launch, 0 for the single-problem kernels
+#define E3K_GEMM_GO(K, n, ...)          \
+  do {                                  \
+    routes_add(#K, n);                  \
+    hipLaunchKernelGGL(K, __VA_ARGS__); \
+  } while (0)
+#define E3K_GEMM_BATCH(K, b, st) E3K_GEMM_GO(K, (b).gb.n, dim3((b).blocks), dim3(256), 0, st, (b).gb)
+namespace {
 
 int validate(const e3k_gemm_problem& P, bool wgrad) {
   if (P.M1 < 0 || P.M2 <= 0 || P.N <= 0 || P.K <= 0) return E3K_ERR_INVALID;
+  if ((int64_t)P.M1 * P.M2 > E3K_GEMM_MAX_ROWS) return E3K_ERR_UNSUPPORTED;      // (the kernels' row arithmetic is int)
   if (P.M1 == 0) return E3K_OK;   // empty problem (a batch without edges): skipped, its pointers may be NULL
   if (!P.A || !P.B || !P.C) return E3K_ERR_INVALID;
   if (P.V < 0 || P.V > e3k::VMAX) return E3K_ERR_UNSUPPORTED;
@@ -1216,12 +1197,11 @@ struct Batcher {
 };
 constexpr int MAX_CALL = 64;   // problems per C-ABI call
 
-// 64-row tiles (gemm_kernel<2>) unless the launch holds at least kSmallGrid 128-row tiles.  Round 3 switched to 128-row
-// tiles from three per CU; re-measured in round 4 (tools/ab_bench.py, 2-3 interleaved rounds): the 64-row form wins at
-// every size met -- trailing Linear forward 56 vs 62 us (twice the tiles: the unequal-K problems of a launch spread more
-// evenly over the CUs), 256 molecules 4.65 vs 4.69 ms, l_max 3 7.03 vs 7.16, the protein net 8.99 vs 9.09 -- so the
-// threshold now sits above anything a layer issues and gemm_kernel<4> is the form kept for launches beyond it.
-constexpr int64_t kSmallGrid = 1 << 20;
+// Plain problems run on 64-row tiles (gemm_kernel<2>).  Round 3 switched to 128-row tiles from three per CU; re-measured in
+// round 4 (tools/ab_bench.py, 2-3 interleaved rounds): the 64-row form wins at every size met -- trailing Linear forward 56 vs
+// 62 us (twice the tiles: the unequal-K problems of a launch spread more evenly over the CUs), 256 molecules 4.65 vs 4.69 ms,
+// l_max 3 7.03 vs 7.16, the protein net 8.99 vs 9.09.  The 128-row form (gemm_kernel<4>) was kept for launches of more than
+// 2^20 such tiles, which no layer issues, and has been removed.
 
 // a forward call, planned: every problem's kind and the order in which the batches take them
 struct FwdPlan {
@@ -1229,7 +1209,6 @@ struct FwdPlan {
   const int* reps;
   const long long* key_stride;
   int n;
-  bool small_grid;
   int kind[MAX_CALL];
   int order[MAX_CALL];
 };
@@ -1243,13 +1222,11 @@ int fwd_batches(const FwdPlan& pl, int k, bool launch, hipStream_t st) {
       b.gb.tile_start[b.gb.n] = b.blocks;
       switch (k) {
         case FWD_PLAIN:
-          if (b.chained)
-            pl.small_grid ? launch_batch(e3k::gemm_kernel<2, true>, b.gb, b.blocks, st) : launch_batch(e3k::gemm_kernel<4, true>, b.gb, b.blocks, st);
-          else
-            pl.small_grid ? launch_batch(e3k::gemm_kernel<2, false>, b.gb, b.blocks, st) : launch_batch(e3k::gemm_kernel<4, false>, b.gb, b.blocks, st);
+          if (b.chained) E3K_GEMM_BATCH((e3k::gemm_kernel<2, true>), b, st);
+          else E3K_GEMM_BATCH((e3k::gemm_kernel<2, false>), b, st);
           break;
-        case FWD_SPLITK: launch_batch(e3k::gemm_splitk_kernel, b.gb, b.blocks, st); break;
-        default: launch_batch(e3k::gemm_outer_kernel, b.gb, b.blocks, st); break;
+        case FWD_SPLITK: E3K_GEMM_BATCH((e3k::gemm_splitk_kernel), b, st); break;
+        default: E3K_GEMM_BATCH((e3k::gemm_outer_kernel), b, st); break;
       }
     }
     b.reset();
@@ -1265,13 +1242,12 @@ int fwd_batches(const FwdPlan& pl, int k, bool launch, hipStream_t st) {
     const int tiles_n = (P.N + e3k::BN - 1) / e3k::BN;
     int64_t blocks;
     if (k == FWD_SPLITK) blocks = ((M + 31) / 32) * ((P.N + 31) / 32);
-    else if (k == FWD_PLAIN && pl.small_grid) blocks = ((M + 63) / 64) * tiles_n;
+    else if (k == FWD_PLAIN) blocks = ((M + 63) / 64) * tiles_n;
     else blocks = ((M + 127) / 128) * tiles_n;
     const bool compact = rp > 1 && P.group_dev && P.row_index && k == FWD_PLAIN;
     if (compact) {
       // (blocks = row tiles x workgroups per row tile: the key groups partition the rows, see fetch_problem)
-      const int64_t bm = pl.small_grid ? 64 : 128;
-      const int64_t row_tiles = (M + bm - 1) / bm, per_row = blocks / row_tiles;
+      const int64_t row_tiles = (M + 63) / 64, per_row = blocks / row_tiles;
       blocks = (row_tiles + rp) * per_row;
     } else {
       blocks *= rp;
@@ -1343,7 +1319,6 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
   // 256 molecules 3.88 -> 3.82 ms, l_max 3 6.39 -> 6.28, 32 molecules 1.52 -> 1.47, force training 5.40 -> 5.33, config_diffusion
   // 3.34 -> 3.29, config_diffusion_CA 8.03 -> 7.76.  Its 51 KB of LDS and 152 registers left three workgroups per CU where a launch
   // has two rounds of them.)
-  int64_t plain_tiles128 = 0;
   for (int i = 0; i < n_problems; ++i) {
     const e3k_gemm_problem& P = problems[i];
     const int64_t M = (int64_t)P.M1 * P.M2;
@@ -1357,16 +1332,13 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
     }
     if (P.chain > 0) {
       kind[i] = FWD_PLAIN;
-      plain_tiles128 += ((M + 127) / 128) * ((P.N + e3k::BN - 1) / e3k::BN);
       continue;
     }
     if (P.V > 0) kind[i] = FWD_OUTER;
     else if (a_vec(P) && b_mode(P) == 2 && P.K >= 256 && P.K % 64 == 0 && ((M + 63) / 64) * ((P.N + e3k::BN - 1) / e3k::BN) < 128)
       kind[i] = FWD_SPLITK;
-    else {
+    else
       kind[i] = FWD_PLAIN;
-      plain_tiles128 += ((M + 127) / 128) * ((P.N + e3k::BN - 1) / e3k::BN);   // keyed: the groups partition these rows
-    }
   }
   // A split-K problem next to plain ones costs the call a launch of its own (the accumulating second round of a layer's input
   // gradients: the gate scalars' K = 256 block of the self-connection goes split-K, its sibling of the trailing Linear plain:
@@ -1377,10 +1349,7 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
     for (int i = 0; i < n_problems; ++i) any_plain = any_plain || kind[i] == FWD_PLAIN;
     if (any_plain)
       for (int i = 0; i < n_problems; ++i)
-        if (kind[i] == FWD_SPLITK && problems[i].K <= 512) {
-          kind[i] = FWD_PLAIN;
-          plain_tiles128 += (((int64_t)problems[i].M1 * problems[i].M2 + 127) / 128) * ((problems[i].N + e3k::BN - 1) / e3k::BN);
-        }
+        if (kind[i] == FWD_SPLITK && problems[i].K <= 512) kind[i] = FWD_PLAIN;
   }
   // ... and the other way round: a PLAIN problem of a few tiles with a long-ish K loop (the radial stack's last-layer input gradient of
   // layer 0: 9 tiles, K = 192, beside its siblings' K = 960 .. 1 920 which go split-K) waits 10 us in a launch of its own for nine
@@ -1393,13 +1362,10 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
         const e3k_gemm_problem& P = problems[i];
         const int64_t M = (int64_t)P.M1 * P.M2;
         if (kind[i] == FWD_PLAIN && P.chain == 0 && !(reps && reps[i] > 1) && a_vec(P) && b_mode(P) == 2 && P.K >= 128 && P.K % 64 == 0 &&
-            ((M + 63) / 64) * ((P.N + e3k::BN - 1) / e3k::BN) < 32) {
+            ((M + 63) / 64) * ((P.N + e3k::BN - 1) / e3k::BN) < 32)
           kind[i] = FWD_SPLITK;
-          plain_tiles128 -= ((M + 127) / 128) * ((P.N + e3k::BN - 1) / e3k::BN);
-        }
       }
   }
-  pl.small_grid = plain_tiles128 < kSmallGrid;
   // longest-processing-time-first: workgroups are dispatched in blockIdx order, so the problems with the longest
   // K loops go first and the short ones fill the tail of the launch
   for (int i = 0; i < n_problems; ++i) pl.order[i] = i;
@@ -1419,7 +1385,7 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
     const e3k_gemm_problem& P = problems[i];
     const int64_t M = (int64_t)P.M1 * P.M2;
     if (kind[i] == FWD_N1 && M > 0)
-      hipLaunchKernelGGL(e3k::gemm_n1_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, P.A, P.B, (int64_t)P.M1, P.M2, P.K, P.a_r1, P.a_r2,
+      E3K_GEMM_GO((e3k::gemm_n1_kernel), 0, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, P.A, P.B, (int64_t)P.M1, P.M2, P.K, P.a_r1, P.a_r2,
                          P.a_k, P.b_k, P.c_r1, P.c_r2, P.alpha, P.bias, P.accumulate, P.act, P.act_cst, P.C);
   }
   for (int k = 0; k < FWD_KINDS; ++k) (void)fwd_batches(pl, k, true, st);      // (passed the dry run: cannot fail)
@@ -1428,7 +1394,8 @@ static int gemm_fwd_impl(const e3k_gemm_problem* problems, int n_problems, const
 }
 
 extern "C" int e3k_gemm(const e3k_gemm_problem* problems, int n_problems, void* stream) {
-  return gemm_fwd_impl(problems, n_problems, nullptr, nullptr, stream);
+  routes_clear();
+  return routes_kept(gemm_fwd_impl(problems, n_problems, nullptr, nullptr, stream));
 }
 
 static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, const int* reps, const long long* key_stride,
@@ -1447,7 +1414,7 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
     const int64_t rows = (int64_t)P.M1 * P.M2;
     int gy = (int)((rows + 31) / 32);
     if (gy > 1024) gy = 1024;
-    hipLaunchKernelGGL(e3k::wgrad_n1_kernel, dim3((P.K + 63) / 64, gy), dim3(256), 0, st, P.A, P.C, (int64_t)P.M1, P.M2, P.K, P.a_r1,
+    E3K_GEMM_GO((e3k::wgrad_n1_kernel), 0, dim3((P.K + 63) / 64, gy), dim3(256), 0, st, P.A, P.C, (int64_t)P.M1, P.M2, P.K, P.a_r1,
                        P.a_r2, P.a_k, P.c_r1, P.c_r2, P.b_k, P.alpha, const_cast<float*>(P.B));
     taken[i] = true;
   }
@@ -1474,7 +1441,7 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
     auto flush = [&]() {
       if (b.blocks) {
         b.gb.tile_start[b.gb.n] = b.blocks;
-        launch_batch(e3k::gemm_wgrad2_kernel, b.gb, b.blocks, st);
+        E3K_GEMM_BATCH((e3k::gemm_wgrad2_kernel), b, st);
       }
       b.reset();
     };
@@ -1519,10 +1486,10 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
     auto flush = [&]() {
       if (b.blocks) {
         b.gb.tile_start[b.gb.n] = b.blocks;
-        if (!outer) tn == 2 ? launch_batch(e3k::gemm_wgrad_kernel<false, 2>, b.gb, b.blocks, st)
-                            : launch_batch(e3k::gemm_wgrad_kernel<false, 1>, b.gb, b.blocks, st);
-        else tn == 2 ? launch_batch(e3k::gemm_wgrad_kernel<true, 2>, b.gb, b.blocks, st)
-                     : launch_batch(e3k::gemm_wgrad_kernel<true, 1>, b.gb, b.blocks, st);
+        if (!outer && tn == 2) E3K_GEMM_BATCH((e3k::gemm_wgrad_kernel<false, 2>), b, st);
+        else if (!outer) E3K_GEMM_BATCH((e3k::gemm_wgrad_kernel<false, 1>), b, st);
+        else if (tn == 2) E3K_GEMM_BATCH((e3k::gemm_wgrad_kernel<true, 2>), b, st);
+        else E3K_GEMM_BATCH((e3k::gemm_wgrad_kernel<true, 1>), b, st);
       }
       b.reset();
     };
@@ -1534,8 +1501,7 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
       const int64_t M = (int64_t)P.M1 * P.M2;
       if (M == 0) continue;
       const int rp = reps && reps[i] > 1 ? reps[i] : 1;
-      int f = a_vec(P) ? 1 : 0;
-      if (g_vec(P)) f |= 8;
+      const int f = g_vec(P) ? 8 : 0;      // (A by scalar loads here: a problem with both operands 16-byte-loadable took gemm_wgrad2_kernel)
       const int wn = 64 * tn;
       const int tiles = ((P.K + e3k::WK - 1) / e3k::WK) * ((P.N + wn - 1) / wn);
       int64_t splits = (kTarget + tiles - 1) / tiles;
@@ -1564,7 +1530,8 @@ static int gemm_wgrad_impl(const e3k_gemm_problem* problems, int n_problems, con
 }
 
 extern "C" int e3k_gemm_wgrad(const e3k_gemm_problem* problems, int n_problems, void* stream) {
-  return gemm_wgrad_impl(problems, n_problems, nullptr, nullptr, stream);
+  routes_clear();
+  return routes_kept(gemm_wgrad_impl(problems, n_problems, nullptr, nullptr, stream));
 }
 
 namespace {
@@ -1603,7 +1570,7 @@ int resolve_segment(const e3k_gemm_segment& sg, e3k_gemm_problem* out, int* reps
 }
 }  // namespace
 
-extern "C" int e3k_gemm_multi(const e3k_gemm_segment* segments, int32_t n_segments, int32_t wgrad, void* stream) {
+static int gemm_multi_impl(const e3k_gemm_segment* segments, int32_t n_segments, int32_t wgrad, void* stream) {
   if (n_segments < 0 || (n_segments && !segments)) return E3K_ERR_INVALID;
   e3k_gemm_problem buf[MAX_CALL];
   int reps[MAX_CALL];
@@ -1617,9 +1584,15 @@ extern "C" int e3k_gemm_multi(const e3k_gemm_segment* segments, int32_t n_segmen
   return wgrad ? gemm_wgrad_impl(buf, n, reps, ks, stream) : gemm_fwd_impl(buf, n, reps, ks, stream);
 }
 
+extern "C" int e3k_gemm_multi(const e3k_gemm_segment* segments, int32_t n_segments, int32_t wgrad, void* stream) {
+  routes_clear();
+  return routes_kept(gemm_multi_impl(segments, n_segments, wgrad, stream));
+}
+
 extern "C" int e3k_gemm_rebased(const e3k_gemm_problem* templates, int n_templates, const void* a_base,
                                 const void* a2_base, const void* b_base, void* c_base, const void* bias_base,
                                 int64_t M1, int32_t wgrad, void* stream) {
+  routes_clear();
   if (M1 < 0) return E3K_ERR_INVALID;
   e3k_gemm_segment sg{};
   sg.templates = templates; sg.n_templates = n_templates;
@@ -1631,6 +1604,7 @@ extern "C" int e3k_gemm_rebased(const e3k_gemm_problem* templates, int n_templat
 extern "C" int e3k_gemm_grouped(const e3k_gemm_problem* templates, int n_templates, const int32_t* perm,
                                 const int32_t* groups_dev, int32_t n_keys, int64_t b_key_stride, int32_t wgrad,
                                 void* stream) {
+  routes_clear();
   if (n_keys <= 0) return E3K_ERR_INVALID;
   e3k_gemm_segment sg{};
   sg.templates = templates; sg.n_templates = n_templates;
@@ -1643,6 +1617,7 @@ extern "C" int e3k_gemm_grouped_rebased(const e3k_gemm_problem* templates, int n
                                         const void* b_base, void* c_base, int64_t M1, const int32_t* perm,
                                         const int32_t* groups_dev, int32_t n_keys, int64_t b_key_stride, int32_t wgrad,
                                         void* stream) {
+  routes_clear();
   if (M1 < 0 || n_keys <= 0) return E3K_ERR_INVALID;
   e3k_gemm_segment sg{};
   sg.templates = templates; sg.n_templates = n_templates;
@@ -1653,21 +1628,21 @@ extern "C" int e3k_gemm_grouped_rebased(const e3k_gemm_problem* templates, int n
 }
 
 extern "C" int e3k_colsum(const float* G, int64_t rows, int32_t cols, int64_t ld, float* out, void* stream) {
+  routes_clear();
   if (rows < 0 || cols <= 0 || !out) return E3K_ERR_INVALID;
   if (rows == 0) return E3K_OK;
   if (!G) return E3K_ERR_INVALID;
   // (a thread's walk down its rows is a chain of load latencies: 64 rows per thread took 15 us for a 1 MB matrix -- 8 rows, 3 us)
   int gy = (int)((rows + 31) / 32);
   if (gy > 1024) gy = 1024;
-  hipLaunchKernelGGL(e3k::colsum_kernel, dim3((cols + 63) / 64, gy), dim3(256), 0, (hipStream_t)stream, G, rows, cols,
-                     ld, out);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
+  E3K_GEMM_GO((e3k::colsum_kernel), 0, dim3((cols + 63) / 64, gy), dim3(256), 0, (hipStream_t)stream, G, rows, cols, ld, out);
+  return routes_kept(hipGetLastError() == hipSuccess ? E3K_OK : E3K_ERR_LAUNCH);
 }
 
 extern "C" int e3k_fctp_reduce_bwd(const float* H, const float* X, const float* A2, int32_t M1, int32_t M2, int32_t U,
                                    int32_t V, int64_t x_r1, int64_t x_r2, int64_t a2_r1, float* dX,
                                    int32_t dx_accumulate, float* dA2, void* stream) {
+  routes_clear();
   if (M1 < 0 || M2 <= 0 || U <= 0 || V <= 0 || V > e3k::VMAX) return E3K_ERR_INVALID;
   if (M1 == 0) return E3K_OK;
   if (!H || !X || !A2 || !dX || !dA2) return E3K_ERR_INVALID;
@@ -1676,17 +1651,17 @@ extern "C" int e3k_fctp_reduce_bwd(const float* H, const float* X, const float* 
   hipStream_t st = (hipStream_t)stream;
   // 16-byte streams need: H rows (U*V floats) and the A2 rows 16-byte aligned
   const bool vec = aligned16(H) && aligned16(A2) && a2_r1 % 4 == 0 && ((int64_t)U * V) % 4 == 0 && 64 % (V / 4 > 0 ? V / 4 : 1) == 0;
-#define E3K_FCTP_VEC(VV)                                                                                              \
-  hipLaunchKernelGGL(e3k::fctp_reduce_vec_kernel<VV>, grid, dim3(256), 0, st, H, X, A2, M1, M2, U, x_r1, x_r2, a2_r1, dX, \
-                     dx_accumulate, dA2)
+#define E3K_FCTP_VEC(VV)                                                                                                   \
+  E3K_GEMM_GO((e3k::fctp_reduce_vec_kernel<VV>), 0, grid, dim3(256), 0, st, H, X, A2, M1, M2, U, x_r1, x_r2, a2_r1, dX, \
+              dx_accumulate, dA2)
   if (vec && V == 32) E3K_FCTP_VEC(32);
   else if (vec && V == 16) E3K_FCTP_VEC(16);
   else if (vec && V == 8) E3K_FCTP_VEC(8);
   else if (vec && V == 4) E3K_FCTP_VEC(4);
   else
-    hipLaunchKernelGGL(e3k::fctp_reduce_kernel, grid, dim3(256), 0, st, H, X, A2, M1, M2, U, V, x_r1, x_r2, a2_r1, dX,
-                       dx_accumulate, dA2);
+    E3K_GEMM_GO((e3k::fctp_reduce_kernel), 0, grid, dim3(256), 0, st, H, X, A2, M1, M2, U, V, x_r1, x_r2, a2_r1, dX, dx_accumulate, dA2);
 #undef E3K_FCTP_VEC
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
+  return routes_kept(hipGetLastError() == hipSuccess ? E3K_OK : E3K_ERR_LAUNCH);
 }
+
+extern "C" const char* e3k_gemm_last_routes(void) { return gemm_routes; }

@@ -211,6 +211,7 @@ SIGNATURES = {
     "e3k_tp_bwd_w": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "e3k_tp_bwd_x_overwrites": (C.c_int, [_P]),
     "e3k_tp_last_route": (C.c_char_p, []),
+    "e3k_gemm_last_routes": (C.c_char_p, []),
     "e3k_tp_table_supported": (C.c_int, [_P]),
     "e3k_tp_fwd_table": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "e3k_tp_bwd_x_table": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),

@@ -81,6 +81,10 @@ typedef struct {
                     V = 0, no bias; it brings A, B, K, their strides and alpha.  Every link runs on the plain kernel. */
 } e3k_gemm_problem;
 
+/* Rows of one problem: M1 * M2 <= E3K_GEMM_MAX_ROWS, else the call fails with E3K_ERR_UNSUPPORTED (the kernels index rows in
+ * 32-bit ints; the margin below 2^31 covers a row tile and a chunk of rows past the last one). */
+#define E3K_GEMM_MAX_ROWS ((1LL << 31) - (1LL << 16))
+
 int e3k_gemm(const e3k_gemm_problem* problems, int n_problems, void* stream);
 
 /* Weight gradient ("TN"):  B[k, n] += alpha * sum_{r1,r2} Aeff[r1,r2,k] * C[r1,r2,n]
@@ -145,6 +149,13 @@ int e3k_colsum(const float* G, int64_t rows, int32_t cols, int64_t ld, float* ou
 int e3k_fctp_reduce_bwd(const float* H, const float* X, const float* A2, int32_t M1, int32_t M2, int32_t U,
                         int32_t V, int64_t x_r1, int64_t x_r2, int64_t a2_r1, float* dX, int32_t dx_accumulate,
                         float* dA2, void* stream);
+
+/* The launches of the calling thread's most recent call of e3k_gemm, e3k_gemm_wgrad, e3k_gemm_multi, e3k_gemm_rebased,
+ * e3k_gemm_grouped, e3k_gemm_grouped_rebased, e3k_colsum or e3k_fctp_reduce_bwd, in launch order and separated by ';': the kernel
+ * as e3k_gemm.hip spells it, with the number of problems of a batched launch in brackets, e.g.
+ * "gemm_n1_kernel;gemm_kernel<2, false>[20];gemm_kernel<2, false>[3];gemm_splitk_kernel[2]".  Empty when the call launched nothing
+ * or failed (every call clears it on entry).  For tests: which kernels a call reached.  Valid until the thread's next such call. */
+const char* e3k_gemm_last_routes(void);
 
 /* ------------------------------------------------------------------------------------------
  * Edge geometry.  Replaces computeEdgeVector (data/compute_edge.py:13-36),

@@ -155,7 +155,7 @@ def test_gemm_wgrad_through_the_c_abi(dev, m1, m2, k, n, gathered):
     (1000, 3, 192, 64, 0, True),
     (333, 5, 96, 200, 1, True),       # edge tiles in rows and columns (per-element predicates), K tail
     (130, 1, 64, 72, 1, False),       # 64-row tiles of the small-grid form, column tail
-    (4700, 1, 384, 64, 1, False),     # enough tiles for the 128-row form
+    (4700, 1, 384, 64, 1, False),     # 74 row tiles of 64: a launch of several rounds of workgroups
     (4704, 1, 64, 1, 0, True),        # one output column (the energy head): a wave per row, not a tile kernel
     (333, 3, 100, 1, 1, False),
 ])
@@ -254,9 +254,9 @@ def test_gemm_k_chain_through_the_c_abi(dev, m1, m2, n, ks, accumulate, bias, kd
 
 def test_gemm_call_that_fails_sizing_writes_nothing(dev):
     """e3k_gemm plans the whole call before its first launch: a problem that passes the argument checks but is too large for one
-    launch ((2^31 - 1) x 1024 rows: ~2^34 tiles) fails the call, and the one-column problem in front of it has not written its C
-    (a retry with `accumulate` set would otherwise add it twice).  The large problem never reaches a kernel: its sizing check
-    precedes its launch."""
+    launch (2^30 rows, 2^20 columns: ~2^38 tiles) fails the call, and the one-column problem in front of it has not written its C
+    (a retry with `accumulate` set would otherwise add it twice) nor launched at all (an empty launch record).  The large problem
+    never reaches a kernel: its sizing check precedes its launch."""
     from e3_layers_amd.backend import lib as L
 
     torch.manual_seed(3)
@@ -271,11 +271,12 @@ def test_gemm_call_that_fails_sizing_writes_nothing(dev):
     small = torch.zeros(64, 64, device=dev)
     q = L.GemmProblem()
     q.A, q.A2, q.B, q.C, q.bias, q.row_index, q.group_dev = small.data_ptr(), None, small.data_ptr(), small.data_ptr(), None, None, None
-    q.M1, q.M2, q.N, q.K, q.V, q.accumulate = 2 ** 31 - 1, 1024, 64, 64, 0, 0
+    q.M1, q.M2, q.N, q.K, q.V, q.accumulate = 2 ** 30, 1, 2 ** 20, 64, 0, 0      # (rows within E3K_GEMM_MAX_ROWS)
     q.a_r1, q.a_r2, q.a_k, q.b_k, q.b_n, q.c_r1, q.c_r2, q.c_n = 64, 64, 1, 64, 1, 64, 64, 1
     q.alpha, q.act, q.act_cst, q.chain = 1.0, 0, 1.0, 0
     arr = (L.GemmProblem * 2)(p, q)
-    assert L.load().e3k_gemm(arr, 2, L.stream_ptr()) != 0
+    assert L.load().e3k_gemm(arr, 2, L.stream_ptr()) == -1      # E3K_ERR_INVALID
+    assert L.load().e3k_gemm_last_routes().decode() == ""
     torch.cuda.synchronize()
     assert torch.equal(c, before)
     # alone, the first problem does write C
