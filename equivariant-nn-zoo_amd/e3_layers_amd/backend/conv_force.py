@@ -9,18 +9,19 @@ Rounds 1-3 served this with the composed path -- one ``autograd.Function`` per k
 ``[E, W]`` tensors: 668 launches and 11.9 ms for 64 molecules.  Here the layer is THREE autograd nodes whose
 bodies issue the kernels back to back:
 
-  ``ForceBlockFn.forward``    x -> y: keyed self-connection + linear_1 -> table-form tensor product -> trailing Linear -> gate
-                              (the same sequence as ``conv_block``; outputs the layer's intermediates x1 / conv as well, so that
-                              the second-order pass below can send cotangents to them)
+  ``ForceBlockFn.forward``    x -> y: keyed self-connection + linear_1 -> tensor product -> trailing Linear -> gate (the same
+                              sequence as ``conv_block``; outputs the layer's intermediates x1 / conv as well, so that the
+                              second-order pass below can send cotangents to them).  The per-edge weights ``w[E, W]`` and
+                              their slope ``dw/dr[E, W]`` are interpolated from the tables T and D (``radial_table``) once
+                              per layer; every tensor-product kernel of the three passes streams those rows.
   ``ForceBlockBwdFn.forward`` the FIRST backward (forces): g_y -> g_x, g_sh, g_r.  Inputs-only (``ops.inputs_only_backward``:
-                              no parameter gradient is formed).  The per-edge weights and their slope come from the tables
-                              T and D (``radial_table``): ``w[E, W]`` and ``dw/dr[E, W]`` never exist -- ``e3k_tp_bwd_e_table``
-                              reduces d/dsh to nine and d/dr to one number per edge in registers.
+                              no parameter gradient is formed).  ``e3k_tp_bwd_xe`` forms the input gradient and reduces
+                              d/dsh to nine and d/dr to one number per edge in registers, in one walk.
   ``ForceBlockBwdFn.backward``  the adjoint of that pass ("u-sweep": runs layer 0 -> L-1 in the final backward): every
                               contraction is multilinear, so the adjoint of each kernel is one of its siblings with operands
                               exchanged -- the three tensor-product terms of the product rule in ONE walk
-                              (``e3k_tp_fwd_jvp_table``), likewise ``e3k_tp_bwd_x_dual_table`` / ``e3k_tp_bwd_w_dual`` -- and
-                              the gradients of T and D are transposed interpolations of ``[E, W]`` weight gradients.
+                              (``e3k_tp_fwd_jvp_table``), likewise the dual input and weight gradients (``e3k_tp_bwd_xw_dual``)
+                              -- and the gradients of T and D are transposed interpolations of ``[E, W]`` weight gradients.
   ``ForceBlockFn.backward``   the ordinary first-order backward ("v-sweep", L-1 -> 0) with the u-sweep's cotangents of x1 and
                               conv added in: parameter gradients straight into the gradient sink.
 
@@ -41,12 +42,7 @@ from . import ops, radial_table
 from .conv_block import ConvBlockPlan, _grad_buffer
 
 ENABLED = _knob("E3K_FORCE_BLOCK")
-# 1: a layer interpolates its per-edge weights w [E, W] (forward) and their slope dw/dr [E, W] (first backward) ONCE and every
-# tensor-product kernel of the three passes streams those rows; 0: every kernel gathers four rows per table and edge itself (the
-# in-kernel form of the energy step).  Five or six kernels per layer read them: 64 molecules 7.03 -> see DESIGN.md ms per step.
-MATERIALIZE = _knob("E3K_FORCE_MATERIALIZE")
 EDGE_ATOMICS = _knob("E3K_FORCE_EDGE_ATOMICS")      # 1: rounds 4-5's atomics on g_sh / g_r (not reproducible run to run)
-FUSE_XW = _knob("E3K_TP_BWD_FUSED")      # the input and the weight gradient of the tensor product in one walk (as conv_native)
 STATS = [0, 0, 0]      # forwards, first backwards (create_graph), u-sweeps (tests)
 _WARNED = [False]
 _DECLINE = [0]
@@ -67,38 +63,16 @@ class declined:
 
 def supported(plan: ConvBlockPlan, dev) -> bool:
     """Layers the force block serves: keyed self-connection inside the block, a tensor-product plan with the second-order kernels
-    (channel-complete: the 64-channel models, l_max <= 3)."""
+    on streamed weights (channel-complete: the 64-channel models, l_max <= 3, including the plans walked by two waves per group)."""
     if not ENABLED or _DECLINE[0] or plan is None or plan.addend or plan.sc_spec is None:
         return False
     hit = plan.__dict__.get("_force_ok")
     if hit is None:
-        h = plan.tp_plan.handle(dev)
-        # (with the weights materialised -- the default -- the second-order kernels also exist for the l_max 3 plans that are walked
-        #  by two waves per group)
-        hit = plan.__dict__["_force_ok"] = bool(L.load().e3k_tp_table2_supported(h)
-                                                or (MATERIALIZE and L.load().e3k_tp_second_order_streamed_supported(h)))
+        hit = plan.__dict__["_force_ok"] = bool(L.load().e3k_tp_second_order_streamed_supported(plan.tp_plan.handle(dev)))
     return hit
 
 
-# ---- raw launches of the table-form tensor-product kernels ------------------------------------------------------------------
-def _tp_fwd_table(x1, sh, T, bins, topo, tp):
-    n, e = x1.shape[0], sh.shape[0]
-    out = torch.empty(n, tp.d_mid, device=x1.device, dtype=torch.float32)
-    L.check(L.load().e3k_tp_fwd_table(tp.handle(x1.device), L.ptr(x1), L.ptr(sh), L.ptr(T), L.ptr(bins.bin), L.ptr(bins.coef),
-                                      L.ptr(topo.src), L.ptr(topo.dst_ptr), L.ptr(topo.dst_perm), n, e, L.ptr(out), L.stream_ptr()),
-            "e3k_tp_fwd_table")
-    return out
-
-
-def _tp_bwd_x_table(sh, T, bins, g_mid, topo, tp):
-    n, e = g_mid.shape[0], sh.shape[0]
-    gx = (torch.empty if tp.bwd_x_overwrites(sh.device) else torch.zeros)(n, tp.d_in, device=sh.device, dtype=torch.float32)
-    L.check(L.load().e3k_tp_bwd_x_table(tp.handle(sh.device), L.ptr(sh), L.ptr(T), L.ptr(bins.bin), L.ptr(bins.coef), L.ptr(g_mid),
-                                        L.ptr(topo.dst), L.ptr(topo.src_ptr), L.ptr(topo.src_perm), n, e, L.ptr(gx), L.stream_ptr()),
-            "e3k_tp_bwd_x_table")
-    return gx
-
-
+# ---- raw launches of the second-order tensor-product kernels ----------------------------------------------------------------
 def _tp_fwd_ptable(x1, sh, packed, bins, topo, tp):
     """the forward from the PACKED table (``radial_table.pack_raw``)"""
     n, e = x1.shape[0], sh.shape[0]
@@ -221,7 +195,7 @@ class _Cfg:
     def __init__(self, plan, topo, groups, bins, in_cf, out_cf, sh_data):
         self.plan, self.topo, self.groups, self.bins = plan, topo, groups, bins
         self.in_cf, self.out_cf, self.sh_data = bool(in_cf), bool(out_cf), bool(sh_data)
-        self.w = self.dw = None      # MATERIALIZE: the layer's per-edge weights / their slope [E, W], interpolated once
+        self.w = self.dw = None      # the layer's per-edge weights / their slope [E, W], interpolated once and streamed
 
     def weights(self, T, D=None):
         """``D``: the slope will be needed too (the geometry requires grad): both tables in one pass"""
@@ -254,7 +228,7 @@ class ForceBlockFn(torch.autograd.Function):
     def forward(ctx, x, m, T, D, sh, r, w_lin1, w_post, cfg: _Cfg):
         L.require_cuda(x, m, T, sh)
         x, m, T, D, sh = L.f32c(x), L.f32c(m), L.f32c(T), L.f32c(D), L.f32c(sh)
-        plan, topo, groups, bins = cfg.plan, cfg.topo, cfg.groups, cfg.bins
+        plan, topo, groups = cfg.plan, cfg.topo, cfg.groups
         n, dev = x.shape[0], x.device
         x_cf = _to_cf(x, plan, cfg.in_cf)
         x1 = torch.empty(n, plan.lin1_spec.d_out, device=dev, dtype=torch.float32)
@@ -262,10 +236,7 @@ class ForceBlockFn(torch.autograd.Function):
         # both readers of x_cf in one launch: the keyed self-connection and linear_1
         ops._run_segments([ops._grp_segs("fwd", x_cf, m, conv, groups, plan.sc_spec, plan.sc_m_off),
                            ops._lin_fwd_segs(x_cf, w_lin1, x1, plan.lin1_spec, 1.0, False)])
-        if MATERIALIZE:
-            mid = ops._tp_fwd_raw(x1, sh, cfg.weights(T, D if ctx.needs_input_grad[4] else None), topo, plan.tp_plan)
-        else:
-            mid = _tp_fwd_table(x1, sh, T, bins, topo, plan.tp_plan)
+        mid = ops._tp_fwd_raw(x1, sh, cfg.weights(T, D if ctx.needs_input_grad[4] else None), topo, plan.tp_plan)
         ops._lin_fwd_raw(mid, w_post, None, conv, plan.post_spec, plan.scale, True)      # conv += scale * Linear(mid)
         y = ops._gate_fwd_raw(conv, plan.gate_spec, cfg.out_cf)
         STATS[0] += 1
@@ -316,22 +287,13 @@ class ForceBlockFn(torch.autograd.Function):
             ops._run_segments([ops._lin_dgrad_segs(g_conv, w_post, g_mid, plan.post_spec, plan.scale, False),
                                ops._grp_segs("dgrad", g_conv, m, g_xcf, groups, plan.sc_spec, plan.sc_m_off)])
             g_w = None
-            if MATERIALIZE:
-                if want_e and FUSE_XW:                    # input, edge (and weight) gradients in one walk (csrc/e3k_tp.hip MODE 8)
-                    g_x1, g_sh, g_r, g_w = _tp_bwd_xe(x1, sh, cfg.weights(T), cfg.slopes(D), g_mid, topo, tp, bool(params and need[2]))
-                elif params and need[2] and FUSE_XW:      # both gradients of the product in one walk (MODE 6)
-                    g_x1, g_w = ops._tp_bwd_xw_raw(x1, sh, cfg.weights(T), g_mid, topo, tp)
-                else:
-                    g_x1 = ops._tp_bwd_x_raw(sh, cfg.weights(T), g_mid, topo, tp)
-                    if want_e:
-                        g_sh, g_r = _tp_bwd_e_table(x1, sh, cfg.weights(T), cfg.slopes(D), None, g_mid, topo, tp)
+            if want_e:                       # input, edge (and weight) gradients in one walk (csrc/e3k_tp.hip MODE 8)
+                g_x1, g_sh, g_r, g_w = _tp_bwd_xe(x1, sh, cfg.weights(T), cfg.slopes(D), g_mid, topo, tp, bool(params and need[2]))
+            elif params and need[2]:         # both gradients of the product in one walk (MODE 6)
+                g_x1, g_w = ops._tp_bwd_xw_raw(x1, sh, cfg.weights(T), g_mid, topo, tp)
             else:
-                g_x1 = _tp_bwd_x_table(sh, T, bins, g_mid, topo, tp)
-                if want_e:
-                    g_sh, g_r = _tp_bwd_e_table(x1, sh, T, D, bins, g_mid, topo, tp)
-            if params and need[2]:
-                if g_w is None:
-                    g_w, _ = ops._tp_bwd_w_raw(x1, sh, None, g_mid, topo, tp, False, True)
+                g_x1 = ops._tp_bwd_x_raw(sh, cfg.weights(T), g_mid, topo, tp)
+            if g_w is not None:
                 g_T = radial_table.interp_bwd_raw(g_w, bins)
         if g_x1_in is not None:
             g_x1 = L.f32c(g_x1_in) if g_x1 is None else g_x1.add_(g_x1_in)
@@ -363,7 +325,7 @@ class ForceBlockBwdFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, g_y, x1, conv, m, T, D, sh, w_lin1, w_post, cfg: _Cfg):
-        plan, topo, groups, bins, tp = cfg.plan, cfg.topo, cfg.groups, cfg.bins, cfg.plan.tp_plan
+        plan, topo, groups, tp = cfg.plan, cfg.topo, cfg.groups, cfg.plan.tp_plan
         g_y = L.f32c(g_y)
         dev, n = conv.device, conv.shape[0]
         g_conv = ops._gate_bwd_raw(conv, g_y, plan.gate_spec, cfg.out_cf)
@@ -371,14 +333,7 @@ class ForceBlockBwdFn(torch.autograd.Function):
         g_xcf = (torch.empty if plan.sc_spec.in_covered else torch.zeros)(n, plan.sc_spec.d_in, device=dev, dtype=torch.float32)
         ops._run_segments([ops._lin_dgrad_segs(g_conv, w_post, g_mid, plan.post_spec, plan.scale, False),
                            ops._grp_segs("dgrad", g_conv, m, g_xcf, groups, plan.sc_spec, plan.sc_m_off)])
-        if MATERIALIZE and FUSE_XW:
-            g_x1, g_sh, g_r, _ = _tp_bwd_xe(x1, sh, cfg.weights(T), cfg.slopes(D), g_mid, topo, tp, False)
-        elif MATERIALIZE:
-            g_x1 = ops._tp_bwd_x_raw(sh, cfg.weights(T), g_mid, topo, tp)
-            g_sh, g_r = _tp_bwd_e_table(x1, sh, cfg.weights(T), cfg.slopes(D), None, g_mid, topo, tp)
-        else:
-            g_x1 = _tp_bwd_x_table(sh, T, bins, g_mid, topo, tp)
-            g_sh, g_r = _tp_bwd_e_table(x1, sh, T, D, bins, g_mid, topo, tp)
+        g_x1, g_sh, g_r, _ = _tp_bwd_xe(x1, sh, cfg.weights(T), cfg.slopes(D), g_mid, topo, tp, False)
         ops._run_segments([ops._lin_dgrad_segs(g_x1, w_lin1, g_xcf, plan.lin1_spec, 1.0, True)])
         g_x = g_xcf if cfg.in_cf else ops._relayout_raw(g_xcf, plan.in_blocks, False)
         STATS[1] += 1
@@ -434,24 +389,12 @@ class ForceBlockBwdFn(torch.autograd.Function):
             u_gx1 = torch.zeros(n, plan.lin1_spec.d_out, device=dev, dtype=torch.float32)
         # tensor-product family: Phi = <u_gx1, g_x1> + <u_sh, g_sh> + <u_r, g_r> is the derivative of <g_mid, TP(x1, sh, w(r))> along
         # (u_gx1, u_sh, u_r)
-        if MATERIALIZE:
-            wv, dwv, kb = cfg.weights(T), cfg.slopes(D), None
-        else:
-            wv, dwv, kb = T, D, bins
-        cot_gmid = _tp_fwd_jvp(x1, u_gx1, sh, u_sh, wv, dwv, kb, u_r, topo, tp)
-        g_T = g_D = None
-        if MATERIALIZE and FUSE_XW and need[1] and need[4]:      # the three walks below as one (csrc/e3k_tp.hip MODE 7)
-            cot_x1, gw_dual, gw_plain = _tp_bwd_xw_dual(x1, u_gx1, sh, u_sh, wv, dwv, u_r, g_mid, topo, tp, bool(need[5]))
-            g_T = radial_table.interp_bwd_raw(gw_dual, bins)
-            if need[5]:
-                g_D = radial_table.interp_bwd_raw(gw_plain, bins, scale=u_r)
-        else:
-            cot_x1 = _tp_bwd_x_dual(sh, u_sh, wv, dwv, kb, u_r, g_mid, topo, tp) if need[1] else None
-            if need[4]:
-                g_T = radial_table.interp_bwd_raw(_tp_bwd_w_dual(x1, u_gx1, sh, u_sh, g_mid, topo, tp), bins)
-            if need[5]:
-                g_w, _ = ops._tp_bwd_w_raw(x1, sh, None, g_mid, topo, tp, False, True)
-                g_D = radial_table.interp_bwd_raw(g_w, bins, scale=u_r)
+        w, dw = cfg.weights(T), cfg.slopes(D)
+        cot_gmid = _tp_fwd_jvp(x1, u_gx1, sh, u_sh, w, dw, None, u_r, topo, tp)
+        # the cotangent of x1 and the weight gradients of the dual and the plain product in one walk (csrc/e3k_tp.hip MODE 7)
+        cot_x1, gw_dual, gw_plain = _tp_bwd_xw_dual(x1, u_gx1, sh, u_sh, w, dw, u_r, g_mid, topo, tp, bool(need[5]))
+        g_T = radial_table.interp_bwd_raw(gw_dual, bins) if need[4] else None
+        g_D = radial_table.interp_bwd_raw(gw_plain, bins, scale=u_r) if need[5] else None
         # trailing Linear: g_mid = scale * Linear^T(g_conv)
         if cot_gconv is None:
             cot_gconv = (torch.empty if plan.post_spec.out_covered else torch.zeros)(n, plan.post_spec.d_out, device=dev, dtype=torch.float32)

@@ -1,19 +1,19 @@
-"""The fused convolution block through the native layer executor (``csrc/e3k_layer.hip``).
+"""The fused convolution block (``backend/conv_block.py``) through the native layer executor (``csrc/e3k_layer.hip``).
 
-Same arithmetic, same kernels and the same stream layout as ``backend/conv_block.py`` -- which stays as the readable
-definition of the sequence and serves whatever this path declines -- but the launches of a layer's forward (and of its
-backward) are issued by ONE C call: Python allocates the outputs (two or three buffers per pass instead of twenty
-tensors), fills one argument struct and returns.  Reference: ``FactorizedConvolution.forward`` + ``Gate``
+The launches of a layer's forward (and of its backward) are issued by ONE C call: Python allocates the outputs (two or
+three buffers per pass instead of twenty tensors), fills one argument struct and returns.  The executor takes a layer
+when ``NativeLayer`` can describe it; ``MessagePassing._block_plan`` builds that description and gives a layer it
+declines no plan, so such a layer takes the composed per-op path -- the readable definition of the arithmetic, against
+which the tests pin this one.  Reference: ``FactorizedConvolution.forward`` + ``Gate``
 (``e3_layers/nn/message_passing.py:91-124, 249``).
 
-Host time per layer: 0.22 -> 0.05 ms forward, 0.30 -> 0.07 ms backward (32 molecules, where the step is host-bound).
-``E3K_LAYER_NATIVE=0`` keeps the Python sequence.
+Host time per layer: 0.22 -> 0.05 ms forward, 0.30 -> 0.07 ms backward (32 molecules, where the step is host-bound),
+against the same sequence issued from Python.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import List, Optional
+from typing import List
 
 import torch
 
@@ -23,8 +23,9 @@ from torch.autograd.function import once_differentiable
 from . import lib as L
 from . import ops, radial_table
 
-ENABLED = _knob("E3K_LAYER_NATIVE")
-AHEAD_STATS = [0]
+# bench.py reads these three to describe the path it measured; the executor, the packed table and the fused
+# tensor-product backward are the only forms there are
+ENABLED = TP_TABLE_PACKED = TP_BWD_FUSED = 1
 PROF_KINDS = {"tp_fwd": 0, "tp_bwd_x": 1, "tp_bwd_w": 2, "rtable_fwd": 3, "rtable_bwd": 4, "radial_last_fwd": 5}
 _LAYERS: List["NativeLayer"] = []      # every layer object created (bench.py arms / reads their per-kernel timers)
 
@@ -39,11 +40,7 @@ class NativeLayer:
         self.plan = plan
         self.handles = {}          # device index -> e3k_layer*
         self.keep = []             # ctypes arrays referenced by the descriptor until create() has copied them
-        self.ok = True
-        try:
-            self.desc = self._describe(plan)
-        except NotImplementedError:
-            self.ok = False
+        self.desc = self._describe(plan)      # (NotImplementedError: the executor does not take this layer)
         _LAYERS.append(self)
 
     def _set(self, rounds) -> L.GemmSet:
@@ -130,9 +127,7 @@ class NativeLayer:
             raise NotImplementedError("layer dims")
         return d
 
-    def handle(self, device) -> Optional[int]:
-        if not self.ok:
-            return None
+    def handle(self, device) -> int:
         idx = device.index if device.index is not None else torch.cuda.current_device()
         h = self.handles.get(idx)
         if h is None:
@@ -171,11 +166,12 @@ class NativeLayer:
             pass
 
 
-def native_layer(plan) -> Optional[NativeLayer]:
+def native_layer(plan) -> NativeLayer:
+    """The plan's executor layer, built on first use (raises NotImplementedError for a layer the executor does not take)."""
     nl = plan.__dict__.get("_native")
     if nl is None:
         nl = plan.__dict__["_native"] = NativeLayer(plan)
-    return nl if nl.ok else None
+    return nl
 
 
 def _record_once(t, stream) -> None:
@@ -213,17 +209,10 @@ class _Carve:
 
 # 1: layers on the knot table whose tensor-product plan has the in-kernel form (e3k_tp_table_supported: the l_max 2 models)
 # interpolate their path weights inside tp_fwd / tp_bwd_x: no interpolation pass, no w[E, W] (0.2-0.3 GB a layer at 256
-# molecules) written, read twice and kept for the backward
+# molecules) written, read twice and kept for the backward.  They read the table PACKED into one 12-byte record per (knot,
+# weight) (e3k_rtable_pack: the cubic's Taylor coefficients about the middle of the knot interval, the two small ones in
+# fp16): one dwordx3 load per path slot
 TP_TABLE = _knob("E3K_TP_TABLE")
-# 1: the addend of an addend-form layer (ConvBlockPlan.addend) is accumulated on in place instead of being copied into the block's buffer
-ADDEND_INPLACE = _knob("E3K_ADDEND_INPLACE")
-
-
-# 1: ... from the table PACKED into one 12-byte record per (knot, weight) (e3k_rtable_pack: the cubic's Taylor coefficients about the
-# middle of the knot interval, the two small ones in fp16): one dwordx3 load per path slot instead of four dword loads out of four
-# rows; 0: the four-row form of round 4
-TP_TABLE_PACKED = _knob("E3K_TP_TABLE_PACKED")
-TP_BWD_FUSED = _knob("E3K_TP_BWD_FUSED")
 
 
 def _packed_buffer(rows: int, width: int, dev) -> torch.Tensor:
@@ -356,7 +345,7 @@ class RadialStackFn(torch.autograd.Function):
             rad.h = _ptr(buf, carve.off["h"])
             if use_table:
                 rad.T = out.data_ptr()
-                if TP_TABLE_PACKED and slope is None and blocks == 1 and in_kernel_table(plan, True, dev):
+                if slope is None and blocks == 1 and in_kernel_table(plan, True, dev):
                     # the in-kernel form's packed table: written by the stack's own launch for all layers (e3k_rtable_pack_multi)
                     out._e3k_packed = _packed_buffer(r, plan.last_spec.d_out, dev)
                     rad.in_kernel, rad.P = 1, out._e3k_packed.data_ptr()
@@ -562,7 +551,7 @@ def _radial_alloc(plan, edge_radial, table, n_edges: int, keep: bool, dev):
     buf = carve.alloc(dev)
     w = None if in_kernel_table(plan, table, dev) else torch.empty(n_edges, width, device=dev, dtype=torch.float32)
     t_tab = torch.empty(r, width, device=dev, dtype=torch.float32) if table is not None else None
-    if t_tab is not None and w is None and TP_TABLE_PACKED:
+    if t_tab is not None and w is None:
         t_tab._e3k_packed = _packed_buffer(r, width, dev)
     return buf, carve, w, t_tab
 
@@ -601,7 +590,7 @@ class NativeConvBlockFn(torch.autograd.Function):
             L.require_cuda(addend)
             # the tensor itself becomes the block's pre-gate buffer (as Linear(base=...) does): the trailing Linear accumulates into
             # it, the gate's backward reads it -- no copy.  (A caller that handed in something that had to be converted gets the copy.)
-            addend_inplace = bool(ADDEND_INPLACE) and addend is given and not (addend.is_leaf and addend.requires_grad)
+            addend_inplace = addend is given and not (addend.is_leaf and addend.requires_grad)
         n, e = x.shape[0], sh.shape[0]
         if addend is not None and tuple(addend.shape) != (n, plan.post_spec.d_out):
             raise ValueError(f"addend {tuple(addend.shape)} is not [N, d_conv] = ({n}, {plan.post_spec.d_out})")
@@ -619,13 +608,11 @@ class NativeConvBlockFn(torch.autograd.Function):
         inker = in_kernel_table(plan, table, dev)
         if stack and inker:
             w = None                                 # the tensor-product kernels read the table rows themselves
-            p_ready = False
-            if TP_TABLE_PACKED:
-                p_tab = getattr(pre, "_e3k_packed", None)      # packed by the stack, with the tables of the other layers
-                p_ready = p_tab is not None
-                if p_tab is None:
-                    with conv_block._on(side, main):     # (packed behind the stack's rows, on the radial stream)
-                        p_tab = _packed_buffer(pre.shape[0], plan.last_spec.d_out, dev)
+            p_tab = getattr(pre, "_e3k_packed", None)      # packed by the stack, with the tables of the other layers
+            p_ready = p_tab is not None
+            if p_tab is None:
+                with conv_block._on(side, main):     # (packed behind the stack's rows, on the radial stream)
+                    p_tab = _packed_buffer(pre.shape[0], plan.last_spec.d_out, dev)
             _stack_radial_struct(a.rad, plan, pre, table, e, None, p_tab, packed=p_ready)
         elif stack and table is None:
             w = pre                                  # per-edge weights straight from the stack
@@ -633,7 +620,6 @@ class NativeConvBlockFn(torch.autograd.Function):
         elif pref is not None and pref[0][0] is edge_radial and pref[0][1] is table and pref[0][2:] == (keep, fork, mode):
             rbuf, rcarve, w, t_tab = pref[1]
             a.has_w = 1
-            AHEAD_STATS[0] += 1
             conv_block.AHEAD_STATS[0] += 1
             if stack:
                 _stack_radial_struct(a.rad, plan, pre, table, e, w)
@@ -653,25 +639,21 @@ class NativeConvBlockFn(torch.autograd.Function):
         nxt_keep = None
         if stack and nxt is not None and fork and conv_block.LOOK_AHEAD and table is not None and not inker:
             plan_n, pre_n = nxt
-            nl_n = native_layer(plan_n)
-            if nl_n is not None:
-                with conv_block._on(side, main):
-                    w_n = torch.empty(e, plan_n.last_spec.d_out, device=dev, dtype=torch.float32)
-                rad_n = L.LayerRadial()
-                _stack_radial_struct(rad_n, plan_n, pre_n, table, e, w_n)
-                a.next, a.next_rad = nl_n.handle(dev), C.pointer(rad_n)
-                nxt_keep = (rad_n, None, None, w_n, None, plan_n, pre_n)
+            with conv_block._on(side, main):
+                w_n = torch.empty(e, plan_n.last_spec.d_out, device=dev, dtype=torch.float32)
+            rad_n = L.LayerRadial()
+            _stack_radial_struct(rad_n, plan_n, pre_n, table, e, w_n)
+            a.next, a.next_rad = native_layer(plan_n).handle(dev), C.pointer(rad_n)
+            nxt_keep = (rad_n, None, None, w_n, None, plan_n, pre_n)
         elif nxt is not None and fork and conv_block.LOOK_AHEAD and not stack:
             plan_n, w_last_n, w_hidden_n = nxt
-            nl_n = native_layer(plan_n)
-            if nl_n is not None:
-                with conv_block._on(side, main):
-                    nbuf, ncarve, w_n, t_n = _radial_alloc(plan_n, edge_radial, table, e, keep, dev)
-                rad_n = L.LayerRadial()
-                _radial_struct(rad_n, plan_n, edge_radial, table, e, keep, w_last_n, w_hidden_n, nbuf, ncarve, w_n, t_n,
-                               getattr(t_n, "_e3k_packed", None) if t_n is not None else None)
-                a.next, a.next_rad = nl_n.handle(dev), C.pointer(rad_n)
-                nxt_keep = (rad_n, nbuf, ncarve, w_n, t_n, plan_n, w_last_n)
+            with conv_block._on(side, main):
+                nbuf, ncarve, w_n, t_n = _radial_alloc(plan_n, edge_radial, table, e, keep, dev)
+            rad_n = L.LayerRadial()
+            _radial_struct(rad_n, plan_n, edge_radial, table, e, keep, w_last_n, w_hidden_n, nbuf, ncarve, w_n, t_n,
+                           getattr(t_n, "_e3k_packed", None) if t_n is not None else None)
+            a.next, a.next_rad = native_layer(plan_n).handle(dev), C.pointer(rad_n)
+            nxt_keep = (rad_n, nbuf, ncarve, w_n, t_n, plan_n, w_last_n)
         # --- node side buffers: one allocation
         carve = _Carve()
         need_relayout = (not in_cf) and bool(tuple(b for b in plan.in_blocks if b[1] > 1 and b[2] > 1))
@@ -810,7 +792,7 @@ class NativeConvBlockFn(torch.autograd.Function):
         a.N, a.E = n, e
         a.in_cf, a.out_cf, a.fork = int(in_cf), int(out_cf), int(fork)
         a.need_x, a.need_attrs, a.need_radial = int(need_x), int(bool(need_attrs and has_sc)), int(need_radial)
-        a.fuse_xw = int(TP_BWD_FUSED)
+        a.fuse_xw = 1
         a.main, a.side, a.side2, a.side3 = main.cuda_stream, side.cuda_stream, side2.cuda_stream, side3.cuda_stream
         a.x_cf = _ptr(buf, off["x_cf"]) if need_relayout else x_in.data_ptr()
         a.sh, a.x1, a.mid = sh.data_ptr(), _ptr(buf, off["x1"]), _ptr(buf, off["mid"])

@@ -58,9 +58,6 @@ class timed_launch:
         return False
 
 _side_streams: Dict[int, "torch.cuda.Stream"] = {}
-# E3K_FWD_FORK=2: also fork while a HIP graph is being captured (multi-stream capture).  ROCm's graph executor did not
-# run the captured branches concurrently (8.45 vs 8.35 ms at 256 molecules), so the default keeps captures single-stream.
-FORK_IN_CAPTURE = _knob("E3K_FWD_FORK") == 2
 
 
 _stream_objects: Dict[tuple, "torch.cuda.Stream"] = {}
@@ -119,7 +116,7 @@ def join_side_streams() -> None:
     know about them: the optimizer / all-reduce call this first."""
     if not _side_streams or not torch.cuda.is_available():
         return
-    if not (FORK_IN_CAPTURE or not torch.cuda.is_current_stream_capturing()):
+    if torch.cuda.is_current_stream_capturing():      # (nothing forks while a graph is captured)
         return
     cur_dev = torch.cuda.current_device()
     for key, st in _side_streams.items():

@@ -22,26 +22,17 @@ from typing import Dict, Tuple
 KNOBS: Dict[str, Tuple[object, str, str]] = {
     # ---- which path a convolution layer takes (nn/message_passing.py) ----
     "E3K_CONV_BLOCK": (1, "path", "a layer as one autograd node (backend/conv_block.py); 0: one autograd.Function per kernel (the definition)"),
-    "E3K_LAYER_NATIVE": (1, "path", "the fused layer's launch sequence issued by csrc/e3k_layer.hip; 0: the same sequence from Python"),
     "E3K_FORCE_BLOCK": (1, "path", "force training: a layer as three autograd nodes on the value + slope tables (backend/conv_force.py); 0: composed per-edge path"),
-    "E3K_FORCE_MATERIALIZE": (1, "path", "force block: per-edge weights / slopes interpolated once per layer and streamed; 0: every kernel gathers the table rows"),
     "E3K_GEMM_CHAIN": (1, "path", "a Linear's terms that add onto one block (an irrep feeding two outputs: the second was an accumulating launch of its own) run as ONE K-chained GEMM problem; 0: one round of launches per term"),
     "E3K_FORCE_EDGE_ATOMICS": (0, "path", "force block: 1 = g_sh / g_r accumulated with float atomics across a plan's groups (rounds 4-5: forces not bit-reproducible); 0 = per-item partials combined in a fixed order"),
     "E3K_BLOCK_ADDEND": (1, "path", "layers with un-keyed node attributes run as fused blocks with the self-connection handed in as addend"),
-    "E3K_ADDEND_INPLACE": (1, "path", "the addend tensor itself is the block's pre-gate buffer (no copy)"),
-    "E3K_ADDEND_FORK": (1, "path", "addend blocks fork their radial branch under the same edge-count rule as keyed blocks"),
     "E3K_BLOCK_LOOK_AHEAD": (1, "path", "a forked layer issues the next layer's radial branch behind its own tensor product"),
     "E3K_CF_CHAIN": (1, "path", "consecutive MessagePassing layers hand their features over channel-fastest"),
-    "E3K_CF_CHAIN_NORM": (1, "path", "... also through LayerNormalization"),
-    "E3K_FUSED_MLP": (1, "path", "hidden chain of the radial MLP in one launch (csrc/e3k_mlp.hip); 0: one GEMM + activation per layer"),
     "E3K_RADIAL_STACK": (1, "path", "the radial MLPs of all layers on one edge embedding evaluated as one batch"),
     "E3K_KW_STACK": (1, "path", "the per-key self-connection weights of all layers formed as one batch"),
-    "E3K_TP_TABLE": (1, "path", "table layers interpolate their path weights inside the tensor-product kernels (no w[E, W]); 0: interpolation pass"),
-    "E3K_TP_TABLE_PACKED": (1, "accuracy", "... from the table packed into 12-byte Taylor records (two small coefficients in fp16: bounded by the guard); 0: four fp32 rows"),
-    "E3K_TP_BWD_FUSED": (1, "path", "the input-gradient walk of the tensor product also writes what shares its per-edge sums: the weight gradient (packed-table layers, one-stream layers with streamed weights), force training's edge gradients and dual weight gradients (csrc/e3k_tp.hip MODE 5-8); 0: one kernel per gradient"),
+    "E3K_TP_TABLE": (1, "path", "table layers interpolate their path weights inside the tensor-product kernels, from the table packed into 12-byte Taylor records (no w[E, W]); 0: interpolation pass"),
     # ---- streams ----
-    "E3K_FWD_FORK": (1, "path", "0: one stream; 1: radial / self-connection / weight-gradient branches on side streams above the edge thresholds; 2: also inside a graph capture"),
-    "E3K_FWD_FORK_SC": (1, "path", "composed path: the self-connection on a third stream"),
+    "E3K_FWD_FORK": (1, "path", "0: one stream; 1: radial / self-connection / weight-gradient branches on side streams above the edge thresholds (never inside a graph capture)"),
     "E3K_WGRAD_SIDE": (1, "path", "sunk weight gradients of forked layers run on a side stream"),
     # ---- thresholds ----
     "E3K_FORK_MIN_EDGES": (25000, "threshold", "per-edge radial layers fork from this many edges (in units of a 1920-weight layer)"),

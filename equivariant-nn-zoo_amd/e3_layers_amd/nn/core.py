@@ -192,9 +192,8 @@ class FullyConnectedNet(nn.Sequential):
             self.add_module(k, v)
         self.hs = hs
         self.act_name = name
-        # hidden chain in one launch (csrc/e3k_mlp.hip) when the widths fit; E3K_FUSED_MLP=0 keeps the per-layer ops
-        self.fused_hidden = (len(hs) >= 3 and name is not None and _knob("E3K_FUSED_MLP") != 0
-                             and ops.mlp_hidden_supported(hs[0], hs[1:-1], name))
+        # hidden chain in one launch (csrc/e3k_mlp.hip) when the widths fit
+        self.fused_hidden = len(hs) >= 3 and ops.mlp_hidden_supported(hs[0], hs[1:-1], name)
 
     def forward(self, x):
         if not self.fused_hidden or not x.is_cuda:

@@ -28,7 +28,7 @@ import torch
 from ..backend.tuning import knob as _knob
 from torch import Tensor
 
-from ..backend import conv_block, ops, radial_table
+from ..backend import conv_block, conv_native, ops, radial_table
 from ..backend.graph import get_topology
 from ..o3 import Irrep, Irreps
 from ..utils.utils import _is_mapping, activations, build, tp_path_exists
@@ -41,7 +41,6 @@ from .sequential import Module
 # 1 (default): the edge-side branch of a convolution (radial MLP) runs on a side stream next to the node-side branch
 # (relayout, self-connection, linear_1); autograd replays the same split in the backward.  Measured +6 % on the bench.
 FWD_FORK = _knob("E3K_FWD_FORK")
-FWD_FORK_SC = _knob("E3K_FWD_FORK_SC")   # 1: the self-connection runs on a third stream (+7 % on the bench)
 # The fork pays when the branches are long enough to hide the extra stream switches (≈ 0.3 ms of host time per
 # step): the yardstick is the size of the per-edge weight tensor, edges x weight_numel, counted in edges of a
 # 1920-weight layer (n_dim 64, l_max 2).  Measured: config_energy 256 molecules (69 k x 1920) +12 %, protein
@@ -64,14 +63,12 @@ RADIAL_STACK = _knob("E3K_RADIAL_STACK")
 # ... while the step is launch-bound: with more edges than this every layer runs its own MLP (its backward then overlaps
 # the earlier layers' backward instead of forming one tail behind the first layer's; measured cross-over)
 STACK_MAX_EDGES = _knob("E3K_STACK_MAX_EDGES")
+# 1: a layer whose self-connection has general (un-keyed) node attributes still runs as a fused block: the self-connection is
+# computed by ops.fctp outside and handed in as an addend (MessagePassing._forward_block_addend)
+BLOCK_ADDEND = _knob("E3K_BLOCK_ADDEND")
 # 1: likewise the per-key self-connection weights M_l of all the layers that read one node_attrs tensor
 # (MessagePassing._kw_stack_rows); not while the all-reduce is overlapped with the backward (run/parallel.py): the
 # self-connection weights are most of a layer's parameters and their gradients would then only exist at the very end
-# 1: a layer whose self-connection has general (un-keyed) node attributes still runs as a fused block: the self-connection is
-# computed by ops.fctp outside and handed in as an addend (MessagePassing._forward_block_addend)
-CF_CHAIN_NORM = _knob("E3K_CF_CHAIN_NORM")      # cf hand-over through LayerNormalization
-BLOCK_ADDEND = _knob("E3K_BLOCK_ADDEND")
-ADDEND_FORK = _knob("E3K_ADDEND_FORK")
 KW_STACK = _knob("E3K_KW_STACK")
 KW_STACK_MAX_EDGES = _knob("E3K_KW_STACK_MAX_EDGES")      # (192 / 256 molecules: -0.10 / -0.03 ms: no limit)
 
@@ -153,7 +150,7 @@ class FactorizedConvolution(Module):
             src.bins()
             src.knot_basis()
         if (FWD_FORK and x.is_cuda and self._fork_pays(data["edge_radial"].shape[0], bool(table))
-                and (ops.FORK_IN_CAPTURE or not torch.cuda.is_current_stream_capturing())):
+                and not torch.cuda.is_current_stream_capturing()):
             # the radial MLP (edge side: one big GEMM) and the node side (relayout, self-connection, linear_1: small
             # launches that leave most CUs idle) are independent until the tensor product: run them on two streams
             with ops.IN_FORK:
@@ -170,18 +167,16 @@ class FactorizedConvolution(Module):
                     ready.record(side)
                 x_cf = x if in_cf else ops.relayout(x, self._in_blocks, True)
                 sc = None
-                if self.sc is not None and FWD_FORK_SC:
+                if self.sc is not None:
                     # third branch: the self-connection only meets the others at the trailing Linear
                     side2 = ops.side_stream(x.device, 1)
                     side2.wait_stream(main)
                     with ops.on_stream(side2, main):
                         sc = self.sc(x_cf, _stream_alias(data["node_attrs"], side2))
-                elif self.sc is not None:
-                    sc = self.sc(x_cf, data["node_attrs"])
                 x1 = self.linear_1(x_cf, in_layout="cf", out_layout="cf")
                 main.wait_event(ready)
                 weight.record_stream(main)
-                if sc is not None and FWD_FORK_SC:
+                if sc is not None:
                     mid = self.tp.tp.fused(x1, data["edge_spherical"], weight, topo)
                     main.wait_stream(side2)
                     sc.record_stream(main)
@@ -258,14 +253,15 @@ class MessagePassing(Module):
         # (LayerNormalization is a per-block reduction over ALL elements of an irrep block: the same numbers in either layout,
         #  so a normalised layer hands over in cf too -- the protein score net's eight layers)
         return (CF_CHAIN and isinstance(nxt, MessagePassing) and isinstance(self.equivariant_nonlin, Gate)
-                and not self.resnet and (not self.normalize or CF_CHAIN_NORM) and not nxt.resnet
+                and not self.resnet and not nxt.resnet
                 and isinstance(nxt.conv, FactorizedConvolution) and nxt.conv.reduce
                 and tuple(irreps_blocks(self.equivariant_nonlin.irreps_out)) == nxt.conv._in_blocks)
 
     # ---- the layer as one autograd node (backend/conv_block.py) --------------------------------------------------
     def _block_plan(self, addend: bool = False):
-        """Static part of the fused block, or None when this layer's structure is not served by it.  ``addend``: the variant
-        whose self-connection is computed OUTSIDE the block and handed in (general node attributes, ``ConvBlockPlan.addend``)."""
+        """Static part of the fused block, or None when this layer's structure is not served by it -- a plan exists exactly when
+        the native layer executor takes the layer (``conv_native.native_layer``).  ``addend``: the variant whose self-connection
+        is computed OUTSIDE the block and handed in (general node attributes, ``ConvBlockPlan.addend``)."""
         slot = "_cb_plan_add" if addend else "_cb_plan"
         plan = self.__dict__.get(slot, False)
         if plan is not False:
@@ -295,6 +291,10 @@ class MessagePassing(Module):
                 sc_spec=sc_spec, sc_m_off=sc_m_off, sc_ld_m=sc_ld, gate_spec=self.equivariant_nonlin._spec,
                 addend=bool(addend and conv.sc is not None))
             plan.guard_key = last.weight
+            try:
+                conv_native.native_layer(plan)      # (the executor's descriptor; its device handle is made on first use)
+            except NotImplementedError:
+                plan = None
         self.__dict__[slot] = plan
         return plan
 
@@ -304,10 +304,6 @@ class MessagePassing(Module):
         apply.  The first layer of a chain computes it (on the radial stream when forked) and leaves the others' rows in
         ``cache`` (which lives as long as this forward pass's edge embedding); every layer takes its own entry out.
         ``slope`` (force training; see ``conv_native.RadialStackFn``): the entry is then the pair (table T, slope table D)."""
-        from ..backend import conv_native
-
-        if not conv_native.ENABLED or conv_native.native_layer(plan) is None:
-            return None
         grad = torch.is_grad_enabled()
         hit = cache.pop(id(self), None)
         if hit is not None and hit[1] == (grad, fork, slope is not None):
@@ -317,7 +313,7 @@ class MessagePassing(Module):
         n_edges = edge_radial.shape[0]
         while m is not None and len(chain) < 16:
             pl = m._block_plan() if m is not self else plan
-            if pl is None or conv_native.native_layer(pl) is None:
+            if pl is None:
                 break
             fc = list(m.conv.fc.children())
             if (pl.mlp_k0, pl.last_spec.d_in, tuple(pl.mlp_alphas), pl.mlp_act, pl.mlp_cst) != sig:
@@ -356,10 +352,6 @@ class MessagePassing(Module):
         ``_next_mp`` chain that has a keyed self-connection on the same attributes (``conv_native.KwStackFn``), or None.
         ``node_attrs``: the tensor the layers share (the rows of the others wait on it); ``attrs``: its alias on the
         self-connection stream when forked."""
-        from ..backend import conv_native
-
-        if not conv_native.ENABLED or conv_native.native_layer(plan) is None:
-            return None
         grad = torch.is_grad_enabled()
         cache = getattr(node_attrs, "_e3k_kw_stack", None)
         if cache is None:
@@ -370,7 +362,7 @@ class MessagePassing(Module):
         chain, m = [], self
         while m is not None and len(chain) < 8:
             pl = m._block_plan() if m is not self else plan
-            if pl is None or pl.sc_spec is None or conv_native.native_layer(pl) is None or pl.sc_spec.v != plan.sc_spec.v:
+            if pl is None or pl.sc_spec is None or pl.sc_spec.v != plan.sc_spec.v:
                 break
             if m is not self and (bool(FWD_FORK and m.conv._fork_pays(n_edges, use_table))
                                   != bool(FWD_FORK and self.conv._fork_pays(n_edges, use_table))):
@@ -461,8 +453,7 @@ class MessagePassing(Module):
             src = radial_table.source_of(radial)
             table = src.bins()
             radial = src.knot_basis()            # [knots + 1, n_basis]: the block's MLP runs on these rows
-        fork = bool(FWD_FORK and conv._fork_pays(n_edges, table is not None)
-                    and (ops.FORK_IN_CAPTURE or not torch.cuda.is_current_stream_capturing()))
+        fork = bool(FWD_FORK and conv._fork_pays(n_edges, table is not None) and not torch.cuda.is_current_stream_capturing())
         if fork:      # gradient contributions of the shared inputs are summed on the streams that produce them
             main = ops.current_stream(x.device)
             side = ops.side_stream(x.device)
@@ -511,10 +502,8 @@ class MessagePassing(Module):
         return y
 
     def _forward_block_addend(self, data, x, sh, radial, out_cf: bool):
-        from ..backend import conv_native
-
         plan = self._block_plan(addend=True) if BLOCK_ADDEND else None
-        if plan is None or not conv_native.ENABLED or conv_native.native_layer(plan) is None:
+        if plan is None:
             return None
         conv = self.conv
         x_cf = x if getattr(x, "_e3k_cf", False) else ops.relayout(x, conv._in_blocks, True)
@@ -528,8 +517,8 @@ class MessagePassing(Module):
             radial = src.knot_basis()
         # no stacks, no look-ahead (the shapes that reach this are the score nets); the radial branch and the weight
         # gradients fork onto their streams under the same rule as the keyed block
-        fork = bool(ADDEND_FORK and FWD_FORK and conv._fork_pays(data["edge_radial"].shape[0], table is not None)
-                    and (ops.FORK_IN_CAPTURE or not torch.cuda.is_current_stream_capturing()))
+        fork = bool(FWD_FORK and conv._fork_pays(data["edge_radial"].shape[0], table is not None)
+                    and not torch.cuda.is_current_stream_capturing())
         if fork:
             main = ops.current_stream(x.device)
             side = ops.side_stream(x.device)
@@ -543,10 +532,9 @@ class MessagePassing(Module):
         """``SequentialGraphNetwork.prepare_data`` hook: the EDGE RECORDS the packed-table tensor-product kernels walk (one 64-byte
         block per edge and CSR direction: ``KnotBins.records``) depend on the batch alone -- topology, knot bins, spherical
         harmonics -- and are shared by all layers: built here when all three are known before the step."""
-        from ..backend import conv_native
         from ..backend.graph import GraphTopo
 
-        if not (conv_native.ENABLED and conv_native.TP_TABLE and conv_native.TP_TABLE_PACKED):
+        if not conv_native.TP_TABLE:
             return
         inv = {loc: g for g, loc in self.input_key_mapping.items()}
         sh_key, rad_key = inv.get("edge_spherical"), inv.get("edge_radial")

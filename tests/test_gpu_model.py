@@ -855,7 +855,7 @@ def test_path_selection_thresholds_to_both_sides_meet_the_oracle(dev, monkeypatc
     """which path a layer takes is chosen by a handful of switches and edge-count thresholds
     (backend/tuning.py).  One 64-molecule batch of the bench model, the float64 oracle evaluated ONCE, and every threshold pushed
     to both sides: forked everywhere / one stream, radial stack on / off, look-ahead, keyed-weight stack, knot table (in-kernel,
-    materialised, off by switch, off by size), native executor / Python block / composed layers, cf hand-over.  Energies 1e-5,
+    materialised, off by switch, off by size), fused layers / composed layers, cf hand-over.  Energies 1e-5,
     every parameter gradient 5e-5, whatever the combination."""
     from e3_layers_amd.backend import conv_block, conv_native, ops, radial_table
     from e3_layers_amd.configs import config_energy
@@ -880,7 +880,6 @@ def test_path_selection_thresholds_to_both_sides_meet_the_oracle(dev, monkeypatc
         "per-edge radial MLPs (table switched off), forked": {(radial_table, "ENABLED"): 0, (mp, "FORK_MIN_EDGES"): off},
         "per-edge radial MLPs (below the table's size threshold), one stream": {(radial_table, "MIN_EDGES_PER_KNOT"): 1e9, (mp, "FORK_MIN_EDGES"): big},
         "table with the weights materialised": {(conv_native, "TP_TABLE"): 0, (mp, "FORK_MIN_EDGES_TABLE"): off},
-        "Python block instead of the native executor": {(conv_native, "ENABLED"): 0},
         "composed layers, forked": {(conv_block, "ENABLED"): 0, (mp, "FORK_MIN_EDGES"): off, (mp, "FORK_MIN_EDGES_TABLE"): off},
         "composed layers, one stream, no cf hand-over": {(conv_block, "ENABLED"): 0, (mp, "FORK_MIN_EDGES"): big, (mp, "FORK_MIN_EDGES_TABLE"): big, (mp, "CF_CHAIN"): 0},
     }

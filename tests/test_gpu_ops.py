@@ -1246,7 +1246,8 @@ def test_radius_graph_kernel_keeps_existing_edges(dev):
                                          ([6, 64, 20], "ssp", 1), ([8, 32, 32, 32, 32, 24], "ssp", 777)])
 def test_fused_radial_mlp_hidden_chain(dev, hs, act, rows, monkeypatch):
     """The one-launch hidden chain (csrc/e3k_mlp.hip) == the oracle's FullyConnectedNet and == the per-layer
-    kernels (E3K_FUSED_MLP=0), values and every gradient; ragged row counts, input widths 6/8/32, 1-4 hidden layers."""
+    kernels (``fused_hidden`` switched off on the same net), values and every gradient; ragged row counts, input widths 6/8/32,
+    1-4 hidden layers."""
     from e3_layers_amd.nn import FullyConnectedNet
     from e3_layers_amd.utils import activations
 

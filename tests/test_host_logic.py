@@ -79,6 +79,31 @@ def test_config_trees_build_and_share_state_dict_names_with_oracle(name):
     assert {k: math.prod(v) for k, v in a.items()} == {k: math.prod(v) for k, v in b.items()}
 
 
+def test_every_shipped_layer_has_a_block_plan_the_native_executor_takes():
+    """The fused layer is issued by the native executor alone (``backend/conv_native.py``): ``MessagePassing._block_plan`` hands
+    out a plan only for a layer the executor takes, and a layer without one runs composed.  Every MessagePassing layer of the
+    shipped configurations has such a plan, in both forms -- the keyed self-connection inside the block, and the addend form for
+    un-keyed node attributes -- so none of them loses its fused path.  Building the descriptors needs no GPU."""
+    import importlib
+
+    from e3_layers_amd.backend import conv_native
+    from e3_layers_amd.nn.message_passing import MessagePassing
+    from e3_layers_amd.utils import build
+
+    configs = [("config_energy", {"l_max": 2}), ("config_energy", {"l_max": 3}), ("config_energy_force", {}),
+               ("config_diffusion", {}), ("config_diffusion_CA", {}), ("config_diffusion_backbone", {})]
+    for name, kw in configs:
+        torch.manual_seed(0)
+        model = build(importlib.import_module(f"e3_layers_amd.configs.{name}").get_config(**kw).model_config)
+        layers = [m for m in model.modules() if isinstance(m, MessagePassing)]
+        assert layers, name
+        for i, layer in enumerate(layers):
+            for addend in (False, True):
+                plan = layer._block_plan(addend=addend)
+                assert plan is not None, (name, kw, i, addend)
+                assert isinstance(conv_native.native_layer(plan), conv_native.NativeLayer), (name, kw, i, addend)
+
+
 def test_tp_group_tables_cover_every_path_once():
     from e3_layers_amd.nn.core import UVUTensorProduct, tp_slots
 

@@ -16,7 +16,6 @@ for b in 32 64 128; do $B --graph-fresh --batch $b > $OUT/bench_graphfresh_b$b.j
 for c in energy_force diffusion diffusion_CA; do $B --config $c > $OUT/bench_$c.json 2>/dev/null; done
 $B --graph-fresh > $OUT/bench_graphfresh_b256.json 2>/dev/null
 $B --launch auto > $OUT/bench_launch_auto.json 2>/dev/null
-E3K_TP_TABLE_PACKED=0 $B > $OUT/bench_four_row_table.json 2>/dev/null      # round 4 form of the in-kernel table, same box
 E3K_RADIAL_TABLE_KEYED=1 $B --config diffusion > $OUT/bench_diffusion_keyed_tables.json 2>/dev/null
 $B --config energy_force --graph-fresh > $OUT/bench_energy_force_graphfresh.json 2>/dev/null
 E3K_FORCE_BLOCK=0 $B --config energy_force --graph-fresh > $OUT/bench_energy_force_composed_graphfresh.json 2>/dev/null      # rounds 1-3's path, same box

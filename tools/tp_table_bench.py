@@ -8,6 +8,7 @@ for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
     sys.path.insert(0, p)
 import torch
 from e3_layers_amd.backend import conv_force, ops, radial_table
+from e3_layers_amd.backend import lib as L
 from e3_layers_amd.backend.graph import build_topology
 from e3_layers_amd.configs import config_energy
 from e3_layers_amd.data.synthetic import synth_qm9
@@ -30,6 +31,25 @@ x = torch.randn(n, tp.d_in, device=dev)
 sh = torch.randn(e, tp.d_sh, device=dev)
 g = torch.randn(n, tp.d_mid, device=dev)
 w = torch.randn(e, tp.w_numel, device=dev)
+
+
+def _tp_fwd_table(x1, sh, T, bins, topo, tp):
+    """the forward reading four fp32 table rows per edge (the form the packed table replaced)"""
+    n, e = x1.shape[0], sh.shape[0]
+    out = torch.empty(n, tp.d_mid, device=x1.device, dtype=torch.float32)
+    L.check(L.load().e3k_tp_fwd_table(tp.handle(x1.device), L.ptr(x1), L.ptr(sh), L.ptr(T), L.ptr(bins.bin), L.ptr(bins.coef),
+                                      L.ptr(topo.src), L.ptr(topo.dst_ptr), L.ptr(topo.dst_perm), n, e, L.ptr(out), L.stream_ptr()),
+            "e3k_tp_fwd_table")
+    return out
+
+
+def _tp_bwd_x_table(sh, T, bins, g_mid, topo, tp):
+    n, e = g_mid.shape[0], sh.shape[0]
+    gx = (torch.empty if tp.bwd_x_overwrites(sh.device) else torch.zeros)(n, tp.d_in, device=sh.device, dtype=torch.float32)
+    L.check(L.load().e3k_tp_bwd_x_table(tp.handle(sh.device), L.ptr(sh), L.ptr(T), L.ptr(bins.bin), L.ptr(bins.coef), L.ptr(g_mid),
+                                        L.ptr(topo.dst), L.ptr(topo.src_ptr), L.ptr(topo.src_perm), n, e, L.ptr(gx), L.stream_ptr()),
+            "e3k_tp_bwd_x_table")
+    return gx
 
 
 def timeit(fn, reps=20):
@@ -90,8 +110,8 @@ for target in targets:
     bins = radial_table.build_bins(r, 4.0, target)
     T = torch.randn(bins.knots + 1, tp.w_numel, device=dev)
     cnt = (bins.ptr[1:] - bins.ptr[:-1]).float()
-    t_f = timeit(lambda: conv_force._tp_fwd_table(x, sh, T, bins, topo, tp))
-    t_x = timeit(lambda: conv_force._tp_bwd_x_table(sh, T, bins, g, topo, tp))
+    t_f = timeit(lambda: _tp_fwd_table(x, sh, T, bins, topo, tp))
+    t_x = timeit(lambda: _tp_bwd_x_table(sh, T, bins, g, topo, tp))
     P = radial_table.pack_raw(T, bins.knots)
     t_p = timeit(lambda: radial_table.pack_raw(T, bins.knots))
     t_fp = timeit(lambda: conv_force._tp_fwd_ptable(x, sh, P, bins, topo, tp))

@@ -1,5 +1,5 @@
-"""Which path the message-passing layers of a configuration take on this batch: the fused layer block (and whether the native
-executor serves it) or the composed per-op path, with the reason.   python tools/which_path.py [energy_force|diffusion|diffusion_CA]"""
+"""Which path the message-passing layers of a configuration take on this batch: the fused layer block (issued by the native
+executor) or the composed per-op path, with the reason.   python tools/which_path.py [energy_force|diffusion|diffusion_CA]"""
 import os
 import sys
 
@@ -8,7 +8,7 @@ for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
     sys.path.insert(0, p)
 import torch
 
-from e3_layers_amd.backend import conv_block, conv_native, radial_table
+from e3_layers_amd.backend import radial_table
 from e3_layers_amd.configs import config_diffusion, config_diffusion_CA, config_energy_force
 from e3_layers_amd.data.synthetic import synth_protein, synth_qm9, synth_qm9_diffusion
 from e3_layers_amd.nn import message_passing as mp
@@ -40,17 +40,16 @@ def traced(self, data, out_cf):
         if sh.requires_grad:
             why = "composed: edge_spherical requires grad (forces)"
         elif plan is None:
-            why = "composed: no block plan for this layer structure"
+            why = "composed: no block plan (layer structure not served, or the native executor declines it)"
         elif self.conv.sc is not None and not self.conv.sc.keyed_pays(get_row_key(data["node_attrs"]), x.shape[0]):
             key = get_row_key(data["node_attrs"])
             why = f"composed: node_attrs not keyed / too few rows per key (key = {None if key is None else key[1]}, rows = {x.shape[0]})"
         else:
             why = "composed: ?"
     else:
-        plan = self._block_plan()
         fc = list(self.conv.fc.children())
-        why = (f"block, native executor = {conv_native.ENABLED and conv_native.native_layer(plan) is not None}, "
-               f"knot table = {radial_table.applicable(radial, fc[-1].weight)}, radial requires grad = {radial.requires_grad}")
+        why = (f"block, knot table = {radial_table.applicable(radial, fc[-1].weight)}, "
+               f"radial requires grad = {radial.requires_grad}")
     log.append(f"N={x.shape[0]} E={radial.shape[0]} {why}")
     return out
 
