@@ -14,11 +14,12 @@ logic tests, gloo runs) and is the reference the device build is tested bit-exac
 """
 from __future__ import annotations
 
-import weakref
 from dataclasses import dataclass
 from typing import Dict, Optional
 
 import torch
+
+from . import memo
 
 TOPO_KEYS = ("_e3k_src", "_e3k_dst", "_e3k_dst_ptr", "_e3k_dst_perm", "_e3k_src_ptr", "_e3k_src_perm")
 
@@ -208,24 +209,14 @@ def build_topology(edge_index: torch.Tensor, num_nodes: int) -> GraphTopo:
     return GraphTopo(src64.to(torch.int32), dst64.to(torch.int32), dst_ptr, dst_perm, src_ptr, src_perm)
 
 
-_cache: "Dict[int, tuple]" = {}
-
-
 def get_topology(data, num_nodes: int) -> GraphTopo:
     """Topology carried by the batch if present, else built from ``data['edge_index']`` and
-    memoised on the identity of that tensor."""
+    remembered on that tensor (``backend/memo.py``)."""
     topo = GraphTopo.from_dict(data)
     if topo is not None and topo.num_nodes == num_nodes and topo.num_edges == data["edge_index"].shape[1]:
         return topo
     ei = data["edge_index"]
-    key = id(ei)
-    hit = _cache.get(key)
-    if hit is not None:
-        ref, version, n, topo = hit
-        if ref() is ei and version == ei._version and n == num_nodes:
-            return topo
-    topo = build_topology(ei, num_nodes)
-    if len(_cache) > 64:
-        _cache.clear()
-    _cache[key] = (weakref.ref(ei), ei._version, num_nodes, topo)
+    topo = memo.recall(ei, "topology", num_nodes)
+    if topo is None:
+        topo = memo.remember(ei, "topology", build_topology(ei, num_nodes), num_nodes)
     return topo

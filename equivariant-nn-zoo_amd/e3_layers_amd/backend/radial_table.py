@@ -34,7 +34,7 @@ import torch
 from .tuning import knob as _knob
 
 from . import lib as L
-from . import ops
+from . import memo, ops
 
 ENABLED = _knob("E3K_RADIAL_TABLE")
 # Target knot counts over [0, r_max]; the spacing actually used is the power of two at or below r_max / target (``layout``):
@@ -189,16 +189,20 @@ class RadialSource:
 
 
 def prepare_bins(r: torch.Tensor, r_max: float, target: int) -> KnotBins:
-    """Knot bins of the radii ``r`` built NOW and left on the tensor (``SequentialGraphNetwork.prepare_data``: the batch's radii are
-    known before the step that reads them); ``prepared_bins(r)`` hands them out while ``r`` has not been written to since."""
+    """Knot bins of the radii ``r`` built NOW and remembered on the tensor (``SequentialGraphNetwork.prepare_data``: the batch's radii
+    are known before the step that reads them; ``backend/memo.py``)."""
     bins = build_bins(r, r_max, target)
-    r._e3k_bins = (r._version, float(r_max), {int(target): bins})
+    memo.remember(r, "bins", {int(target): bins}, float(r_max))
+    memo.remember(r, "bins_r_max", float(r_max))
     return bins
 
 
-def prepared_bins(r: torch.Tensor) -> Optional[dict]:
-    hit = getattr(r, "_e3k_bins", None)
-    return hit[2] if (hit is not None and hit[0] == r._version) else None
+def prepared_bins(r: torch.Tensor, r_max: Optional[float] = None) -> Optional[dict]:
+    """{target knot count: KnotBins} prepared on ``r`` for a table that ends at ``r_max``, or None.  Without ``r_max`` (a look at
+    what a preparation left, the tests'): for the ``r_max`` it was prepared with."""
+    if r_max is None:
+        r_max = memo.recall(r, "bins_r_max")
+    return None if r_max is None else memo.recall(r, "bins", float(r_max))
 
 
 _KNOT_CACHE = {}

@@ -173,7 +173,7 @@ class Collation:
         self._describe()
 
     def renew(self) -> None:
-        """New output tensors in the same Batch container (``CollatedStep`` records a buffer again on tensors no memo knows)."""
+        """New output tensors in the same Batch container (``CollatedStep`` records a buffer again on tensors that carry no memo, ``backend/memo.py``)."""
         fresh = self.ds.empty_batch(self.G, self.n_cap, self.e_cap)
         self.batch.data.clear()
         self.batch.data.update(fresh.data)

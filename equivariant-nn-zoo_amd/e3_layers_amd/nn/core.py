@@ -22,7 +22,7 @@ from ..backend.tuning import knob as _knob
 from torch import nn
 
 from ..backend import lib as L
-from ..backend import ops
+from ..backend import memo, ops
 from ..backend.graph import GraphTopo
 from ..o3 import Irrep, Irreps
 from ..utils.utils import act_output_parity, act_second_moment_const, activation_name
@@ -61,18 +61,13 @@ def combine_row_keys(tensors):
     return (index, n) if index is not None else None
 
 
-_groups_cache: Dict[int, tuple] = {}
-
-
 def row_groups(index: torch.Tensor, n_keys: int) -> "ops.RowGroups":
     """Group rows by key with device-side ops only (stable sort, scatter-add counts, cumsum): no host
-    synchronisation, so a forward can be captured in a HIP graph.  Memoised per key tensor so the
+    synchronisation, so a forward can be captured in a HIP graph.  Remembered on the key tensor (``backend/memo.py``) so the
     layers of one forward (and their backward) share one sort."""
-    import weakref
-
-    hit = _groups_cache.get(id(index))
-    if hit is not None and hit[0]() is index and hit[1] == n_keys:
-        return hit[2]
+    hit = memo.recall(index, "groups", n_keys)
+    if hit is not None:
+        return hit
     idx = index.reshape(-1)
     if idx.is_cuda and n_keys <= 256 and idx.dtype == torch.int64:
         # csrc/e3k_graph.hip: one single-workgroup launch (a radix sort + scatter_add + cumsum + gather otherwise)
@@ -97,10 +92,7 @@ def row_groups(index: torch.Tensor, n_keys: int) -> "ops.RowGroups":
         reps = perm[starts.clamp(max=max(idx.numel() - 1, 0))]
         bounds = torch.stack([starts, counts], dim=1).to(torch.int32).contiguous()
         groups = ops.RowGroups(perm.to(torch.int32), bounds, reps, n_keys)
-    if len(_groups_cache) > 16:
-        _groups_cache.clear()
-    _groups_cache[id(index)] = (weakref.ref(index), n_keys, groups)
-    return groups
+    return memo.remember(index, "groups", groups, n_keys)
 
 
 def irreps_blocks(irreps: Irreps) -> List[Tuple[int, int, int]]:

@@ -12,7 +12,7 @@ from typing import Dict, Tuple
 import torch
 from torch import Tensor, nn
 
-from ..backend import ops, radial_table
+from ..backend import memo, ops, radial_table
 from ..o3 import Irreps
 from ..utils.utils import build
 from .core import set_row_key
@@ -99,7 +99,7 @@ class RadialBasisEncoding(Module):
         if per_row == 1 and c.cutoff.kind == 0 and b.r_min == 0.0:
             # a pure function of one radius per row, constant beyond r_max: the convolutions may evaluate their radial MLPs
             # on a knot table instead of per edge (backend/radial_table.py); any op that builds a new tensor drops the tag
-            out._e3k_radial_src = radial_table.RadialSource(self, x.reshape(-1), out._version, prepared=radial_table.prepared_bins(x))
+            out._e3k_radial_src = radial_table.RadialSource(self, x.reshape(-1), out._version, prepared=radial_table.prepared_bins(x, b.r_max))
         return ({"radial_embedding": out},
                 {"radial_embedding": (attrs["input"][0], self.irreps_out["radial_embedding"])})
 
@@ -148,17 +148,12 @@ class OneHotEncoding(Module):
 
     def forward(self, data, attrs):
         src = data["input"]
-        # the same index VIEW object for the same source tensor (and version): the key groups of the keyed
-        # self-connection are memoised on the identity of this tensor (nn/core.py: row_groups), so a batch that is
-        # stepped repeatedly (batch.view()) sorts its species once, not once per step
-        memo = getattr(src, "_e3k_flat_index", None)
-        if memo is not None and memo[0] == src._version:
-            idx = memo[1]
-        else:
-            # a COPY, not a view: a view keeps a C++ reference to its base, and base -> attribute -> view -> base is a
-            # cycle through the C++ reference counts that nothing ever collects
-            idx = src.squeeze(-1).clone()
-            src._e3k_flat_index = (src._version, idx)
+        # the same index tensor for the same source tensor (and version): the key groups of the keyed self-connection are
+        # remembered on it (nn/core.py: row_groups), so a batch that is stepped repeatedly (batch.view()) sorts its species once,
+        # not once per step.  A COPY, not a view (backend/memo.py)
+        idx = memo.recall(src, "flat_index")
+        if idx is None:
+            idx = memo.remember(src, "flat_index", src.squeeze(-1).clone())
         if idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1:      # one launch instead of zeros + scatter + conversion
             from ..backend import lib as L
 

@@ -28,7 +28,7 @@ import torch
 from ..backend.tuning import knob as _knob
 from torch import Tensor
 
-from ..backend import conv_block, conv_native, ops, radial_table
+from ..backend import conv_block, conv_native, memo, ops, radial_table
 from ..backend.graph import get_topology
 from ..o3 import Irrep, Irreps
 from ..utils.utils import _is_mapping, activations, build, tp_path_exists
@@ -81,18 +81,14 @@ def _stream_alias(t: Tensor, stream) -> Tensor:
     side stream and reach the main stream once."""
     if not (t.requires_grad and torch.is_grad_enabled()):
         return t
-    cache = getattr(t, "_e3k_alias", None)
-    if cache is None:
-        cache = t._e3k_alias = {}
-    key = stream.cuda_stream
-    ref = cache.get(key)
+    slot = ("alias", stream.cuda_stream)
+    ref = memo.recall(t, slot)
     alias = ref() if ref is not None else None
     if alias is None:
         alias = t.view_as(t)
-        # weak: the view already points at ``t`` (``_base``); a strong reference back would be a cycle that only the
-        # cyclic collector frees -- 0.3 MB of device memory per step piled up between its runs.  The consumers' autograd
-        # graphs keep the alias alive for as long as it matters.
-        cache[key] = weakref.ref(alias)
+        # weak (backend/memo.py): a strong reference piled up 0.3 MB of device memory per step between the cyclic collector's
+        # runs.  The consumers' autograd graphs keep the alias alive for as long as it matters.
+        memo.remember(t, slot, weakref.ref(alias))
         for attr in ("_e3k_key", "_e3k_data_only", "_e3k_param_only", "_e3k_blocks"):      # row keys / provenance marks / the block count
             # of a keyed source's stacked knot basis (ADVICE r5: without it the guard differenced across the tables' seams) ride along
             if hasattr(t, attr):
@@ -353,9 +349,9 @@ class MessagePassing(Module):
         ``node_attrs``: the tensor the layers share (the rows of the others wait on it); ``attrs``: its alias on the
         self-connection stream when forked."""
         grad = torch.is_grad_enabled()
-        cache = getattr(node_attrs, "_e3k_kw_stack", None)
+        cache = memo.recall(node_attrs, "kw_stack")
         if cache is None:
-            cache = node_attrs._e3k_kw_stack = {}
+            cache = memo.remember(node_attrs, "kw_stack", {})
         hit = cache.pop(id(self), None)
         if hit is not None and hit[1] == (grad, fork, id(groups)):
             return hit[0]
@@ -475,9 +471,9 @@ class MessagePassing(Module):
             if table is not None:
                 cache = src._stack
             else:      # per-edge MLPs: the rows of the layers wait on the edge embedding of this forward pass
-                cache = getattr(data["edge_radial"], "_e3k_stack", None)
+                cache = memo.recall(data["edge_radial"], "stack")
                 if cache is None:
-                    cache = data["edge_radial"]._e3k_stack = {}
+                    cache = memo.remember(data["edge_radial"], "stack", {})
             pre = self._stack_rows(cache, radial, data["edge_radial"], plan, fork, table is not None)
         if pre is not None:      # the MLPs of all the layers on this edge embedding ran as one batch (conv_native.RadialStackFn)
             if nmp is not None and fork and table is not None:
@@ -545,7 +541,7 @@ class MessagePassing(Module):
         for _, layer in network.layers:      # the layer that produces this convolution's edge embedding: its radii carry the bins
             if rad_key in getattr(layer, "output_key_mapping", {}).values() and hasattr(layer, "basis"):
                 r_key = next((g for g, loc in layer.input_key_mapping.items() if loc == "input"), None)
-                bins = radial_table.prepared_bins(data[r_key]) if (r_key in avail and r_key in data) else None
+                bins = radial_table.prepared_bins(data[r_key], layer.basis.r_max) if (r_key in avail and r_key in data) else None
                 for b in (bins or {}).values():
                     b.records(topo, sh, "dst")
                     if torch.is_grad_enabled() or self.training:

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import torch
 
-from ..backend import ops
+from ..backend import memo, ops
 from ..o3 import Irreps
 from ..utils.utils import _is_mapping, build
 from .sequential import Module
@@ -76,9 +76,9 @@ class Pooling(Module):
     def _row_pointers(counts, device):
         """int32 [G + 1] row pointers of the per-graph node counts; memoised on the counts tensor (``prepare_batch`` builds them
         ahead of the step: they are batch data)."""
-        hit = getattr(counts, "_e3k_ptr", None)
-        if hit is not None and hit[0] == counts._version and hit[1].device == device:
-            return hit[1]
+        hit = memo.recall(counts, "ptr", device)
+        if hit is not None:
+            return hit
         n = counts.view(-1).to(device)
         ptr = torch.empty(n.numel() + 1, dtype=torch.int32, device=device)
         if n.is_cuda and n.dtype == torch.int64 and n.is_contiguous():
@@ -88,8 +88,7 @@ class Pooling(Module):
         else:
             ptr[0] = 0
             ptr[1:] = torch.cumsum(n, 0).to(torch.int32)
-        counts._e3k_ptr = (counts._version, ptr)
-        return ptr
+        return memo.remember(counts, "ptr", ptr, device)
 
     def prepare_batch(self, network, data, avail) -> None:
         """``SequentialGraphNetwork.prepare_data`` hook: the segment pointers depend on ``_n_nodes`` alone."""

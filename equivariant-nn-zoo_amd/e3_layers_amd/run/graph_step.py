@@ -22,6 +22,8 @@ from typing import Any, Callable
 import numpy as np
 import torch
 
+from ..backend import memo
+
 
 class CapturedStep:
     def __init__(self, fn: Callable[[], Any], warmup: int = 3, device=None, generators=()):
@@ -204,23 +206,6 @@ def bucket_capacity(sizes, node_multiple: int = 32, edge_multiple: int = 1024):
     return -(-n_cap // node_multiple) * node_multiple, e_cap
 
 
-def forget_batch_memos(batch=None) -> None:
-    """Drops what the framework remembers about a batch by the identity of its tensors: CSR views (``backend/graph.py``),
-    species groups (``nn/core.py``) and the memos attached to the tensors themselves (``_e3k_*`` attributes: the flat species
-    index of ``OneHotEncoding``, stream aliases)."""
-    from ..backend import graph as _graph
-    from ..nn import core as _core
-
-    _graph._cache.clear()
-    _core._groups_cache.clear()
-    if batch is not None:
-        for k in batch.keys():
-            v = batch[k]
-            if torch.is_tensor(v):
-                for name in [a for a in vars(v) if a.startswith("_e3k_")] if hasattr(v, "__dict__") else []:
-                    delattr(v, name)
-
-
 class BucketedStep:
     """``step = BucketedStep(train_on, example)``: ``train_on(batch)`` is captured once on a copy of the padded batch
     ``example``; ``step(padded)`` copies the next padded batch of the same bucket into the captured tensors and replays.
@@ -237,11 +222,9 @@ class BucketedStep:
         self.keys = [k for k in self.static.keys() if torch.is_tensor(self.static[k])]
 
         def captured_fn():
-            # The per-batch memos (CSR views keyed on the identity of ``edge_index``, species groups keyed on the key tensor, the
-            # flat species index OneHotEncoding keeps on its input tensor)
-            # would hit on the static tensors and leave the CSR build / grouping kernels OUT of the graph: the replay would then
-            # walk the warm-up batch's topology.  Forget them, so that these kernels are part of what is captured.
-            forget_batch_memos(self.static)
+            # the static tensors' contents change between replays: the CSR build / grouping kernels must be part of what is
+            # captured (the recording rule of backend/memo.py)
+            memo.forget(self.static)
             return fn(self.static.view())
 
         self.captured = CapturedStep(captured_fn, warmup=warmup, generators=generators)
@@ -342,7 +325,7 @@ class PipelinedBucketedStep:
         torch.cuda.synchronize(self.dev)
         del warm
         for b in range(2):
-            static = example.clone()        # (fresh tensors: no per-batch memo of the framework knows them yet)
+            static = example.clone()        # (fresh tensors: they carry no memo yet, backend/memo.py)
             if self.keys is None:
                 self.keys = [k for k in static.keys() if torch.is_tensor(static[k])]
                 self._given = list(static.keys())      # (what the caller's batches carry: everything else is the preparation's)
@@ -367,16 +350,15 @@ class PipelinedBucketedStep:
         """Buffer b's step has to record itself again (a knot table was refined or switched off: ``CapturedStep.stale``).  Its
         preparation graph is recorded again FIRST, on new tensors holding the buffer's present contents: the step's recording must
         find the batch as the first one did -- prepared by a graph, inputs untouched since (the copies of ``_enqueue_prepare`` bump
-        the inputs' version counters: the record of what was prepared from what, and every per-tensor memo, would count as stale,
-        the eager warm-up would rebuild them outside any graph and the new recording would replay the batch it was recorded on) --
-        and after a refinement the preparation builds the finer resolution's bins and edge records."""
+        the inputs' version counters: the record of what was prepared from what, and every memo of ``backend/memo.py``, count as
+        stale, the eager warm-up would rebuild them outside any graph and the new recording would replay the batch it was recorded
+        on) -- and after a refinement the preparation builds the finer resolution's bins and edge records."""
         torch.cuda.synchronize(self.dev)
         static = self.static[b]
         fresh = {k: (static.data[k].clone() if torch.is_tensor(static.data[k]) else static.data[k]) for k in self._given}
         static.data.clear()                 # (same container: the step's closure reads it when it records; the preparation's own keys are
         static.data.update(fresh)           # gone -- a layer that finds its output present keeps it)
         static._e3k_done = None
-        forget_batch_memos()
         self.prep_graphs[b] = None          # (its pool holds the old bins)
         warm = static.clone()
         self.prepare(warm)                  # (eagerly first: see __init__)
@@ -517,14 +499,13 @@ class _CollatedBuffers(PipelinedBucketedStep):
         return g
 
     def _record_again(self, b: int) -> None:
-        """As ``PipelinedBucketedStep._record_again``: the preparation graph is recorded again first, on NEW output tensors (no
-        per-tensor memo knows them), collating the ids the buffer holds."""
+        """As ``PipelinedBucketedStep._record_again``: the preparation graph is recorded again first, on NEW output tensors (they
+        carry no memo), collating the ids the buffer holds."""
         torch.cuda.synchronize(self.dev)
         c = self.collations[b]
         self.prep_graphs[b] = None          # (its pool holds the old bins)
         c.renew()
         c.batch._e3k_done = None
-        forget_batch_memos()
         c()
         warm = c.batch.clone()
         self.prepare(warm)                  # (eagerly first: see __init__)

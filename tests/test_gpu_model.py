@@ -1410,13 +1410,8 @@ def test_training_steps_do_not_accumulate_device_memory(dev, monkeypatch):
             model(fresh)["total_energy"].square().mean().backward()
             opt.step()
 
-        from e3_layers_amd.backend import graph as topo_cache
-        from e3_layers_amd.nn import core
-
-        def settled():      # the two bounded memo tables (topology per edge_index, key groups per index) emptied
+        def settled():      # (nothing to empty by hand: every memo lives on a tensor of its batch, backend/memo.py)
             torch.cuda.synchronize()
-            topo_cache._cache.clear()
-            core._groups_cache.clear()
             return torch.cuda.memory_allocated()
 
         for _ in range(5):

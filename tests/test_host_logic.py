@@ -481,3 +481,92 @@ def test_linear_terms_that_add_onto_one_block_become_one_k_chain(monkeypatch):
     assert [cnt for _, cnt in plain.rounds] == [n - 1, 1]
     assert all(plain.rounds[r][0][i].chain == 0 for r in range(2) for i in range(plain.rounds[r][1]))
     assert plain.rounds[1][0][0].accumulate == 1 and plain.rounds[1][0][0].C == h.C
+
+
+# ---- per-batch memos (backend/memo.py) -----------------------------------------------------------------
+def test_memo_hits_on_the_same_tensor_version_and_key_only():
+    from e3_layers_amd.backend import memo
+
+    t, value = torch.arange(6), object()
+    assert memo.recall(t, "slot", 3) is None
+    assert memo.remember(t, "slot", value, 3) is value
+    assert memo.recall(t, "slot", 3) is value
+    assert memo.recall(t, "slot", 4) is None and memo.recall(t, "slot") is None        # another key
+    assert memo.recall(t, "other", 3) is None and memo.recall(t, ("slot", 1), 3) is None
+    assert memo.recall(t.clone(), "slot", 3) is None and memo.recall(t.view(2, 3), "slot", 3) is None
+    assert {"t": t}["t"] is t and memo.recall(t, "slot", 3) is value
+    t.copy_(torch.zeros(6, dtype=t.dtype))                                             # written to: the value describes other contents
+    assert memo.recall(t, "slot", 3) is None
+    memo.remember(t, "slot", value, 3)
+    torch._foreach_copy_([t], [torch.ones(6, dtype=t.dtype)])
+    assert memo.recall(t, "slot", 3) is None
+
+
+def test_memo_forget_empties_every_tensor_of_a_batch_and_leaves_the_marks():
+    from e3_layers_amd.backend import memo
+    from e3_layers_amd.data.synthetic import synth_qm9
+    from e3_layers_amd.nn.core import get_row_key, set_row_key
+
+    batch = synth_qm9(0, 3)
+    tensors = [batch[k] for k in batch.keys() if torch.is_tensor(batch[k])]
+    assert len(tensors) >= 4
+    for i, t in enumerate(tensors):
+        memo.remember(t, "a", i)
+        memo.remember(t, ("b", 7), i, "key")
+    set_row_key(batch["pos"], batch["_node_segment"], 3)
+    memo.forget(batch)
+    for t in tensors:
+        assert memo.recall(t, "a") is None and memo.recall(t, ("b", 7), "key") is None
+    assert get_row_key(batch["pos"]) is not None and get_row_key(batch["pos"])[1] == 3
+    memo.forget(batch)                                                                 # (nothing left: not an error)
+
+
+def test_memo_value_is_freed_with_its_tensor_without_the_cyclic_collector():
+    import gc
+    import weakref
+
+    from e3_layers_amd.backend import memo
+
+    class Value:
+        pass
+
+    gc.collect()
+    gc.disable()
+    try:
+        t, value = torch.arange(4), Value()
+        gone = weakref.ref(value)
+        memo.remember(t, "slot", value)
+        del value
+        assert gone() is not None
+        del t
+        assert gone() is None
+    finally:
+        gc.enable()
+
+
+def test_row_groups_follow_an_index_tensor_overwritten_in_place():
+    """An eager loop that writes the next batch into the same tensors: the groups are those of the present contents."""
+    from e3_layers_amd.nn.core import row_groups
+
+    index = torch.tensor([2, 0, 1, 0, 2, 2])
+    first = row_groups(index, 3)
+    assert row_groups(index, 3) is first and row_groups(index, 4) is not first
+    assert first.perm.tolist() == [1, 3, 2, 0, 4, 5] and first.bounds.tolist() == [[0, 2], [2, 1], [3, 3]]
+    index.copy_(torch.tensor([1, 1, 1, 0, 2, 0]))
+    second = row_groups(index, 3)
+    assert second.perm.tolist() == [3, 5, 0, 1, 2, 4] and second.bounds.tolist() == [[0, 2], [2, 3], [5, 1]]
+
+
+def test_prepared_bins_are_handed_out_for_their_own_r_max_only(monkeypatch):
+    """(the bins are a stand-in: building them takes the device; this is about what they are remembered under)"""
+    from e3_layers_amd.backend import radial_table
+
+    stand_in = object()
+    monkeypatch.setattr(radial_table, "build_bins", lambda r, r_max, target: stand_in)
+    r = torch.rand(32) * 4.0
+    assert radial_table.prepared_bins(r, 4.0) is None
+    assert radial_table.prepare_bins(r, 4.0, 512) is stand_in
+    assert radial_table.prepared_bins(r, 4.0) == {512: stand_in}
+    assert radial_table.prepared_bins(r, 5.0) is None
+    r.mul_(0.5)
+    assert radial_table.prepared_bins(r, 4.0) is None
