@@ -260,6 +260,7 @@ __global__ __launch_bounds__(256) void edge_records_kernel(const int32_t* __rest
 extern "C" int e3k_edge_records(const int32_t* perm, const int32_t* nbr, const int32_t* bin, const float* coef, const float* sh,
                                 int32_t d_sh, int64_t E, int32_t* rec, void* stream) {
   if (E < 0 || d_sh <= 0 || d_sh > 9 || (bin != nullptr) != (coef != nullptr)) return E3K_ERR_INVALID;
+  if (E >= 0x7fffffffLL) return E3K_ERR_UNSUPPORTED;      // (perm holds int32 edge ids)
   if (E == 0) return E3K_OK;
   if (!perm || !nbr || !sh || !rec || (reinterpret_cast<uintptr_t>(rec) & 63)) return E3K_ERR_INVALID;
   hipLaunchKernelGGL(e3k::edge_records_kernel, dim3((unsigned)((E * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, perm, nbr, bin,

@@ -446,8 +446,8 @@ __global__ __launch_bounds__(256) void rtable_interp_packed_kernel(const uint32_
 // curvature (measured at random init, 2-3 k columns: per-column 1-4e-6 where the table-wide ratio is 1.1-1.8e-7), so the two have
 // tolerances of their own; the launch reports est = max(table-wide, col_weight * per-column) with col_weight = the tolerances'
 // ratio, to be compared with the table-wide tolerance.  One launch for up to 16 tables (the
-// radial stack's layers): a workgroup = 64 columns x 4 row quarters; the LAST workgroup of a table (ticket counter in the
-// table's state) reduces the per-column maxima to the estimate.  state [4]: [0] running maximum of the estimate since the host
+// radial stack's layers): a workgroup = 64 columns x 4 row ranges; a second launch, one workgroup per table, reduces the per-column
+// maxima to the estimate (rtable_guard_reduce_kernel).  state [4]: [0] running maximum of the estimate since the host
 // last reset it (what a replayed HIP graph leaves behind: the captured step never re-enters Python), [1] the estimate of this
 // launch, [2] unused, [3] the per-column ratio of this launch (un-weighted).  A non-finite table entry
 // gives +inf.
@@ -616,6 +616,7 @@ extern "C" int e3k_rtable_pack_multi(const float* const* T, int32_t K, const int
 extern "C" int e3k_rtable_interp_packed(const void* P, const int32_t* bin_perm, const int32_t* bin, const float* coef, int64_t E,
                                         int32_t K, int32_t W, float* w, void* stream) {
   if (E < 0 || K < 4 || W <= 0) return E3K_ERR_INVALID;
+  if (E >= 0x7fffffffLL) return E3K_ERR_UNSUPPORTED;
   if (E == 0) return E3K_OK;
   if (!P || !bin_perm || !bin || !coef || !w) return E3K_ERR_INVALID;
   hipLaunchKernelGGL(e3k::rtable_interp_packed_kernel, dim3((unsigned)((E + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
@@ -672,7 +673,7 @@ extern "C" int e3k_rtable_bins_keyed(const float* r, const int64_t* key, int32_t
 extern "C" int e3k_rtable_interp_fwd(const float* T, const int32_t* bin_perm, const int32_t* bin, const float* coef, int64_t E,
                                      int32_t K, int32_t W, float* w, void* stream) {
   if (E < 0 || K < 4 || W <= 0) return E3K_ERR_INVALID;
-  if (W % 4) return E3K_ERR_UNSUPPORTED;
+  if (W % 4 || E >= 0x7fffffffLL) return E3K_ERR_UNSUPPORTED;      // (bin_perm holds int32 edge ids: e3k_rtable_bins refuses such an E too)
   if (E == 0) return E3K_OK;
   if (!T || !bin_perm || !bin || !coef || !w) return E3K_ERR_INVALID;
   hipLaunchKernelGGL(e3k::rtable_interp_fwd_kernel, dim3((unsigned)((E + 3) / 4)), dim3(256), 0, (hipStream_t)stream, T, bin_perm,
@@ -685,7 +686,7 @@ extern "C" int e3k_rtable_interp_fwd(const float* T, const int32_t* bin_perm, co
 extern "C" int e3k_rtable_interp_fwd2(const float* T, const float* T2, const int32_t* bin_perm, const int32_t* bin, const float* coef,
                                       int64_t E, int32_t K, int32_t W, float* w, float* w2, void* stream) {
   if (E < 0 || K < 4 || W <= 0) return E3K_ERR_INVALID;
-  if (W % 4) return E3K_ERR_UNSUPPORTED;
+  if (W % 4 || E >= 0x7fffffffLL) return E3K_ERR_UNSUPPORTED;      // (bin_perm holds int32 edge ids: e3k_rtable_bins refuses such an E too)
   if (E == 0) return E3K_OK;
   if (!T || !T2 || !bin_perm || !bin || !coef || !w || !w2) return E3K_ERR_INVALID;
   hipLaunchKernelGGL(e3k::rtable_interp_fwd_kernel, dim3((unsigned)((E + 3) / 4)), dim3(256), 0, (hipStream_t)stream, T, bin_perm,
@@ -702,7 +703,7 @@ extern "C" int e3k_rtable_interp_bwd(const float* g_w, const float* coef, const 
                                      const int32_t* bin_ptr, const int32_t* bin_seg, const int32_t* bin_perm, int64_t E, int32_t K,
                                      int32_t W, float* workspace, float* g_T, int32_t accumulate, void* stream) {
   if (E < 0 || K < 4 || W <= 0) return E3K_ERR_INVALID;
-  if (W % 4) return E3K_ERR_UNSUPPORTED;
+  if (W % 4 || E >= 0x7fffffffLL) return E3K_ERR_UNSUPPORTED;      // (bin_perm holds int32 edge ids: e3k_rtable_bins refuses such an E too)
   if (!g_T || !bin_ptr || !bin_seg || !workspace || (E > 0 && (!g_w || !coef || !bin_perm))) return E3K_ERR_INVALID;
   const int n_chunks = (W + 255) / 256;
   const int64_t cap = rtable_seg_cap(E, K);

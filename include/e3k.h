@@ -344,7 +344,8 @@ int e3k_csr_build(const int64_t* edge_index, int64_t N, int64_t E, int32_t* src,
  * neighbour node of an edge -- src for the destination CSR, dst for the source CSR) as ONE 64-byte block per edge, in walk order:
  *   rec[t] = { nbr[e], bin[e], coef[e, 0..3], sh[e, 0..8], e },  e = perm[t]        (bin / coef NULL: zeros; d_sh < 9: zero padded)
  * replacing the chain perm[t] -> e -> {nbr, bin, coef, sh}[e] of dependent scalar loads in front of every edge's row loads
- * (reference: what `x[edge_src]`, `edge_spherical[e]`, `weight[e]` index, nn/message_passing.py:96-109).  rec: 64-byte aligned. */
+ * (reference: what `x[edge_src]`, `edge_spherical[e]`, `weight[e]` index, nn/message_passing.py:96-109).  rec: 64-byte aligned.
+ * E < 2^31 - 1 (perm holds int32 edge ids): E3K_ERR_UNSUPPORTED beyond. */
 int e3k_edge_records(const int32_t* perm, const int32_t* nbr, const int32_t* bin, const float* coef, const float* sh, int32_t d_sh,
                      int64_t E, int32_t* rec, void* stream);
 
@@ -414,7 +415,8 @@ int e3k_collate_gather(const e3k_collate_field* fields, int32_t n_fields, int32_
  *   e3k_rtable_interp_bwd g_T[j,:] (+)= sum over the edges whose stencil holds row j of their weight for it (times scale[e] when
  *                         scale is given) times g_w[e,:]; every row written; no atomics: per-segment partial sums in the
  *                         workspace, then a fixed-order combination (bit-identical run to run).
- * W must be a multiple of 4.
+ * W must be a multiple of 4 (else E3K_ERR_UNSUPPORTED).  E < 2^31 - 1 everywhere (bin_perm holds int32 edge ids), at most 4 001
+ * table rows for e3k_rtable_bins / _keyed: E3K_ERR_UNSUPPORTED beyond.
  * ------------------------------------------------------------------------------------------ */
 int64_t e3k_rtable_bins_workspace_ints(int64_t E, int32_t K);
 int e3k_rtable_bins(const float* r, int64_t E, float h_inv, int32_t K, int32_t* bin, float* coef,
@@ -462,8 +464,9 @@ int e3k_rtable_interp_packed(const void* P, const int32_t* bin_perm, const int32
  *     reported          est   = max(est_g, col_weight * est_c)        (col_weight = table-wide tolerance / per-column tolerance)
  * for up to 16 tables of `rows` rows in ONE launch (the layers of a radial stack).  states[t] float [4]: [0] running maximum of
  * est since the caller last zeroed it (atomic max: survives HIP-graph replays, which never re-enter the host code that would
- * read a per-launch value), [1] est of this launch, [2] internal ticket counter (zero it once at allocation), [3] est_c of this
- * launch.  scratch[t] float [16 * widths[t]].  A non-finite table entry gives est = +inf.  rows < 5: nothing to do. */
+ * read a per-launch value), [1] est of this launch, [2] unused (never read or written), [3] est_c of this launch.
+ * scratch[t] float [16 * widths[t]].  A non-finite table entry gives +inf in [0], [1] and [3].  rows < 5: nothing to do, nothing
+ * written. */
 int e3k_rtable_guard(const float* const* tables, float* const* states, float* const* scratch, const int32_t* widths, int32_t n,
                      int32_t rows, float floor_rel, float col_weight, int32_t packed, void* stream);
 
