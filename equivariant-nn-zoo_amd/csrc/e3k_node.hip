@@ -210,83 +210,158 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
   for (; r < rows; r += step) gx[r * in_dim + c] = eval(r);
 }
 
-// the same for channel-fastest outputs whose segments sit on 16-byte boundaries (what consecutive MessagePassing layers hand
-// over): a thread owns FOUR consecutive input columns (one segment, one mode: segment bounds are multiples of four), every access
-// is a float4, a wave walks its own (few) rows.  Same arithmetic per element, same bits.
+// ---- 16-byte forms -----------------------------------------------------------------------------------------------------
+// For rows whose segments sit on 16-byte boundaries (launcher: gate_vec_ok).  A workgroup owns ONE segment and a run of rows, a
+// lane owns four consecutive channels u..u+3 of one row: every lane of a wave runs the same mode, every access is a float4, and
+// the lanes of a gated block load that block's g_y and x once and form both the gated gradients and the gate scalar's dot over
+// m from them.  The per-lane loads (1 + 2 dim, 3 dim with g_y2) are all issued before the first use (dim is a template
+// argument).  Per-element arithmetic and the order of the dot over m are those of the scalar kernels: same bits.
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__global__ __launch_bounds__(256) void gate_bwd4_kernel(const float* __restrict__ x, const float* __restrict__ gy,
-                                                         const float* __restrict__ gy2, int64_t rows, int in_dim, int out_dim,
-                                                         GateArgs ga, float* __restrict__ gx) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = (blockIdx.x * 64 + lane) * 4;
-  if (c >= in_dim) return;
-  int mode = -1, go = 0, xi = 0, dim = 0, mul = 0, act = 0;
-  float cst = 0.f;
-  for (int k = 0; k < ga.n; ++k) {
-    const e3k_gate_seg& s = ga.s[k];
-    if (s.kind == 0) {
-      const int rel = c - s.in_off;
-      if (rel >= 0 && rel < s.mul) {
-        mode = 0, go = s.out_off + rel, act = s.act, cst = s.cst;
-        break;
-      }
-    } else {
-      const int relg = c - s.gate_off;
-      if (relg >= 0 && relg < s.mul) {
-        mode = 1, go = s.out_off + relg, xi = s.in_off + relg, dim = s.dim, mul = s.mul, act = s.act, cst = s.cst;
-        break;
-      }
-      const int rel = c - s.in_off;
-      if (rel >= 0 && rel < s.mul * s.dim) {
-        const int m = rel / s.mul, u = rel - m * s.mul;
-        mode = 2, go = s.out_off + m * s.mul + u, xi = s.gate_off + u, act = s.act, cst = s.cst;
-        break;
-      }
+__device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) {
+  *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
+}
+__device__ __forceinline__ float4 ld4_sum(const float* p, const float* p2) {
+  float4 a = ld4(p);
+  if (p2) {
+    const float4 b = ld4(p2);
+    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+  }
+  return a;
+}
+// g[m][j] = g_y (+ g_y2) of (channel u + j, component m).  Channel-fastest rows hold one component of the four channels in one
+// float4; e3nn rows hold the 4 dim values of the four channels contiguously, channel-major.
+template <int CF, int DIM>
+__device__ __forceinline__ void gate_load_g(const e3k_gate_seg& s, const float* gr, const float* gr2, int u, float (&g)[DIM][4]) {
+  if (CF) {
+#pragma unroll
+    for (int m = 0; m < DIM; ++m) {
+      const int o = s.out_off + m * s.mul + u;
+      const float4 a = ld4_sum(gr + o, gr2 ? gr2 + o : nullptr);
+      g[m][0] = a.x; g[m][1] = a.y; g[m][2] = a.z; g[m][3] = a.w;
+    }
+  } else {
+    const int o = s.out_off + u * DIM;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+      const float4 a = ld4_sum(gr + o + 4 * k, gr2 ? gr2 + o + 4 * k : nullptr);
+      g[(4 * k) % DIM][(4 * k) / DIM] = a.x;
+      g[(4 * k + 1) % DIM][(4 * k + 1) / DIM] = a.y;
+      g[(4 * k + 2) % DIM][(4 * k + 2) / DIM] = a.z;
+      g[(4 * k + 3) % DIM][(4 * k + 3) / DIM] = a.w;
     }
   }
-  auto eval = [&](int64_t r) -> float4 {
+}
+
+template <int CF, int DIM>
+__device__ __forceinline__ void gate_bwd_gated(const e3k_gate_seg& s, const float* __restrict__ xr, const float* __restrict__ gr,
+                                               const float* __restrict__ gr2, float* __restrict__ gxr, int u) {
+  float g[DIM][4], xv[DIM][4];
+  gate_load_g<CF, DIM>(s, gr, gr2, u, g);
+  const float4 xg4 = ld4(xr + s.gate_off + u);
+#pragma unroll
+  for (int m = 0; m < DIM; ++m) {
+    const float4 a = ld4(xr + s.in_off + m * s.mul + u);
+    xv[m][0] = a.x; xv[m][1] = a.y; xv[m][2] = a.z; xv[m][3] = a.w;
+  }
+  const float xg[4] = {xg4.x, xg4.y, xg4.z, xg4.w};
+  float sc[4], gs[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sc[j] = s.cst * act_f(s.act, xg[j]);
+#pragma unroll
+  for (int m = 0; m < DIM; ++m)
+    st4(gxr + s.in_off + m * s.mul + u, g[m][0] * sc[0], g[m][1] * sc[1], g[m][2] * sc[2], g[m][3] * sc[3]);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float dot = 0.f;
+#pragma unroll
+    for (int m = 0; m < DIM; ++m) dot = fmaf(g[m][j], xv[m][j], dot);
+    gs[j] = dot * s.cst * act_df(s.act, xg[j]);
+  }
+  st4(gxr + s.gate_off + u, gs[0], gs[1], gs[2], gs[3]);
+}
+
+// grid: x = runs of rb rows, y = segment
+template <int CF>
+__global__ __launch_bounds__(256) void gate_bwd4_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                                                         const float* __restrict__ gy2, int64_t rows, int in_dim, int out_dim,
+                                                         GateArgs ga, int rb, float* __restrict__ gx) {
+  const e3k_gate_seg& s = ga.s[blockIdx.y];
+  const int q = s.mul >> 2;
+  const int64_t row0 = (int64_t)blockIdx.x * rb;
+  for (int i = threadIdx.x; i < rb * q; i += 256) {
+    const int rr = i / q, u = (i - rr * q) * 4;
+    const int64_t r = row0 + rr;
+    if (r >= rows) break;
     const float* xr = x + r * in_dim;
     const float* gr = gy + r * out_dim;
     const float* gr2 = gy2 ? gy2 + r * out_dim : nullptr;
-    auto G = [&](int i) -> float4 {
-      float4 a = ld4(gr + i);
-      if (gr2) {
-        const float4 b = ld4(gr2 + i);
-        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    float* gxr = gx + r * in_dim;
+    if (s.kind == 0) {
+      const float4 g = ld4_sum(gr + s.out_off + u, gr2 ? gr2 + s.out_off + u : nullptr), xc = ld4(xr + s.in_off + u);
+      st4(gxr + s.in_off + u, g.x * s.cst * act_df(s.act, xc.x), g.y * s.cst * act_df(s.act, xc.y),
+          g.z * s.cst * act_df(s.act, xc.z), g.w * s.cst * act_df(s.act, xc.w));
+    } else {
+      switch (s.dim) {
+        case 1: gate_bwd_gated<CF, 1>(s, xr, gr, gr2, gxr, u); break;
+        case 3: gate_bwd_gated<CF, 3>(s, xr, gr, gr2, gxr, u); break;
+        case 5: gate_bwd_gated<CF, 5>(s, xr, gr, gr2, gxr, u); break;
+        default: gate_bwd_gated<CF, 7>(s, xr, gr, gr2, gxr, u); break;
       }
-      return a;
-    };
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (mode == 0) {
-      const float4 g = G(go), xc = ld4(xr + c);
-      v.x = g.x * cst * act_df(act, xc.x); v.y = g.y * cst * act_df(act, xc.y);
-      v.z = g.z * cst * act_df(act, xc.z); v.w = g.w * cst * act_df(act, xc.w);
-    } else if (mode == 1) {
-      float4 dot = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int m = 0; m < dim; ++m) {
-        const float4 g = G(go + m * mul), xv = ld4(xr + xi + m * mul);
-        dot.x = fmaf(g.x, xv.x, dot.x); dot.y = fmaf(g.y, xv.y, dot.y); dot.z = fmaf(g.z, xv.z, dot.z); dot.w = fmaf(g.w, xv.w, dot.w);
-      }
-      const float4 xc = ld4(xr + c);
-      v.x = dot.x * cst * act_df(act, xc.x); v.y = dot.y * cst * act_df(act, xc.y);
-      v.z = dot.z * cst * act_df(act, xc.z); v.w = dot.w * cst * act_df(act, xc.w);
-    } else if (mode == 2) {
-      const float4 g = G(go), xg = ld4(xr + xi);
-      v.x = g.x * (cst * act_f(act, xg.x)); v.y = g.y * (cst * act_f(act, xg.y));
-      v.z = g.z * (cst * act_f(act, xg.z)); v.w = g.w * (cst * act_f(act, xg.w));
     }
-    return v;
-  };
-  int64_t r = (int64_t)blockIdx.y * 4 + w;
-  const int64_t step = (int64_t)gridDim.y * 4;
-  for (; r + 3 * step < rows; r += 4 * step) {
-    const float4 v0 = eval(r), v1 = eval(r + step), v2 = eval(r + 2 * step), v3 = eval(r + 3 * step);
-    *reinterpret_cast<float4*>(gx + r * in_dim + c) = v0;
-    *reinterpret_cast<float4*>(gx + (r + step) * in_dim + c) = v1;
-    *reinterpret_cast<float4*>(gx + (r + 2 * step) * in_dim + c) = v2;
-    *reinterpret_cast<float4*>(gx + (r + 3 * step) * in_dim + c) = v3;
   }
-  for (; r < rows; r += step) *reinterpret_cast<float4*>(gx + r * in_dim + c) = eval(r);
+}
+
+template <int CF, int DIM>
+__device__ __forceinline__ void gate_fwd_gated(const e3k_gate_seg& s, const float* __restrict__ xr, float* __restrict__ yr, int u) {
+  float xv[DIM][4];
+  const float4 xg4 = ld4(xr + s.gate_off + u);
+#pragma unroll
+  for (int m = 0; m < DIM; ++m) {
+    const float4 a = ld4(xr + s.in_off + m * s.mul + u);
+    xv[m][0] = a.x; xv[m][1] = a.y; xv[m][2] = a.z; xv[m][3] = a.w;
+  }
+  const float sc[4] = {s.cst * act_f(s.act, xg4.x), s.cst * act_f(s.act, xg4.y), s.cst * act_f(s.act, xg4.z),
+                       s.cst * act_f(s.act, xg4.w)};
+  if (CF) {
+#pragma unroll
+    for (int m = 0; m < DIM; ++m)
+      st4(yr + s.out_off + m * s.mul + u, xv[m][0] * sc[0], xv[m][1] * sc[1], xv[m][2] * sc[2], xv[m][3] * sc[3]);
+  } else {
+    float v[4 * DIM];      // e3nn order: channel-major
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int m = 0; m < DIM; ++m) v[j * DIM + m] = xv[m][j] * sc[j];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) st4(yr + s.out_off + u * DIM + 4 * k, v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+  }
+}
+
+template <int CF>
+__global__ __launch_bounds__(256) void gate_fwd4_kernel(const float* __restrict__ x, int64_t rows, int in_dim, int out_dim,
+                                                         GateArgs ga, int rb, float* __restrict__ y) {
+  const e3k_gate_seg& s = ga.s[blockIdx.y];
+  const int q = s.mul >> 2;
+  const int64_t row0 = (int64_t)blockIdx.x * rb;
+  for (int i = threadIdx.x; i < rb * q; i += 256) {
+    const int rr = i / q, u = (i - rr * q) * 4;
+    const int64_t r = row0 + rr;
+    if (r >= rows) break;
+    const float* xr = x + r * in_dim;
+    float* yr = y + r * out_dim;
+    if (s.kind == 0) {
+      const float4 xc = ld4(xr + s.in_off + u);
+      st4(yr + s.out_off + u, s.cst * act_f(s.act, xc.x), s.cst * act_f(s.act, xc.y), s.cst * act_f(s.act, xc.z),
+          s.cst * act_f(s.act, xc.w));
+    } else {
+      switch (s.dim) {
+        case 1: gate_fwd_gated<CF, 1>(s, xr, yr, u); break;
+        case 3: gate_fwd_gated<CF, 3>(s, xr, yr, u); break;
+        case 5: gate_fwd_gated<CF, 5>(s, xr, yr, u); break;
+        default: gate_fwd_gated<CF, 7>(s, xr, yr, u); break;
+      }
+    }
+  }
 }
 
 // backward of gate_bwd (cotangent gh on gx): g_gy = (d y / d x) gh  — one thread per OUTPUT element
@@ -981,6 +1056,52 @@ int make_gate(const e3k_gate_seg* segs, int32_t n_segs, e3k::GateArgs& ga) {
   }
   return E3K_OK;
 }
+
+// The 16-byte gate kernels apply when every segment starts on a 16-byte boundary, carries a multiple of four channels and stays
+// inside its rows, the gated blocks have dim 1, 3, 5 or 7, and the segments tile the WRITTEN row exactly (the input row for the
+// backward, the output row for the forward): those kernels walk segments, so a column no segment owns would stay unwritten,
+// where the scalar kernels store a zero.  Base-pointer alignment is the caller's part.
+bool gate_vec_ok(int32_t in_dim, int32_t out_dim, const e3k_gate_seg* segs, int32_t n_segs, bool backward) {
+  if (in_dim % 4 || out_dim % 4) return false;
+  int64_t lo[2 * e3k::MAXBLK], hi[2 * e3k::MAXBLK];
+  int n = 0;
+  for (int k = 0; k < n_segs; ++k) {
+    const e3k_gate_seg& s = segs[k];
+    const int64_t len = (int64_t)s.mul * s.dim;
+    if (s.mul % 4 || s.in_off % 4 || s.out_off % 4 || s.in_off < 0 || s.out_off < 0) return false;
+    if (s.in_off + len > in_dim || s.out_off + len > out_dim) return false;
+    if (s.kind == 0) {
+      if (s.dim != 1) return false;
+    } else {
+      if (s.dim != 1 && s.dim != 3 && s.dim != 5 && s.dim != 7) return false;
+      if (s.gate_off % 4 || s.gate_off < 0 || (int64_t)s.gate_off + s.mul > in_dim) return false;
+    }
+    if (backward) {
+      lo[n] = s.in_off, hi[n++] = s.in_off + len;
+      if (s.kind != 0) lo[n] = s.gate_off, hi[n++] = (int64_t)s.gate_off + s.mul;
+    } else {
+      lo[n] = s.out_off, hi[n++] = s.out_off + len;
+    }
+  }
+  const int64_t end = backward ? in_dim : out_dim;
+  int64_t at = 0;
+  for (int done = 0; done < n; ++done) {      // n <= 32: pick the interval that starts where the last one ended
+    int j = -1;
+    for (int i = 0; i < n; ++i)
+      if (lo[i] == at) { j = i; break; }
+    if (j < 0) return false;
+    at = hi[j];
+    lo[j] = -1;
+  }
+  return at == end;
+}
+// rows per workgroup of the 16-byte kernels: one (row, channel quad) item per thread for the widest segment
+int gate_rows_per_block(const e3k_gate_seg* segs, int32_t n_segs) {
+  int qmax = 1;
+  for (int k = 0; k < n_segs; ++k) qmax = segs[k].mul / 4 > qmax ? segs[k].mul / 4 : qmax;
+  return qmax >= 256 ? 1 : 256 / qmax;
+}
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }  // namespace
 
 /* blocks / segs are HOST arrays (copied into the kernel arguments). */
@@ -1007,6 +1128,19 @@ extern "C" int e3k_gate_fwd(const float* x, int64_t rows, int32_t in_dim, int32_
   if (rows < 0 || in_dim <= 0 || out_dim <= 0) return E3K_ERR_INVALID;
   if (rows == 0) return E3K_OK;
   if (!x || !y) return E3K_ERR_INVALID;
+  if (al16(x) && al16(y) && gate_vec_ok(in_dim, out_dim, segs, n_segs, false)) {
+    const int rb = gate_rows_per_block(segs, n_segs);
+    const int64_t gx = (rows + rb - 1) / rb;
+    if (gx <= 0x7fffffffLL) {
+      const dim3 grid((unsigned)gx, (unsigned)n_segs);
+      if (out_cf)
+        hipLaunchKernelGGL(e3k::gate_fwd4_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, rows, in_dim, out_dim, ga, rb, y);
+      else
+        hipLaunchKernelGGL(e3k::gate_fwd4_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, x, rows, in_dim, out_dim, ga, rb, y);
+      E3K_CHECK_LAUNCH();
+      return E3K_OK;
+    }
+  }
   hipLaunchKernelGGL(e3k::gate_fwd_kernel, e3k::grid_cols_deep(out_dim, rows, 2048), dim3(256), 0, (hipStream_t)stream, x,
                      rows, in_dim, out_dim, ga, y);
   E3K_CHECK_LAUNCH();
@@ -1023,25 +1157,35 @@ extern "C" int e3k_gate_bwd(const float* x, const float* g_y, const float* g_y2,
   if (rows < 0 || in_dim <= 0 || out_dim <= 0) return E3K_ERR_INVALID;
   if (rows == 0) return E3K_OK;
   if (!x || !g_y || !g_x) return E3K_ERR_INVALID;
-  // rows per wave of the float4 form (isolated, 4 608 rows: scalar form 30.9 us; 1 / 2 / 4 / 8 rows per wave 26.4 / 23.2 / 25.3 / 31.8)
-  constexpr int kGateRows = 2;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  bool vec = out_cf && in_dim % 4 == 0 && out_dim % 4 == 0 && al16(x) && al16(g_y) && al16(g_x) && (!g_y2 || al16(g_y2));
-  for (int k = 0; k < n_segs && vec; ++k)
-    vec = segs[k].in_off % 4 == 0 && segs[k].out_off % 4 == 0 && segs[k].mul % 4 == 0 && (segs[k].kind == 0 || segs[k].gate_off % 4 == 0);
-  if (vec) {
-    const int gx = (in_dim / 4 + 63) / 64;
-    int64_t gy = (rows + 4 * kGateRows - 1) / (4 * kGateRows);      // kGateRows rows per wave
-    if (gy < 1) gy = 1;
-    hipLaunchKernelGGL(e3k::gate_bwd4_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, x, g_y, g_y2, rows,
-                       in_dim, out_dim, ga, g_x);
-    E3K_CHECK_LAUNCH();
-    return E3K_OK;
+  if (al16(x) && al16(g_y) && al16(g_x) && (!g_y2 || al16(g_y2)) && gate_vec_ok(in_dim, out_dim, segs, n_segs, true)) {
+    const int rb = gate_rows_per_block(segs, n_segs);
+    const int64_t gx = (rows + rb - 1) / rb;
+    if (gx <= 0x7fffffffLL) {
+      const dim3 grid((unsigned)gx, (unsigned)n_segs);
+      if (out_cf)
+        hipLaunchKernelGGL(e3k::gate_bwd4_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, g_y, g_y2, rows, in_dim, out_dim,
+                           ga, rb, g_x);
+      else
+        hipLaunchKernelGGL(e3k::gate_bwd4_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, x, g_y, g_y2, rows, in_dim, out_dim,
+                           ga, rb, g_x);
+      E3K_CHECK_LAUNCH();
+      return E3K_OK;
+    }
   }
   hipLaunchKernelGGL(e3k::gate_bwd_kernel, e3k::grid_cols_deep(in_dim, rows, 4096), dim3(256), 0, (hipStream_t)stream, x, g_y,
                      g_y2, rows, in_dim, out_dim, ga, g_x);
   E3K_CHECK_LAUNCH();
   return E3K_OK;
+}
+
+/* Which gate kernel e3k_gate_fwd (backward = 0) or e3k_gate_bwd (backward = 1) launches for these segments when every base
+   pointer is 16-byte aligned: 1 = the 16-byte form, 0 = the scalar form.  Host only, no launch. */
+extern "C" int e3k_gate_path(int32_t in_dim, int32_t out_dim, const e3k_gate_seg* segs, int32_t n_segs, int32_t backward) {
+  e3k::GateArgs ga{};
+  const int rc = make_gate(segs, n_segs, ga);
+  if (rc != E3K_OK) return rc;
+  if (in_dim <= 0 || out_dim <= 0) return E3K_ERR_INVALID;
+  return gate_vec_ok(in_dim, out_dim, segs, n_segs, backward != 0) ? 1 : 0;
 }
 
 extern "C" int e3k_gate_bwd2(const float* x, const float* g_y, const float* g_hat, int64_t rows, int32_t in_dim,

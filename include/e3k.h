@@ -511,6 +511,11 @@ int e3k_gate_fwd(const float* x, int64_t rows, int32_t in_dim, int32_t out_dim, 
                  int32_t n_segs, int32_t out_cf, float* y, void* stream);
 int e3k_gate_bwd(const float* x, const float* g_y, const float* g_y2, int64_t rows, int32_t in_dim, int32_t out_dim,
                  const e3k_gate_seg* segs, int32_t n_segs, int32_t out_cf, float* g_x, void* stream);
+/* Which kernel e3k_gate_fwd (backward = 0) / e3k_gate_bwd (backward = 1) picks for these segments when every base pointer is
+ * 16-byte aligned: 1 = the 16-byte form (one segment per workgroup, four channels per lane), 0 = the scalar form.  The 16-byte
+ * form needs offsets and channel counts that are multiples of four, gated blocks of dim 1, 3, 5 or 7, and segments that tile
+ * the written row exactly.  Host only: nothing is launched. */
+int e3k_gate_path(int32_t in_dim, int32_t out_dim, const e3k_gate_seg* segs, int32_t n_segs, int32_t backward);
 /* double backward of the gate: g_hat [rows,in_dim] is the cotangent of e3k_gate_bwd's g_x;
  * g_gy [rows,out_dim] = (dy/dx) g_hat,  g_x [rows,in_dim] = d/dx <g_hat, gate_bwd(x, g_y)>  (either may be NULL). */
 int e3k_gate_bwd2(const float* x, const float* g_y, const float* g_hat, int64_t rows, int32_t in_dim, int32_t out_dim,
@@ -613,6 +618,9 @@ int e3k_mlp_hidden_fwd(const float* x, int64_t E, int32_t k0, int32_t h, int32_t
 int e3k_mlp_hidden_bwd(const float* x, int64_t E, int32_t k0, int32_t h, int32_t n_layers, const float* const* weights,
                        const float* alphas, int32_t act, float cst, const float* const* z, const float* g_out,
                        float* const* g_weights, float* g_x, void* stream);
+/* Rows per tile of the hidden chain for E rows and n_nets nets in one launch: 64, or 16 when the 64-row tiles of all the nets
+ * would not give every compute unit a workgroup (the knot rows of the radial tables).  Host only: nothing is launched. */
+int e3k_mlp_tile_rows(int64_t E, int32_t n_nets);
 
 /* Several MLPs of ONE shape over the SAME input rows in one launch each way (the radial MLPs of all the layers of a
  * network read one edge embedding: nn/message_passing.py:74-79,93 per layer).  g_x is per net (the caller sums). */
