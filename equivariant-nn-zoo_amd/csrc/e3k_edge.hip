@@ -178,8 +178,10 @@ __global__ __launch_bounds__(256) void sph_harm_kernel(const float* __restrict__
   if (e >= E) return;
   const float vx = vec[3 * e], vy = vec[3 * e + 1], vz = vec[3 * e + 2];
   float ux = vx, uy = vy, uz = vz, inv = 1.f;
+  bool clamped = false;   // |v| <= 1e-12: the divisor is the constant 1e-12 (F.normalize), so its backward has no projection
   if (sa.normalize) {
     const float r = sqrtf(vx * vx + vy * vy + vz * vz);
+    clamped = !(r > 1e-12f);
     inv = 1.0f / fmaxf(r, 1e-12f);
     ux *= inv;
     uy *= inv;
@@ -207,8 +209,8 @@ __global__ __launch_bounds__(256) void sph_harm_kernel(const float* __restrict__
   }
   if constexpr (BWD) {
     if (sa.normalize) {
-      // u = v / |v|:  dL/dv = (g - u (u . g)) / |v|
-      const float dot = gx * ux + gy * uy + gz * uz;
+      // u = v / |v|:  dL/dv = (g - u (u . g)) / |v|;   u = v * 1e12 under the clamp:  dL/dv = g * 1e12
+      const float dot = clamped ? 0.f : gx * ux + gy * uy + gz * uz;
       gx = (gx - ux * dot) * inv;
       gy = (gy - uy * dot) * inv;
       gz = (gz - uz * dot) * inv;
@@ -231,9 +233,11 @@ __global__ __launch_bounds__(256) void sph_harm_bwd2_kernel(const float* __restr
   if (e >= E) return;
   const Du vx(vec[3 * e], g_hat[3 * e]), vy(vec[3 * e + 1], g_hat[3 * e + 1]), vz(vec[3 * e + 2], g_hat[3 * e + 2]);
   Du ux = vx, uy = vy, uz = vz, inv(1.f);
+  bool clamped = false;
   if (sa.normalize) {
     const Du r = du_sqrt(vx * vx + vy * vy + vz * vz);
-    inv = (r.v > 1e-12f) ? Du(1.f) / r : Du(1e12f);
+    clamped = !(r.v > 1e-12f);
+    inv = clamped ? Du(1.0f / 1e-12f) : Du(1.f) / r;
     ux = ux * inv;
     uy = uy * inv;
     uz = uz * inv;
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(256) void sph_harm_bwd2_kernel(const float* __restr
   }
   if (g_vec2) {
     if (sa.normalize) {
-      const Du dot = gx * ux + gy * uy + gz * uz;
+      const Du dot = clamped ? Du() : gx * ux + gy * uy + gz * uz;
       gx = (gx - ux * dot) * inv;
       gy = (gy - uy * dot) * inv;
       gz = (gz - uz * dot) * inv;
@@ -447,6 +451,14 @@ __global__ __launch_bounds__(256) void radial_bwd2_kernel(const float* __restric
 // side with torch.cumsum, fill).  Distance test exactly as the reference states it: fp32
 // sqrt(dx^2 + dy^2 + dz^2) < r_max, strict, no fused multiply-add.
 // ---------------------------------------------------------------------------------------
+// A product rounded to fp32 on its own.  The file is built with -ffp-contract=fast, under which the backend fuses any fmul into a
+// neighbouring fadd; __fmul_rn / __fadd_rn are plain x * y and x + y in this toolchain (and __fsqrt_rn the 1-ulp native square
+// root), so they guard nothing.  The empty asm makes the rounded product a value the optimiser has to materialise.
+__device__ __forceinline__ float rounded_product(float a, float b) {
+  float p = a * b;
+  asm volatile("" : "+v"(p));
+  return p;
+}
 template <bool FILL>
 __global__ __launch_bounds__(256) void radius_graph_kernel(const float* __restrict__ pos,
                                                             const int32_t* __restrict__ g_start,
@@ -469,11 +481,11 @@ __global__ __launch_bounds__(256) void radius_graph_kernel(const float* __restri
     bool keep = false;
     if (j < end) {
       if (j != i) {
-        const float dx = __fsub_rn(px, pos[3 * (int64_t)j]);
-        const float dy = __fsub_rn(py, pos[3 * (int64_t)j + 1]);
-        const float dz = __fsub_rn(pz, pos[3 * (int64_t)j + 2]);
-        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-        keep = __fsqrt_rn(d2) < r_max;
+        const float dx = px - pos[3 * (int64_t)j];
+        const float dy = py - pos[3 * (int64_t)j + 1];
+        const float dz = pz - pos[3 * (int64_t)j + 2];
+        const float d2 = (rounded_product(dx, dx) + rounded_product(dy, dy)) + rounded_product(dz, dz);
+        keep = sqrtf(d2) < r_max;   // (sqrtf is correctly rounded as built: no fast-math flag)
       }
       if (!keep && oe > ob) {   // pre-existing edges stay (binary search in i's sorted old neighbours)
         int lo = ob, hi = oe;
@@ -604,6 +616,11 @@ extern "C" int e3k_radial_basis_fwd(const float* r, int64_t E, const float* bess
   return E3K_OK;
 }
 
+extern "C" int e3k_radial_basis_bwd_unroll(int32_t n_basis) {
+  if (n_basis <= 0 || n_basis > e3k::RB_MAXB) return -1;
+  return n_basis <= 8 ? 8 : n_basis <= 16 ? 16 : n_basis <= 32 ? 32 : 64;
+}
+
 extern "C" int e3k_radial_basis_bwd(const float* r, const float* g_out, int64_t E, const float* bessel_w,
                                     int32_t n_basis, float r_max, float r_min, float p, int32_t one_over_r,
                                     int32_t cutoff_kind, float* g_r, float* g_w, void* stream) {
@@ -616,10 +633,12 @@ extern "C" int e3k_radial_basis_bwd(const float* r, const float* g_out, int64_t 
 #define E3K_RB_LAUNCH(MB)                                                                                            \
   hipLaunchKernelGGL(e3k::radial_bwd_kernel<MB>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, r, g_out, E, \
                      bessel_w, n_basis, r_max, r_min, p, one_over_r, cutoff_kind, g_r, g_w)
-  if (n_basis <= 8) E3K_RB_LAUNCH(8);
-  else if (n_basis <= 16) E3K_RB_LAUNCH(16);
-  else if (n_basis <= 32) E3K_RB_LAUNCH(32);
-  else E3K_RB_LAUNCH(64);
+  switch (e3k_radial_basis_bwd_unroll(n_basis)) {
+    case 8: E3K_RB_LAUNCH(8); break;
+    case 16: E3K_RB_LAUNCH(16); break;
+    case 32: E3K_RB_LAUNCH(32); break;
+    default: E3K_RB_LAUNCH(64); break;
+  }
 #undef E3K_RB_LAUNCH
   E3K_CHECK_LAUNCH();
   return E3K_OK;

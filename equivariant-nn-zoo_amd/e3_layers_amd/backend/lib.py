@@ -196,6 +196,7 @@ SIGNATURES = {
     "e3k_sph_harm_bwd2": (C.c_int, [_P, _P, _P, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P]),
     "e3k_radial_basis_fwd": (C.c_int, [_P, _I64, _P, _I32, _F, _F, _F, _I32, _I32, _P, _P]),
     "e3k_radial_basis_bwd": (C.c_int, [_P, _P, _I64, _P, _I32, _F, _F, _F, _I32, _I32, _P, _P, _P]),
+    "e3k_radial_basis_bwd_unroll": (C.c_int, [_I32]),
     "e3k_radial_basis_bwd2": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I32, _F, _F, _F, _I32, _I32, _P, _P, _P, _P]),
     "e3k_keyed_weights_fwd": (C.c_int, [_P, _P, C.POINTER(KwInstr), _I32, _I32, _I32, _I64, _P, _P]),
     "e3k_keyed_weights_bwd_workspace": (C.c_int64, [C.POINTER(KwInstr), _I32, _I32, _I32]),

@@ -169,8 +169,11 @@ int e3k_edge_vector_bwd(const float* g_vec, const float* g_len, const float* edg
                         const int32_t* dst_ptr, const int32_t* dst_perm, const int32_t* src_ptr,
                         const int32_t* src_perm, int64_t N, float* g_pos, void* stream);
 
-/* lmask: bit l set => degree l present (l <= 3), output blocks in ascending-l order of the set
- * bits, repeated per `ls` entry; normalization: 0 component, 1 integral, 2 norm. */
+/* ls: a HOST list of n_ls <= 8 degrees, each 0 .. 3, in any order and with repeats; the output holds one block of 2l + 1 components
+ * per entry, in the order of the list (dim = sum of 2l + 1).  normalization: 0 component, 1 integral, 2 norm.
+ * normalize != 0 evaluates at u = vec / max(|vec|, 1e-12) (torch.nn.functional.normalize): the zero vector gives u = 0 (every block
+ * of l >= 1 is zero), a vector shorter than 1e-12 is scaled by 1e12 and NOT brought to unit length; in both cases the backward passes
+ * treat the divisor as the constant 1e-12 (no projection onto the tangent plane). */
 int e3k_sph_harm_fwd(const float* vec, int64_t E, const int32_t* ls, int32_t n_ls, int32_t normalize,
                      int32_t normalization, float* sh, void* stream);
 int e3k_sph_harm_bwd(const float* vec, const float* g_sh, int64_t E, const int32_t* ls, int32_t n_ls,
@@ -184,9 +187,13 @@ int e3k_sph_harm_bwd2(const float* vec, const float* g_sh, const float* g_hat, i
 /* cutoff_kind: 0 polynomial (p), 1 symmetric (x^2-1)^2 */
 int e3k_radial_basis_fwd(const float* r, int64_t E, const float* bessel_w, int32_t n_basis, float r_max, float r_min,
                          float p, int32_t one_over_r, int32_t cutoff_kind, float* out, void* stream);
+/* g_r [E] is written; g_w [n_basis] is ACCUMULATED with atomics (the caller zeroes it).  Either may be NULL, not both. */
 int e3k_radial_basis_bwd(const float* r, const float* g_out, int64_t E, const float* bessel_w, int32_t n_basis,
                          float r_max, float r_min, float p, int32_t one_over_r, int32_t cutoff_kind, float* g_r,
                          float* g_w, void* stream);
+/* The compile-time bound of e3k_radial_basis_bwd's basis loop for n_basis: 8, 16, 32 or 64 (the smallest that holds n_basis), or -1
+ * for a count the launcher refuses (n_basis <= 0 or > 64).  Host only: nothing is launched. */
+int e3k_radial_basis_bwd_unroll(int32_t n_basis);
 /* double backward: hat_r [E] / hat_w [n_basis] are the cotangents of e3k_radial_basis_bwd's g_r / g_w (either
  * may be NULL = zero).  g_gout [E,n_basis] = d out along (hat_r, hat_w); g_r [E] written, g_w [n_basis]
  * ACCUMULATED (caller zeroes): the second derivatives contracted with g_out.  Outputs may be NULL. */
