@@ -1,0 +1,241 @@
+// Capped neighbour list and the velocity-Verlet updates (run/md.py): what a force evaluation needs between two replays of
+// the model's graph when the atoms move.
+//
+// The capped list is the radius graph of e3k_edge.hip (same distance test, same edge order) written into a FIXED [2, e_cap]
+// buffer: nothing about its size goes to the host, so the build is part of a captured HIP graph.  The batch is one padded by
+// run/graph_step.pad_batch -- its last graph is the ghost graph, which is not searched; the slots behind the real edges are
+// filled with the ghost edges run/graph_step.ghost_sample defines, so that for positions that fit the buffer equals
+// pad_batch(batch with computeEdgeIndex's edges, n_cap, e_cap)["edge_index"] bit for bit.
+//
+// Three launches: count (one wave per source node), scan (one workgroup: offsets, per-graph counts, E_real, the overflow
+// report), fill (node waves + tail blocks).  Every store is guarded by its slot index < e_cap; every node id read from the
+// batch's own bookkeeping is clamped to [0, N] before it is used as an address.
+#include "e3k_common.h"
+
+namespace e3k {
+
+constexpr int32_t NLIST_OVERFLOW = 32;      // value ORed into the persistent flag, i.e. bit 5 (values 1, 4, 8, 16: edge endpoints, one-hot types, table keys, collation)
+
+// (restated from e3k_edge.hip: the file is built with -ffp-contract=fast; the empty asm makes the rounded product a value the
+//  optimiser has to materialise, so no fmul is fused into the neighbouring fadd)
+__device__ __forceinline__ float rounded_product(float a, float b) {
+  float p = a * b;
+  asm volatile("" : "+v"(p));
+  return p;
+}
+
+__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// One wave per source node i walks its own graph's nodes 64 at a time; a ballot compacts the kept pairs in ascending j.
+// node_seg [N]: graph of every node; node_ptr [G + 2]: first node of every graph (the ghost graph is graph G: its nodes count 0).
+template <bool FILL>
+__global__ __launch_bounds__(256) void nlist_kernel(const float* __restrict__ pos, const int64_t* __restrict__ node_seg,
+                                                    const int64_t* __restrict__ node_ptr, int64_t N, int32_t G, float r_max,
+                                                    int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+                                                    int64_t e_cap, int32_t node_blocks, int64_t* __restrict__ edge_index,
+                                                    int64_t* __restrict__ edge_seg) {
+  if constexpr (FILL) {
+    if ((int)blockIdx.x >= node_blocks) {
+      // the ghost tail: slot k >= E_real holds ghost edge k - E_real -- (a, a + 1) with a = kk % (n_ghost - 1), flipped on odd rounds
+      const int64_t e_real = offsets[N] < e_cap ? offsets[N] : e_cap;
+      const int64_t gs = clampi(node_ptr[G], 0, N);
+      const int64_t m = N - gs - 1;      // n_ghost - 1
+      const int64_t stride = (int64_t)(gridDim.x - node_blocks) * 256;
+      for (int64_t k = e_real + (int64_t)(blockIdx.x - node_blocks) * 256 + threadIdx.x; k < e_cap; k += stride) {
+        int64_t s, d;
+        if (m >= 1) {
+          const int64_t kk = k - e_real, a = kk % m;
+          const bool flip = ((kk / m) & 1) != 0;
+          s = gs + (flip ? a + 1 : a);
+          d = gs + (flip ? a : a + 1);
+        } else {      // fewer than two ghost nodes (reported as overflow by the scan): a self loop on the last node, in range
+          s = d = N - 1;
+        }
+        edge_index[k] = s;
+        edge_index[e_cap + k] = d;
+        if (edge_seg) edge_seg[k] = G;
+      }
+      return;
+    }
+  }
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= N) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t g = node_seg[i];
+  if (g < 0 || g >= G) {      // the ghost graph (or a bad segment id): not searched
+    if constexpr (!FILL) {
+      if (lane == 0) counts[i] = 0;
+    }
+    return;
+  }
+  const int64_t beg = clampi(node_ptr[g], 0, N), end = clampi(node_ptr[g + 1], 0, N);
+  const float px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
+  const int64_t off = FILL ? offsets[i] : 0;
+  int cnt = 0;
+  for (int64_t j0 = beg; j0 < end; j0 += 64) {
+    const int64_t j = j0 + lane;
+    bool keep = false;
+    if (j < end && j != i) {
+      const float dx = px - pos[3 * j];
+      const float dy = py - pos[3 * j + 1];
+      const float dz = pz - pos[3 * j + 2];
+      const float d2 = (rounded_product(dx, dx) + rounded_product(dy, dy)) + rounded_product(dz, dz);
+      keep = sqrtf(d2) < r_max;   // (sqrtf is correctly rounded as built: no fast-math flag)
+    }
+    const unsigned long long mask = __ballot(keep);
+    if constexpr (FILL) {
+      const int64_t at = off + cnt + __popcll(mask & ((1ull << lane) - 1ull));
+      if (keep && at < e_cap) {      // (overflow: the list is cut at e_cap)
+        edge_index[at] = i;
+        edge_index[e_cap + at] = j;
+        if (edge_seg) edge_seg[at] = g;
+      }
+    }
+    cnt += __popcll(mask);
+  }
+  if constexpr (!FILL) {
+    if (lane == 0) counts[i] = cnt;
+  }
+}
+
+// One workgroup: offsets [N + 1] = exclusive scan of counts (offsets[N] = E_real), n_edges [G + 1] = the graphs' shares of the
+// list as written (cut at e_cap; the ghost graph takes the rest), state[0] = E_real; overflow: the flag bit and state[1] += 1.
+__global__ __launch_bounds__(1024) void nlist_scan_kernel(const int32_t* __restrict__ counts, const int64_t* __restrict__ node_ptr,
+                                                          int64_t N, int32_t G, int64_t e_cap, int64_t* __restrict__ offsets,
+                                                          int64_t* __restrict__ n_edges, int64_t* __restrict__ state,
+                                                          int32_t* __restrict__ flag) {
+  __shared__ int64_t part[1024];
+  const int t = threadIdx.x;
+  const int64_t chunk = (N + 1023) / 1024;
+  const int64_t b = t * chunk, e = b + chunk < N ? b + chunk : N;
+  int64_t local = 0;
+  for (int64_t i = b; i < e; ++i) local += counts[i];
+  part[t] = local;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const int64_t add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int64_t run = part[t] - local;
+  for (int64_t i = b; i < e; ++i) {
+    offsets[i] = run;
+    run += counts[i];
+  }
+  const int64_t total = part[1023];
+  if (t == 0) offsets[N] = total;
+  __threadfence_block();
+  __syncthreads();
+  for (int g = t; g <= G; g += 1024) {
+    if (g < G) {
+      int64_t lo = offsets[clampi(node_ptr[g], 0, N)], hi = offsets[clampi(node_ptr[g + 1], 0, N)];
+      lo = lo < e_cap ? lo : e_cap;
+      hi = hi < e_cap ? hi : e_cap;
+      n_edges[g] = hi > lo ? hi - lo : 0;
+    } else {
+      n_edges[g] = e_cap - (total < e_cap ? total : e_cap);
+    }
+  }
+  if (t == 0) {
+    const int64_t n_ghost = N - clampi(node_ptr[G], 0, N);
+    state[0] = total;
+    if (total > e_cap || (total < e_cap && n_ghost < 2)) {
+      state[1] += 1;
+      atomicOr(flag, NLIST_OVERFLOW);
+    }
+  }
+}
+
+// velocity Verlet, first half: v += dt/2 f / m, x += dt v on the n real nodes (3n components, one per thread)
+__global__ __launch_bounds__(256) void md_drift_kernel(float* __restrict__ x, float* __restrict__ v, const float* __restrict__ f,
+                                                       const float* __restrict__ mass, int64_t n3, float dt) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n3) return;
+  const float vn = v[c] + (0.5f * dt) * f[c] / mass[c / 3];
+  v[c] = vn;
+  x[c] = x[c] + dt * vn;
+}
+
+// second half: v += dt/2 f / m and the graphs' kinetic energies.  One wave per graph; lane l sums the nodes l, l + 64, ... of the
+// graph in ascending order, the 64 partial sums meet in a fixed butterfly: the same bits every run (no atomics).  The step's record
+// is complete in the same launch: potential[g] = energy[g] (the force graph's static output, overwritten by the next replay).
+__global__ __launch_bounds__(256) void md_kick_kernel(float* __restrict__ v, const float* __restrict__ f, const float* __restrict__ mass,
+                                                      const int64_t* __restrict__ node_ptr, int32_t G, int64_t n, float dt,
+                                                      float* __restrict__ kinetic, const float* __restrict__ energy,
+                                                      float* __restrict__ potential) {
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= G) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t beg = clampi(node_ptr[g], 0, n), end = clampi(node_ptr[g + 1], 0, n);
+  float ke = 0.f;
+  for (int64_t i = beg + lane; i < end; i += 64) {
+    const float m = mass[i], h = 0.5f * dt / m;
+    const float vx = v[3 * i] + h * f[3 * i], vy = v[3 * i + 1] + h * f[3 * i + 1], vz = v[3 * i + 2] + h * f[3 * i + 2];
+    v[3 * i] = vx;
+    v[3 * i + 1] = vy;
+    v[3 * i + 2] = vz;
+    ke += 0.5f * m * ((vx * vx + vy * vy) + vz * vz);
+  }
+  ke = wave_sum(ke);
+  if (lane == 0) {
+    if (kinetic) kinetic[g] = ke;
+    if (potential) potential[g] = energy[g];
+  }
+}
+
+}  // namespace e3k
+
+static bool nlist_args_ok(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G) {
+  return pos && node_seg && node_ptr && N >= 1 && N < (int64_t)1 << 31 && G >= 0;
+}
+
+extern "C" int e3k_nlist_count(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                               int32_t* counts, void* stream) {
+  if (!nlist_args_ok(pos, node_seg, node_ptr, N, G) || !counts) return E3K_ERR_INVALID;
+  hipLaunchKernelGGL(e3k::nlist_kernel<false>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pos, node_seg,
+                     node_ptr, N, G, r_max, counts, (const int64_t*)nullptr, (int64_t)0, 0, (int64_t*)nullptr, (int64_t*)nullptr);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_nlist_fill(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                              const int32_t* counts, int64_t e_cap, int64_t* offsets, int64_t* edge_index, int64_t* n_edges,
+                              int64_t* edge_segment, int64_t* state, int32_t* flag, void* stream) {
+  if (!nlist_args_ok(pos, node_seg, node_ptr, N, G) || !counts || !offsets || !edge_index || !n_edges || !state || !flag ||
+      e_cap < 0 || e_cap >= (int64_t)1 << 31)
+    return E3K_ERR_INVALID;
+  hipLaunchKernelGGL(e3k::nlist_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, node_ptr, N, G, e_cap, offsets,
+                     n_edges, state, flag);
+  E3K_CHECK_LAUNCH();
+  const int node_blocks = (int)((N + 3) / 4);
+  int64_t tail_blocks = (e_cap + 255) / 256;      // the tail is at most the whole buffer (an empty list)
+  if (tail_blocks > 256) tail_blocks = 256;
+  if (tail_blocks < 1) tail_blocks = 1;
+  hipLaunchKernelGGL(e3k::nlist_kernel<true>, dim3((unsigned)(node_blocks + tail_blocks)), dim3(256), 0, (hipStream_t)stream, pos,
+                     node_seg, node_ptr, N, G, r_max, (int32_t*)nullptr, (const int64_t*)offsets, e_cap, node_blocks, edge_index,
+                     edge_segment);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_md_drift(float* x, float* v, const float* f, const float* mass, int64_t n, float dt, void* stream) {
+  if (n < 0) return E3K_ERR_INVALID;
+  if (n == 0) return E3K_OK;
+  if (!x || !v || !f || !mass) return E3K_ERR_INVALID;
+  hipLaunchKernelGGL(e3k::md_drift_kernel, dim3((unsigned)((3 * n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, v, f, mass,
+                     3 * n, dt);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_md_kick(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt,
+                           float* kinetic, const float* energy, float* potential, void* stream) {
+  if (n < 0 || G < 0) return E3K_ERR_INVALID;
+  if (n == 0 || G == 0) return E3K_OK;
+  if (!v || !f || !mass || !node_ptr || (potential && !energy)) return E3K_ERR_INVALID;
+  hipLaunchKernelGGL(e3k::md_kick_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, f, mass, node_ptr, G, n,
+                     dt, kinetic, energy, potential);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}

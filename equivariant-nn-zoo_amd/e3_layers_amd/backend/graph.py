@@ -65,6 +65,18 @@ _flag_ring = None              # until the device had drained (hipHostMalloc syn
 _flag_next = 0                 # happened mid-step
 
 
+NLIST_OVERFLOW = 32            # value in the persistent flag (bit 5): a capped neighbour list (csrc/e3k_nlist.hip) did not fit its buffer
+
+
+class EdgeCapacityExceeded(ValueError):
+    """A capped neighbour list held more edges than its buffer (``data/compute_edge.computeEdgeIndexCapped``): the list that was
+    written is valid but cut short, so whatever was computed on it is wrong.  Reported, never a fault: grow the capacity and redo."""
+
+
+_NLIST_MSG = ("a capped neighbour list did not fit its edge capacity: the real edges were cut at e_cap (valid indices, wrong "
+              "physics) -- raise the capacity (run/md.ReplayedForceField.grow) and redo the steps since the last check")
+
+
 _EDGE_MSG = ("an earlier batch's edge_index held node ids outside [0, num_nodes): its topology is invalid (such edges were "
              "attached to node 0)")
 
@@ -75,12 +87,14 @@ def _check_pending_flags() -> None:
     (``FusedAdamEMA.step`` polls), or by ``check_indices()`` (blocking: evaluation, before a graph capture, tests)."""
     while _pending_flags and _pending_flags[0][0].query():
         _, host, msg, sticky = _pending_flags.pop(0)
+        if sticky is not None and int(host[0]) == NLIST_OVERFLOW:
+            raise EdgeCapacityExceeded(_NLIST_MSG)
         if int(host[0]) != 0:
             # (a persistent flag -- ``sticky`` -- was cleared on the device by the same launch that sent this value home
             #  (``e3k_flag_fetch_clear``, in stream order): every flagged batch is reported exactly once, nothing that was flagged
             #  between this copy and a later host-side clear can be lost (ADVICE r5), and a caller that catches the error and skips
             #  the batch does not see it again on later, valid batches (ADVICE r4))
-            raise ValueError(msg)
+            raise ValueError(msg + ("; " + _NLIST_MSG if sticky is not None and int(host[0]) & NLIST_OVERFLOW else ""))
 
 
 def poll_indices() -> None:

@@ -1,4 +1,4 @@
 from .data import Data, Batch
-from .compute_edge import computeEdgeVector, computeEdgeIndex
+from .compute_edge import computeEdgeVector, computeEdgeIndex, computeEdgeIndexCapped
 
-__all__ = ["Data", "Batch", "computeEdgeVector", "computeEdgeIndex"]
+__all__ = ["Data", "Batch", "computeEdgeVector", "computeEdgeIndex", "computeEdgeIndexCapped"]

@@ -118,21 +118,34 @@ _EDGE_KEYS = ("edge_index", "edge_vector", "edge_length", "_n_edges", "_edge_seg
 def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = None, snr: float = 0.16,
                    n_steps: int = 1, continuous: bool = True, eps: float = 1e-3,
                    preprocess: Sequence[Callable] = (), static_edges: bool = False, graph: bool = False,
-                   n_iter: Optional[int] = None):
+                   n_iter: Optional[int] = None, edge_capacity: Optional[int] = None, r_max: Optional[float] = None):
     """``pc_sampler(model, batch, generator=None, noise_fn=None) -> (batch, n_function_evaluations)``.
 
     preprocess: the dataset's ``(data, attrs) -> (data, attrs)`` functions (``data_config.preprocess``) that
         rebuild ``edge_index`` when the model tree has no ``edge_index`` layer of its own.
     static_edges: the edge set does not depend on the positions (fully connected graphs): build it once.
     graph: with ``static_edges``, capture one corrector+predictor step in a HIP graph and replay it.
+    edge_capacity: with ``graph`` on CUTOFF graphs (no ``static_edges``): the batch is padded with a ghost graph to this many edges
+        (``run/graph_step.pad_batch``) and the captured step rebuilds the neighbour list from the moved positions with the capped
+        device builder (``data/compute_edge.computeEdgeIndexCapped``).  A list that outgrew the capacity during the loop raises
+        ``EdgeCapacityExceeded`` when the loop ends.  The ghost nodes would take part in batch-wide reductions, so only per-node
+        updates are served: a corrector other than ``NoneCorrector`` is refused.
+    r_max: the cutoff of the capped builder; required with ``edge_capacity`` (``preprocess`` is not consulted for it).
     n_iter: stop after this many of the ``sde.N`` reverse steps (harness addition: benchmarks and parity tests
         time / check the first steps of the N=1000 schedule instead of shrinking N, which changes dt and betas).
     """
     inverse_scaler = inverse_scaler or (lambda b: b)
     predictor = predictor or NonePredictor
     corrector = corrector or NoneCorrector
-    if graph and not static_edges:
+    if graph and not static_edges and edge_capacity is None:
         raise ValueError("graph capture needs static_edges=True (a changing edge count changes every launch)")
+    if edge_capacity is not None:
+        if not graph or static_edges:
+            raise ValueError("edge_capacity belongs to graph=True on cutoff graphs (static_edges=False)")
+        if corrector is not NoneCorrector:
+            raise ValueError("edge_capacity: the ghost graph's nodes would enter the corrector's batch-wide norms; only NoneCorrector is served")
+        if r_max is None:
+            raise ValueError("edge_capacity needs the cutoff of the neighbour list: pass r_max")
 
     def rebuild_edges(batch):
         for k in _EDGE_KEYS:
@@ -178,8 +191,13 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
             b = moved(corr.update_fn(b, generator, noise_fn))
             return moved(pred.update_fn(b, generator, noise_fn))
 
+        def capped_updates():
+            return [lambda b: corr.update_fn(b, generator, noise_fn), lambda b: pred.update_fn(b, generator, noise_fn)]
+
         with torch.no_grad():
-            if graph:
+            if graph and edge_capacity is not None:
+                batch = _capped_graph_loop(batch, capped_updates(), keys, timesteps, steps, int(edge_capacity), float(r_max))
+            elif graph:
                 # static buffers: the diffused tensors and t; the step writes its result back into them
                 state = {k: batch[k].clone() for k in keys}
 
@@ -219,6 +237,64 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
         return inverse_scaler(batch), steps * (n_steps + 1)
 
     return pc_sampler
+
+
+def _capped_graph_loop(batch, updates, keys, timesteps, steps: int, e_cap: int, r_max: float):
+    """The reverse steps as replays of ONE graph on cutoff graphs: the batch padded to ``e_cap`` edges, the neighbour list rebuilt
+    inside the graph after every update in ``updates`` (corrector, predictor).  The ghost graph's rows of the diffused tensors are
+    never written back: its nodes stay where they are."""
+    from ..data.compute_edge import check_edge_capacity, computeEdgeIndex, computeEdgeIndexCapped
+    from .graph_step import GHOST_DEGREE, CapturedStep, pad_batch
+
+    dev = batch["_n_nodes"].device
+    for k in _EDGE_KEYS:
+        batch.pop(k)
+    new, attrs = computeEdgeIndex(batch.data, batch.attrs, r_max=r_max)      # eager, once: the sizes of the padded batch
+    batch.attrs.update(attrs)
+    batch.update(new)
+    n, e = batch.n_nodes, int(new["edge_index"].shape[1])
+    if e > e_cap:
+        from ..backend.graph import EdgeCapacityExceeded
+
+        raise EdgeCapacityExceeded(f"the first neighbour list has {e} edges: edge_capacity={e_cap} is too small")
+    n_cap = -(-(n + max(2, -(-(e_cap - e) // GHOST_DEGREE))) // 32) * 32
+    batch["t"] = torch.full((len(batch), 1), float(timesteps[0]), device=dev)
+    padded = pad_batch(batch, n_cap, e_cap)
+    padded["_nlist_state"] = torch.zeros(2, dtype=torch.int64, device=dev)
+    t_dev = padded["t"]
+    state = {k: padded[k] for k in keys}
+
+    def relisted(b):
+        # a fresh view of the padded batch with the moved tensors: what the model left in ``b`` (edge vectors, harmonics, radial
+        # embeddings of the OLD list) stays behind, as the reference's loop drops it (:236-241)
+        fresh = padded.view()
+        for k in keys:
+            fresh[k] = b[k]
+        computeEdgeIndexCapped(fresh.data, fresh.attrs, r_max=r_max)      # in place, on the device, inside the capture
+        return fresh
+
+    def captured():
+        work = padded.view()
+        for update in updates:
+            work = relisted(update(work))
+        for k in keys:
+            state[k][:n].copy_(work[k][:n])
+
+    saved = {k: v.clone() for k, v in state.items()}
+    t_dev.fill_(float(timesteps[0]))
+    step = CapturedStep(captured, warmup=1, device=dev)      # (the warm-up run moved the state: put it back)
+    for k in keys:
+        state[k].copy_(saved[k])
+    for i in range(steps):
+        t_dev.copy_(timesteps[i].expand_as(t_dev))
+        step()
+    check_edge_capacity(padded["_nlist_state"])
+    out = padded[list(range(len(padded) - 1))]      # the real graphs
+    for k in ("_graph_weight", "_node_weight"):
+        out.pop(k)
+    for k in keys:
+        out[k] = state[k][:n].clone()
+    return out
 
 
 def get_sampling_fn(config, sde: VPSDE, inverse_scaler, eps: float, **kwargs):

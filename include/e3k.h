@@ -660,6 +660,41 @@ int e3k_radius_graph_fill(const float* pos, const int32_t* graph_start, const in
                           int64_t* edge_index, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Capped neighbour list (csrc/e3k_nlist.hip): the radius graph above into a buffer of FIXED size, for loops that
+ * evaluate a model over and over while the atoms move inside one captured HIP graph.
+ * Replaces computeEdgeIndex (e3_layers/data/compute_edge.py:38-113) where the sampling loop drops and rebuilds
+ * edge_index after every update (e3_layers/run/sde_sampling.py:236-241) and where an MD driver (torchMD.ipynb) calls the
+ * model on moved positions: same distance test, same edge order, no pre-existing edges, nothing read back by the host.
+ * The batch is a padded one (run/graph_step.pad_batch): graphs 0 .. G-1 are real, graph G is the ghost graph and is not
+ * searched.
+ *   node_seg [N] int64: graph of every node; node_ptr [G + 2] int64: first node of every graph (node_ptr[G + 1] = N).
+ *   e3k_nlist_count writes counts [N] (kept pairs per source node; 0 for ghost nodes).
+ *   e3k_nlist_fill scans them on the device into offsets [N + 1] (workspace) and writes
+ *     edge_index int64 [2, e_cap]: the E_real real edges, then in the slots [E_real, e_cap) ghost edge kk = k - E_real of
+ *       run/graph_step.ghost_sample: (a, a + 1) + node_ptr[G], a = kk % (n_ghost - 1), endpoints swapped when
+ *       kk / (n_ghost - 1) is odd -- for positions that fit, bit for bit pad_batch's edge_index of the rebuilt batch;
+ *     n_edges [G + 1] int64 (ghost graph last), edge_segment [e_cap] int64 (NULL: not wanted), state[0] = E_real.
+ *   Overflow (E_real > e_cap, or slots left over with fewer than two ghost nodes to take them): the real edges are cut
+ *   at e_cap, every index written is a node of the batch, nothing is written outside the buffers; the value 32 (bit 5) is ORed into
+ *   *flag (the device's persistent flag) and state[1] is incremented. */
+int e3k_nlist_count(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                    int32_t* counts, void* stream);
+int e3k_nlist_fill(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                   const int32_t* counts, int64_t e_cap, int64_t* offsets, int64_t* edge_index, int64_t* n_edges,
+                   int64_t* edge_segment, int64_t* state, int32_t* flag, void* stream);
+
+/* Velocity Verlet around a force evaluation (the integrator of torchMD.ipynb's driver) on the n real nodes of a padded
+ * batch -- the ghost nodes behind them never move.  x, v, f [n, 3], mass [n].
+ *   e3k_md_drift: v += dt/2 f / m;  x += dt v.
+ *   e3k_md_kick : v += dt/2 f / m;  kinetic [G] = per-graph sum of m v^2 / 2 through node_ptr [G + 1] int64 (NULL: not
+ *                 wanted).  One wave per graph, fixed summation order, no atomics: the same bits every run.
+ *                 potential [G] (NULL: not wanted) = energy [G], the force evaluation's static output, kept for the step's
+ *                 record in the same launch. */
+int e3k_md_drift(float* x, float* v, const float* f, const float* mass, int64_t n, float dt, void* stream);
+int e3k_md_kick(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt,
+                float* kinetic, const float* energy, float* potential, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training-step plumbing on the flat parameter vector.
  * Replaces clip_grad_norm_ + optim.step() + ema.update() (e3_layers/run/trainer.py:374-386) and the variant that
  * skips the optimizer step on a non-finite gradient (e3_layers/run/sde_utils.py:233-248): torch.optim.Adam
