@@ -209,6 +209,9 @@ SIGNATURES = {
     "e3k_radius_graph_fill": (C.c_int, [_P, _P, _P, _I64, _F, _P, _P, _P, _I64, _P, _P]),
     "e3k_nlist_count": (C.c_int, [_P, _P, _P, _I64, _I32, _F, _P, _P]),
     "e3k_nlist_fill": (C.c_int, [_P, _P, _P, _I64, _I32, _F, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "e3k_nlist_count_crit": (C.c_int, [_P, _P, _P, _I64, _I32, _F, _P, _I64, C.c_uint32, _I32, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "e3k_nlist_fill_crit": (C.c_int, [_P, _P, _P, _I64, _I32, _F, _P, _I64, C.c_uint32, _I32, C.c_uint32, C.c_uint32, _P, _P, _I64, _P, _P, _P, _P, _P, _P,
+                                      _P]),
     "e3k_md_drift": (C.c_int, [_P, _P, _P, _P, _I64, _F, _P]),
     "e3k_md_kick": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _F, _P, _P, _P, _P]),
     "e3k_tp_plan_create": (C.c_int, [C.POINTER(TpGroup), _I32, _I32, _I32, _I32, _I32, C.POINTER(_P)]),

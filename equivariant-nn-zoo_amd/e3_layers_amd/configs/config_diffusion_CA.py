@@ -73,19 +73,29 @@ def criteria(data, edge_index):
     return torch.logical_or(mask, extra < 0.02)
 
 
-def get_config(spec="", l_max=2, num_layers=8, n_dim=64):
+def pair_criterion(seed=0):
+    """``criteria`` as a declarative rule (``data.SequenceOrRandom``: same chain and |i - j| < 5, or a 2 % subset drawn by a counter-based
+    hash instead of the device generator): ``get_config(edge_criteria=pair_criterion())`` gives the tree whose reverse-diffusion loop
+    ``run/sde_sampling.get_pc_sampler(graph=True, edge_capacity=...)`` replays as one HIP graph."""
+    from ..data import SequenceOrRandom
+
+    return SequenceOrRandom("chain_id", 5, 0.02, seed=seed)
+
+
+def get_config(spec="", l_max=2, num_layers=8, n_dim=64, edge_criteria=criteria):
     data = ConfigDict()
     data.std = 25.83
     data.scaler = getScaler([("CA", ("shift", "mean")), ("CA", ("scale", 1 / data.std))])
     data.inverse_scaler = getScaler([("CA", ("scale", data.std))])
     data.preprocess = [masked2indexed, partial(crop, max_nodes=384)]
-    return score_config({"CA": 3}, data, l_max, num_layers, n_dim)
+    return score_config({"CA": 3}, data, l_max, num_layers, n_dim, edge_criteria=edge_criteria)
 
 
-def score_config(diffusion_keys, data, l_max, num_layers, n_dim, side_atoms=()):
+def score_config(diffusion_keys, data, l_max, num_layers, n_dim, side_atoms=(), edge_criteria=criteria):
     """The tree both protein configs share (``config_diffusion_CA.py:66-194``, ``config_diffusion_backbone.py:64-194``):
     one ``score_{key}`` head per diffusion key; ``side_atoms`` (backbone: C, N, O relative positions) are mixed into the
-    node features after ``layer3`` by a ``Concat`` (``config_diffusion_backbone.py:169-176``)."""
+    node features after ``layer3`` by a ``Concat`` (``config_diffusion_backbone.py:169-176``).  ``edge_criteria``: the pair rule of
+    the model's own ``edge_index`` layer (the reference's ``criteria`` callback, or ``pair_criterion()``)."""
     config = ConfigDict()
     model = ConfigDict()
     config.data_config, config.model_config = data, model
@@ -132,6 +142,6 @@ def score_config(diffusion_keys, data, l_max, num_layers, n_dim, side_atoms=()):
         lc.layers = list(lc.layers) + [(f"score_{key}", {"module": PointwiseLinear,
                                                          "irreps_in": (features, "node_features"),
                                                          "irreps_out": ("1x1o", f"score_{key}")})]
-    lc.layers = [("edge_index", partial(computeEdgeIndex, r_max=8.0 / data.std, key="CA", criteria=criteria))] + list(lc.layers)
+    lc.layers = [("edge_index", partial(computeEdgeIndex, r_max=8.0 / data.std, key="CA", criteria=edge_criteria))] + list(lc.layers)
     model.update(lc)
     return config

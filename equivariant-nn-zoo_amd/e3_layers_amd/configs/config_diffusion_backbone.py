@@ -9,12 +9,12 @@ from functools import partial
 
 from ..utils import getScaler
 from .config_dict import ConfigDict
-from .config_diffusion_CA import crop, masked2indexed, score_config
+from .config_diffusion_CA import criteria, crop, masked2indexed, pair_criterion, score_config  # noqa: F401 (pair_criterion: re-exported)
 
 ATOMS = ("N", "CA", "C", "O")
 
 
-def get_config(spec="", l_max=2, num_layers=8, n_dim=64):
+def get_config(spec="", l_max=2, num_layers=8, n_dim=64, edge_criteria=criteria):
     data = ConfigDict()
     data.std = 25.83
     data.scaler = getScaler([("O", ("shift", "C", -1)), ("C", ("shift", "CA", -1)), ("N", ("shift", "CA", -1)),
@@ -22,4 +22,5 @@ def get_config(spec="", l_max=2, num_layers=8, n_dim=64):
     data.inverse_scaler = getScaler([(["C", "CA", "N", "O"], ("scale", data.std)), ("C", ("shift", "CA")),
                                      ("N", ("shift", "CA")), ("O", ("shift", "C"))])
     data.preprocess = [masked2indexed, partial(crop, max_nodes=384, atoms=ATOMS)]
-    return score_config({"CA": 3, "C": 3, "O": 3, "N": 3}, data, l_max, num_layers, n_dim, side_atoms=("C", "N", "O"))
+    return score_config({"CA": 3, "C": 3, "O": 3, "N": 3}, data, l_max, num_layers, n_dim, side_atoms=("C", "N", "O"),
+                        edge_criteria=edge_criteria)

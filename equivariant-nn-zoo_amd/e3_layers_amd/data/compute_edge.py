@@ -16,12 +16,19 @@ reference's edge order without a sort) — the per-step edge rebuild of the samp
 (``e3_layers/run/sde_sampling.py:237-242``) then never leaves the GPU.  ``criteria`` callbacks are
 arbitrary Python over the candidate list and keep the torch path on whichever device holds the data.
 
+``PairCriterion`` / ``SequenceOrRandom`` state the protein nets' pair rule (``e3_layers/configs/config_diffusion_CA.py:58-64``: same
+chain and ``|i - j| < 5``, or a 2 % random subset) declaratively: as a ``criteria`` callback it is the torch restatement of the rule, and
+the capped builder below evaluates the same rule -- the same counter-based draws, bit for bit -- inside its kernels.
+
 ``computeEdgeIndexCapped`` is the same radius graph for loops that call the model over and over while the atoms move (MD, relaxation,
 the reverse-diffusion loop on cutoff graphs): it rewrites the FIXED ``[2, e_cap]`` ``edge_index`` of a batch padded by
 ``run/graph_step.pad_batch`` in place (``csrc/e3k_nlist.hip``), reads nothing back, and is therefore part of a captured HIP graph.
+``computeEdgeIndex`` hands a batch that carries ``_nlist_state`` (the marker the capped loops put into their padded batch) over to it:
+a model that owns its ``edge_index`` layer gets the capped build inside a capture without knowing of it.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Tuple
 
 import torch
@@ -56,6 +63,113 @@ def computeEdgeVector(data: Dict[str, Tensor], attrs: Dict[str, Tuple[str, str]]
 
 
 computeEdgeVector.data_only_inputs = ("pos", "edge_index")      # (SequentialGraphNetwork.prepare_data: parameter-free, reads these keys)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Declarative pair criteria: a rule on ordered candidate pairs that the torch path AND the capped builder's kernels evaluate
+# ---------------------------------------------------------------------------------------------------------------------
+_M32 = 0xFFFFFFFF
+
+
+def _mix32(h):
+    """One round of the "lowbias32" finaliser on int64 values in [0, 2^32): an int64 multiply wraps and keeps the low 32 bits, the
+    mask throws the rest away -- the kernel's uint32 arithmetic (``csrc/e3k_nlist.hip: mix32``), bit for bit."""
+    h = h ^ (h >> 16)
+    h = (h * 0x7feb352d) & _M32
+    h = h ^ (h >> 15)
+    h = (h * 0x846ca68b) & _M32
+    return h ^ (h >> 16)
+
+
+def pair_hash(seed, draw, src, dst) -> Tensor:
+    """The 32-bit hash of (seed low, seed high, draw index, src, dst) as an int64 tensor in [0, 2^32): ``h = mix(h ^ word)`` over the
+    five words (each taken modulo 2^32) from ``0x9E3779B9``.  Every argument is an int or an int64 tensor; they broadcast."""
+    dev = next((x.device for x in (src, dst, draw, seed) if torch.is_tensor(x)), None)
+
+    def word(x):
+        return torch.as_tensor(x, dtype=torch.int64, device=dev) & _M32
+
+    if torch.is_tensor(seed):
+        lo, hi = word(seed), word(torch.as_tensor(seed, dtype=torch.int64, device=dev) >> 32)
+    else:
+        lo, hi = word(int(seed) & _M32), word((int(seed) >> 32) & _M32)
+    h = _mix32(lo ^ 0x9E3779B9)
+    for w in (hi, word(draw), word(src), word(dst)):
+        h = _mix32(h ^ w)
+    return h
+
+
+class PairCriterion:
+    """A pair rule both edge builders recognise.  As a callable it is a ``criteria`` callback of ``computeEdgeIndex``
+    (``(data, edge_index) -> bool mask`` over the ordered candidate pairs, global node indices); ``computeEdgeIndexCapped`` does not
+    call it: it evaluates the rule's terms (``segment``, ``window``, ``threshold``, ``keep_all``, ``seed``) in its kernels."""
+
+    segment, window, p, seed = None, 0, 0.0, 0
+
+    def __init__(self):
+        self._draw = 0
+
+    def reset(self, draw: int = 0) -> None:
+        """The draw index the next call WITHOUT device cells uses (the host-side counter; it goes up by one per call)."""
+        self._draw = int(draw)
+
+    @property
+    def threshold(self) -> int:
+        """floor(p 2^32), the bound a pair's hash stays below to be drawn (p = 1 does not fit 32 bits: ``keep_all``)."""
+        return min(int(math.floor(self.p * 4294967296.0)), _M32)
+
+    @property
+    def keep_all(self) -> bool:
+        return self.p >= 1.0
+
+    def predicate(self, data, edge_index: Tensor, draw) -> Tensor:
+        """The rule at draw index ``draw`` (an int, or an int64 tensor on the candidates' device): bool [n_candidates]."""
+        src, dst = edge_index[0], edge_index[1]
+        keep = torch.zeros(src.shape[0], dtype=torch.bool, device=src.device)
+        if self.window > 0 and self.segment is not None:
+            seg = _segment_key(data, self.segment, None).to(src.device)
+            keep = torch.logical_and(seg[src] == seg[dst], (src - dst).abs() < self.window)
+        if self.keep_all:
+            return torch.ones_like(keep)
+        if self.threshold > 0:
+            keep = torch.logical_or(keep, pair_hash(self.seed, draw, src, dst) < self.threshold)
+        return keep
+
+    def __call__(self, data, edge_index: Tensor) -> Tensor:
+        rng = data["_nlist_rng"] if "_nlist_rng" in data else None
+        if rng is not None:      # the batch's device cells name the draw (read, never written here: the capped builder advances them)
+            return self.predicate(data, edge_index, rng.reshape(-1)[0].to(edge_index.device))
+        draw = self._draw
+        self._draw += 1
+        return self.predicate(data, edge_index, draw)
+
+
+class SequenceOrRandom(PairCriterion):
+    """``(segment[src] == segment[dst] and |src - dst| < window) or bernoulli(p)`` on global node indices -- the shipped protein rule
+    is ``SequenceOrRandom("chain_id", 5, 0.02)``.  ``window=0`` switches the sequence term off, ``p=0`` the random one; ``p=1`` keeps
+    every candidate.  The Bernoulli draw is counter-based and stateless per pair: ``pair_hash(seed, draw, src, dst) < floor(p 2^32)``,
+    where ``draw`` is the number of the list build -- the same for every pair of one build, one more for the next build."""
+
+    def __init__(self, segment: str = "chain_id", window: int = 5, p: float = 0.02, seed: int = 0):
+        super().__init__()
+        if window < 0 or not 0.0 <= p <= 1.0 or not 0 <= int(seed) < 1 << 64:
+            raise ValueError("SequenceOrRandom needs window >= 0, 0 <= p <= 1 and a seed of at most 64 bits")
+        self.segment, self.window, self.p, self.seed = segment, int(window), float(p), int(seed)
+
+    def __repr__(self):
+        return f"SequenceOrRandom(segment={self.segment!r}, window={self.window}, p={self.p}, seed={self.seed})"
+
+
+def _segment_key(data, name: str, n_nodes) -> Tensor:
+    """The criterion's segment field of the batch as int64 [N] (stored as [N] or [N, 1])."""
+    if name not in data:
+        raise ValueError(f"the pair criterion's segment field {name!r} is not in the batch")
+    seg = data[name]
+    if seg.dtype != torch.int64 or seg.dim() not in (1, 2) or (seg.dim() == 2 and seg.shape[1] != 1) or \
+            (n_nodes is not None and seg.shape[0] != n_nodes):
+        raise ValueError(f"the pair criterion's segment field {name!r} must be an int64 tensor of shape [N] or [N, 1] "
+                         f"(got {str(seg.dtype).replace('torch.', '')} {tuple(seg.shape)})")
+    return seg.reshape(-1)
 
 
 def _all_pairs(n_nodes: Tensor, device) -> Tensor:
@@ -130,6 +244,8 @@ def _radius_graph_device(data, attrs, pos: Tensor, r_max: float):
 
 
 def computeEdgeIndex(data, attrs, r_max: float = None, key: str = "pos", criteria=None):
+    if "_nlist_state" in data:      # a padded batch of a capped loop: the fixed-size list, rewritten in place inside the capture
+        return computeEdgeIndexCapped(data, attrs, r_max=r_max, key=key, criteria=criteria)
     pos = torch.as_tensor(data[key], dtype=torch.get_default_dtype())
     if pos.is_cuda and criteria is None and r_max is not None:
         return _radius_graph_device(data, attrs, pos, r_max)
@@ -202,6 +318,21 @@ def nlist_state(device) -> Tensor:
     return st
 
 
+_nlist_rngs: dict = {}        # device index -> int64 [2]: next draw index, draw index in use
+
+
+def nlist_rng(device) -> Tensor:
+    """The device's draw-index cells of the capped builder's criterion form for batches that carry none (``_nlist_rng``): int64 [2] =
+    (draw index of the next build, draw index of the build in progress).  Allocated on first use, OUTSIDE a capture."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    rng = _nlist_rngs.get(idx)
+    if rng is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("nlist_rng() must be called before the capture starts (give the batch a '_nlist_rng' tensor)")
+        rng = _nlist_rngs[idx] = torch.zeros(2, dtype=torch.int64, device=torch.device("cuda", idx))
+    return rng
+
+
 def check_edge_capacity(state: Tensor = None, device=None) -> None:
     """Blocks until the device is idle, then raises ``EdgeCapacityExceeded`` if a capped build overflowed since the last check (the
     overflow counter of ``state``, the device's persistent flag bit, or a flag copy already on its way home) -- and clears all three."""
@@ -248,9 +379,15 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
     More than ``e_cap`` edges: the list is cut (valid indices), bit ``NLIST_OVERFLOW`` of the device's persistent flag is set and the
     overflow counter (``data['_nlist_state'][1]``, else ``nlist_state(device)``) goes up: ``check_edge_capacity`` raises.
 
-    Not served (``computeEdgeIndex`` does both, eagerly): ``criteria`` callbacks, edges kept from before with carried attributes."""
-    if criteria is not None:
-        raise ValueError("computeEdgeIndexCapped takes no criteria callback (arbitrary Python over the candidate list): use computeEdgeIndex")
+    ``criteria``: a ``PairCriterion`` -- a pair is kept inside the cutoff OR by the rule, which the kernels evaluate (the segment field
+    is read from the batch; the draw index from ``data['_nlist_rng']``, int64 [2], else ``nlist_rng(device)``: every build draws with
+    the first cell and adds one to it).  The list then equals ``computeEdgeIndex(criteria=...)``'s at the same draw index.
+
+    Not served (``computeEdgeIndex`` does both, eagerly): ``criteria`` callbacks that are arbitrary Python, edges kept from before with
+    carried attributes."""
+    if criteria is not None and not isinstance(criteria, PairCriterion):
+        raise ValueError("computeEdgeIndexCapped takes no criteria callback (arbitrary Python over the candidate list), only a "
+                         "PairCriterion: use computeEdgeIndex")
     if r_max is None:
         raise ValueError("computeEdgeIndexCapped needs r_max")
     data = getattr(data, "data", data)      # (a Batch: its tensor dict, as the layer graph hands it over)
@@ -282,15 +419,35 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
     node_ptr = _node_pointers(n_nodes)
     state = data["_nlist_state"] if "_nlist_state" in data else nlist_state(dev)
     flag = persistent_flag(dev)
+    seg_key = rng = None
+    if criteria is not None:
+        if criteria.window > 0 and criteria.segment is not None:
+            seg_key = _segment_key(data, criteria.segment, total)
+            L.require_cuda(seg_key)
+            if not seg_key.is_contiguous():
+                raise ValueError(f"the pair criterion's segment field {criteria.segment!r} must be contiguous")
+        rng = data["_nlist_rng"] if "_nlist_rng" in data else nlist_rng(dev)
+        L.require_cuda(rng)
+        if rng.dtype != torch.int64 or not rng.is_contiguous() or rng.numel() != 2:
+            raise ValueError("_nlist_rng must be a contiguous int64 tensor of 2 elements (next draw index, draw index in use)")
     lib = L.load()
     counts = torch.empty(total, dtype=torch.int32, device=dev)
     offsets = torch.empty(total + 1, dtype=torch.int64, device=dev)
     pos_d = pos.detach()
-    L.check(lib.e3k_nlist_count(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts),
-                                L.stream_ptr()), "e3k_nlist_count")
-    L.check(lib.e3k_nlist_fill(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts), e_cap,
-                               L.ptr(offsets), L.ptr(ei), L.ptr(n_edges), L.ptr(seg), L.ptr(state), L.ptr(flag), L.stream_ptr()),
-            "e3k_nlist_fill")
+    if criteria is None:
+        L.check(lib.e3k_nlist_count(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts),
+                                    L.stream_ptr()), "e3k_nlist_count")
+        L.check(lib.e3k_nlist_fill(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts), e_cap,
+                                   L.ptr(offsets), L.ptr(ei), L.ptr(n_edges), L.ptr(seg), L.ptr(state), L.ptr(flag), L.stream_ptr()),
+                "e3k_nlist_fill")
+    else:
+        rule = (L.ptr(seg_key), criteria.window, criteria.threshold, int(criteria.keep_all), criteria.seed & _M32,
+                (criteria.seed >> 32) & _M32, L.ptr(rng))
+        L.check(lib.e3k_nlist_count_crit(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), *rule,
+                                         L.ptr(counts), L.stream_ptr()), "e3k_nlist_count_crit")
+        L.check(lib.e3k_nlist_fill_crit(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), *rule,
+                                        L.ptr(counts), e_cap, L.ptr(offsets), L.ptr(ei), L.ptr(n_edges), L.ptr(seg), L.ptr(state),
+                                        L.ptr(flag), L.stream_ptr()), "e3k_nlist_fill_crit")
     attrs["_n_edges"] = ("graph", "1x0e")
     for k in TOPO_KEYS + ("edge_vector", "edge_length"):
         data.pop(k, None)

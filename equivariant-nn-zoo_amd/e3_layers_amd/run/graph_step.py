@@ -133,54 +133,55 @@ def ghost_positions(n_nodes: int, dtype=torch.float32) -> torch.Tensor:
     return pos
 
 
-def ghost_sample(like, n_nodes: int, n_edges: int):
+def ghost_sample(like, n_nodes: int, n_edges: int, key: str = "pos"):
     """A sample with ``n_nodes`` (>= 2 when it has edges) collinear nodes and ``n_edges`` nearest-neighbour edges, with the
-    keys of ``like`` (a ``Data`` sample on the host: ``pos``, ``species``, ``edge_index``, per-graph targets)."""
+    keys of ``like`` (a ``Data`` sample on the host: ``pos``, ``species``, ``edge_index``, per-graph targets).  ``key``: the field
+    that holds the positions (the protein batches' ``CA``); every other node field takes the first node's value."""
     from ..data.data import Data
 
     if n_nodes < (2 if n_edges else 1):
         raise ValueError(f"a ghost graph with {n_edges} edges needs at least two nodes (got {n_nodes}): raise the node capacity")
-    pos = ghost_positions(n_nodes, like["pos"].dtype)
+    pos = ghost_positions(n_nodes, like[key].dtype)
     k = torch.arange(n_edges, dtype=torch.int64)
     a = k % max(n_nodes - 1, 1)
     flip = (k // max(n_nodes - 1, 1)) % 2 == 1
     src, dst = torch.where(flip, a + 1, a), torch.where(flip, a, a + 1)
     tensors = {}
-    for key in like.keys():
-        v = like[key]
-        if key == "pos":
-            tensors[key] = pos
-        elif key == "edge_index":
-            tensors[key] = torch.stack([src, dst]).to(v.dtype)
-        elif key == "_n_nodes":
-            tensors[key] = torch.full_like(v, n_nodes)
-        elif key == "_n_edges":
-            tensors[key] = torch.full_like(v, n_edges)
-        elif torch.is_tensor(v) and (like.attrs.get(key, ("",))[0] == "node"
-                                     or (key not in like.attrs and v.dim() >= 1 and v.shape[0] == like["pos"].shape[0])):
-            tensors[key] = v[:1].expand(n_nodes, *v.shape[1:]).clone()      # node-wise (species): the first node's value
-        elif torch.is_tensor(v) and like.attrs.get(key, ("",))[0] == "edge":
-            tensors[key] = (v[:1].expand(n_edges, *v.shape[1:]).clone() if v.shape[0] else v.new_zeros((n_edges,) + tuple(v.shape[1:])))
+    for name in like.keys():
+        v = like[name]
+        if name == key:
+            tensors[name] = pos
+        elif name == "edge_index":
+            tensors[name] = torch.stack([src, dst]).to(v.dtype)
+        elif name == "_n_nodes":
+            tensors[name] = torch.full_like(v, n_nodes)
+        elif name == "_n_edges":
+            tensors[name] = torch.full_like(v, n_edges)
+        elif torch.is_tensor(v) and (like.attrs.get(name, ("",))[0] == "node"
+                                     or (name not in like.attrs and v.dim() >= 1 and v.shape[0] == like[key].shape[0])):
+            tensors[name] = v[:1].expand(n_nodes, *v.shape[1:]).clone()      # node-wise (species): the first node's value
+        elif torch.is_tensor(v) and like.attrs.get(name, ("",))[0] == "edge":
+            tensors[name] = (v[:1].expand(n_edges, *v.shape[1:]).clone() if v.shape[0] else v.new_zeros((n_edges,) + tuple(v.shape[1:])))
         elif torch.is_tensor(v):
-            tensors[key] = torch.zeros_like(v)                               # graph-wise targets
+            tensors[name] = torch.zeros_like(v)                               # graph-wise targets
         else:
-            tensors[key] = v
+            tensors[name] = v
     return Data(attrs=dict(like.attrs), **tensors)
 
 
-def pad_batch(batch, n_cap: int, e_cap: int):
+def pad_batch(batch, n_cap: int, e_cap: int, key: str = "pos"):
     """``batch`` (host or device) + one ghost graph so that it has exactly ``n_cap`` nodes and ``e_cap`` edges; returns the
     padded Batch (on the batch's device) with ``_graph_weight`` [G + 1, 1] = 1 / G for the real graphs, 0 for the ghost, and
-    ``_node_weight`` [n_cap, 1] = 1 / N for the real nodes, 0 for the ghost's."""
+    ``_node_weight`` [n_cap, 1] = 1 / N for the real nodes, 0 for the ghost's.  ``key``: the field that holds the positions."""
     from ..data.data import Batch
     from ..data.loader import samples_of
 
-    dev = batch["pos"].device
+    dev = batch[key].device
     samples = samples_of(batch)
-    n, e = int(batch["pos"].shape[0]), int(batch["edge_index"].shape[1])
+    n, e = int(batch[key].shape[0]), int(batch["edge_index"].shape[1])
     if n_cap < n + 2 or e_cap < e:
         raise ValueError(f"batch with {n} nodes / {e} edges does not fit the bucket ({n_cap}, {e_cap}; two ghost nodes are the minimum)")
-    samples.append(ghost_sample(samples[0], n_cap - n, e_cap - e))
+    samples.append(ghost_sample(samples[0], n_cap - n, e_cap - e, key))
     out = Batch.from_data_list(samples, attrs=dict(samples[0].attrs))
     w = torch.full((len(samples), 1), 1.0 / (len(samples) - 1), dtype=torch.float32)
     w[-1] = 0.0

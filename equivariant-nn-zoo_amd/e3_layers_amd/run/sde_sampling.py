@@ -28,6 +28,7 @@ from typing import Callable, Dict, Optional, Sequence
 import torch
 
 from ..backend.graph import TOPO_KEYS
+from ..data.compute_edge import PairCriterion
 from .sde_utils import VPSDE, _node_t, _randn, get_score_fn, prior_sampling, reverse_step
 
 class _Registry(dict):
@@ -118,7 +119,8 @@ _EDGE_KEYS = ("edge_index", "edge_vector", "edge_length", "_n_edges", "_edge_seg
 def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = None, snr: float = 0.16,
                    n_steps: int = 1, continuous: bool = True, eps: float = 1e-3,
                    preprocess: Sequence[Callable] = (), static_edges: bool = False, graph: bool = False,
-                   n_iter: Optional[int] = None, edge_capacity: Optional[int] = None, r_max: Optional[float] = None):
+                   n_iter: Optional[int] = None, edge_capacity: Optional[int] = None, r_max: Optional[float] = None,
+                   criteria=None):
     """``pc_sampler(model, batch, generator=None, noise_fn=None) -> (batch, n_function_evaluations)``.
 
     preprocess: the dataset's ``(data, attrs) -> (data, attrs)`` functions (``data_config.preprocess``) that
@@ -129,8 +131,14 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
         (``run/graph_step.pad_batch``) and the captured step rebuilds the neighbour list from the moved positions with the capped
         device builder (``data/compute_edge.computeEdgeIndexCapped``).  A list that outgrew the capacity during the loop raises
         ``EdgeCapacityExceeded`` when the loop ends.  The ghost nodes would take part in batch-wide reductions, so only per-node
-        updates are served: a corrector other than ``NoneCorrector`` is refused.
-    r_max: the cutoff of the capped builder; required with ``edge_capacity`` (``preprocess`` is not consulted for it).
+        updates are served: a corrector other than ``NoneCorrector`` is refused.  The positions are the first diffusion key of the
+        SDE.  A model whose tree starts with an ``edge_index`` layer of its own (the protein score nets) keeps it: the loop does not
+        rebuild, the model's layer finds the padded batch and rebuilds through the capped builder, with the layer's own cutoff, key
+        and pair criterion -- which must be a ``data.PairCriterion`` (``config_diffusion_CA.pair_criterion()``), not a callback.
+    r_max: the cutoff of the capped builder; required with ``edge_capacity`` (``preprocess`` is not consulted for it).  Not
+        consulted when the model owns its ``edge_index`` layer.
+    criteria: with ``edge_capacity``, a ``data.PairCriterion`` for the list the loop rebuilds itself.  Build k of a run draws with
+        index k, counted from 0, replayed or eager (the eager loop resets the criterion it finds here or in the model's layer).
     n_iter: stop after this many of the ``sde.N`` reverse steps (harness addition: benchmarks and parity tests
         time / check the first steps of the N=1000 schedule instead of shrinking N, which changes dt and betas).
     """
@@ -146,6 +154,8 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
             raise ValueError("edge_capacity: the ghost graph's nodes would enter the corrector's batch-wide norms; only NoneCorrector is served")
         if r_max is None:
             raise ValueError("edge_capacity needs the cutoff of the neighbour list: pass r_max")
+        if criteria is not None and not isinstance(criteria, PairCriterion):
+            raise ValueError("edge_capacity: criteria must be a data.PairCriterion (the capped builder evaluates it in its kernels)")
 
     def rebuild_edges(batch):
         for k in _EDGE_KEYS:
@@ -177,6 +187,9 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                 batch.update(build_topology(batch["edge_index"], batch.n_nodes).as_dict())
         t_dev = batch["t"]
         keys = list(sde.irreps)
+        for crit in (criteria, _layer_criterion(_own_edge_layer(model))):
+            if isinstance(crit, PairCriterion):
+                crit.reset()      # build k of this run draws with index k
 
         def moved(b):
             # positions changed: the geometry cached in the batch by the model's first layer is stale
@@ -196,7 +209,8 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
 
         with torch.no_grad():
             if graph and edge_capacity is not None:
-                batch = _capped_graph_loop(batch, capped_updates(), keys, timesteps, steps, int(edge_capacity), float(r_max))
+                batch = _capped_graph_loop(batch, model, capped_updates(), keys, timesteps, steps, int(edge_capacity), float(r_max),
+                                           criteria)
             elif graph:
                 # static buffers: the diffused tensors and t; the step writes its result back into them
                 state = {k: batch[k].clone() for k in keys}
@@ -239,62 +253,121 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
     return pc_sampler
 
 
-def _capped_graph_loop(batch, updates, keys, timesteps, steps: int, e_cap: int, r_max: float):
+def _own_edge_layer(model):
+    """The model's own ``edge_index`` layer when its tree starts with one (a plain callable, e.g. the protein nets'
+    ``partial(computeEdgeIndex, r_max=..., key="CA", criteria=...)``), else None."""
+    layers = getattr(model, "layers", None)
+    if not layers:
+        return None
+    name, layer = layers[0]
+    return layer if name == "edge_index" and callable(layer) and not isinstance(layer, torch.nn.Module) else None
+
+
+def _layer_criterion(layer):
+    return (getattr(layer, "keywords", None) or {}).get("criteria")
+
+
+class _CappedLoop:
     """The reverse steps as replays of ONE graph on cutoff graphs: the batch padded to ``e_cap`` edges, the neighbour list rebuilt
-    inside the graph after every update in ``updates`` (corrector, predictor).  The ghost graph's rows of the diffused tensors are
-    never written back: its nodes stay where they are."""
-    from ..data.compute_edge import check_edge_capacity, computeEdgeIndex, computeEdgeIndexCapped
-    from .graph_step import GHOST_DEGREE, CapturedStep, pad_batch
+    inside the graph -- by the loop after every update in ``updates`` (corrector, predictor), or by the model's own ``edge_index``
+    layer in every model call (it finds ``_nlist_state`` in the batch and builds the capped list).  The ghost graph's rows of the
+    diffused tensors are never written back: its nodes stay where they are.
 
-    dev = batch["_n_nodes"].device
-    for k in _EDGE_KEYS:
-        batch.pop(k)
-    new, attrs = computeEdgeIndex(batch.data, batch.attrs, r_max=r_max)      # eager, once: the sizes of the padded batch
-    batch.attrs.update(attrs)
-    batch.update(new)
-    n, e = batch.n_nodes, int(new["edge_index"].shape[1])
-    if e > e_cap:
-        from ..backend.graph import EdgeCapacityExceeded
+    Construction sizes, pads and captures (``t0``: the time of the warm-up step); ``rewind()`` puts the state and the draw index
+    back on the start, ``run()`` replays, ``result()`` checks the capacity and unpads (``tools/sample_bench.py`` times ``run`` alone)."""
 
-        raise EdgeCapacityExceeded(f"the first neighbour list has {e} edges: edge_capacity={e_cap} is too small")
-    n_cap = -(-(n + max(2, -(-(e_cap - e) // GHOST_DEGREE))) // 32) * 32
-    batch["t"] = torch.full((len(batch), 1), float(timesteps[0]), device=dev)
-    padded = pad_batch(batch, n_cap, e_cap)
-    padded["_nlist_state"] = torch.zeros(2, dtype=torch.int64, device=dev)
-    t_dev = padded["t"]
-    state = {k: padded[k] for k in keys}
+    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None):
+        from functools import partial
 
-    def relisted(b):
-        # a fresh view of the padded batch with the moved tensors: what the model left in ``b`` (edge vectors, harmonics, radial
-        # embeddings of the OLD list) stays behind, as the reference's loop drops it (:236-241)
-        fresh = padded.view()
-        for k in keys:
-            fresh[k] = b[k]
-        computeEdgeIndexCapped(fresh.data, fresh.attrs, r_max=r_max)      # in place, on the device, inside the capture
-        return fresh
+        from ..data.compute_edge import computeEdgeIndex, computeEdgeIndexCapped
+        from .graph_step import GHOST_DEGREE, CapturedStep, pad_batch
 
-    def captured():
-        work = padded.view()
-        for update in updates:
-            work = relisted(update(work))
-        for k in keys:
-            state[k][:n].copy_(work[k][:n])
+        dev = batch["_n_nodes"].device
+        own = _own_edge_layer(model)
+        if own is not None:
+            criteria, pos_key = _layer_criterion(own), (getattr(own, "keywords", None) or {}).get("key", keys[0])
+            if criteria is not None and not isinstance(criteria, PairCriterion):
+                raise ValueError("edge_capacity: the model's edge_index layer uses a criteria callback (arbitrary Python, a host "
+                                 "synchronisation per call); build the tree with a data.PairCriterion to replay it")
+            build = own
+        else:
+            pos_key = keys[0]
+            build = partial(computeEdgeIndex, r_max=r_max, key=pos_key, criteria=criteria)
+        for k in _EDGE_KEYS:
+            batch.pop(k)
+        # eager, once: the sizes of the padded batch.  The same function, the same criterion, the draw of build 0 -- read from the
+        # cells, which the eager path never advances, so no draw is consumed
+        rng = torch.zeros(2, dtype=torch.int64, device=dev)
+        batch.data["_nlist_rng"] = rng
+        new, attrs = build(batch.data, batch.attrs)
+        batch.data.pop("_nlist_rng")
+        batch.attrs.update(attrs)
+        batch.update(new)
+        n, e = batch.n_nodes, int(new["edge_index"].shape[1])
+        if e > e_cap:
+            from ..backend.graph import EdgeCapacityExceeded
 
-    saved = {k: v.clone() for k, v in state.items()}
-    t_dev.fill_(float(timesteps[0]))
-    step = CapturedStep(captured, warmup=1, device=dev)      # (the warm-up run moved the state: put it back)
-    for k in keys:
-        state[k].copy_(saved[k])
-    for i in range(steps):
-        t_dev.copy_(timesteps[i].expand_as(t_dev))
-        step()
-    check_edge_capacity(padded["_nlist_state"])
-    out = padded[list(range(len(padded) - 1))]      # the real graphs
-    for k in ("_graph_weight", "_node_weight"):
-        out.pop(k)
-    for k in keys:
-        out[k] = state[k][:n].clone()
-    return out
+            raise EdgeCapacityExceeded(f"the first neighbour list has {e} edges: edge_capacity={e_cap} is too small")
+        n_cap = -(-(n + max(2, -(-(e_cap - e) // GHOST_DEGREE))) // 32) * 32
+        batch["t"] = torch.full((len(batch), 1), float(t0), device=dev)
+        padded = pad_batch(batch, n_cap, e_cap, key=pos_key)
+        padded["_nlist_state"] = torch.zeros(2, dtype=torch.int64, device=dev)
+        padded.data["_nlist_rng"] = rng
+        state = {k: padded[k] for k in keys}
+
+        def relisted(b):
+            # a fresh view of the padded batch with the moved tensors: what the model left in ``b`` (edge vectors, harmonics, radial
+            # embeddings of the OLD list) stays behind, as the reference's loop drops it (:236-241)
+            fresh = padded.view()
+            for k in keys:
+                fresh[k] = b[k]
+            if own is None:      # in place, on the device, inside the capture (a model that owns its edge layer does this itself)
+                computeEdgeIndexCapped(fresh.data, fresh.attrs, r_max=r_max, key=pos_key, criteria=criteria)
+            return fresh
+
+        def captured():
+            work = padded.view()
+            for update in updates:
+                work = relisted(update(work))
+            for k in keys:
+                state[k][:n].copy_(work[k][:n])
+
+        self.padded, self.state, self.rng, self.keys, self.n, self.first_edges = padded, state, rng, keys, n, e
+        self.t_dev = padded["t"]
+        self.saved = {k: v.clone() for k, v in state.items()}
+        self.t_dev.fill_(float(t0))
+        self.step = CapturedStep(captured, warmup=1, device=dev)
+
+    def rewind(self) -> None:
+        """(the warm-up run moved the state and drew: both go back to the start)"""
+        for k in self.keys:
+            self.state[k].copy_(self.saved[k])
+        self.rng.zero_()
+
+    def run(self, timesteps, steps: int) -> None:
+        t_dev = self.t_dev
+        for i in range(steps):
+            t_dev.copy_(timesteps[i].expand_as(t_dev))
+            self.step()
+
+    def result(self):
+        from ..data.compute_edge import check_edge_capacity
+
+        padded = self.padded
+        check_edge_capacity(padded["_nlist_state"])
+        out = padded[list(range(len(padded) - 1))]      # the real graphs
+        for k in ("_graph_weight", "_node_weight"):
+            out.pop(k)
+        for k in self.keys:
+            out[k] = self.state[k][:self.n].clone()
+        return out
+
+
+def _capped_graph_loop(batch, model, updates, keys, timesteps, steps: int, e_cap: int, r_max: float, criteria=None):
+    loop = _CappedLoop(batch, model, updates, keys, float(timesteps[0]), e_cap, r_max, criteria)
+    loop.rewind()
+    loop.run(timesteps, steps)
+    return loop.result()
 
 
 def get_sampling_fn(config, sde: VPSDE, inverse_scaler, eps: float, **kwargs):

@@ -683,6 +683,26 @@ int e3k_nlist_fill(const float* pos, const int64_t* node_seg, const int64_t* nod
                    const int32_t* counts, int64_t e_cap, int64_t* offsets, int64_t* edge_index, int64_t* n_edges,
                    int64_t* edge_segment, int64_t* state, int32_t* flag, void* stream);
 
+/* The same with a declarative pair criterion evaluated in the kernels (data/compute_edge.SequenceOrRandom).
+ * Replaces the criteria callback of computeEdgeIndex (e3_layers/data/compute_edge.py:72-75) as the protein score nets use it
+ * (e3_layers/configs/config_diffusion_CA.py:58-64: same chain and |i - j| < 5, or a 2 % random subset), which forces the
+ * all-pairs candidate list and a host synchronisation per model call.  A pair (i, j), j != i, of one real graph is kept when
+ *   |pos_i - pos_j| < r_max,  or  segment_key[i] == segment_key[j] and |i - j| < window,  or  hash(seed, draw, i, j) < threshold
+ * with i, j the batch's global node indices; same edge order, buffers and overflow contract as above.
+ *   segment_key [N] int64 (NULL or window 0: no sequence term); threshold = floor(p 2^32) (0: no random term); keep_all != 0:
+ *   p = 1, every candidate pair is kept.  hash: the lowbias32 finaliser mix(h) = (h ^= h >> 16, h *= 0x7feb352d, h ^= h >> 15,
+ *   h *= 0x846ca68b, h ^= h >> 16) chained as h = mix(h ^ word) over seed_lo, seed_hi, draw (low 32 bits), i, j from 0x9E3779B9.
+ *   rng [2] int64 = (next draw index, draw index in use): e3k_nlist_count_crit draws with rng[0]; e3k_nlist_fill_crit's scan
+ *   copies rng[0] to rng[1] and adds one to rng[0], its fill pass draws with rng[1] -- one draw per build, the index goes up once
+ *   per build, nothing read by the host. */
+int e3k_nlist_count_crit(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                         const int64_t* segment_key, int64_t window, uint32_t threshold, int32_t keep_all, uint32_t seed_lo,
+                         uint32_t seed_hi, int64_t* rng, int32_t* counts, void* stream);
+int e3k_nlist_fill_crit(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                        const int64_t* segment_key, int64_t window, uint32_t threshold, int32_t keep_all, uint32_t seed_lo,
+                        uint32_t seed_hi, int64_t* rng, const int32_t* counts, int64_t e_cap, int64_t* offsets, int64_t* edge_index,
+                        int64_t* n_edges, int64_t* edge_segment, int64_t* state, int32_t* flag, void* stream);
+
 /* Velocity Verlet around a force evaluation (the integrator of torchMD.ipynb's driver) on the n real nodes of a padded
  * batch -- the ghost nodes behind them never move.  x, v, f [n, 3], mass [n].
  *   e3k_md_drift: v += dt/2 f / m;  x += dt v.

@@ -1,34 +1,210 @@
 #!/usr/bin/env python3
-"""Reverse-diffusion sampling throughput: config_diffusion score network, B molecules, fully
-connected graphs; first `n_iter` steps of the N=1000 predictor-corrector schedule, eager launches vs one HIP graph
-per step.  Usage: python tools/sample_bench.py [B] [n_iter]"""
-import os, sys, time
+"""Reverse-diffusion sampling throughput.
+
+Molecules (the default): config_diffusion score network, B molecules, fully connected graphs; first `n_iter` steps of the N=1000
+predictor-corrector schedule, eager launches vs one HIP graph per step.  Usage: python tools/sample_bench.py [B] [n_iter]
+
+Proteins (``--protein``): config_diffusion_CA as shipped but built with the declarative pair criterion
+(``config_diffusion_CA.pair_criterion()``), 4 x 384 synthetic residues, Euler-Maruyama predictor: the replayed loop of
+``get_pc_sampler(graph=True, edge_capacity=...)`` (the model's own edge layer rebuilds the capped list inside the graph) against the
+eager sampler loop on the same tree and start -- the only way to sample these nets before.
+
+    python tools/sample_bench.py --protein --steps 100 --out profiles/protein_sampler_replay.json
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/sample_bench.py --protein --trace-steps 40
+    python tools/sample_bench.py --launches DIR_A/..._kernel_stats.csv 10 DIR_B/..._kernel_stats.csv 40    (launches per replayed step)
+
+Protocol (tools/md_bench.py's): device events around ``--steps`` reverse steps after a warm-up, the two variants alternating in one
+process, ``--reps`` repetitions each (min / median / max); host-busy time is the wall time of the enqueue loop before the closing
+synchronisation.  No threshold is asserted: the numbers are quoted in README.md and DESIGN.md."""
+import argparse, csv, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
     sys.path.insert(0, p)
 import torch
-from e3_layers_amd.configs import config_diffusion
-from e3_layers_amd.data.synthetic import synth_qm9_diffusion
-from e3_layers_amd.run.sde_sampling import EulerMaruyamaPredictor, LangevinCorrector, get_pc_sampler
-from e3_layers_amd.run.sde_utils import VPSDE
-from e3_layers_amd.utils import build
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
-n_iter = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-dev = torch.device("cuda:0")
-torch.manual_seed(0)
-model = build(config_diffusion.get_config().model_config).to(dev).eval()
-batch = synth_qm9_diffusion(1, B).to(dev)
-print(f"B={B} N={batch['pos'].shape[0]} E={batch['edge_index'].shape[1]}")
-for graph in (False, True):
-    sde = VPSDE({"pos": 3}, N=1000)
-    sampler = get_pc_sampler(sde, EulerMaruyamaPredictor, LangevinCorrector, snr=0.16, static_edges=True, graph=graph,
-                             n_iter=n_iter)
-    sampler(model, batch)          # warm-up (plans, allocator)
+
+def molecules(argv):
+    from e3_layers_amd.configs import config_diffusion
+    from e3_layers_amd.data.synthetic import synth_qm9_diffusion
+    from e3_layers_amd.run.sde_sampling import EulerMaruyamaPredictor, LangevinCorrector, get_pc_sampler
+    from e3_layers_amd.run.sde_utils import VPSDE
+    from e3_layers_amd.utils import build
+
+    B = int(argv[0]) if len(argv) > 0 else 128
+    n_iter = int(argv[1]) if len(argv) > 1 else 50
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = build(config_diffusion.get_config().model_config).to(dev).eval()
+    batch = synth_qm9_diffusion(1, B).to(dev)
+    print(f"B={B} N={batch['pos'].shape[0]} E={batch['edge_index'].shape[1]}")
+    for graph in (False, True):
+        sde = VPSDE({"pos": 3}, N=1000)
+        sampler = get_pc_sampler(sde, EulerMaruyamaPredictor, LangevinCorrector, snr=0.16, static_edges=True, graph=graph,
+                                 n_iter=n_iter)
+        sampler(model, batch)          # warm-up (plans, allocator)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out, nfe = sampler(model, batch)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"graph={graph}: {dt / n_iter * 1e3:.2f} ms per reverse step ({nfe} network evaluations, incl. capture when graph), "
+              f"{B * n_iter / dt:.0f} molecule-steps/s; finite={bool(torch.isfinite(out['pos']).all())}")
+
+
+# ---- proteins: the replayed loop against the eager loop ---------------------------------------------------------------------------
+def protein_setup(n_prot, n_res, dev):
+    from e3_layers_amd.configs import config_diffusion_CA
+    from e3_layers_amd.data.synthetic import synth_protein
+    from e3_layers_amd.run.sde_utils import VPSDE, prior_sampling
+    from e3_layers_amd.utils import build
+
+    crit = config_diffusion_CA.pair_criterion()
+    torch.manual_seed(0)
+    model = build(config_diffusion_CA.get_config(edge_criteria=crit).model_config).to(dev).eval()
+    sde = VPSDE({"CA": 3}, N=1000)
+    sde.alphas = sde.alphas.to(dev)
+    batch = synth_protein(1, n_prot, n_res=n_res).to(dev)
+    batch = prior_sampling(sde, batch, torch.Generator(device=dev).manual_seed(1))      # x_T: where the sampler starts
+    timesteps = torch.linspace(sde.T, 1e-3, sde.N, device=dev)
+    return model, sde, batch, timesteps, crit
+
+
+def predictor(model, sde):
+    from e3_layers_amd.run.sde_sampling import EulerMaruyamaPredictor
+    from e3_layers_amd.run.sde_utils import get_score_fn
+
+    return EulerMaruyamaPredictor(sde, get_score_fn(sde, model, train=False))
+
+
+def eager_loop(model, sde, batch, timesteps, crit, n_steps):
+    """pc_sampler's eager path with NoneCorrector: set the time, predictor update (one model call: its edge layer builds the list,
+    all pairs -> criterion -> edge count read back), drop the per-edge keys."""
+    from e3_layers_amd.run.sde_sampling import _EDGE_KEYS
+
+    pred = predictor(model, sde)
+    state = {"b": batch.clone()}
+    state["b"]["t"] = torch.empty(len(batch), 1, device=timesteps.device)
+    crit.reset()
+
+    def loop():
+        b = state["b"]
+        t_dev = b["t"]
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            for i in range(n_steps):
+                t_dev.copy_(timesteps[i].expand_as(t_dev))
+                b = pred.update_fn(b)
+                for k in _EDGE_KEYS:
+                    b.pop(k)
+        state["b"] = b
+        return time.perf_counter() - t0
+
+    return loop
+
+
+def replay_loop(model, sde, batch, timesteps, slack):
+    """The capped loop of get_pc_sampler(graph=True, edge_capacity=...): sized, padded and captured here, outside the timed region."""
+    from e3_layers_amd.data import computeEdgeIndex
+    from e3_layers_amd.run.sde_sampling import _CappedLoop
+
+    b = batch.clone()
+    b.attrs["t"] = ("graph", "1x0e")
+    pred = predictor(model, sde)
+    probe = b.clone()
+    layer = model.layers[0][1]
+    probe.data["_nlist_rng"] = torch.zeros(2, dtype=torch.int64, device=timesteps.device)
+    new, _ = layer(probe.data, probe.attrs)
+    e_cap = -(-int(slack * new["edge_index"].shape[1]) // 1024) * 1024
+    with torch.no_grad():
+        return _CappedLoop(b, model, [lambda w: w, lambda w: pred.update_fn(w)], ["CA"], float(timesteps[0]), e_cap, None), e_cap
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out, nfe = sampler(model, batch)
+    a.record()
+    host = fn()
+    b.record()
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f"graph={graph}: {dt / n_iter * 1e3:.2f} ms per reverse step ({nfe} network evaluations, incl. capture when graph), "
-          f"{B * n_iter / dt:.0f} molecule-steps/s; finite={bool(torch.isfinite(out['pos']).all())}")
+    return a.elapsed_time(b), host
+
+
+def total_calls(path):
+    with open(path) as f:
+        return sum(int(r["Calls"]) for r in csv.DictReader(f))
+
+
+def protein(argv):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--protein", action="store_true")
+    ap.add_argument("--proteins", type=int, default=4)
+    ap.add_argument("--residues", type=int, default=384)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--slack", type=float, default=1.15, help="edge capacity = slack x the first list, rounded up to 1024")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda:0")
+    model, sde, batch, timesteps, crit = protein_setup(args.proteins, args.residues, dev)
+    loop, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
+
+    def replay(n):
+        def run():
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                loop.run(timesteps, n)
+            return time.perf_counter() - t0
+        return run
+
+    if args.trace_steps:
+        loop.rewind()
+        replay(args.trace_steps)()
+        torch.cuda.synchronize()
+        print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues}))
+        return
+    loop.rewind()
+    replay(args.warmup)()
+    eager_loop(model, sde, batch, timesteps, crit, args.warmup)()
+    rows = {"replay": [], "eager": [], "replay_host": [], "eager_host": []}
+    edges = []
+    for _ in range(args.reps):
+        loop.rewind()
+        ms, host = timed(replay(args.steps))
+        edges.append(int(loop.padded["_nlist_state"][0]))
+        loop.result()                               # (after the closing event: an overflowed repetition would raise here)
+        rows["replay"].append(ms / args.steps)
+        rows["replay_host"].append(1e3 * host / args.steps)
+        ms, host = timed(eager_loop(model, sde, batch, timesteps, crit, args.steps))
+        rows["eager"].append(ms / args.steps)
+        rows["eager_host"].append(1e3 * host / args.steps)
+
+    def mmm(v):
+        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
+
+    doc = {"workload": "reverse diffusion (Euler-Maruyama, NoneCorrector, first steps of N=1000) on config_diffusion_CA as shipped, "
+                       "built with pair_criterion(); synth_protein",
+           "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues,
+           "nodes": int(batch["CA"].shape[0]), "edges_first_list": loop.first_edges, "edges_last_list": edges, "e_cap": e_cap,
+           "n_cap": int(loop.padded["CA"].shape[0]), "steps": args.steps, "reps": args.reps, "recaptures": loop.step.recaptures,
+           "replay_ms_per_step": mmm(rows["replay"]), "eager_ms_per_step": mmm(rows["eager"]),
+           "replay_host_busy_ms_per_step": mmm(rows["replay_host"]), "eager_host_busy_ms_per_step": mmm(rows["eager_host"]),
+           "speedup_median": round(statistics.median(rows["eager"]) / statistics.median(rows["replay"]), 3)}
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    argv = sys.argv[1:]
+    if "--launches" in argv:
+        a, na, b, nb = argv[argv.index("--launches") + 1:][:4]
+        print(json.dumps({"launches_per_replayed_reverse_step": (total_calls(b) - total_calls(a)) / (int(nb) - int(na)),
+                          "steps": [int(na), int(nb)]}))
+    elif "--protein" in argv:
+        protein(argv)
+    else:
+        molecules(argv)
