@@ -234,6 +234,132 @@ __global__ __launch_bounds__(256) void md_kick_kernel(float* __restrict__ v, con
   }
 }
 
+// A standard normal for (seed, draw, node, word): the pair hash chain with dst = 2 word and 2 word + 1 gives u1 in (0, 1] and
+// u2 in [0, 1) (24 bits each, exact in fp32); Box-Muller's cosine branch.  h_node: the chain up to and including the node word.
+// logf, sqrtf, cospif are the precise library functions; 2 u2 is exact, so the cosine sees no argument rounding.
+// data/compute_edge.normal_draw restates it.
+__device__ __forceinline__ float normal_draw(uint32_t h_node, uint32_t word) {
+  const uint32_t h1 = mix32(h_node ^ (2u * word)), h2 = mix32(h_node ^ (2u * word + 1u));
+  const float u1 = (float)((h1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(h2 >> 8) * 0x1p-24f;
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
+
+// The thermostatted second half step: v <- c v + (s / sqrt(m)) xi, then md_kick_kernel's v += dt/2 f / m (f NULL: skipped) and
+// its records, in its walk.  c v and the noise term are rounded products that meet in a plain add: with c = 1, s = 0 the first
+// line returns v (the noise is an exact zero), whatever the compiler contracts, and the rest is md_kick_kernel's expression.
+__global__ __launch_bounds__(256) void md_kick_langevin_kernel(float* __restrict__ v, const float* __restrict__ f,
+                                                               const float* __restrict__ mass, const int64_t* __restrict__ node_ptr,
+                                                               int32_t G, int64_t n, float dt, float c, float s, uint32_t seed_lo,
+                                                               uint32_t seed_hi, uint32_t draw, uint32_t word0,
+                                                               float* __restrict__ kinetic, const float* __restrict__ energy,
+                                                               float* __restrict__ potential) {
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= G) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t beg = clampi(node_ptr[g], 0, n), end = clampi(node_ptr[g + 1], 0, n);
+  const uint32_t h_wave = mix32(mix32(mix32(0x9E3779B9u ^ seed_lo) ^ seed_hi) ^ draw);      // what does not depend on the node
+  float ke = 0.f;
+  for (int64_t i = beg + lane; i < end; i += 64) {
+    const float m = mass[i], a = s / sqrtf(m);
+    const uint32_t h_i = mix32(h_wave ^ (uint32_t)i);
+    float vx = rounded_product(c, v[3 * i]) + rounded_product(a, normal_draw(h_i, word0));
+    float vy = rounded_product(c, v[3 * i + 1]) + rounded_product(a, normal_draw(h_i, word0 + 1u));
+    float vz = rounded_product(c, v[3 * i + 2]) + rounded_product(a, normal_draw(h_i, word0 + 2u));
+    if (f) {
+      const float h = 0.5f * dt / m;
+      vx = vx + h * f[3 * i];
+      vy = vy + h * f[3 * i + 1];
+      vz = vz + h * f[3 * i + 2];
+    }
+    v[3 * i] = vx;
+    v[3 * i + 1] = vy;
+    v[3 * i + 2] = vz;
+    ke += 0.5f * m * ((vx * vx + vy * vy) + vz * vz);
+  }
+  ke = wave_sum(ke);
+  if (lane == 0) {
+    if (kinetic) kinetic[g] = ke;
+    if (potential) potential[g] = energy[g];
+  }
+}
+
+// FIRE (Bitzek et al. 2006, the step rule of ASE's optimiser) with the adaptive state PER GRAPH: one wave per graph, three
+// walks over its atoms -- the reductions, the velocity update with |dr|^2, the move.  state [G, 4] = (dt, alpha, n_pos, fmax).
+struct FireParams {
+  float ftol, dt_max, maxstep, n_min, f_inc, f_dec, alpha_start, f_alpha;
+};
+
+__global__ __launch_bounds__(256) void fire_step_kernel(float* __restrict__ x, float* __restrict__ v, const float* __restrict__ f,
+                                                        const int64_t* __restrict__ node_ptr, int32_t G, int64_t n,
+                                                        float* __restrict__ state, const FireParams p,
+                                                        const float* __restrict__ energy, float* __restrict__ energy_record,
+                                                        float* __restrict__ fmax_record) {
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= G) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t beg = clampi(node_ptr[g], 0, n), end = clampi(node_ptr[g + 1], 0, n);
+  float dt = state[4 * g], alpha = state[4 * g + 1], n_pos = state[4 * g + 2];
+  float fv = 0.f, ff = 0.f, vv = 0.f, f2max = 0.f;
+  for (int64_t i = beg + lane; i < end; i += 64) {
+    const float fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
+    const float vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
+    const float f2 = (fx * fx + fy * fy) + fz * fz;
+    fv += (fx * vx + fy * vy) + fz * vz;
+    ff += f2;
+    vv += (vx * vx + vy * vy) + vz * vz;
+    f2max = fmaxf(f2max, f2);
+  }
+  fv = wave_sum(fv);
+  ff = wave_sum(ff);
+  vv = wave_sum(vv);
+  const float fmax = sqrtf(wave_max_f(f2max));
+  const bool frozen = fmax < p.ftol;      // (wave-uniform, like every branch below: the reductions leave all lanes the same values)
+  if (frozen) {
+    for (int64_t i = beg + lane; i < end; i += 64) v[3 * i] = v[3 * i + 1] = v[3 * i + 2] = 0.f;
+  } else {
+    float keep = 0.f, mix = 0.f;      // v <- keep v + mix f
+    if (fv < 0.f) {
+      dt = dt * p.f_dec;
+      alpha = p.alpha_start;
+      n_pos = 0.f;
+    } else {
+      keep = 1.0f - alpha;
+      mix = ff > 0.f ? alpha * (sqrtf(vv) / sqrtf(ff)) : 0.f;
+      if (n_pos > p.n_min) {
+        dt = fminf(dt * p.f_inc, p.dt_max);
+        alpha = alpha * p.f_alpha;
+      }
+      n_pos = n_pos + 1.0f;
+    }
+    float v2 = 0.f;
+    for (int64_t i = beg + lane; i < end; i += 64) {
+      const float fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
+      const float vx = (keep * v[3 * i] + mix * fx) + dt * fx;
+      const float vy = (keep * v[3 * i + 1] + mix * fy) + dt * fy;
+      const float vz = (keep * v[3 * i + 2] + mix * fz) + dt * fz;
+      v[3 * i] = vx;
+      v[3 * i + 1] = vy;
+      v[3 * i + 2] = vz;
+      v2 += (vx * vx + vy * vy) + vz * vz;
+    }
+    const float norm_dr = dt * sqrtf(wave_sum(v2));
+    const float move = norm_dr > p.maxstep ? dt * (p.maxstep / norm_dr) : dt;      // dr = move v
+    for (int64_t i = beg + lane; i < end; i += 64) {
+      x[3 * i] = x[3 * i] + move * v[3 * i];
+      x[3 * i + 1] = x[3 * i + 1] + move * v[3 * i + 1];
+      x[3 * i + 2] = x[3 * i + 2] + move * v[3 * i + 2];
+    }
+  }
+  if (lane == 0) {
+    state[4 * g] = dt;
+    state[4 * g + 1] = alpha;
+    state[4 * g + 2] = n_pos;
+    state[4 * g + 3] = fmax;
+    if (energy_record) energy_record[g] = energy[g];
+    if (fmax_record) fmax_record[g] = fmax;
+  }
+}
+
 }  // namespace e3k
 
 static bool nlist_args_ok(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G) {
@@ -321,6 +447,31 @@ extern "C" int e3k_md_kick(float* v, const float* f, const float* mass, const in
   if (!v || !f || !mass || !node_ptr || (potential && !energy)) return E3K_ERR_INVALID;
   hipLaunchKernelGGL(e3k::md_kick_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, f, mass, node_ptr, G, n,
                      dt, kinetic, energy, potential);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_md_kick_langevin(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt,
+                                    float c, float s, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t word0,
+                                    float* kinetic, const float* energy, float* potential, void* stream) {
+  if (n < 0 || G < 0 || !(c >= 0.f && c <= 1.f) || !(s >= 0.f)) return E3K_ERR_INVALID;
+  if (n == 0 || G == 0) return E3K_OK;
+  if (!v || !mass || !node_ptr || (potential && !energy)) return E3K_ERR_INVALID;
+  hipLaunchKernelGGL(e3k::md_kick_langevin_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, f, mass,
+                     node_ptr, G, n, dt, c, s, seed_lo, seed_hi, draw, word0, kinetic, energy, potential);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_fire_step(float* x, float* v, const float* f, const int64_t* node_ptr, int32_t G, int64_t n, float* state,
+                             float ftol, float dt_max, float maxstep, int32_t n_min, float f_inc, float f_dec, float alpha_start,
+                             float f_alpha, const float* energy, float* energy_record, float* fmax_record, void* stream) {
+  if (n < 0 || G < 0 || !(ftol >= 0.f) || !(dt_max > 0.f) || !(maxstep > 0.f) || n_min < 0) return E3K_ERR_INVALID;
+  if (G == 0) return E3K_OK;
+  if (!node_ptr || !state || (n > 0 && (!x || !v || !f)) || (energy_record && !energy)) return E3K_ERR_INVALID;
+  const e3k::FireParams p{ftol, dt_max, maxstep, (float)n_min, f_inc, f_dec, alpha_start, f_alpha};
+  hipLaunchKernelGGL(e3k::fire_step_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, v, f, node_ptr, G, n,
+                     state, p, energy, energy_record, fmax_record);
   E3K_CHECK_LAUNCH();
   return E3K_OK;
 }

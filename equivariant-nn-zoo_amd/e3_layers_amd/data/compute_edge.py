@@ -99,6 +99,19 @@ def pair_hash(seed, draw, src, dst) -> Tensor:
     return h
 
 
+def normal_draw(seed, draw, node, word, dtype=torch.float32) -> Tensor:
+    """The counter-based standard normal of the thermostat kernel (``csrc/e3k_nlist.hip: normal_draw``) for (seed, draw index,
+    node, word): ``u1 = ((h1 >> 8) + 1) 2^-24`` in (0, 1] and ``u2 = (h2 >> 8) 2^-24`` in [0, 1) from
+    ``h1, h2 = pair_hash(seed, draw, node, 2 word), pair_hash(seed, draw, node, 2 word + 1)`` -- bit for bit the kernel's -- and
+    ``sqrt(-2 ln u1) cos(2 pi u2)`` in ``dtype`` through torch (the kernel: fp32 ``logf``, ``sqrtf``, ``cospif``).  Component c of a
+    step's thermostat draw is word c with the step number as draw index; ``thermalize`` uses words 4 + c and a counter of its own.
+    Arguments as ``pair_hash``'s: ints or int64 tensors, broadcasting."""
+    two_w = 2 * (word if torch.is_tensor(word) else int(word))
+    u1 = ((pair_hash(seed, draw, node, two_w) >> 8) + 1).to(dtype) * 2.0 ** -24
+    u2 = (pair_hash(seed, draw, node, two_w + 1) >> 8).to(dtype) * 2.0 ** -24
+    return torch.sqrt(-2.0 * torch.log(u1)) * torch.cos((2.0 * math.pi) * u2)
+
+
 class PairCriterion:
     """A pair rule both edge builders recognise.  As a callable it is a ``criteria`` callback of ``computeEdgeIndex``
     (``(data, edge_index) -> bool mask`` over the ordered candidate pairs, global node indices); ``computeEdgeIndexCapped`` does not

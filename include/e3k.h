@@ -714,6 +714,36 @@ int e3k_md_drift(float* x, float* v, const float* f, const float* mass, int64_t 
 int e3k_md_kick(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt,
                 float* kinetic, const float* energy, float* potential, void* stream);
 
+/* The thermostatted second half step (the Langevin integrator of torchMD.ipynb's driver: Integrator(..., gamma, T)) and the
+ * Maxwell-Boltzmann draw (its maxwell_boltzmann), in e3k_md_kick's walk with e3k_md_kick's records:
+ *   v <- c v + (s / sqrt(m)) xi;   v <- v + dt/2 f / m  (f NULL: skipped);   kinetic, potential as e3k_md_kick files them.
+ * c = exp(-gamma dt), s = sqrt((1 - c^2) kT) (the caller forms them in float64): the exact Ornstein-Uhlenbeck step, stable for any
+ * gamma dt; c = 1, s = 0 is e3k_md_kick bit for bit; c = 0, s = sqrt(kT), f = NULL draws Maxwell-Boltzmann velocities.
+ * xi: a counter-based standard normal, the same bits for the same (seed, draw, node i, word w), w = word0 + component:
+ *   h1 = hash(seed_lo, seed_hi, draw, i, 2 w), h2 = hash(seed_lo, seed_hi, draw, i, 2 w + 1)   (the pair hash above)
+ *   u1 = ((h1 >> 8) + 1) 2^-24 in (0, 1],  u2 = (h2 >> 8) 2^-24 in [0, 1)   (exact in fp32)
+ *   xi = sqrtf(-2 logf(u1)) cospif(2 u2)   (precise library functions; |xi| <= sqrt(48 ln 2) = 5.77)
+ * i is the node's row in v.  A step's thermostat draw uses word0 = 0 with the step number as draw; thermalize uses word0 = 4 with
+ * a counter of its own (data/compute_edge.normal_draw restates xi on the host).  0 <= c <= 1 and s >= 0, or invalid. */
+int e3k_md_kick_langevin(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt,
+                         float c, float s, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t word0, float* kinetic,
+                         const float* energy, float* potential, void* stream);
+
+/* One FIRE iteration (Bitzek et al., PRL 97, 170201; the step rule of ASE's optimiser, which stands in for the notebook's
+ * minimize_bfgs) on forces f [n, 3] at x, every graph with its OWN adaptive state: state [G, 4] fp32 = (dt, alpha, n_pos, fmax).
+ * One wave per graph, fixed-order sums, no atomics.  Per graph, with P = sum f.v and fmax = max_i |f_i|:
+ *   fmax < ftol: v <- 0, x untouched (frozen; graphs share no edges, so it stays frozen while it goes on being evaluated);
+ *   else P < 0:  v <- 0, dt <- dt f_dec, alpha <- alpha_start, n_pos <- 0;
+ *   else:        v <- (1 - alpha) v + alpha |v| f / |f|;  if n_pos > n_min: dt <- min(dt f_inc, dt_max), alpha <- alpha f_alpha;
+ *                n_pos <- n_pos + 1          (P = 0 counts as downhill -- ASE asks P > 0 -- so that the first iteration from
+ *                                             v = 0 does not halve dt);
+ *   then (both):  v <- v + dt f (unit masses);  dr = dt v, scaled to length maxstep if its norm over the graph exceeds it;  x += dr.
+ * The state row is written back with fmax; energy_record [G] = energy [G] and fmax_record [G] = fmax where the pointers are given.
+ * An empty graph is frozen with fmax = 0. */
+int e3k_fire_step(float* x, float* v, const float* f, const int64_t* node_ptr, int32_t G, int64_t n, float* state, float ftol,
+                  float dt_max, float maxstep, int32_t n_min, float f_inc, float f_dec, float alpha_start, float f_alpha,
+                  const float* energy, float* energy_record, float* fmax_record, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training-step plumbing on the flat parameter vector.
  * Replaces clip_grad_norm_ + optim.step() + ema.update() (e3_layers/run/trainer.py:374-386) and the variant that

@@ -4,6 +4,8 @@ evaluation, the neighbour list rebuilt inside it, two integrator launches beside
 (computeEdgeIndex on the device + the eager model call + an element-wise torch integrator), on the same start.
 
     python tools/md_bench.py --molecules 32 64 1 --steps 200 --out profiles/md_replay.json
+    python tools/md_bench.py --integrator langevin --out profiles/md_langevin.json      (the thermostatted step against the NVE step)
+    python tools/md_bench.py --fire --out profiles/md_fire.json                         (the FIRE iteration against its eager loop)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/md_bench.py --trace-steps 60 --molecules 32
     python tools/md_bench.py --launches DIR_A/…_kernel_stats.csv 10 DIR_B/…_kernel_stats.csv 60      (launches per replayed step)
 
@@ -75,6 +77,53 @@ def eager_steps(model, batch, r_max, x0, v0, dt, n_steps):
     return loop
 
 
+def eager_fire(model, batch, r_max, x0, fire, n_steps):
+    """computeEdgeIndex + the eager model + the torch path of the FIRE iteration on device tensors: every branch of every graph is
+    decided on the host, as a minimiser written beside the model would do it."""
+    from e3_layers_amd.data import computeEdgeIndex
+    from e3_layers_amd.run import md as M
+
+    def force(x):
+        b = batch.view()
+        b["pos"] = x
+        for k in ("edge_index", "_n_edges", "_edge_segment"):
+            b.pop(k)
+        new, attrs = computeEdgeIndex(b.data, b.attrs, r_max=r_max)
+        b.attrs.update(attrs)
+        b.update(new)
+        out = model(b)
+        return out["energy"].reshape(-1), out["forces"]
+
+    x, v, state = x0.clone(), torch.zeros_like(x0), fire.state.clone()
+    node_ptr = fire.ff.node_ptr
+
+    def loop():
+        t0 = time.perf_counter()
+        for _ in range(n_steps):
+            energy, f = force(x)
+            M._fire_step_torch(x, v, f.detach(), node_ptr, state, fire)
+        return time.perf_counter() - t0
+
+    return loop
+
+
+def replay_fire(fire, ff, n_steps):
+    """The launches of ``Fire.run``'s inner loop (the graph + ``e3k_fire_step``), without the chunk's closing synchronisation."""
+    from e3_layers_amd.run import md as M
+
+    n_graphs = ff.node_ptr.numel() - 1
+    rec = torch.zeros(2, n_steps, n_graphs, device=ff.dev)
+
+    def loop():
+        t0 = time.perf_counter()
+        for i in range(n_steps):
+            energy, forces = ff.evaluate()
+            M._fire_step(ff.pos, fire.v, forces, ff.node_ptr, fire.state, fire, energy, rec[0, i], rec[1, i])
+        return time.perf_counter() - t0
+
+    return loop
+
+
 def replay_start(md, ff, x0, v0):
     """Puts the replayed run on the start (verified forces there): outside the timed region."""
     ff.pos.copy_(x0)
@@ -99,7 +148,7 @@ def replay_steps(md, ff, n_steps):
         for i in range(n_steps):
             M._drift(ff.pos, md.v, forces, md.mass, md.dt)
             energy, forces = ff.evaluate()
-            M._kick(md.v, forces, md.mass, ff.node_ptr, md.dt, kin[i], energy, pot[i])
+            md._second_half(i, forces, energy, kin[i], pot[i])      # e3k_md_kick, or e3k_md_kick_langevin with draw index i
         return time.perf_counter() - t0
 
     return loop
@@ -135,13 +184,74 @@ def bench(n_mol, steps, warmup, reps, dt, dev):
         rows["eager"].append(ms / steps)
         rows["eager_host"].append(1e3 * host / steps)
 
-    def mmm(v):
-        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
-
     return {"molecules": n_mol, "atoms": int(x0.shape[0]), "edges_at_start": int(batch["edge_index"].shape[1]), "e_cap": ff.e_cap,
             "n_cap": ff.n_cap, "steps": steps, "reps": reps, "dt": dt, "regrowths": md.regrowths, "recaptures": ff.recaptures,
             "replay_ms_per_step": mmm(rows["replay"]), "eager_ms_per_step": mmm(rows["eager"]),
             "replay_host_busy_ms_per_step": mmm(rows["replay_host"]), "eager_host_busy_ms_per_step": mmm(rows["eager_host"]),
+            "speedup_median": round(statistics.median(rows["eager"]) / statistics.median(rows["replay"]), 3)}
+
+
+def mmm(v):
+    return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
+
+
+def bench_langevin(n_mol, steps, warmup, reps, dt, kT, gamma, dev):
+    """The thermostatted step against the NVE step of the same build on ONE force field: the two differ in their second launch."""
+    from e3_layers_amd.run.md import Langevin, ReplayedForceField, VelocityVerlet
+
+    model, batch, r_max, x0, v0 = setup(n_mol, dev)
+    ff = ReplayedForceField(model, batch, r_max)
+    mds = {"nve": VelocityVerlet(ff, torch.ones(x0.shape[0]), dt), "langevin": Langevin(ff, torch.ones(x0.shape[0]), dt, kT, gamma, seed=1)}
+    rows = {k: [] for k in ("nve", "langevin", "nve_host", "langevin_host")}
+    for name, md in mds.items():
+        replay_start(md, ff, x0, v0)
+        md.run(warmup, check_every=warmup)
+    for _ in range(reps):
+        for name, md in mds.items():
+            replay_start(md, ff, x0, v0)
+            ms, host = timed(replay_steps(md, ff, steps))
+            ff.check()
+            rows[name].append(ms / steps)
+            rows[name + "_host"].append(1e3 * host / steps)
+    return {"molecules": n_mol, "atoms": int(x0.shape[0]), "e_cap": ff.e_cap, "steps": steps, "reps": reps, "dt": dt, "kT": kT,
+            "gamma": gamma, "regrowths": sum(md.regrowths for md in mds.values()), "recaptures": ff.recaptures,
+            "nve_ms_per_step": mmm(rows["nve"]), "langevin_ms_per_step": mmm(rows["langevin"]),
+            "nve_host_busy_ms_per_step": mmm(rows["nve_host"]), "langevin_host_busy_ms_per_step": mmm(rows["langevin_host"]),
+            "langevin_over_nve_median": round(statistics.median(rows["langevin"]) / statistics.median(rows["nve"]), 4)}
+
+
+def make_fire(ff):
+    from e3_layers_amd.run.md import Fire
+
+    return Fire(ff, ftol=1e-9, dt=0.01, dt_max=0.1, maxstep=0.2)      # (a tolerance nothing reaches: every iteration moves every graph)
+
+
+def bench_fire(n_mol, steps, warmup, reps, dev):
+    from e3_layers_amd.run.md import ReplayedForceField
+
+    model, batch, r_max, x0, _ = setup(n_mol, dev)
+    ff = ReplayedForceField(model, batch, r_max)
+    fire = make_fire(ff)
+    ff.pos.copy_(x0)
+    fire.run(warmup, check_every=warmup)
+    fire.reset()
+    eager_fire(model, batch, r_max, x0, fire, warmup)()
+    rows = {k: [] for k in ("replay", "eager", "replay_host", "eager_host")}
+    for _ in range(reps):
+        ff.pos.copy_(x0)
+        fire.reset()
+        ms, host = timed(replay_fire(fire, ff, steps))
+        ff.check()
+        rows["replay"].append(ms / steps)
+        rows["replay_host"].append(1e3 * host / steps)
+        fire.reset()
+        ms, host = timed(eager_fire(model, batch, r_max, x0, fire, steps))
+        rows["eager"].append(ms / steps)
+        rows["eager_host"].append(1e3 * host / steps)
+    return {"molecules": n_mol, "atoms": int(x0.shape[0]), "e_cap": ff.e_cap, "iterations": steps, "reps": reps,
+            "regrowths": fire.regrowths, "recaptures": ff.recaptures,
+            "replay_ms_per_iteration": mmm(rows["replay"]), "eager_ms_per_iteration": mmm(rows["eager"]),
+            "replay_host_busy_ms_per_iteration": mmm(rows["replay_host"]), "eager_host_busy_ms_per_iteration": mmm(rows["eager_host"]),
             "speedup_median": round(statistics.median(rows["eager"]) / statistics.median(rows["replay"]), 3)}
 
 
@@ -158,6 +268,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--dt", type=float, default=0.01)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--integrator", choices=("nve", "langevin"), default="nve", help="langevin: the thermostatted step against the NVE step")
+    ap.add_argument("--fire", action="store_true", help="the FIRE iteration against its eager loop")
+    ap.add_argument("--kT", type=float, default=0.25, help="thermostat temperature in the model's energy units (v0 has variance 0.25)")
+    ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
     ap.add_argument("--launches", nargs=4, metavar=("CSV_A", "STEPS_A", "CSV_B", "STEPS_B"), default=None)
     args = ap.parse_args()
@@ -168,19 +282,30 @@ def main():
         return
     dev = torch.device("cuda:0")
     if args.trace_steps:
-        from e3_layers_amd.run.md import ReplayedForceField, VelocityVerlet
+        from e3_layers_amd.run.md import Langevin, ReplayedForceField, VelocityVerlet
 
         model, batch, r_max, x0, v0 = setup(args.molecules[0], dev)
         ff = ReplayedForceField(model, batch, r_max)
-        md = VelocityVerlet(ff, torch.ones(x0.shape[0]), args.dt)
-        md.v.copy_(v0)
-        md.run(args.trace_steps, check_every=args.trace_steps)
+        if args.fire:
+            make_fire(ff).run(args.trace_steps, check_every=args.trace_steps)
+        else:
+            mass = torch.ones(x0.shape[0])
+            md = Langevin(ff, mass, args.dt, args.kT, args.gamma) if args.integrator == "langevin" else VelocityVerlet(ff, mass, args.dt)
+            md.v.copy_(v0)
+            md.run(args.trace_steps, check_every=args.trace_steps)
         torch.cuda.synchronize()
-        print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0]}))
+        print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0], "integrator": args.integrator, "fire": args.fire}))
         return
-    results = [bench(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
-    doc = {"workload": "velocity Verlet on config_energy_force (as shipped), synth_qm9, unit masses", "device": torch.cuda.get_device_name(0),
-           "results": results}
+    if args.fire:
+        workload = "FIRE relaxation with per-graph state on config_energy_force (as shipped), synth_qm9: replayed iteration vs the eager loop"
+        results = [bench_fire(n, args.steps, args.warmup, args.reps, dev) for n in args.molecules]
+    elif args.integrator == "langevin":
+        workload = "Langevin step vs velocity-Verlet step, both replayed, on config_energy_force (as shipped), synth_qm9, unit masses"
+        results = [bench_langevin(n, args.steps, args.warmup, args.reps, args.dt, args.kT, args.gamma, dev) for n in args.molecules]
+    else:
+        workload = "velocity Verlet on config_energy_force (as shipped), synth_qm9, unit masses"
+        results = [bench(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
+    doc = {"workload": workload, "device": torch.cuda.get_device_name(0), "results": results}
     text = json.dumps(doc, indent=1)
     print(text)
     if args.out:
