@@ -713,10 +713,12 @@ __global__ __launch_bounds__(256) void normact_bwd2_kernel(const float* __restri
     const float* xr = x + r * row_dim;
     const float* gr = gy + r * row_dim;
     const float* hr = h + r * row_dim;
+    bool covered = false;
     for (int k = 0; k < ba.n; ++k) {
       const e3k_block& b = ba.b[k];
       const int rel = c - b.off;
       if (rel >= 0 && rel < b.mul * b.dim) {
+        covered = true;
         const int m = rel / b.mul, u = rel - m * b.mul;   // input element (m, u), channel-fastest
         float n2 = 0.f, gx_ = 0.f, hx = 0.f, hg = 0.f;
         for (int q = 0; q < b.dim; ++q) {
@@ -733,6 +735,10 @@ __global__ __launch_bounds__(256) void normact_bwd2_kernel(const float* __restri
         if (g_x) g_x[i] = d * xm * hg + d2 * xm * hx * gx_ + d * (hm * gx_ + hx * gm);
         break;
       }
+    }
+    if (!covered) {   // a column no block covers: zero in both outputs, as the forward and the first backward store
+      if (g_gy) g_gy[i] = 0.f;
+      if (g_x) g_x[i] = 0.f;
     }
   }
 }

@@ -1801,7 +1801,7 @@ class LayerNormFn(torch.autograd.Function):
     def forward(ctx, x, std, blocks):
         L.require_cuda(x, std)
         x, std = L.f32c(x), L.f32c(std)
-        y = torch.empty_like(x)
+        y = torch.empty_like(x) if _blocks_cover(blocks, x.shape[1]) else torch.zeros_like(x)
         inv = torch.empty(x.shape[0], len(blocks), device=x.device, dtype=torch.float32)
         L.check(L.load().e3k_layernorm_fwd(L.ptr(x), x.shape[0], x.shape[1], _blocks(blocks), len(blocks), L.ptr(std),
                                            L.ptr(y), L.ptr(inv), L.stream_ptr()), "e3k_layernorm_fwd")
@@ -1816,7 +1816,7 @@ class LayerNormFn(torch.autograd.Function):
             gx, gstd = LayerNormBwdFn.apply(x, std, inv, gy, ctx.blocks)
             return (gx if ctx.needs_input_grad[0] else None), (gstd if ctx.needs_input_grad[1] else None), None
         gy = L.f32c(gy)
-        gx = torch.empty_like(x)
+        gx = torch.empty_like(x) if _blocks_cover(ctx.blocks, x.shape[1]) else torch.zeros_like(x)
         gstd = torch.zeros_like(std)
         L.check(L.load().e3k_layernorm_bwd(L.ptr(x), L.ptr(gy), L.ptr(inv), x.shape[0], x.shape[1], _blocks(ctx.blocks),
                                            len(ctx.blocks), L.ptr(std), L.ptr(gx), L.ptr(gstd), L.stream_ptr()),

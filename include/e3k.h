@@ -530,9 +530,10 @@ int e3k_gate_bwd2(const float* x, const float* g_y, const float* g_hat, int64_t 
 
 /* NormActivation (e3nn.nn.NormActivation as built at e3_layers/nn/message_passing.py:212-219; the 'norm'
  * nonlinearity_type of MessagePassing): per irrep channel n2 = max(sum_m x_m^2, epsilon^2), n = sqrt(n2),
- * y_m = x_m * act(n) / n (normalize = 1).  blocks cover the row (uncovered columns come out zero); input
+ * y_m = x_m * act(n) / n (normalize = 1; normalize = 0: y_m = x_m * act(n); epsilon = 0: y_m = x_m * act(sum_m x_m^2), no
+ * clamp).  Columns that no block covers come out ZERO in every output of the three functions (y; g_x; g_gy and g_x); input
  * channel-fastest [2l+1][mul], output e3nn layout [mul][2l+1] at the same offsets; act ids as e3k_act_fwd, raw
- * (no second-moment constant). */
+ * (no second-moment constant).  At most 16 blocks. */
 int e3k_norm_act_fwd(const float* x, int64_t rows, int32_t row_dim, const e3k_block* blocks, int32_t n_blocks, int32_t act,
                      float epsilon, int32_t normalize, float* y, void* stream);
 int e3k_norm_act_bwd(const float* x, const float* g_y, int64_t rows, int32_t row_dim, const e3k_block* blocks,
@@ -542,7 +543,11 @@ int e3k_norm_act_bwd(const float* x, const float* g_y, int64_t rows, int32_t row
 int e3k_norm_act_bwd2(const float* x, const float* g_y, const float* h, int64_t rows, int32_t row_dim, const e3k_block* blocks,
                       int32_t n_blocks, int32_t act, float epsilon, int32_t normalize, float* g_gy, float* g_x, void* stream);
 
-/* per-irreps-block RMS normalisation (LayerNormalization, nn/pointwise.py:32-51), e3nn layout */
+/* per-irreps-block RMS normalisation (LayerNormalization, nn/pointwise.py:32-51), e3nn layout:
+ *   inv_norm[r, k] = (sum_j x_j^2 / mul_k + 1e-6)^-1/2 over the mul_k * dim_k elements of block k,  y_j = x_j * inv_norm * std[k].
+ * All three functions WRITE y / g_x / g_gy ON THE BLOCK COLUMNS ONLY: a column that no block covers is left as the caller
+ * handed it over (the kernels walk blocks, one wave per row; a caller whose table has a gap zero-fills first).  At most 16
+ * blocks.  e3k_layernorm_bwd: g_std [n_blocks] ACCUMULATED (caller zeroes). */
 int e3k_layernorm_fwd(const float* x, int64_t rows, int32_t row_dim, const e3k_block* blocks, int32_t n_blocks,
                       const float* std, float* y, float* inv_norm, void* stream);
 int e3k_layernorm_bwd(const float* x, const float* g_y, const float* inv_norm, int64_t rows, int32_t row_dim,
@@ -576,7 +581,7 @@ int e3k_segment_sum(const float* x, const int32_t* ptr, int64_t n_seg, int32_t d
  * with W_j the [U][V][Wout] weight block of instruction j of FullyConnectedTensorProduct(x, node_attrs)
  * (e3_layers/nn/message_passing.py:81-87, e3nn 'uvw' weight order) at element offset w_off of the flat weight,
  * and its U*Wout columns at m_off of M (columns packed in instruction order, row stride ld_m).
- * a [n_keys, V] (V <= 32; the keys are tiled 64 per workgroup).  backward: g_a [n_keys,V] ACCUMULATED (caller zeroes), g_W flat like W:
+ * a [n_keys, V] (V <= 32; the keys are tiled 64 per workgroup, or 512 when the columns alone make 1024 or more workgroups).  backward: g_a [n_keys,V] ACCUMULATED (caller zeroes), g_W flat like W:
  * written (accumulate_w = 0) or added to (accumulate_w = 1); either may be NULL.  g_a needs a device `workspace` of
  * e3k_keyed_weights_bwd_workspace(...) floats (per-block partial sums, reduced by a second launch — same-address
  * atomics from every block serialise).  `instr` is a HOST array. */
