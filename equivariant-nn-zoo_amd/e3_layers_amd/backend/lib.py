@@ -217,6 +217,9 @@ SIGNATURES = {
     "e3k_md_kick_langevin": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P,
                                        _P, _P]),
     "e3k_fire_step": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _F, _F, _F, _I32, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "e3k_md_drift_shake": (C.c_int, [_P, _P, _P, _P, _I64, _F, _P, _P, _P, _I64, _I64, _P, _I64, _F, _I32, _P, _P]),
+    "e3k_md_kick_rattle": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P,
+                                     _P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P, _F, _I32, _P, _P]),
     "e3k_tp_plan_create": (C.c_int, [C.POINTER(TpGroup), _I32, _I32, _I32, _I32, _I32, C.POINTER(_P)]),
     "e3k_tp_plan_destroy": (None, [_P]),
     "e3k_tp_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),

@@ -18,6 +18,9 @@ fixed capacity (``csrc/e3k_nlist.hip``).  More edges than the capacity is a REPO
     Fire(ff, ftol=1e-3).run(500)              # relax first: every molecule at its own pace, the graph + one launch per iteration
     md = Langevin(ff, masses, dt=0.5, kT=0.025, gamma=0.1, seed=7)      # the graph + two launches per step, as NVE
     md.thermalize()                           # Maxwell-Boltzmann velocities at kT
+
+    bonds = BondConstraints(hydrogen_bonds(pos, species == 1, ff.node_ptr, 1.3), pos=pos, node_ptr=ff.node_ptr, masses=masses)
+    md = Langevin(ff, masses, dt=2.0, kT=0.025, gamma=0.1, constraints=bonds)      # SHAKE / RATTLE inside the same two launches
 """
 from __future__ import annotations
 
@@ -31,7 +34,8 @@ from ..backend.graph import EdgeCapacityExceeded
 from ..data.compute_edge import check_edge_capacity, computeEdgeIndex, computeEdgeIndexCapped, normal_draw
 from .graph_step import GHOST_DEGREE, CapturedStep, bucket_capacity, pad_batch
 
-__all__ = ["EdgeCapacityExceeded", "ReplayedForceField", "VelocityVerlet", "Langevin", "Fire"]
+__all__ = ["EdgeCapacityExceeded", "ReplayedForceField", "VelocityVerlet", "Langevin", "Fire", "BondConstraints", "ConstraintFailure",
+           "hydrogen_bonds"]
 
 _EDGE_KEYS = ("edge_index", "edge_vector", "edge_length", "_n_edges", "_edge_segment")
 
@@ -258,6 +262,257 @@ def _fire_step_torch(x, v, f, node_ptr, state, fire, energy=None, energy_record=
             fmax_record[g] = fmax
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Bond-length constraints (csrc/e3k_constraint.hip): SHAKE inside the first half step, RATTLE inside the second.
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_SATELLITES = 4
+
+
+class ConstraintFailure(RuntimeError):
+    """Stars did not meet their stopping rule within ``max_iter`` sweeps since the last check: ``shake`` and ``rattle`` count them.
+    The driver is back at the last verified step and its counters are cleared."""
+
+    def __init__(self, shake: int, rattle: int):
+        self.shake, self.rattle = int(shake), int(rattle)
+        super().__init__(f"bond constraints not met since the last check: SHAKE failed on {self.shake} stars, RATTLE on "
+                         f"{self.rattle}; the state is that of the last verified step (a smaller dt or a larger max_iter)")
+
+
+def hydrogen_bonds(pos, light, node_ptr, max_length: float):
+    """``pairs`` [C, 2] (heavy, light) for ``BondConstraints``: every atom of the boolean mask ``light`` [N] with the nearest
+    non-light atom of its own graph within ``max_length`` (ties: the lowest index); a light atom with no partner in range stays
+    free.  No species table is guessed: the caller says which atoms are light."""
+    x = pos.detach().cpu().double()
+    light = torch.as_tensor(light).detach().cpu().reshape(-1).bool()
+    if light.numel() != x.shape[0]:
+        raise ValueError(f"a mask of {light.numel()} for {x.shape[0]} atoms")
+    bounds = node_ptr.detach().cpu().tolist()
+    pairs = []
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        li = torch.nonzero(light[a:b]).reshape(-1) + a
+        hv = torch.nonzero(~light[a:b]).reshape(-1) + a
+        if li.numel() == 0 or hv.numel() == 0:
+            continue
+        d = (x[li][:, None, :] - x[hv][None, :, :]).norm(dim=2)
+        dmin, j = d.min(dim=1)
+        keep = dmin <= max_length
+        pairs.append(torch.stack([hv[j[keep]], li[keep]], 1))
+    out = torch.cat(pairs) if pairs else torch.zeros(0, 2, dtype=torch.int64)
+    return out.to(pos.device)
+
+
+class BondConstraints:
+    """Fixed distances between pairs of atoms, as disjoint STARS: a centre with 1 to 4 satellites, every satellite in exactly one
+    constraint, no atom in two stars -- the bonds-to-hydrogen set (CH4 and NH4+ need the four).  Stars share no atom, so one thread
+    owns a star: no atomics, the same bits every run.  Anything else is refused with a ``ValueError`` that names the atoms: a pair
+    across two graphs, a duplicate or a self pair, two constraints between atoms that each have another (chains, rings, rigid
+    water's H-H, an atom that would be a satellite twice), more than four satellites, a length <= 0, a non-positive or non-finite
+    mass on a constrained atom.
+
+    ``pairs`` [C, 2] int64 node indices of the unpadded batch; ``lengths`` [C] (None: the present distances in ``pos``).  The atom
+    of a pair that has other constraints is the centre (an isolated pair: its first atom).  ``tol``: the relative length error
+    SHAKE stops at, and RATTLE's |r.v_rel| <= tol d0 (|v_c| + |v_s|); below 16 ulp of the positions' dtype it is refused (fp32
+    cannot reach it).  ``max_iter`` sweeps at most.
+
+    Built once, on ``pos``'s device: ``star_ptr`` [S + 1] into ``star_atom`` / ``star_len`` (centre first, then the satellites,
+    each with its length beside it), ``free_atom`` (the atoms in no star), both sorted by graph with ``graph_star_ptr`` /
+    ``graph_free_ptr`` [G + 1]; ``dof`` [G] = 3 n_g - c_g; ``counters`` int32 [2]: SHAKE's and RATTLE's failures."""
+
+    def __init__(self, pairs, lengths=None, *, pos, node_ptr, masses, tol: float = 1e-5, max_iter: int = 32):
+        dev, dtype = pos.device, pos.dtype
+        n = int(pos.shape[0])
+        ptr = node_ptr.detach().cpu().to(torch.int64).reshape(-1)
+        n_graphs = ptr.numel() - 1
+        if n_graphs < 0 or int(ptr[-1]) != n:
+            raise ValueError(f"node_ptr ends at {int(ptr[-1]) if ptr.numel() else None} for {n} atoms")
+        if not tol >= 16 * torch.finfo(dtype).eps / 2:
+            raise ValueError(f"tol = {tol} is below 16 ulp of {dtype} ({16 * torch.finfo(dtype).eps / 2:.3g}): it cannot be reached")
+        if max_iter < 1:
+            raise ValueError("max_iter >= 1")
+        self.tol, self.max_iter, self.n, self.n_graphs = float(tol), int(max_iter), n, n_graphs
+        pairs = torch.as_tensor(pairs).detach().cpu().to(torch.int64).reshape(-1, 2)
+        a, b = pairs[:, 0], pairs[:, 1]
+        n_con = pairs.shape[0]
+
+        def refuse(mask, what):
+            if bool(mask.any()):
+                rows = pairs[mask][:8].tolist()
+                raise ValueError(f"{what}: atoms {', '.join(f'({i}, {j})' for i, j in rows)}" + (" ..." if int(mask.sum()) > 8 else ""))
+
+        refuse((pairs < 0).any(1) | (pairs >= n).any(1), f"constraint between atoms outside 0..{n - 1}")
+        refuse(a == b, "an atom constrained to itself")
+        seg = torch.bucketize(torch.arange(n), ptr[1:], right=True)
+        refuse(seg[a] != seg[b], "a constraint across two graphs")
+        key = torch.minimum(a, b) * n + torch.maximum(a, b)
+        _, inverse, counts = torch.unique(key, return_inverse=True, return_counts=True)
+        refuse(counts[inverse] > 1, "a duplicate constraint")
+        deg = torch.bincount(pairs.reshape(-1), minlength=n)
+        refuse((deg[a] > 1) & (deg[b] > 1), "not a star (a chain, a ring, or an atom that would be a satellite of two centres): both "
+               "ends of a constraint have other constraints")
+        centre = torch.where(deg[a] >= deg[b], a, b)
+        sat = a + b - centre
+        refuse(deg[centre] > MAX_SATELLITES, f"a centre with more than {MAX_SATELLITES} satellites")
+        x = pos.detach().cpu().double()
+        if lengths is None:
+            length = (x[sat] - x[centre]).norm(dim=1)
+        else:
+            length = torch.as_tensor(lengths).detach().cpu().double().reshape(-1)
+            if length.numel() != n_con:
+                raise ValueError(f"{length.numel()} lengths for {n_con} constraints")
+        refuse(~(length > 0) | ~torch.isfinite(length), "a constraint of length <= 0 (or not finite)")
+        m = masses.detach().cpu().double().reshape(-1)
+        if m.numel() != n:
+            raise ValueError(f"{m.numel()} masses for {n} atoms")
+        bad = ~(m > 0) | ~torch.isfinite(m)
+        refuse(bad[a] | bad[b], "a constrained atom whose mass is not positive and finite")
+
+        order = torch.argsort(centre, stable=True)      # by centre (so by graph), a star's satellites in the order of ``pairs``
+        centre, sat, length = centre[order], sat[order], length[order]
+        star_centre, star_of, n_sat = torch.unique_consecutive(centre, return_inverse=True, return_counts=True)
+        n_stars = star_centre.numel()
+        star_ptr = torch.zeros(n_stars + 1, dtype=torch.int64)
+        star_ptr[1:] = torch.cumsum(n_sat + 1, 0)
+        first = torch.zeros(n_stars, dtype=torch.int64)
+        first[1:] = torch.cumsum(n_sat, 0)[:-1]
+        rank = torch.arange(n_con) - first[star_of]      # the satellite's place in its star
+        star_atom = torch.zeros(n_stars + n_con, dtype=torch.int64)
+        star_len = torch.zeros(n_stars + n_con, dtype=torch.float64)
+        star_atom[star_ptr[:-1]] = star_centre
+        star_atom[star_ptr[:-1][star_of] + 1 + rank] = sat
+        star_len[star_ptr[:-1][star_of] + 1 + rank] = length
+        free = torch.nonzero(deg == 0).reshape(-1)
+
+        def graph_ptr(nodes):
+            out = torch.zeros(n_graphs + 1, dtype=torch.int64)
+            out[1:] = torch.cumsum(torch.bincount(seg[nodes], minlength=n_graphs), 0)
+            return out
+
+        self.n_stars, self.n_free, self.n_slots, self.n_constraints = n_stars, int(free.numel()), n_stars + n_con, n_con
+        self.max_sat = int(n_sat.max()) if n_stars else 0
+        self.star_ptr, self.star_atom = star_ptr.to(dev), star_atom.to(dev)
+        self.star_len = star_len.to(dtype).to(dev).contiguous()
+        self.free_atom = free.to(dev)
+        self.graph_star_ptr, self.graph_free_ptr = graph_ptr(star_centre).to(dev), graph_ptr(free).to(dev)
+        self.dof = (3 * (ptr[1:] - ptr[:-1]) - torch.bincount(seg[centre], minlength=n_graphs)).to(dev)
+        self.counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._shake_counter, self._rattle_counter = self.counters[0:1], self.counters[1:2]
+        # the same tables padded to [S, 5] for the torch path (a slot behind a star's own holds its centre and is masked out)
+        idx = star_centre[:, None].repeat(1, MAX_SATELLITES + 1)
+        valid = torch.zeros(n_stars, MAX_SATELLITES + 1, dtype=torch.bool)
+        d0 = torch.ones(n_stars, MAX_SATELLITES, dtype=torch.float64)
+        valid[:, 0] = True
+        idx[star_of, 1 + rank], valid[star_of, 1 + rank], d0[star_of, rank] = sat, True, length
+        self._idx, self._valid, self._d0 = idx.to(dev), valid.to(dev), d0.to(dtype).to(dev)
+
+    @property
+    def pairs(self):
+        """[C, 2] (centre, satellite), in the tables' order."""
+        return torch.stack([self._idx[:, :1].expand(-1, MAX_SATELLITES)[self._valid[:, 1:]], self._idx[:, 1:][self._valid[:, 1:]]], 1)
+
+    @property
+    def lengths(self):
+        return self._d0[self._valid[:, 1:]]
+
+
+def _table_args(con):
+    return (L.ptr(con.star_ptr), L.ptr(con.star_atom), L.ptr(con.star_len), con.n_stars, con.n_slots, L.ptr(con.free_atom), con.n_free)
+
+
+def _drift_shake(x, v, f, mass, dt: float, con) -> None:
+    """``_drift`` with SHAKE on the stars (``e3k_md_drift_shake``).  ``f`` None: positions only -- the lengths are enforced at the
+    present positions along the present bonds, nothing else moves."""
+    if x.is_cuda:
+        L.check(L.load().e3k_md_drift_shake(L.ptr(x), L.ptr(v), L.ptr(f), L.ptr(mass), x.shape[0], float(dt), *_table_args(con),
+                                            con.tol, con.max_iter, L.ptr(con._shake_counter), L.stream_ptr()), "e3k_md_drift_shake")
+        return
+    idx, valid = con._idx, con._valid
+    x0 = x[idx]                                         # [S, 5, 3]: the old positions, before anything moves
+    if f is not None:
+        v.add_(f / mass[:, None], alpha=0.5 * dt)
+        x.add_(v, alpha=dt)
+    if con.n_stars == 0:
+        return
+    ro = x0[:, 1:] - x0[:, :1]                          # the old bond vectors; everything below is relative to the centre's old position
+    p = x0 - x0[:, :1]
+    vh = v[idx]
+    if f is not None:
+        p = p + dt * vh
+    q = p.clone()
+    inv_m = 1.0 / mass[idx]
+    on_k, d02 = valid[:, 1:], con._d0 * con._d0
+    fail = torch.zeros(con.n_stars, dtype=torch.bool)
+    # a pass visits the constraints in stored order and corrects those outside the tolerance; it ends after a pass that found none
+    # (a star that is within it is not touched again: the passes are each star's own); pass number max_iter only looks
+    for it in range(con.max_iter + 1):
+        moved = False
+        for k in range(con.max_sat):
+            r = p[:, 1 + k] - p[:, 0]
+            diff = d02[:, k] - (r * r).sum(-1)
+            out = on_k[:, k] & ~(diff.abs() <= 2.0 * con.tol * d02[:, k])
+            if not bool(out.any()):
+                continue
+            moved = True
+            rr = (r * ro[:, k]).sum(-1)
+            on = out & (rr > 0) if it < con.max_iter else torch.zeros_like(out)
+            fail |= out & ~on
+            g = torch.where(on, diff / (2.0 * rr * (inv_m[:, 0] + inv_m[:, 1 + k])), torch.zeros_like(rr))
+            p[:, 1 + k] += (g * inv_m[:, 1 + k])[:, None] * ro[:, k]
+            p[:, 0] -= (g * inv_m[:, 0])[:, None] * ro[:, k]
+        if not moved:
+            break
+    x[idx[valid]] = (x0[:, :1] + p)[valid]
+    if f is not None:
+        v[idx[valid]] = (vh + (p - q) / dt)[valid]
+    con.counters[0] += int(fail.sum())
+
+
+def _kick_rattle(x, v, f, mass, node_ptr, dt: float, c: float, s: float, seed: int, draw: int, word0: int, con, kinetic, energy=None,
+                 potential=None) -> None:
+    """``_kick_langevin`` with RATTLE on the stars (``e3k_md_kick_rattle``): the velocities are projected along the present bonds
+    and ``kinetic`` is the energy of the projected velocities."""
+    if v.is_cuda:
+        L.check(L.load().e3k_md_kick_rattle(L.ptr(v), L.ptr(f), L.ptr(mass), L.ptr(node_ptr), node_ptr.numel() - 1, v.shape[0], float(dt),
+                                            float(c), float(s), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, draw & 0xFFFFFFFF,
+                                            int(word0), L.ptr(kinetic), L.ptr(energy), L.ptr(potential), L.ptr(x), *_table_args(con),
+                                            L.ptr(con.graph_star_ptr), L.ptr(con.graph_free_ptr), con.tol, con.max_iter,
+                                            L.ptr(con._rattle_counter), L.stream_ptr()), "e3k_md_kick_rattle")
+        return
+    if not (c == 1.0 and s == 0.0):      # (the plain kick draws nothing: the NVE driver's path, bit for bit)
+        node = torch.arange(v.shape[0], dtype=torch.int64)[:, None]
+        xi = normal_draw(seed, draw, node, word0 + torch.arange(3, dtype=torch.int64)[None, :], v.dtype)
+        v.mul_(c).add_((s / torch.sqrt(mass))[:, None] * xi)
+    if f is not None:
+        v.add_(f / mass[:, None], alpha=0.5 * dt)
+    if con.n_stars:
+        idx, valid = con._idx, con._valid
+        xs = x[idx]
+        r = xs[:, 1:] - xs[:, :1]
+        r2 = (r * r).sum(-1)
+        u = v[idx]
+        inv_m = 1.0 / mass[idx]
+        on_k = valid[:, 1:]
+        fail = torch.zeros(con.n_stars, dtype=torch.bool)
+        for it in range(con.max_iter + 1):      # passes as in _drift_shake
+            moved = False
+            for k in range(con.max_sat):
+                rv = (r[:, k] * (u[:, 1 + k] - u[:, 0])).sum(-1)
+                lim = con.tol * con._d0[:, k] * (u[:, 0].norm(dim=-1) + u[:, 1 + k].norm(dim=-1))
+                out = on_k[:, k] & ~(rv.abs() <= lim)
+                if not bool(out.any()):
+                    continue
+                moved = True
+                on = out & (r2[:, k] > 0) if it < con.max_iter else torch.zeros_like(out)
+                fail |= out & ~on
+                g = torch.where(on, rv / (r2[:, k] * (inv_m[:, 0] + inv_m[:, 1 + k])), torch.zeros_like(rv))
+                u[:, 1 + k] -= (g * inv_m[:, 1 + k])[:, None] * r[:, k]
+                u[:, 0] += (g * inv_m[:, 0])[:, None] * r[:, k]
+            if not moved:
+                break
+        v[idx[valid]] = u[valid]
+        con.counters[1] += int(fail.sum())
+    _kick_host(v, None, mass, node_ptr, dt, kinetic, energy, potential)
+
+
 class _ChunkedDriver:
     """What the integrators and the minimiser share: iterations are enqueued in chunks of ``check_every``; the list's capacity is
     checked once per chunk (the one synchronisation); a chunk that overflowed is thrown away -- positions and the driver's own
@@ -309,6 +564,11 @@ class _ChunkedDriver:
     def _finished(self) -> bool:
         return False
 
+    def _chunk_failure(self, start: int, stop: int):
+        """Called where the chunk's capacity check has synchronised: an exception to raise AFTER the chunk (iterations ``start`` to
+        ``stop`` of this run) has been rolled back, or None."""
+        return None
+
     def _run_chunks(self, n_steps: int, check_every: int) -> int:
         """Up to ``n_steps`` iterations; returns how many were done (fewer only when ``_finished()`` said so)."""
         done = 0
@@ -321,6 +581,14 @@ class _ChunkedDriver:
                     self._step(i, self.steps_done + i - done)
                 try:
                     self.ff.check()
+                    failure = self._chunk_failure(done, done + chunk)
+                    if failure is not None:      # back to the last verified iteration, and the caller hears of it
+                        self.x.copy_(snap_x)
+                        for t, snap in zip(self._tensors(), snaps):
+                            t.copy_(snap)
+                        self.restores += 1
+                        self._after_restore()
+                        raise failure
                     self._commit_chunk()
                     break
                 except EdgeCapacityExceeded:
@@ -344,17 +612,27 @@ class VelocityVerlet(_ChunkedDriver):
     ``masses`` [N]; ``dt`` in the model's units.  ``v`` [N, 3] starts at zero: set it, or ``thermalize``, before ``run``.
 
     One step = drift kernel, the force field's graph, kick kernel (which also files the step's potential and kinetic energies:
-    two launches outside the graph).  Every ``check_every`` steps the list's capacity is checked
+    two launches outside the graph).  ``constraints``: a ``BondConstraints`` set -- the two launches become ``e3k_md_drift_shake`` and
+    ``e3k_md_kick_rattle`` (still two), the kinetic record is that of the projected velocities, ``dof`` counts 3 n - c; a star that
+    did not converge is found at the chunk's check: the chunk is rolled back and ``ConstraintFailure`` raised.  Every ``check_every`` steps the list's capacity is checked
     (the one synchronisation); a chunk that overflowed is thrown away -- positions, velocities and records go back to the last
     verified step, the capacity grows, the chunk runs again -- so an overflowed step never reaches the caller."""
 
-    def __init__(self, ff, masses, dt: float, grow_factor: float = 1.5, seed: int = 0):
+    def __init__(self, ff, masses, dt: float, grow_factor: float = 1.5, seed: int = 0, *, constraints=None):
         super().__init__(ff, grow_factor)
         self.dt, self.seed = float(dt), int(seed)
         x = ff.pos
         self.mass = masses.to(device=x.device, dtype=x.dtype).reshape(-1).contiguous()
         if self.mass.numel() != x.shape[0]:
             raise ValueError(f"{self.mass.numel()} masses for {x.shape[0]} atoms")
+        if constraints is not None:
+            con = constraints
+            if con.n != x.shape[0] or con.n_graphs != ff.node_ptr.numel() - 1 or con.star_len.dtype != x.dtype or \
+                    con.star_len.device != x.device:
+                raise ValueError("the constraints were built for another batch, dtype or device")
+            if self.dt == 0.0:
+                raise ValueError("constrained steps need dt != 0 (the velocity correction divides by it)")
+        self.constraints = constraints
         self.v = torch.zeros_like(x).contiguous()
         self.thermalizations = 0      # the draw counter of thermalize()
         self._forces = None      # forces at the present positions (the graph's static tensor), None: not evaluated yet
@@ -366,9 +644,51 @@ class VelocityVerlet(_ChunkedDriver):
         kT = getattr(self, "kT", None) if kT is None else float(kT)
         if kT is None or kT < 0:
             raise ValueError("thermalize() needs kT >= 0")
+        if self.constraints is not None:      # drawn and projected onto the constraints in the one launch
+            _kick_rattle(self.x, self.v, None, self.mass, self.ff.node_ptr, 0.0, 0.0, kT ** 0.5, self.seed, self.thermalizations,
+                         THERMALIZE_WORD, self.constraints, None)
+            self.thermalizations += 1
+            return
         _kick_langevin(self.v, None, self.mass, self.ff.node_ptr, 0.0, 0.0, kT ** 0.5, self.seed, self.thermalizations, THERMALIZE_WORD,
                        None)
         self.thermalizations += 1
+
+    @property
+    def dof(self):
+        """[G]: each graph's degrees of freedom, 3 n_g minus its constraints."""
+        if self.constraints is not None:
+            return self.constraints.dof
+        return 3 * (self.ff.node_ptr[1:] - self.ff.node_ptr[:-1])
+
+    def project(self) -> None:
+        """Enforces the constraints' lengths at the present positions (moving each star's atoms along its present bonds) and
+        projects ``v`` onto them: for sets whose ``lengths`` are not the geometry's own.  Synchronises; raises ``ConstraintFailure``
+        if a star did not converge."""
+        con = self.constraints
+        if con is None:
+            raise ValueError("project() needs constraints")
+        _drift_shake(self.x, self.v, None, self.mass, 0.0, con)
+        _kick_rattle(self.x, self.v, None, self.mass, self.ff.node_ptr, 0.0, 1.0, 0.0, 0, 0, 0, con, None)
+        self._forces = None      # the positions moved
+        failure = self._chunk_failure(0, 0)
+        if failure is not None:
+            raise failure
+
+    def _ou(self):
+        return 1.0, 0.0      # (c, s) of the second half step: no thermostat
+
+    def _chunk_failure(self, start: int, stop: int):
+        con = self.constraints
+        if con is None:
+            return None
+        shake, rattle = con.counters.tolist()      # (the device is idle: the capacity check has synchronised)
+        if shake == 0 and rattle == 0:
+            return None
+        con.counters.zero_()
+        if stop > start:
+            self._pot[start:stop].zero_()
+            self._kin[start:stop].zero_()
+        return ConstraintFailure(shake, rattle)
 
     def _tensors(self):
         return (self.v,)
@@ -381,14 +701,24 @@ class VelocityVerlet(_ChunkedDriver):
 
     def _after_restore(self) -> None:
         _, self._forces = self._verified_forces()      # the forces at the snapshot's positions, on the grown list
+        if self.constraints is not None:
+            self.constraints.counters.zero_()          # what the thrown-away steps counted
 
     def _second_half(self, k: int, forces, energy, kinetic, potential) -> None:
         _kick(self.v, forces, self.mass, self.ff.node_ptr, self.dt, kinetic, energy, potential)
 
     def _step(self, i: int, k: int) -> None:
-        _drift(self.x, self.v, self._chunk_forces, self.mass, self.dt)
+        con = self.constraints
+        if con is None:
+            _drift(self.x, self.v, self._chunk_forces, self.mass, self.dt)
+            energy, self._chunk_forces = self.ff.evaluate()
+            self._second_half(k, self._chunk_forces, energy, self._kin[i], self._pot[i])
+            return
+        _drift_shake(self.x, self.v, self._chunk_forces, self.mass, self.dt, con)
         energy, self._chunk_forces = self.ff.evaluate()
-        self._second_half(k, self._chunk_forces, energy, self._kin[i], self._pot[i])
+        c, s = self._ou()
+        _kick_rattle(self.x, self.v, self._chunk_forces, self.mass, self.ff.node_ptr, self.dt, c, s, self.seed, k, THERMOSTAT_WORD, con,
+                     self._kin[i], energy, self._pot[i])
 
     def run(self, n_steps: int, check_every: int = 50):
         """``n_steps`` steps; returns {"potential": [n_steps, G], "kinetic": [n_steps, G]} (per graph, after every step); the state
@@ -417,13 +747,16 @@ class Langevin(VelocityVerlet):
     ``xi`` is counter-based (``data/compute_edge.normal_draw``) with the ABSOLUTE step number as its draw index: a chunk that is
     rolled back and redone after an overflow sees the same noise, and a trajectory does not depend on ``check_every``."""
 
-    def __init__(self, ff, masses, dt: float, kT: float, gamma: float, seed: int = 0, grow_factor: float = 1.5):
+    def __init__(self, ff, masses, dt: float, kT: float, gamma: float, seed: int = 0, grow_factor: float = 1.5, *, constraints=None):
         if kT < 0 or gamma < 0:
             raise ValueError("kT >= 0 and gamma >= 0")
-        super().__init__(ff, masses, dt, grow_factor, seed)
+        super().__init__(ff, masses, dt, grow_factor, seed, constraints=constraints)
         self.kT, self.gamma = float(kT), float(gamma)
         self.c = math.exp(-self.gamma * self.dt)                    # (float64 on the host; the kernel takes them as floats)
         self.s = math.sqrt(-math.expm1(-2.0 * self.gamma * self.dt) * self.kT)
+
+    def _ou(self):
+        return self.c, self.s
 
     def _second_half(self, k: int, forces, energy, kinetic, potential) -> None:
         _kick_langevin(self.v, forces, self.mass, self.ff.node_ptr, self.dt, self.c, self.s, self.seed, k, THERMOSTAT_WORD, kinetic,

@@ -749,6 +749,48 @@ int e3k_fire_step(float* x, float* v, const float* f, const int64_t* node_ptr, i
                   float dt_max, float maxstep, int32_t n_min, float f_inc, float f_dec, float alpha_start, float f_alpha,
                   const float* energy, float* energy_record, float* fmax_record, void* stream);
 
+/* Bond-length constraints for the two half steps above (csrc/e3k_constraint.hip; SHAKE: Ryckaert, Ciccotti, Berendsen 1977; RATTLE:
+ * Andersen 1983).  The constraints form disjoint STARS -- a centre with 1..4 satellites, every constraint centre--satellite, no atom
+ * in two stars (the bonds-to-hydrogen set) -- so one thread owns a star: no atomics in the arithmetic, the same bits every run.
+ * Tables, built once by the caller:
+ *   star_ptr [n_stars + 1] int64: star t is the slots [star_ptr[t], star_ptr[t + 1]) (2..5 of them) of
+ *   star_atom [n_slots] int64 and star_len [n_slots] fp32: the centre first (its length slot is not read), then the satellites,
+ *             each with the length of its bond beside it;
+ *   free_atom [n_free] int64: the atoms in no star;  stars and free atoms are sorted by graph (the free atoms of a graph ascending):
+ *   graph_star_ptr, graph_free_ptr [G + 1] int64: each graph's range of stars and of free_atom entries.
+ * Every index read from a table is clamped before it is used as an address.  tol > 0 (1e-5 is the usual fp32 setting; below
+ * 16 2^-24 fp32 cannot reach it), max_iter >= 1 sweeps.  counter: one DEVICE int32 per call site; a star that does not meet its
+ * stopping rule within max_iter sweeps adds 1 to it and is written as it stands (valid numbers, wrong physics): the caller reads the
+ * counter where it synchronises anyway and throws the steps since the last reading away.
+ *
+ * e3k_md_drift_shake replaces e3k_md_drift.  Threads: one per star, behind them one per free atom (e3k_md_drift's expressions,
+ *   unchanged).  A star, in coordinates relative to its centre's OLD position (a 10 A coordinate's rounding stays out of a 1 A bond):
+ *   v_half = v + dt/2 f / m;  p = old + dt v_half;  passes over its constraints in stored order, with r = p_sat - p_centre and the
+ *   OLD bond vector r_old as the direction: a constraint with |r.r - d0^2| > 2 tol d0^2 is corrected,
+ *   g = (d0^2 - r.r) / (2 r.r_old (1/m_c + 1/m_s));  p_sat += g / m_s r_old;  p_centre -= g / m_c r_old;  the star is done after a
+ *   pass that corrected nothing (at most max_iter correcting passes, then one that only looks).  Then x = centre_old + p and
+ *   v = v_half + (p - p_unconstrained) / dt.  r.r_old <= 0 (the bond turned over within the step) counts as a failure.
+ *   f NULL: positions only (no kick, no move, v and the free atoms untouched): the lengths are enforced at the present positions
+ *   along the present bonds.  Otherwise dt != 0.
+ * e3k_md_kick_rattle replaces e3k_md_kick / e3k_md_kick_langevin (their arguments, then x and the tables).  One wave per graph; its
+ *   lanes take the graph's stars l, l + 64, ..., then its free atoms l, l + 64, ....  Every atom gets e3k_md_kick_langevin's update
+ *   (c = 1, s = 0: the plain kick; f NULL: no kick; c = 0, s = sqrt(kT), f NULL: a Maxwell-Boltzmann draw); a star's velocities
+ *   are then projected along its present bond vectors r = x_sat - x_centre:  g = r.(v_sat - v_centre) / (r.r (1/m_c + 1/m_s));
+ *   v_sat -= g / m_s r;  v_centre += g / m_c r;  in passes as above, a constraint being corrected while
+ *   |r.v_rel| > tol d0 (|v_centre| + |v_sat|).  kinetic [G] is the energy
+ *   of the PROJECTED velocities (a lane adds its stars' atoms, then its free atoms; the lanes meet in e3k_md_kick's butterfly);
+ *   potential as e3k_md_kick files it.  With no star the two calls give e3k_md_drift's and e3k_md_kick_langevin's values (s = 0
+ *   draws nothing where that kernel adds an exact zero).
+ *   node_ptr [G + 1] is checked and otherwise unused: the walk follows the tables. */
+int e3k_md_drift_shake(float* x, float* v, const float* f, const float* mass, int64_t n, float dt, const int64_t* star_ptr,
+                       const int64_t* star_atom, const float* star_len, int64_t n_stars, int64_t n_slots, const int64_t* free_atom,
+                       int64_t n_free, float tol, int32_t max_iter, int32_t* counter, void* stream);
+int e3k_md_kick_rattle(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt, float c,
+                       float s, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t word0, float* kinetic, const float* energy,
+                       float* potential, const float* x, const int64_t* star_ptr, const int64_t* star_atom, const float* star_len,
+                       int64_t n_stars, int64_t n_slots, const int64_t* free_atom, int64_t n_free, const int64_t* graph_star_ptr,
+                       const int64_t* graph_free_ptr, float tol, int32_t max_iter, int32_t* counter, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training-step plumbing on the flat parameter vector.
  * Replaces clip_grad_norm_ + optim.step() + ema.update() (e3_layers/run/trainer.py:374-386) and the variant that

@@ -6,6 +6,7 @@ evaluation, the neighbour list rebuilt inside it, two integrator launches beside
     python tools/md_bench.py --molecules 32 64 1 --steps 200 --out profiles/md_replay.json
     python tools/md_bench.py --integrator langevin --out profiles/md_langevin.json      (the thermostatted step against the NVE step)
     python tools/md_bench.py --fire --out profiles/md_fire.json                         (the FIRE iteration against its eager loop)
+    python tools/md_bench.py --constraints --out profiles/md_constraints.json           (the SHAKE / RATTLE step against the plain step)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/md_bench.py --trace-steps 60 --molecules 32
     python tools/md_bench.py --launches DIR_A/…_kernel_stats.csv 10 DIR_B/…_kernel_stats.csv 60      (launches per replayed step)
 
@@ -154,6 +155,79 @@ def replay_steps(md, ff, n_steps):
     return loop
 
 
+def bonds_to_hydrogen(batch, x0, ff, reach=1.3):
+    """(constraints, masses) for the benchmark: H 1, the rest 12; every H within ``reach`` of a heavy atom is bound to the nearest
+    one.  synth_qm9's geometries are random, not chemistry: a heavy atom that would collect more than four keeps its first four."""
+    from e3_layers_amd.run.md import MAX_SATELLITES, BondConstraints, hydrogen_bonds
+
+    light = batch["species"].reshape(-1) == 1
+    mass = torch.where(light, 1.0, 12.0).to(x0)
+    pairs = hydrogen_bonds(x0, light, ff.node_ptr, reach).cpu()
+    order = torch.argsort(pairs[:, 0], stable=True)
+    pairs = pairs[order]
+    first = torch.searchsorted(pairs[:, 0].contiguous(), pairs[:, 0].contiguous())
+    pairs = pairs[torch.arange(pairs.shape[0]) - first < MAX_SATELLITES]
+    return BondConstraints(pairs, pos=x0, node_ptr=ff.node_ptr, masses=mass), mass
+
+
+def constrained_steps(md, ff, n_steps):
+    """The launches of the constrained ``VelocityVerlet._step`` (``e3k_md_drift_shake``, the graph, ``e3k_md_kick_rattle``), as
+    ``replay_steps`` issues the plain ones."""
+    from e3_layers_amd.run import md as M
+
+    n_graphs = ff.node_ptr.numel() - 1
+    pot = torch.zeros(n_steps, n_graphs, device=ff.dev)
+    kin = torch.zeros_like(pot)
+    forces, con = md._forces, md.constraints
+
+    def loop():
+        nonlocal forces
+        t0 = time.perf_counter()
+        for i in range(n_steps):
+            M._drift_shake(ff.pos, md.v, forces, md.mass, md.dt, con)
+            energy, forces = ff.evaluate()
+            M._kick_rattle(ff.pos, md.v, forces, md.mass, ff.node_ptr, md.dt, 1.0, 0.0, 0, i, M.THERMOSTAT_WORD, con, kin[i], energy, pot[i])
+        return time.perf_counter() - t0
+
+    return loop
+
+
+def bench_constraints(n_mol, steps, warmup, reps, dt, dev):
+    """The constrained step against the plain step of the same build on ONE force field, the same masses and the same (projected)
+    start: the two differ in their two launches outside the graph."""
+    from e3_layers_amd.run.md import ReplayedForceField, VelocityVerlet
+
+    model, batch, r_max, x0, v0 = setup(n_mol, dev)
+    ff = ReplayedForceField(model, batch, r_max)
+    con, mass = bonds_to_hydrogen(batch, x0, ff)
+    mds = {"plain": VelocityVerlet(ff, mass, dt), "constrained": VelocityVerlet(ff, mass, dt, constraints=con)}
+    mds["constrained"].v.copy_(v0)
+    ff.pos.copy_(x0)
+    mds["constrained"].project()
+    v0 = mds["constrained"].v.clone()             # both start on the constraint surface
+    loops = {"plain": replay_steps, "constrained": constrained_steps}
+    rows = {k: [] for k in ("plain", "constrained", "plain_host", "constrained_host")}
+    for name, md in mds.items():
+        replay_start(md, ff, x0, v0)
+        md.run(warmup, check_every=warmup)
+    for _ in range(reps):
+        for name, md in mds.items():
+            replay_start(md, ff, x0, v0)
+            ms, host = timed(loops[name](md, ff, steps))
+            ff.check()
+            rows[name].append(ms / steps)
+            rows[name + "_host"].append(1e3 * host / steps)
+    failures = con.counters.tolist()
+    diff = statistics.median(rows["constrained"]) - statistics.median(rows["plain"])
+    return {"molecules": n_mol, "atoms": int(x0.shape[0]), "constraints": con.n_constraints, "stars": con.n_stars, "e_cap": ff.e_cap,
+            "steps": steps, "reps": reps, "dt": dt, "tol": con.tol, "max_iter": con.max_iter, "shake_failures": failures[0],
+            "rattle_failures": failures[1], "regrowths": sum(md.regrowths for md in mds.values()), "recaptures": ff.recaptures,
+            "plain_ms_per_step": mmm(rows["plain"]), "constrained_ms_per_step": mmm(rows["constrained"]),
+            "plain_host_busy_ms_per_step": mmm(rows["plain_host"]), "constrained_host_busy_ms_per_step": mmm(rows["constrained_host"]),
+            "constrained_minus_plain_us_median": round(1e3 * diff, 2),
+            "constrained_over_plain_median": round(statistics.median(rows["constrained"]) / statistics.median(rows["plain"]), 4)}
+
+
 def timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -270,6 +344,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--integrator", choices=("nve", "langevin"), default="nve", help="langevin: the thermostatted step against the NVE step")
     ap.add_argument("--fire", action="store_true", help="the FIRE iteration against its eager loop")
+    ap.add_argument("--constraints", action="store_true", help="the step with bonds to hydrogen constrained against the plain step")
     ap.add_argument("--kT", type=float, default=0.25, help="thermostat temperature in the model's energy units (v0 has variance 0.25)")
     ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
@@ -289,16 +364,27 @@ def main():
         if args.fire:
             make_fire(ff).run(args.trace_steps, check_every=args.trace_steps)
         else:
-            mass = torch.ones(x0.shape[0])
-            md = Langevin(ff, mass, args.dt, args.kT, args.gamma) if args.integrator == "langevin" else VelocityVerlet(ff, mass, args.dt)
+            mass, kw = torch.ones(x0.shape[0]), {}
+            if args.constraints:
+                con, mass = bonds_to_hydrogen(batch, x0, ff)
+                kw = {"constraints": con}
+            md = Langevin(ff, mass, args.dt, args.kT, args.gamma, **kw) if args.integrator == "langevin" else \
+                VelocityVerlet(ff, mass, args.dt, **kw)
             md.v.copy_(v0)
+            if args.constraints:
+                md.project()
             md.run(args.trace_steps, check_every=args.trace_steps)
         torch.cuda.synchronize()
-        print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0], "integrator": args.integrator, "fire": args.fire}))
+        print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0], "integrator": args.integrator, "fire": args.fire,
+                          "constraints": args.constraints}))
         return
     if args.fire:
         workload = "FIRE relaxation with per-graph state on config_energy_force (as shipped), synth_qm9: replayed iteration vs the eager loop"
         results = [bench_fire(n, args.steps, args.warmup, args.reps, dev) for n in args.molecules]
+    elif args.constraints:
+        workload = ("velocity-Verlet step with the bonds to hydrogen constrained (SHAKE / RATTLE) vs the plain step, both replayed, on "
+                    "config_energy_force (as shipped), synth_qm9, masses 1 (H) and 12")
+        results = [bench_constraints(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
     elif args.integrator == "langevin":
         workload = "Langevin step vs velocity-Verlet step, both replayed, on config_energy_force (as shipped), synth_qm9, unit masses"
         results = [bench_langevin(n, args.steps, args.warmup, args.reps, args.dt, args.kT, args.gamma, dev) for n in args.molecules]
