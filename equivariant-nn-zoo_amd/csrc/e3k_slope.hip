@@ -333,6 +333,7 @@ int check_shape(int32_t n_nets, int32_t n_hidden, int64_t R, int32_t k0, int32_t
                 float r_min) {
   if (n_nets <= 0 || n_nets > 16 || n_hidden < 1 || n_hidden > e3k::SL_MAXL || R <= 0) return E3K_ERR_INVALID;
   if ((H != 32 && H != 64) || k0 <= 0 || k0 > H || (act != 1 && act != 2 && act != 4 && act != 0)) return E3K_ERR_UNSUPPORTED;
+  if (R >= 0x7fffffffLL) return E3K_ERR_UNSUPPORTED;      // (the kernels index the knot rows with int, as e3k_edge_records its edges)
   if (cutoff_kind < 0 || cutoff_kind > 1 || !(r_max > r_min)) return E3K_ERR_INVALID;
   return E3K_OK;
 }

@@ -973,7 +973,15 @@ int e3k_radial_stack_bwd(const e3k_layer* const* layers, const e3k_radial_stack_
  * the backward) -> D_l = H'_l W_last_l (the layers' LAST_FWD GEMM sets). */
 int e3k_radial_slope_fwd(const e3k_layer* const* layers, const e3k_layer_radial* rads, int32_t n, const e3k_slope_ctx* slope,
                          float* const* hp, float* const* D, void* stream);
-/* pieces (also exported for tests); w_hidden[i * 4 + l]: layer l of net i */
+/* pieces (also exported for tests).  n_nets <= 16 chains of n_hidden <= 4 layers on the same R knots; w_hidden[i * 4 + l]: layer l of
+ * net i, fp32 [k_l, H] with k_0 = k0, k_l = H; H in {32, 64}, 0 < k0 <= H; act in {0 identity, 1 ssp, 2 silu, 4 tanh} (the others have
+ * no second derivative here: E3K_ERR_UNSUPPORTED); cutoff_kind 0 polynomial (p), 1 symmetric (x^2 - 1)^2; r_max > r_min;
+ * 0 < R < 2^31 - 1 (beyond: E3K_ERR_UNSUPPORTED).  With one_over_r set every knot must be > 0: r = 0 gives 0 * inf = NaN in its row.
+ *   forward : hp[i] [R, H] WRITTEN (fp32 rounding of the float64 tangent); a row with r >= r_max is exactly zero.
+ *   backward: g_hidden[i * 4 + l] (fp32 [k_l, H]) and g_bessel (fp32 [k0], summed over the nets) are ADDED to -- the caller zeroes or
+ *             accumulates; NULL entries of g_hidden and a NULL g_bessel are skipped (the array g_hidden itself must not be NULL).
+ *             acc: e3k_slope_tangent_bwd_scratch(...) doubles, 8-byte aligned, written before they are read: it may be handed
+ *             over uninitialised, and its contents afterwards are not part of the interface. */
 int e3k_slope_tangent_fwd(const float* const* w_hidden, int32_t n_nets, int32_t n_hidden, const float* alphas, const float* knots,
                           int64_t R, const float* bessel_w, int32_t k0, int32_t H, float r_max, float r_min, float p,
                           int32_t one_over_r, int32_t cutoff_kind, int32_t act, float cst, float* const* hp, void* stream);

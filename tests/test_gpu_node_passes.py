@@ -42,16 +42,33 @@ def _sig(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
+def _ssp(x):
+    return np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x))) - np.log(2.0)
+
+
 def _act(a, x):
-    return {2: x * _sig(x), 3: np.tanh(x) * np.abs(x), 4: np.tanh(x)}[a]
+    """activation ids of csrc/e3k_act.h: 0 identity, 1 ssp, 2 silu, 3 tanhlu, 4 tanh, 5 abs (only the one asked for is evaluated)"""
+    return {0: lambda: x + 0.0, 1: lambda: _ssp(x), 2: lambda: x * _sig(x), 3: lambda: np.tanh(x) * np.abs(x), 4: lambda: np.tanh(x),
+            5: lambda: np.abs(x)}[a]()
 
 
 def _dact(a, x):
-    s, th = _sig(x), np.tanh(x)
-    return {2: s * (1.0 + x * (1.0 - s)), 3: (1.0 - th * th) * np.abs(x) + th * np.sign(x), 4: 1.0 - th * th}[a]
+    if a in (0, 1, 5):
+        return {0: lambda: np.ones_like(x), 1: lambda: _sig(x), 5: lambda: np.sign(x)}[a]()
+    if a == 2:
+        s = _sig(x)
+        return s * (1.0 + x * (1.0 - s))
+    th = np.tanh(x)
+    return (1.0 - th * th) * np.abs(x) + th * np.sign(x) if a == 3 else 1.0 - th * th
 
 
 def _err_act(a, x):
+    """identity and abs are exact; ssp = max(x, 0) + log(1 + exp(-|x|)) - ln 2 cancels at 0: ABSOLUTE (2 |x| + 8) u (the derivation is
+    in the docstring of tests/test_gpu_node_matrix.py); its derivative is the sigmoid, inside D(x) below like the others"""
+    if a in (0, 5):
+        return np.zeros_like(x)
+    if a == 1:
+        return (2.0 * np.abs(x) + 8.0) * U
     return ((1.5 * np.abs(x) + 6.0) * U + 2.0 * U) * np.abs(_act(a, x))
 
 
