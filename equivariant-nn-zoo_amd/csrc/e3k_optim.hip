@@ -41,11 +41,14 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   if (threadIdx.x == 0) atomicAdd(state + 5, (part[0] + part[1]) + (part[2] + part[3]));
 }
 
+// veto (every tick; NULL: none): a device cell the captured step's neighbour-list build raises (run/score_step.py).  While it is not
+// zero the step does not happen: the skip flag is set whatever the gradient norm says, neither counter advances, and the effective
+// EMA decay of the launch is 1, so that adam_ema_kernel's ev -= (1 - d)(ev - p) is the identity.
 __global__ void tick_kernel(float* __restrict__ state, float beta1, float beta2, float max_norm, int have_norm,
-                            int skip_nonfinite) {
+                            int skip_nonfinite, const int64_t* __restrict__ veto) {
   const float sumsq = state[5];
   const bool bad = have_norm && !isfinite(sumsq);
-  const bool skip = skip_nonfinite && bad;
+  const bool skip = (skip_nonfinite && bad) || (veto && veto[0] != 0);
   state[6] = skip ? 1.f : 0.f;
   state[5] = 0.f;
   float t = state[0];
@@ -66,9 +69,11 @@ __global__ void tick_kernel(float* __restrict__ state, float beta1, float beta2,
 // both ticks in ONE launch (round 6: a step without a gradient norm).  Folding them into the update kernel itself was built and
 // measured: every workgroup has to have read the old state before anybody writes the new one, i.e. a ticket -- 2 048 atomics on
 // one address took the update from 24 to 43-46 us (profiles/r06_trace_graph_energy.txt of that build); one tiny launch it is.
-__global__ void tick_both_kernel(float* __restrict__ state, float beta1, float beta2, float ema_decay, int use_num_updates) {
-  const float t = state[0] + 1.f;
-  state[6] = 0.f;
+__global__ void tick_both_kernel(float* __restrict__ state, float beta1, float beta2, float ema_decay, int use_num_updates,
+                                 const int64_t* __restrict__ veto) {
+  const bool vetoed = veto && veto[0] != 0;
+  const float t = state[0] + (vetoed ? 0.f : 1.f);
+  state[6] = vetoed ? 1.f : 0.f;
   state[5] = 0.f;
   state[0] = t;
   state[1] = (float)(1.0 - pow((double)beta1, (double)fmaxf(t, 1.f)));
@@ -76,26 +81,28 @@ __global__ void tick_both_kernel(float* __restrict__ state, float beta1, float b
   state[7] = 0.f;
   state[4] = 1.f;
   float* ema_state = state + 8;
-  const float k = ema_state[0] + 1.f;
+  const float k = ema_state[0] + (vetoed ? 0.f : 1.f);
   ema_state[0] = k;
   float d = ema_decay;
   if (use_num_updates) {
     const float alt = (1.f + k) / (10.f + k);
     d = alt < d ? alt : d;
   }
-  ema_state[1] = d;
+  ema_state[1] = vetoed ? 1.f : d;
 }
 
-__global__ void ema_tick_kernel(float* __restrict__ ema_state, float ema_decay, int use_num_updates) {
+__global__ void ema_tick_kernel(float* __restrict__ ema_state, float ema_decay, int use_num_updates,
+                                const int64_t* __restrict__ veto) {
   // ema_state[0] number of updates so far, [1] effective decay of THIS update
-  const float k = ema_state[0] + 1.f;
+  const bool vetoed = veto && veto[0] != 0;
+  const float k = ema_state[0] + (vetoed ? 0.f : 1.f);
   ema_state[0] = k;
   float d = ema_decay;
   if (use_num_updates) {
     const float alt = (1.f + k) / (10.f + k);
     d = alt < d ? alt : d;
   }
-  ema_state[1] = d;
+  ema_state[1] = vetoed ? 1.f : d;
 }
 
 template <bool EMA>
@@ -191,10 +198,9 @@ extern "C" int e3k_sq_error(const float* pred, const float* target, const float*
   return E3K_OK;
 }
 
-extern "C" int e3k_adam_ema_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
-                                 int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                 float ema_decay, int32_t ema_use_num_updates, float max_grad_norm,
-                                 int32_t skip_nonfinite, float* state, void* stream) {
+static int adam_ema_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, float ema_decay, int32_t ema_use_num_updates,
+                         float max_grad_norm, int32_t skip_nonfinite, float* state, const int64_t* veto, void* stream) {
   if (n < 0 || !(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
     return E3K_ERR_INVALID;
   if (ema && !(ema_decay >= 0.f && ema_decay <= 1.f)) return E3K_ERR_INVALID;
@@ -213,13 +219,14 @@ extern "C" int e3k_adam_ema_step(float* param, const float* grad, float* exp_avg
     E3K_CHECK_LAUNCH();
   }
   if (ema && !have_norm) {      // (the same values tick_kernel + ema_tick_kernel leave behind, one launch)
-    hipLaunchKernelGGL(e3k::tick_both_kernel, dim3(1), dim3(1), 0, st, state, beta1, beta2, ema_decay, ema_use_num_updates);
+    hipLaunchKernelGGL(e3k::tick_both_kernel, dim3(1), dim3(1), 0, st, state, beta1, beta2, ema_decay, ema_use_num_updates, veto);
     E3K_CHECK_LAUNCH();
   } else {
-    hipLaunchKernelGGL(e3k::tick_kernel, dim3(1), dim3(1), 0, st, state, beta1, beta2, max_grad_norm, have_norm, skip_nonfinite);
+    hipLaunchKernelGGL(e3k::tick_kernel, dim3(1), dim3(1), 0, st, state, beta1, beta2, max_grad_norm, have_norm, skip_nonfinite,
+                       veto);
     E3K_CHECK_LAUNCH();
     if (ema) {
-      hipLaunchKernelGGL(e3k::ema_tick_kernel, dim3(1), dim3(1), 0, st, state + 8, ema_decay, ema_use_num_updates);
+      hipLaunchKernelGGL(e3k::ema_tick_kernel, dim3(1), dim3(1), 0, st, state + 8, ema_decay, ema_use_num_updates, veto);
       E3K_CHECK_LAUNCH();
     }
   }
@@ -233,4 +240,21 @@ extern "C" int e3k_adam_ema_step(float* param, const float* grad, float* exp_avg
   }
   E3K_CHECK_LAUNCH();
   return E3K_OK;
+}
+
+extern "C" int e3k_adam_ema_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                                 int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                 float ema_decay, int32_t ema_use_num_updates, float max_grad_norm,
+                                 int32_t skip_nonfinite, float* state, void* stream) {
+  return adam_ema_step(param, grad, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, weight_decay, ema_decay, ema_use_num_updates,
+                       max_grad_norm, skip_nonfinite, state, nullptr, stream);
+}
+
+extern "C" int e3k_adam_ema_step_vetoed(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                                        int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                        float ema_decay, int32_t ema_use_num_updates, float max_grad_norm,
+                                        int32_t skip_nonfinite, float* state, const int64_t* veto, void* stream) {
+  if (!veto) return E3K_ERR_INVALID;
+  return adam_ema_step(param, grad, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, weight_decay, ema_decay, ema_use_num_updates,
+                       max_grad_norm, skip_nonfinite, state, veto, stream);
 }

@@ -278,6 +278,10 @@ SIGNATURES = {
     "e3k_layernorm_bwd": (C.c_int, [_P, _P, _P, _I64, _I32, C.POINTER(Block), _I32, _P, _P, _P, _P]),
     "e3k_layernorm_bwd2": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, C.POINTER(Block), _I32, _P, _P, _P, _P, _P]),
     "e3k_adam_ema_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I32, _F, _I32, _P, _P]),
+    "e3k_adam_ema_step_vetoed": (C.c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I32, _F, _I32, _P, _P, _P]),
+    "e3k_vpsde_perturb": (C.c_int, [_P, _P, _I64, _I32, _I32, _F, _F, _F, _F, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "e3k_denoise_loss": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
+    "e3k_score_step_record": (C.c_int, [_P, _P, _P, _P, _I32, _P]),
     "e3k_segment_sum": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 

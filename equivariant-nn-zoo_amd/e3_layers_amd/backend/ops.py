@@ -1943,6 +1943,61 @@ def sq_error(pred, target, weight=None, scale: float = 1.0):
     return SqErrorFn.apply(pred, target, weight, float(scale))
 
 
+def vpsde_perturb(x0, node_seg, n_graphs: int, beta_0: float, beta_1: float, eps: float, T: float, seed: int, draw, word0: int = 0):
+    """The VP-SDE perturbation with counter-based draws (``csrc/e3k_score.hip``): ``(t [G + 1], x_t, z [N, D], std [N])`` for
+    ``x0`` [N, D] and ``node_seg`` [N] int64; rows whose segment is not one of the ``n_graphs`` real graphs (the ghost graph of a
+    padded batch) keep ``x0``, with ``z = 0``, ``std = 1`` and ``t = 0.5``.  ``draw``: a DEVICE int64 cell (its first element is the
+    draw index; read, not written: a captured step hands in its own step counter).  One launch, no host synchronisation."""
+    L.require_cuda(x0, node_seg, draw)
+    x0 = L.f32c(x0.detach())
+    if x0.dim() != 2 or node_seg.dtype != torch.int64 or node_seg.numel() != x0.shape[0] or not node_seg.is_contiguous():
+        raise ValueError("vpsde_perturb needs x0 [N, D] and a contiguous int64 node_seg [N]")
+    if draw.dtype != torch.int64 or draw.numel() < 1 or not draw.is_contiguous():
+        raise ValueError("vpsde_perturb: draw must be a contiguous int64 device tensor (its first element is the draw index)")
+    n, d = x0.shape
+    t = torch.empty(n_graphs + 1, device=x0.device, dtype=torch.float32)
+    x_t, z = torch.empty_like(x0), torch.empty_like(x0)
+    std = torch.empty(n, device=x0.device, dtype=torch.float32)
+    L.check(L.load().e3k_vpsde_perturb(L.ptr(x0), L.ptr(node_seg), n, d, int(n_graphs), float(beta_0), float(beta_1), float(eps), float(T),
+                                       int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, L.ptr(draw), int(word0), L.ptr(t),
+                                       L.ptr(x_t), L.ptr(z), L.ptr(std), L.stream_ptr()), "e3k_vpsde_perturb")
+    return t, x_t, z, std
+
+
+class DenoiseLossFn(torch.autograd.Function):
+    """sum_i w_i mean_c (-raw - std_i x_t + z)^2 (w = 1 / N without weights) -- the denoising loss of a score head that emits
+    ``raw`` with score = -raw / std - x_t, and its gradient with respect to ``raw``, in one launch."""
+
+    @staticmethod
+    def forward(ctx, raw, x_t, z, std, weight):
+        L.require_cuda(raw, x_t, z, std, weight)
+        r, x, zz = L.f32c(raw), L.f32c(x_t), L.f32c(z)
+        s = L.f32c(std).reshape(-1)
+        w = None if weight is None else L.f32c(weight).reshape(-1)
+        if r.dim() != 2 or x.shape != r.shape or zz.shape != r.shape or s.numel() != r.shape[0] or (w is not None and w.numel() != r.shape[0]):
+            raise ValueError("denoise_loss needs raw, x_t, z [N, D], std [N] and weight [N] or None")
+        loss = torch.empty((), device=r.device, dtype=torch.float32)
+        grad = torch.empty_like(r)
+        L.check(L.load().e3k_denoise_loss(L.ptr(r), L.ptr(x), L.ptr(zz), L.ptr(s), L.ptr(w), r.shape[0], r.shape[1], L.ptr(loss),
+                                          L.ptr(grad), L.stream_ptr()), "e3k_denoise_loss")
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        unit = _UNIT.get(g.device.index)
+        if unit is not None and g.data_ptr() == unit.data_ptr():
+            return grad, None, None, None, None
+        return grad * g, None, None, None, None
+
+
+def denoise_loss(raw, x_t, z, std, w=None):
+    """``(w * ((-raw - std * x_t + z) ** 2).mean(-1)).sum()`` (``w`` [N] per node; None: the mean over the nodes) -- first order only,
+    differentiated with respect to ``raw``."""
+    return DenoiseLossFn.apply(raw, x_t, z, std, w)
+
+
 def segment_sum(x, ptr, seg_index, mean=False):
     return SegmentSumFn.apply(_c(x), ptr, seg_index, bool(mean))
 

@@ -115,19 +115,28 @@ class FusedAdamEMA:
         self.grads.zero()
 
     @torch.no_grad()
-    def step(self) -> None:
-        """(all-reduce of the flat gradient is the caller's: ``self.grads.all_reduce_mean()``)"""
+    def step(self, veto: Optional[torch.Tensor] = None) -> None:
+        """(all-reduce of the flat gradient is the caller's: ``self.grads.all_reduce_mean()``)
+
+        ``veto``: a device int64 cell (its first element is read by the step's tick kernels).  While it is not zero the step does
+        not happen -- parameters, moments and the EMA shadow keep their bits and neither counter advances
+        (``e3k_adam_ema_step_vetoed``): a captured step whose neighbour list overflowed (``run/score_step.py``)."""
         from ..backend import ops
 
         from ..backend.graph import poll_indices
 
         poll_indices()               # device-side index checks of the batches so far (edge endpoints, row keys): no sync
         ops.join_side_streams()      # weight gradients written by side-stream kernels (gradient sink) are complete
-        L.check(L.load().e3k_adam_ema_step(
-            L.ptr(self.flat), L.ptr(self.grads.buffer), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.ema),
-            self.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay,
-            int(self.ema_use_num_updates), self.max_grad_norm, int(self.skip_nonfinite), L.ptr(self.state),
-            L.stream_ptr()), "e3k_adam_ema_step")
+        args = (L.ptr(self.flat), L.ptr(self.grads.buffer), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.ema),
+                self.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay,
+                int(self.ema_use_num_updates), self.max_grad_norm, int(self.skip_nonfinite), L.ptr(self.state))
+        if veto is None:
+            L.check(L.load().e3k_adam_ema_step(*args, L.stream_ptr()), "e3k_adam_ema_step")
+        else:
+            L.require_cuda(veto)
+            if veto.dtype != torch.int64 or veto.numel() < 1 or not veto.is_contiguous():
+                raise ValueError("veto must be a contiguous int64 device tensor (its first element is the cell)")
+            L.check(L.load().e3k_adam_ema_step_vetoed(*args, L.ptr(veto), L.stream_ptr()), "e3k_adam_ema_step_vetoed")
         if self.max_steps_ahead > 0 and not torch.cuda.is_current_stream_capturing():
             done = torch.cuda.Event()
             done.record()
@@ -145,6 +154,10 @@ class FusedAdamEMA:
     @property
     def steps_taken(self) -> int:
         return int(self.state[0].item())
+
+    @property
+    def ema_updates(self) -> int:
+        return int(self.state[8].item())
 
     @property
     def last_grad_norm(self) -> float:

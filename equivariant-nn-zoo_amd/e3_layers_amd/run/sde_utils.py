@@ -125,6 +125,70 @@ def sde_perturb(sde: VPSDE, batch, eps: float = 1e-5, generator=None):
     return sde.marginal(pert, generator=generator)
 
 
+def sde_perturb_counter(sde: VPSDE, batch, seed: int, draw, eps: float = 1e-5, dtype=None):
+    """``sde_perturb`` with counter-based draws: t and z are functions of (``seed``, draw index, graph / node, component), so the same
+    ``(seed, draw)`` gives the same noised batch wherever and whenever it is asked for -- a replayed training step whose neighbour
+    list overflowed is redone on exactly the batch it was vetoed on (``run/score_step.py``).  -> (pert, misc) as ``sde_perturb``.
+
+    Per real graph g: ``u = (pair_hash(seed, draw, 0xFFFFFFFF, g) >> 8) 2^-24``, ``t = eps + (T - eps) u``; per node i and component c
+    (counted over the diffusion keys in order): ``z = normal_draw(seed, draw, i, c)``; ``x_t = exp(lm) x_0 + sqrt(-expm1(2 lm)) z``.
+    The rows of a padded batch's ghost graph (``_graph_weight`` present: the last graph) keep their geometry: ``z = 0``, ``std = 1``,
+    ``t = 0.5``.
+
+    ``draw``: an int, or an int64 tensor (on device tensors a DEVICE cell, read by the kernel without a host synchronisation).
+    Device tensors: one ``e3k_vpsde_perturb`` launch per key (fp32).  CPU tensors: the torch restatement of the same hashes and
+    formulas in ``dtype`` (default: the batch's) -- its float64 form is what the kernel test holds the kernel to."""
+    from ..data.compute_edge import normal_draw, pair_hash
+
+    keys = list(sde.irreps)
+    x_first = batch[keys[0]]
+    dev = x_first.device
+    seg = batch.nodeSegment()
+    n_all = len(batch)
+    n_real = n_all - 1 if "_graph_weight" in batch else n_all
+    # (device: only whole keys are replaced, so a new container over the same tensors does; host: the clone sde_perturb makes)
+    pert = batch.view() if dev.type == "cuda" else batch.clone()
+    pert.attrs["t"] = ("graph", "1x0e")
+    zs, word0, std = {}, 0, None
+    if dev.type == "cuda":
+        from ..backend import ops
+
+        cell = draw if torch.is_tensor(draw) else torch.tensor([int(draw)], dtype=torch.int64, device=dev)
+        for key in keys:
+            t, x_t, z, s = ops.vpsde_perturb(batch[key], seg, n_real, sde.beta_0, sde.beta_1, eps, sde.T, seed, cell, word0)
+            pert[key], zs[key] = x_t, z
+            word0 += int(batch[key].shape[1])
+            if std is None:
+                pert["t"], std = t[:n_all], s.reshape(-1, 1)
+        return pert, {"zs": zs, "std": std}
+    dtype = x_first.dtype if dtype is None else dtype
+    f32 = torch.float32
+    g = torch.arange(n_all, dtype=torch.int64)
+    u = (pair_hash(seed, draw, 0xFFFFFFFF, g) >> 8).to(dtype) * 2.0 ** -24
+    # the parameters as the floats the kernel receives: eps, T - eps, q = -(beta_1 - beta_0) / 4, h = -beta_0 / 2
+    eps32, t_end = torch.tensor(eps, dtype=f32), torch.tensor(sde.T, dtype=f32)
+    b0, b1 = torch.tensor(sde.beta_0, dtype=f32), torch.tensor(sde.beta_1, dtype=f32)
+    span, q, h = (t_end - eps32).to(dtype), (-0.25 * (b1 - b0)).to(dtype), (-0.5 * b0).to(dtype)
+    real = g < n_real
+    t = torch.where(real, eps32.to(dtype) + span * u, torch.full_like(u, 0.5))
+    lm = t * (q * t + h)
+    a_g, s_g = torch.exp(lm), torch.sqrt(-torch.expm1(2.0 * lm))
+    node_real = real[seg].reshape(-1, 1)
+    a = torch.where(node_real, a_g[seg].reshape(-1, 1), torch.ones((), dtype=dtype))
+    s = torch.where(node_real, s_g[seg].reshape(-1, 1), torch.ones((), dtype=dtype))
+    node = torch.arange(seg.shape[0], dtype=torch.int64).reshape(-1, 1)
+    for key in keys:
+        x = batch[key].to(dtype)
+        d = int(x.shape[1])
+        z = normal_draw(seed, draw, node, word0 + torch.arange(d, dtype=torch.int64).reshape(1, -1), dtype)
+        z = torch.where(node_real, z, torch.zeros((), dtype=dtype))
+        pert.data[key] = torch.where(node_real, a * x + s * z, x)
+        zs[key] = z
+        word0 += d
+    pert.data["t"] = t.reshape(-1, 1)
+    return pert, {"zs": zs, "std": s}
+
+
 def sde_loss_of(sde: VPSDE, model, pert, misc, train: bool = True, node_weight=None) -> Tuple[torch.Tensor, dict]:
     """Second half of ``sde_loss``: the score network on the noised batch and the denoising loss."""
     scores = get_score_fn(sde, model, train)(pert)

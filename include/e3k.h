@@ -813,6 +813,44 @@ int e3k_adam_ema_step(float* param, const float* grad, float* exp_avg, float* ex
                       float lr, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
                       int32_t ema_use_num_updates, float max_grad_norm, int32_t skip_nonfinite, float* state,
                       void* stream);
+/* The same step under a device-side veto (run/score_step.py: the capped neighbour-list build of a replayed step raises the cell
+ * when the list did not fit, after the optimizer launch has long been recorded).  veto: one DEVICE int64, read by the tick(s).
+ * While veto[0] != 0 the step does not happen: param, the moments and the EMA shadow keep their bits, state[0] (steps taken) and
+ * state[8] (EMA updates) do not advance, state[5] is reset, state[6] = 1, and the effective EMA decay of the launch (state[9]) is
+ * 1.  veto[0] == 0: the step above, bit for bit.  veto NULL: invalid. */
+int e3k_adam_ema_step_vetoed(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                             float lr, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                             int32_t ema_use_num_updates, float max_grad_norm, int32_t skip_nonfinite, float* state,
+                             const int64_t* veto, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The diffusion score nets' training step around the model (csrc/e3k_score.hip), for a step that is captured once and replayed
+ * on a capped neighbour list (run/score_step.py).  Replaces t ~ U(eps, T) and VPSDE.marginal (e3_layers/run/sde_utils.py:54-66,
+ * :143-160) and the loss of get_sde_loss_fn (:161-171 with the score of :176-187), whose draws come from a torch generator: here
+ * every draw is a function of (seed, draw index, graph or node, word), the pair hash and the normal xi of e3k_md_kick_langevin
+ * above, so a step that has to be redone is redone on exactly the same noised batch.
+ *
+ * e3k_vpsde_perturb: one launch, one thread per node component.  x0, x_t, z [N, D], std [N], t [G + 1], node_seg [N] int64;
+ *   draw: one DEVICE int64 read by every thread and not written (its low 32 bits are the draw index).  Per graph g < G:
+ *     u = (hash(seed_lo, seed_hi, draw, 0xFFFFFFFF, g) >> 8) 2^-24;   t_g = fma(T - eps, u, eps);
+ *     lm = t (q t + h),  q = -(beta_1 - beta_0) / 4,  h = -beta_0 / 2  (fp32, q t + h one FMA);   a = expf(lm);
+ *     s = sqrtf(-expm1f(2 lm))      (1 - expf(2 lm) would lose most of its bits at small t)
+ *   per node i of graph g and component c:  z = xi(seed, draw, i, word0 + c);  x_t = fma(a, x0, s z);  std_i = s.
+ *   Rows with node_seg outside [0, G) (the ghost graph of a padded batch): x_t = x0, z = 0, std = 1; t[G] = 0.5.
+ *   Several diffused keys: one call per key with word0 = the sum of the earlier keys' D; every call files the same t.
+ *   0 <= eps <= T, 0 <= beta_0 <= beta_1, 1 <= D <= 1024, or invalid.
+ * e3k_denoise_loss: err = -raw - std_i x_t + z (= score std + z with score = -raw / std - x_t);
+ *   loss[0] = sum_i w_i (1 / D) sum_c err^2;   grad [N, D] = -2 w_i / D err (the gradient with respect to raw), the same launch.
+ *   weight [N] (NULL: 1 / N each).  One workgroup, fixed summation order.
+ * e3k_score_step_record: one thread.  cells [2] DEVICE int64 = (step, first_bad):  ring[step mod W] = loss[0];  if overflow[0] != 0
+ *   and first_bad < 0: first_bad = step;  step += 1.  overflow: the capped builder's overflow counter (state[1] of e3k_nlist_fill).
+ * ------------------------------------------------------------------------------------------ */
+int e3k_vpsde_perturb(const float* x0, const int64_t* node_seg, int64_t N, int32_t D, int32_t G, float beta_0, float beta_1,
+                      float eps, float T, uint32_t seed_lo, uint32_t seed_hi, const int64_t* draw, uint32_t word0, float* t,
+                      float* x_t, float* z, float* std, void* stream);
+int e3k_denoise_loss(const float* raw, const float* x_t, const float* z, const float* std, const float* weight, int64_t N,
+                     int32_t D, float* loss, float* grad, void* stream);
+int e3k_score_step_record(const float* loss, const int64_t* overflow, int64_t* cells, float* ring, int32_t W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A convolution layer as ONE call (csrc/e3k_layer.hip): FactorizedConvolution + Gate
