@@ -197,14 +197,39 @@ def pad_batch(batch, n_cap: int, e_cap: int, key: str = "pos"):
 GHOST_DEGREE = 16      # ghost edges per ghost node the capacities below aim for (the edge kernels walk a node's edges in one wave)
 
 
+def ghost_node_capacity(n: int, ghost_edges: int, multiple: int = 32) -> int:
+    """The node capacity for ``n`` real nodes and a ghost graph of ``ghost_edges`` edges: at least two ghost nodes, about
+    ``GHOST_DEGREE`` edges per ghost node, rounded up to ``multiple``."""
+    return -(-(n + max(2, -(-ghost_edges // GHOST_DEGREE))) // multiple) * multiple
+
+
 def bucket_capacity(sizes, node_multiple: int = 32, edge_multiple: int = 1024):
     """(n_cap, e_cap) for batches of ``sizes`` = [(n_nodes, n_edges), ...]: every batch fits with at least two ghost nodes, and
     the ghost graph that absorbs a batch's missing edges has about ``GHOST_DEGREE`` edges per node -- a ghost node with
     hundreds of edges is a wave that walks hundreds of edges on its own while the chip waits (measured: 40 ms instead of
     3.5 ms per step at 128 molecules with 21 ghost nodes for 3 300 ghost edges)."""
     e_cap = -(-max(e for _, e in sizes) // edge_multiple) * edge_multiple
-    n_cap = max(n + max(2, -(-(e_cap - e) // GHOST_DEGREE)) for n, e in sizes)
-    return -(-n_cap // node_multiple) * node_multiple, e_cap
+    return max(ghost_node_capacity(n, e_cap - e, node_multiple) for n, e in sizes), e_cap
+
+
+def copy_into(static, padded, keys, hint: str = "") -> None:
+    """The fields ``keys`` of ``padded`` into the captured tensors ``static``: one multi-tensor launch per dtype instead of one copy
+    per field (eleven fields: 53 us in front of every replay); a field on another device, of another dtype or not contiguous is
+    copied on its own.  A shape that is not the bucket's is refused (``hint``: what the caller's message adds)."""
+    by_dtype = {}
+    for k in keys:
+        dst, src = static[k], padded[k]
+        if dst.shape != src.shape:
+            raise ValueError(f"{k}: {tuple(src.shape)} does not fit the captured {tuple(dst.shape)} (another bucket?"
+                             f"{' ' + hint if hint else ''})")
+        if src.device == dst.device and src.dtype == dst.dtype and src.is_contiguous() and dst.is_contiguous():
+            pair = by_dtype.setdefault(dst.dtype, ([], []))
+            pair[0].append(dst)
+            pair[1].append(src)
+        else:
+            dst.copy_(src, non_blocking=True)
+    for dsts, srcs in by_dtype.values():
+        torch._foreach_copy_(dsts, srcs)
 
 
 class BucketedStep:
@@ -235,19 +260,7 @@ class BucketedStep:
         return self.captured.recaptures
 
     def __call__(self, padded):
-        by_dtype = {}
-        for k in self.keys:
-            dst, src = self.static[k], padded[k]
-            if dst.shape != src.shape:
-                raise ValueError(f"{k}: {tuple(src.shape)} does not fit the captured {tuple(dst.shape)} (another bucket?)")
-            if src.device == dst.device and src.dtype == dst.dtype and src.is_contiguous() and dst.is_contiguous():
-                pair = by_dtype.setdefault(dst.dtype, ([], []))
-                pair[0].append(dst)
-                pair[1].append(src)
-            else:
-                dst.copy_(src, non_blocking=True)
-        for dsts, srcs in by_dtype.values():      # one multi-tensor launch per dtype instead of one copy per field (eleven fields:
-            torch._foreach_copy_(dsts, srcs)      # 53 us in front of every replay)
+        copy_into(self.static, padded, self.keys)
         out = self.captured()
         if self.tail is not None:
             self.tail()
@@ -308,23 +321,10 @@ class PipelinedBucketedStep:
 
     def __init__(self, prepare: Callable[[Any], Any], fn: Callable[[Any], Any], example, warmup: int = 3, generators=(),
                  tail: Callable[[], Any] = None):
-        from ..backend.graph import capture_flag
-
-        self.tail = tail
-        self.prepare = prepare
-        self.dev = example["pos"].device
-        self.prep_stream = stream_beside(torch.cuda.current_stream(self.dev))
+        self._setup_schedule(prepare, tail, example["pos"].device)
         self.static, self.prep_graphs, self.steps = [], [], []
-        self.ev_prep = [torch.cuda.Event() for _ in range(2)]
-        self.ev_step = [torch.cuda.Event() for _ in range(2)]
-        self._holds = [None, None]          # which padded batch (by identity) buffer b has been prepared for
-        self._step_ran = [False, False]
         self.keys = None
-        capture_flag(self.dev)              # (the persistent index-check flag captured builds fold into: before any recording)
-        warm = example.clone()              # one eager preparation first: nothing a capture records may be a kernel's first launch
-        prepare(warm)                       # in the process (lazy initialisation inside a capture is not something to rely on)
-        torch.cuda.synchronize(self.dev)
-        del warm
+        self._prepare_eagerly(example)
         for b in range(2):
             static = example.clone()        # (fresh tensors: they carry no memo yet, backend/memo.py)
             if self.keys is None:
@@ -342,6 +342,25 @@ class PipelinedBucketedStep:
             # like BucketedStep's do
             self.steps.append(CapturedStep((lambda s=static: fn(s.view())), warmup=warmup if b == 0 else 1, generators=generators))
         self.captured = self.steps[0]       # (bench.py / tests: .graph, .recaptures of the first buffer's step)
+
+    def _setup_schedule(self, prepare, tail, dev) -> None:
+        """The state of the two-buffer schedule (``__call__``), before any recording."""
+        from ..backend.graph import capture_flag
+
+        self.tail, self.prepare, self.dev = tail, prepare, dev
+        self.prep_stream = stream_beside(torch.cuda.current_stream(dev))
+        self.ev_prep = [torch.cuda.Event() for _ in range(2)]
+        self.ev_step = [torch.cuda.Event() for _ in range(2)]
+        self._holds = [None, None]          # which padded batch (by identity) buffer b has been prepared for
+        self._step_ran = [False, False]
+        capture_flag(dev)                   # (the persistent index-check flag captured builds fold into: before any recording)
+
+    def _prepare_eagerly(self, batch) -> None:
+        """One eager preparation of a copy of ``batch`` before a recording: nothing a capture records may be a kernel's first
+        launch in the process (lazy initialisation inside a capture is not something to rely on)."""
+        warm = batch.clone()
+        self.prepare(warm)
+        torch.cuda.synchronize(self.dev)
 
     @property
     def recaptures(self) -> int:
@@ -361,10 +380,7 @@ class PipelinedBucketedStep:
         static.data.update(fresh)           # gone -- a layer that finds its output present keeps it)
         static._e3k_done = None
         self.prep_graphs[b] = None          # (its pool holds the old bins)
-        warm = static.clone()
-        self.prepare(warm)                  # (eagerly first: see __init__)
-        torch.cuda.synchronize(self.dev)
-        del warm
+        self._prepare_eagerly(static)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.prepare(static)
@@ -374,20 +390,7 @@ class PipelinedBucketedStep:
 
     def _enqueue_prepare(self, b: int, padded) -> None:
         """On the CURRENT stream: the padded batch into buffer b's static tensors, then its preparation graph."""
-        static = self.static[b]
-        by_dtype = {}
-        for k in self.keys:
-            dst, src = static[k], padded[k]
-            if dst.shape != src.shape:
-                raise ValueError(f"{k}: {tuple(src.shape)} does not fit the captured {tuple(dst.shape)} (another bucket?)")
-            if src.device == dst.device and src.dtype == dst.dtype and src.is_contiguous() and dst.is_contiguous():
-                pair = by_dtype.setdefault(dst.dtype, ([], []))
-                pair[0].append(dst)
-                pair[1].append(src)
-            else:
-                dst.copy_(src, non_blocking=True)
-        for dsts, srcs in by_dtype.values():
-            torch._foreach_copy_(dsts, srcs)
+        copy_into(self.static[b], padded, self.keys)
         self.prep_graphs[b].replay()
         self._holds[b] = padded
 
@@ -456,33 +459,20 @@ class _CollatedBuffers(PipelinedBucketedStep):
     pinned buffer and replays P[b].  ``__call__`` and the two-buffer schedule are the parent's."""
 
     def __init__(self, ds, item, prepare, fn, warmup: int, generators, tail, ring: _IdsRing):
-        from ..backend.graph import capture_flag
-
-        self.tail = tail
-        self.prepare = prepare
-        self.dev = ds.device
+        self._setup_schedule(prepare, tail, ds.device)
         self.ring = ring
-        self.prep_stream = stream_beside(torch.cuda.current_stream(self.dev))
         self.collations = [ds.collation(item.G, *item.capacity) for _ in range(2)]
         self.static = [c.batch for c in self.collations]
         self.prep_graphs, self.steps = [], []
-        self.ev_prep = [torch.cuda.Event() for _ in range(2)]
-        self.ev_step = [torch.cuda.Event() for _ in range(2)]
-        self._holds = [None, None]
         self._held_by = [None, None]        # the last batch each buffer was prepared for (CollatedStep.last_static)
-        self._step_ran = [False, False]
         self.keys = list(self.static[0].keys())
         self._given = []                    # (everything in a buffer is regenerated from its ids)
-        capture_flag(self.dev)
         ids = torch.from_numpy(item.ids)
         for b, c in enumerate(self.collations):
             c.ids.copy_(ids)
-            c()                             # eagerly first (see PipelinedBucketedStep.__init__), then recorded with the preparation
+            c()                             # eagerly first (see _prepare_eagerly), then recorded with the preparation
             if b == 0:
-                warm = c.batch.clone()
-                prepare(warm)
-                torch.cuda.synchronize(self.dev)
-                del warm
+                self._prepare_eagerly(c.batch)
             torch.cuda.synchronize(self.dev)
             self.prep_graphs.append(self._record_prepare(b))
             self._held_by[b] = item
@@ -508,10 +498,7 @@ class _CollatedBuffers(PipelinedBucketedStep):
         c.renew()
         c.batch._e3k_done = None
         c()
-        warm = c.batch.clone()
-        self.prepare(warm)                  # (eagerly first: see __init__)
-        torch.cuda.synchronize(self.dev)
-        del warm
+        self._prepare_eagerly(c.batch)
         self.prep_graphs[b] = self._record_prepare(b)
 
     def _enqueue_prepare(self, b: int, item) -> None:

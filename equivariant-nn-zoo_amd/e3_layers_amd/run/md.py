@@ -31,13 +31,12 @@ import torch
 
 from ..backend import lib as L
 from ..backend.graph import EdgeCapacityExceeded
-from ..data.compute_edge import check_edge_capacity, computeEdgeIndex, computeEdgeIndexCapped, normal_draw
-from .graph_step import GHOST_DEGREE, CapturedStep, bucket_capacity, pad_batch
+from ..data.compute_edge import computeEdgeIndex, computeEdgeIndexCapped, normal_draw
+from .capped import EDGE_KEYS, CappedBucket
+from .graph_step import CapturedStep, bucket_capacity
 
 __all__ = ["EdgeCapacityExceeded", "ReplayedForceField", "VelocityVerlet", "Langevin", "Fire", "BondConstraints", "ConstraintFailure",
            "hydrogen_bonds"]
-
-_EDGE_KEYS = ("edge_index", "edge_vector", "edge_length", "_n_edges", "_edge_segment")
 
 
 class ReplayedForceField:
@@ -52,7 +51,7 @@ class ReplayedForceField:
             raise RuntimeError("ReplayedForceField needs a device batch: there is no CPU fallback for graph replay")
         if edge_slack < 1.0:
             raise ValueError("edge_slack must be >= 1")
-        carried = [k for k, v in batch.attrs.items() if v[0] == "edge" and k in batch and k not in _EDGE_KEYS]
+        carried = [k for k, v in batch.attrs.items() if v[0] == "edge" and k in batch and k not in EDGE_KEYS]
         if carried:
             raise ValueError(f"the edge attributes {carried} cannot follow a rebuilt neighbour list")
         self.model, self.r_max, self.key = model, float(r_max), key
@@ -60,7 +59,7 @@ class ReplayedForceField:
         self.edge_slack, self.warmup, self.edge_multiple = float(edge_slack), warmup, int(edge_multiple)
         self.dev = batch[key].device
         self._base = batch.clone()
-        for k in _EDGE_KEYS:
+        for k in EDGE_KEYS:
             self._base.pop(k)
         self.n_real = int(batch[key].shape[0])
         self.n_graphs = len(batch)
@@ -82,17 +81,13 @@ class ReplayedForceField:
         n, e = self.n_real, int(new["edge_index"].shape[1])
         want = max(int(e * self.edge_slack) + 1, int(e_min))
         _, e_cap = bucket_capacity([(n, want)], edge_multiple=self.edge_multiple)
-        n_cap = n + max(2, -(-(e_cap - e) // GHOST_DEGREE))      # ghost nodes for the tail as it is NOW (about GHOST_DEGREE edges each)
-        n_cap = -(-n_cap // 32) * 32
-        static = pad_batch(base, n_cap, e_cap)
-        static["_nlist_state"] = torch.zeros(2, dtype=torch.int64, device=self.dev)
-        static[self.key] = static[self.key].contiguous()
-        self.static, self.n_cap, self.e_cap = static, n_cap, e_cap
-        self.pos = static[self.key][:self.n_real]      # the real nodes' positions: write here, then evaluate()
+        bucket = self._bucket = CappedBucket.around_list(base, e_cap, self.key)
+        self.static, self.n_cap, self.e_cap = bucket.padded, bucket.n_cap, bucket.e_cap
+        self.pos = self.static[self.key][:self.n_real]      # the real nodes' positions: write here, then evaluate()
         model = self.model
 
         def evaluate():
-            work = static.view()
+            work = bucket.view()
             computeEdgeIndexCapped(work.data, work.attrs, r_max=self.r_max, key=self.key)
             out = model(work)
             return out[self.energy_key].reshape(-1)[:self.n_graphs], out[self.forces_key][:self.n_real]
@@ -117,7 +112,7 @@ class ReplayedForceField:
     @property
     def n_edges(self) -> torch.Tensor:
         """Device int64 scalar: the real edges the last evaluation's list needed (more than ``e_cap``: it overflowed)."""
-        return self.static["_nlist_state"][0]
+        return self._bucket.state[0]
 
     # ---- evaluation -------------------------------------------------------------------------------------------------
     def evaluate(self):
@@ -147,7 +142,7 @@ class ReplayedForceField:
         overflow's report) since the last check, and clears the condition."""
         over, self._overflow = self._overflow, False
         try:
-            check_edge_capacity(self.static["_nlist_state"])
+            self._bucket.check()
         except EdgeCapacityExceeded:
             over = True
         if over:

@@ -24,11 +24,11 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from ..data.compute_edge import PairCriterion
-from .sde_sampling import _layer_criterion, _own_edge_layer
+from ..backend.graph import EdgeCapacityExceeded
+from ..data.compute_edge import PairCriterion, check_edge_capacity
+from .capped import EDGE_KEYS, REBUILT_KEYS, CappedBucket, edge_layer_of, real_graphs, replayable_criterion
+from .graph_step import CapturedStep, copy_into, ghost_node_capacity, pad_batch
 from .sde_utils import VPSDE, sde_perturb_counter
-
-_REBUILT = ("edge_index", "_n_edges", "_edge_segment")      # the in-graph build rewrites all of them: never copied in
 
 
 class StepWindow:
@@ -85,9 +85,9 @@ def eager_score_step(model, sde: VPSDE, opt, batch, s: int, seed: int = 0, eps: 
     from .parallel import backward_parameters
 
     pert, misc = sde_perturb_counter(sde, batch, seed, int(s), eps)
-    crit = _layer_criterion(_own_edge_layer(model))
-    if isinstance(crit, PairCriterion):
-        crit.reset(int(s))
+    own = edge_layer_of(model)
+    if own is not None and isinstance(own.criterion, PairCriterion):
+        own.criterion.reset(int(s))
     model.train(True)
     result = model(pert)
     loss = _loss_of(ops, sde, result, pert, misc, None)
@@ -110,14 +110,13 @@ def _loss_of(ops, sde, result, pert, misc, weight):
 def score_list_sizes(model, sde: VPSDE, batch, draws: Sequence[int], seed: int = 0, eps: float = 1e-5) -> List[int]:
     """The sizes of the un-capped neighbour lists the model's own ``edge_index`` layer builds for the un-padded ``batch`` noised at
     the draw indices ``draws`` (eager: one host read per draw)."""
-    layer = _own_edge_layer(model)
-    crit = _layer_criterion(layer)
+    own = edge_layer_of(model)
     sizes = []
     for s in draws:
         pert, _ = sde_perturb_counter(sde, batch, seed, int(s), eps)
-        if isinstance(crit, PairCriterion):
-            crit.reset(int(s))
-        new, _ = layer(pert.data, pert.attrs)
+        if isinstance(own.criterion, PairCriterion):
+            own.criterion.reset(int(s))
+        new, _ = own.layer(pert.data, pert.attrs)
         sizes.append(int(new["edge_index"].shape[1]))
     return sizes
 
@@ -153,18 +152,14 @@ class ReplayedScoreStep:
 
     def __init__(self, model, sde: VPSDE, opt, example, *, edge_capacity: int, node_capacity: Optional[int] = None, seed: int = 0,
                  check_every: int = 8, eps: float = 1e-5):
-        own = _own_edge_layer(model)
+        own = edge_layer_of(model)
         if own is None:
             raise ValueError("ReplayedScoreStep needs a model whose tree starts with its own edge_index layer (the protein score nets)")
-        kw = getattr(own, "keywords", None) or {}
-        crit = _layer_criterion(own)
-        if crit is not None and not isinstance(crit, PairCriterion):
-            raise ValueError("edge_capacity: the model's edge_index layer uses a criteria callback (arbitrary Python, a host "
-                             "synchronisation per call); build the tree with a data.PairCriterion to replay it")
-        if kw.get("r_max") is None:
+        crit = replayable_criterion(own)
+        if own.r_max is None:
             raise ValueError("the model's edge_index layer carries no cutoff (r_max)")
-        self.model, self.sde, self.opt, self.layer, self.crit = model, sde, opt, own, crit
-        self.pos_key, self.r_max = kw.get("key", "pos"), float(kw["r_max"])
+        self.model, self.sde, self.opt, self.layer, self.crit = model, sde, opt, own.layer, crit
+        self.pos_key, self.r_max = own.key or "pos", float(own.r_max)
         self.seed, self.eps = int(seed), float(eps)
         self.dev = example[self.pos_key].device
         self._example = example
@@ -183,21 +178,11 @@ class ReplayedScoreStep:
         sizes rounded up to 1024 (``edge_capacity_for`` is the same before there is a step to ask)."""
         return quantile_capacity([e for b in batches for e in self.list_sizes(b, range(int(draws)))], quantile)
 
-    def _sized_node_capacity(self, n: int, e_cap: int, e_min: int) -> int:
-        """As the sampler's capped loop sizes it: about GHOST_DEGREE ghost edges per ghost node at the smallest list to expect."""
-        from .graph_step import GHOST_DEGREE
-
-        if self._node_capacity is not None:
-            return int(self._node_capacity)
-        return -(-(n + max(2, -(-max(e_cap - e_min, 0) // GHOST_DEGREE))) // 32) * 32
-
     def pad(self, batch):
         """The padded batch of this bucket for a protein batch without edges: an empty edge list and ``e_cap`` ghost edges (the
         in-graph build rewrites all of them).  Raises ValueError for a batch that does not fit the node capacity."""
-        from .graph_step import pad_batch
-
         b = batch.view()
-        for k in _REBUILT + ("edge_vector", "edge_length"):
+        for k in EDGE_KEYS:
             b.pop(k)
         dev = b[self.pos_key].device
         b.data["edge_index"] = torch.zeros(2, 0, dtype=torch.int64, device=dev)
@@ -211,7 +196,6 @@ class ReplayedScoreStep:
     def _capture(self, e_cap: int) -> None:
         from ..backend import memo, ops
         from ..backend import lib as L
-        from .graph_step import CapturedStep
         from .parallel import backward_parameters
 
         dev, opt = self.dev, self.opt
@@ -221,30 +205,26 @@ class ReplayedScoreStep:
         probe = self.list_sizes(self._example, range(8))
         fits = [s for s, e in enumerate(probe) if e <= e_cap]
         if not fits:
-            from ..backend.graph import EdgeCapacityExceeded
-
             raise EdgeCapacityExceeded(f"the example's lists at the draws 0..7 have {min(probe)}..{max(probe)} edges: "
                                        f"edge_capacity={e_cap} is too small")
-        self.n_cap = self._sized_node_capacity(int(self._example[self.pos_key].shape[0]), e_cap, min(probe))
+        # the ghost nodes for the smallest list to expect, as the sampler's capped loop sizes them
+        self.n_cap = int(self._node_capacity) if self._node_capacity is not None else \
+            ghost_node_capacity(int(self._example[self.pos_key].shape[0]), e_cap - min(probe))
         self._padded_example = self.pad(self._example)
-        static = self._padded_example.clone()
-        self.keys = [k for k in static.keys() if torch.is_tensor(static[k]) and k not in _REBUILT]
+        static = self.static = self._padded_example.clone()
+        self.keys = [k for k in static.keys() if torch.is_tensor(static[k]) and k not in REBUILT_KEYS]
         ring_len = self.window.check_every
-        self.nlist_state = torch.zeros(2, dtype=torch.int64, device=dev)      # (edges of the last build, builds that overflowed)
-        self.nlist_rng = torch.zeros(2, dtype=torch.int64, device=dev)
+        bucket = CappedBucket(static, self.pos_key, rng=True)
+        self.nlist_state, self.nlist_rng = bucket.state, bucket.rng
         self.cells = torch.tensor([self.window.step, -1], dtype=torch.int64, device=dev)      # (step, first_bad)
         self.ring = torch.zeros(ring_len, dtype=torch.float32, device=dev)
-        static.data["_nlist_state"] = self.nlist_state
-        static.data["_nlist_rng"] = self.nlist_rng
-        self.static = static
-        n_real = len(static) - 1
         weight = static["_node_weight"]
         lib = L.load()
         warming = self._warming = [False]
 
         def captured():
             memo.forget(static)      # the static tensors' contents change between replays (the recording rule of backend/memo.py)
-            work = static.view()
+            work = bucket.view()
             pert, misc = sde_perturb_counter(self.sde, work, self.seed, self.cells, self.eps)
             self.model.train(True)
             result = self.model(pert)      # (its edge layer finds _nlist_state: the capped build, inside the capture)
@@ -259,7 +239,7 @@ class ReplayedScoreStep:
                 self.cells[:1].fill_(self._fit_draw)
             return loss
 
-        assert n_real >= 1
+        assert bucket.n_graphs >= 1
         self._fit_draw = fits[0]
         self._quietly(lambda: setattr(self, "captured", CapturedStep(captured, warmup=2, device=dev)))
 
@@ -294,24 +274,10 @@ class ReplayedScoreStep:
 
     # ------------------------------------------------------------------ the device side of StepWindow
     def _load(self, padded) -> None:
-        """The padded batch into the static tensors: one multi-tensor copy per dtype (``BucketedStep``'s)."""
-        by_dtype = {}
-        for k in self.keys:
-            dst, src = self.static[k], padded[k]
-            if dst.shape != src.shape:
-                raise ValueError(f"{k}: {tuple(src.shape)} does not fit the captured {tuple(dst.shape)} (another bucket? pad() again after grow())")
-            if src.device == dst.device and src.dtype == dst.dtype and src.is_contiguous() and dst.is_contiguous():
-                pair = by_dtype.setdefault(dst.dtype, ([], []))
-                pair[0].append(dst)
-                pair[1].append(src)
-            else:
-                dst.copy_(src, non_blocking=True)
-        for dsts, srcs in by_dtype.values():
-            torch._foreach_copy_(dsts, srcs)
+        """The padded batch into the static tensors."""
+        copy_into(self.static, padded, self.keys, hint="pad() again after grow()")
 
     def replay(self, padded) -> None:
-        from ..backend.graph import EdgeCapacityExceeded
-
         if self.captured.stale:
             # a knot table the graph interpolates from was refined: CapturedStep would run this step eagerly and record again.  An
             # eager step on the capped list raises from the index checks when the list does not fit -- possibly half way through; so
@@ -332,9 +298,6 @@ class ReplayedScoreStep:
         return int(packed[0]), int(packed[1]), packed[2:].tolist()
 
     def _clear(self) -> None:
-        from ..backend.graph import EdgeCapacityExceeded
-        from ..data.compute_edge import check_edge_capacity
-
         try:
             check_edge_capacity(self.nlist_state)      # the counter, the persistent flag's bit and the flag copies on their way home
         except EdgeCapacityExceeded:
@@ -349,10 +312,7 @@ class ReplayedScoreStep:
         return self.eager_step(source if source is not None else self._unpadded(padded), s)
 
     def _unpadded(self, padded):
-        out = padded[list(range(len(padded) - 1))]      # the real graphs
-        for k in ("_graph_weight", "_node_weight") + _REBUILT:
-            out.pop(k)
-        return out
+        return real_graphs(padded, drop=REBUILT_KEYS)
 
     # ------------------------------------------------------------------ the caller's side
     def eager_step(self, batch, s: int):

@@ -23,12 +23,15 @@ is identical for the default ``n_steps=1``.
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Callable, Dict, Optional, Sequence
 
 import torch
 
-from ..backend.graph import TOPO_KEYS
-from ..data.compute_edge import PairCriterion
+from ..backend.graph import TOPO_KEYS, EdgeCapacityExceeded
+from ..data.compute_edge import PairCriterion, computeEdgeIndex, computeEdgeIndexCapped
+from .capped import EDGE_KEYS, CappedBucket, builder_cells, edge_layer_of, replayable_criterion
+from .graph_step import CapturedStep
 from .sde_utils import VPSDE, _node_t, _randn, get_score_fn, prior_sampling, reverse_step
 
 class _Registry(dict):
@@ -113,7 +116,7 @@ class NoneCorrector(Corrector):
         return batch
 
 
-_EDGE_KEYS = ("edge_index", "edge_vector", "edge_length", "_n_edges", "_edge_segment") + TOPO_KEYS
+SAMPLER_EDGE_KEYS = EDGE_KEYS + TOPO_KEYS      # what the loop drops after every update: the list and the CSR topology built on it
 
 
 def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = None, snr: float = 0.16,
@@ -158,7 +161,7 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
             raise ValueError("edge_capacity: criteria must be a data.PairCriterion (the capped builder evaluates it in its kernels)")
 
     def rebuild_edges(batch):
-        for k in _EDGE_KEYS:
+        for k in SAMPLER_EDGE_KEYS:
             batch.pop(k)
         for fn in preprocess:
             new, attrs = fn(batch.data, batch.attrs)
@@ -187,7 +190,8 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                 batch.update(build_topology(batch["edge_index"], batch.n_nodes).as_dict())
         t_dev = batch["t"]
         keys = list(sde.irreps)
-        for crit in (criteria, _layer_criterion(_own_edge_layer(model))):
+        own = edge_layer_of(model)
+        for crit in (criteria, own and own.criterion):
             if isinstance(crit, PairCriterion):
                 crit.reset()      # build k of this run draws with index k
 
@@ -209,8 +213,11 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
 
         with torch.no_grad():
             if graph and edge_capacity is not None:
-                batch = _capped_graph_loop(batch, model, capped_updates(), keys, timesteps, steps, int(edge_capacity), float(r_max),
-                                           criteria)
+                loop = CappedLoop(batch, model, capped_updates(), keys, float(timesteps[0]), int(edge_capacity), float(r_max),
+                                  criteria)
+                loop.rewind()
+                loop.run(timesteps, steps)
+                batch = loop.result()
             elif graph:
                 # static buffers: the diffused tensors and t; the step writes its result back into them
                 state = {k: batch[k].clone() for k in keys}
@@ -253,21 +260,7 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
     return pc_sampler
 
 
-def _own_edge_layer(model):
-    """The model's own ``edge_index`` layer when its tree starts with one (a plain callable, e.g. the protein nets'
-    ``partial(computeEdgeIndex, r_max=..., key="CA", criteria=...)``), else None."""
-    layers = getattr(model, "layers", None)
-    if not layers:
-        return None
-    name, layer = layers[0]
-    return layer if name == "edge_index" and callable(layer) and not isinstance(layer, torch.nn.Module) else None
-
-
-def _layer_criterion(layer):
-    return (getattr(layer, "keywords", None) or {}).get("criteria")
-
-
-class _CappedLoop:
+class CappedLoop:
     """The reverse steps as replays of ONE graph on cutoff graphs: the batch padded to ``e_cap`` edges, the neighbour list rebuilt
     inside the graph -- by the loop after every update in ``updates`` (corrector, predictor), or by the model's own ``edge_index``
     layer in every model call (it finds ``_nlist_state`` in the batch and builds the capped list).  The ghost graph's rows of the
@@ -277,27 +270,18 @@ class _CappedLoop:
     back on the start, ``run()`` replays, ``result()`` checks the capacity and unpads (``tools/sample_bench.py`` times ``run`` alone)."""
 
     def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None):
-        from functools import partial
-
-        from ..data.compute_edge import computeEdgeIndex, computeEdgeIndexCapped
-        from .graph_step import GHOST_DEGREE, CapturedStep, pad_batch
-
         dev = batch["_n_nodes"].device
-        own = _own_edge_layer(model)
+        own = edge_layer_of(model)
         if own is not None:
-            criteria, pos_key = _layer_criterion(own), (getattr(own, "keywords", None) or {}).get("key", keys[0])
-            if criteria is not None and not isinstance(criteria, PairCriterion):
-                raise ValueError("edge_capacity: the model's edge_index layer uses a criteria callback (arbitrary Python, a host "
-                                 "synchronisation per call); build the tree with a data.PairCriterion to replay it")
-            build = own
+            criteria, pos_key, build = replayable_criterion(own), own.key or keys[0], own.layer
         else:
             pos_key = keys[0]
             build = partial(computeEdgeIndex, r_max=r_max, key=pos_key, criteria=criteria)
-        for k in _EDGE_KEYS:
+        for k in SAMPLER_EDGE_KEYS:
             batch.pop(k)
         # eager, once: the sizes of the padded batch.  The same function, the same criterion, the draw of build 0 -- read from the
         # cells, which the eager path never advances, so no draw is consumed
-        rng = torch.zeros(2, dtype=torch.int64, device=dev)
+        rng = builder_cells(dev)
         batch.data["_nlist_rng"] = rng
         new, attrs = build(batch.data, batch.attrs)
         batch.data.pop("_nlist_rng")
@@ -305,14 +289,10 @@ class _CappedLoop:
         batch.update(new)
         n, e = batch.n_nodes, int(new["edge_index"].shape[1])
         if e > e_cap:
-            from ..backend.graph import EdgeCapacityExceeded
-
             raise EdgeCapacityExceeded(f"the first neighbour list has {e} edges: edge_capacity={e_cap} is too small")
-        n_cap = -(-(n + max(2, -(-(e_cap - e) // GHOST_DEGREE))) // 32) * 32
         batch["t"] = torch.full((len(batch), 1), float(t0), device=dev)
-        padded = pad_batch(batch, n_cap, e_cap, key=pos_key)
-        padded["_nlist_state"] = torch.zeros(2, dtype=torch.int64, device=dev)
-        padded.data["_nlist_rng"] = rng
+        bucket = self.bucket = CappedBucket.around_list(batch, e_cap, pos_key, rng=rng)      # (the cells the sizing build read)
+        padded = bucket.padded
         state = {k: padded[k] for k in keys}
 
         def relisted(b):
@@ -351,23 +331,11 @@ class _CappedLoop:
             self.step()
 
     def result(self):
-        from ..data.compute_edge import check_edge_capacity
-
-        padded = self.padded
-        check_edge_capacity(padded["_nlist_state"])
-        out = padded[list(range(len(padded) - 1))]      # the real graphs
-        for k in ("_graph_weight", "_node_weight"):
-            out.pop(k)
+        self.bucket.check()
+        out = self.bucket.real_graphs()
         for k in self.keys:
             out[k] = self.state[k][:self.n].clone()
         return out
-
-
-def _capped_graph_loop(batch, model, updates, keys, timesteps, steps: int, e_cap: int, r_max: float, criteria=None):
-    loop = _CappedLoop(batch, model, updates, keys, float(timesteps[0]), e_cap, r_max, criteria)
-    loop.rewind()
-    loop.run(timesteps, steps)
-    return loop.result()
 
 
 def get_sampling_fn(config, sde: VPSDE, inverse_scaler, eps: float, **kwargs):

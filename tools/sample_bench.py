@@ -79,7 +79,7 @@ def predictor(model, sde):
 def eager_loop(model, sde, batch, timesteps, crit, n_steps):
     """pc_sampler's eager path with NoneCorrector: set the time, predictor update (one model call: its edge layer builds the list,
     all pairs -> criterion -> edge count read back), drop the per-edge keys."""
-    from e3_layers_amd.run.sde_sampling import _EDGE_KEYS
+    from e3_layers_amd.run.sde_sampling import SAMPLER_EDGE_KEYS
 
     pred = predictor(model, sde)
     state = {"b": batch.clone()}
@@ -94,7 +94,7 @@ def eager_loop(model, sde, batch, timesteps, crit, n_steps):
             for i in range(n_steps):
                 t_dev.copy_(timesteps[i].expand_as(t_dev))
                 b = pred.update_fn(b)
-                for k in _EDGE_KEYS:
+                for k in SAMPLER_EDGE_KEYS:
                     b.pop(k)
         state["b"] = b
         return time.perf_counter() - t0
@@ -104,19 +104,18 @@ def eager_loop(model, sde, batch, timesteps, crit, n_steps):
 
 def replay_loop(model, sde, batch, timesteps, slack):
     """The capped loop of get_pc_sampler(graph=True, edge_capacity=...): sized, padded and captured here, outside the timed region."""
-    from e3_layers_amd.data import computeEdgeIndex
-    from e3_layers_amd.run.sde_sampling import _CappedLoop
+    from e3_layers_amd.run.capped import builder_cells, edge_layer_of
+    from e3_layers_amd.run.sde_sampling import CappedLoop
 
     b = batch.clone()
     b.attrs["t"] = ("graph", "1x0e")
     pred = predictor(model, sde)
     probe = b.clone()
-    layer = model.layers[0][1]
-    probe.data["_nlist_rng"] = torch.zeros(2, dtype=torch.int64, device=timesteps.device)
-    new, _ = layer(probe.data, probe.attrs)
+    probe.data["_nlist_rng"] = builder_cells(timesteps.device)
+    new, _ = edge_layer_of(model).layer(probe.data, probe.attrs)
     e_cap = -(-int(slack * new["edge_index"].shape[1]) // 1024) * 1024
     with torch.no_grad():
-        return _CappedLoop(b, model, [lambda w: w, lambda w: pred.update_fn(w)], ["CA"], float(timesteps[0]), e_cap, None), e_cap
+        return CappedLoop(b, model, [lambda w: w, lambda w: pred.update_fn(w)], ["CA"], float(timesteps[0]), e_cap, None), e_cap
 
 
 def timed(fn):
@@ -172,7 +171,7 @@ def protein(argv):
     for _ in range(args.reps):
         loop.rewind()
         ms, host = timed(replay(args.steps))
-        edges.append(int(loop.padded["_nlist_state"][0]))
+        edges.append(int(loop.bucket.state[0]))
         loop.result()                               # (after the closing event: an overflowed repetition would raise here)
         rows["replay"].append(ms / args.steps)
         rows["replay_host"].append(1e3 * host / args.steps)
@@ -187,7 +186,7 @@ def protein(argv):
                        "built with pair_criterion(); synth_protein",
            "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues,
            "nodes": int(batch["CA"].shape[0]), "edges_first_list": loop.first_edges, "edges_last_list": edges, "e_cap": e_cap,
-           "n_cap": int(loop.padded["CA"].shape[0]), "steps": args.steps, "reps": args.reps, "recaptures": loop.step.recaptures,
+           "n_cap": loop.bucket.n_cap, "steps": args.steps, "reps": args.reps, "recaptures": loop.step.recaptures,
            "replay_ms_per_step": mmm(rows["replay"]), "eager_ms_per_step": mmm(rows["eager"]),
            "replay_host_busy_ms_per_step": mmm(rows["replay_host"]), "eager_host_busy_ms_per_step": mmm(rows["eager_host"]),
            "speedup_median": round(statistics.median(rows["eager"]) / statistics.median(rows["replay"]), 3)}
