@@ -60,6 +60,27 @@ static inline int zero_fill(void* p, int64_t bytes, hipStream_t st) {
   return 0;
 }
 
+__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// A product rounded to fp32 on its own.  The files are built with -ffp-contract=fast, under which the backend fuses any fmul into a
+// neighbouring fadd; __fmul_rn / __fadd_rn are plain x * y and x + y in this toolchain (and __fsqrt_rn the 1-ulp native square
+// root), so they guard nothing.  The empty asm makes the rounded product a value the optimiser has to materialise.
+__device__ __forceinline__ float rounded_product(float a, float b) {
+  float p = a * b;
+  asm volatile("" : "+v"(p));
+  return p;
+}
+
+// The radius graph's distance test, exactly as the reference states it: fp32 sqrt(dx^2 + dy^2 + dz^2) < r_max, strict, no fused
+// multiply-add (sqrtf is correctly rounded as built: no fast-math flag).  (px, py, pz): the source node; j: the candidate's row of pos.
+__device__ __forceinline__ bool within_cutoff(float px, float py, float pz, const float* __restrict__ pos, int64_t j, float r_max) {
+  const float dx = px - pos[3 * j];
+  const float dy = py - pos[3 * j + 1];
+  const float dz = pz - pos[3 * j + 2];
+  const float d2 = (rounded_product(dx, dx) + rounded_product(dy, dy)) + rounded_product(dz, dz);
+  return sqrtf(d2) < r_max;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -448,17 +448,9 @@ __global__ __launch_bounds__(256) void radial_bwd2_kernel(const float* __restric
 // One wave per source node i walks its own graph's nodes 64 at a time; a ballot compacts the kept
 // pairs in ascending j, so the edge list comes out in the reference's order — graphs concatenated,
 // (i, j) lexicographic inside a graph — without a sort.  Two passes (count, exclusive scan on the host
-// side with torch.cumsum, fill).  Distance test exactly as the reference states it: fp32
-// sqrt(dx^2 + dy^2 + dz^2) < r_max, strict, no fused multiply-add.
+// side with torch.cumsum, fill).  Distance test exactly as the reference states it: within_cutoff
+// of e3k_common.h.
 // ---------------------------------------------------------------------------------------
-// A product rounded to fp32 on its own.  The file is built with -ffp-contract=fast, under which the backend fuses any fmul into a
-// neighbouring fadd; __fmul_rn / __fadd_rn are plain x * y and x + y in this toolchain (and __fsqrt_rn the 1-ulp native square
-// root), so they guard nothing.  The empty asm makes the rounded product a value the optimiser has to materialise.
-__device__ __forceinline__ float rounded_product(float a, float b) {
-  float p = a * b;
-  asm volatile("" : "+v"(p));
-  return p;
-}
 template <bool FILL>
 __global__ __launch_bounds__(256) void radius_graph_kernel(const float* __restrict__ pos,
                                                             const int32_t* __restrict__ g_start,
@@ -480,13 +472,7 @@ __global__ __launch_bounds__(256) void radius_graph_kernel(const float* __restri
     const int j = j0 + lane;
     bool keep = false;
     if (j < end) {
-      if (j != i) {
-        const float dx = px - pos[3 * (int64_t)j];
-        const float dy = py - pos[3 * (int64_t)j + 1];
-        const float dz = pz - pos[3 * (int64_t)j + 2];
-        const float d2 = (rounded_product(dx, dx) + rounded_product(dy, dy)) + rounded_product(dz, dz);
-        keep = sqrtf(d2) < r_max;   // (sqrtf is correctly rounded as built: no fast-math flag)
-      }
+      if (j != i) keep = within_cutoff(px, py, pz, pos, j, r_max);
       if (!keep && oe > ob) {   // pre-existing edges stay (binary search in i's sorted old neighbours)
         int lo = ob, hi = oe;
         while (lo < hi) {

@@ -1,7 +1,7 @@
-// Capped neighbour list and the velocity-Verlet updates (run/md.py): what a force evaluation needs between two replays of
-// the model's graph when the atoms move.
+// Capped neighbour list: what a force evaluation (run/md.py), a sampling step or a score step needs in front of the model when
+// the atoms move.
 //
-// The capped list is the radius graph of e3k_edge.hip (same distance test, same edge order) written into a FIXED [2, e_cap]
+// The capped list is the radius graph of e3k_edge.hip (same distance test -- within_cutoff of e3k_common.h -- and edge order) written into a FIXED [2, e_cap]
 // buffer: nothing about its size goes to the host, so the build is part of a captured HIP graph.  The batch is one padded by
 // run/graph_step.pad_batch -- its last graph is the ghost graph, which is not searched; the slots behind the real edges are
 // filled with the ghost edges run/graph_step.ghost_sample defines, so that for positions that fit the buffer equals
@@ -12,25 +12,16 @@
 // batch's own bookkeeping is clamped to [0, N] before it is used as an address.
 //
 // The criterion form (e3k_nlist_count_crit / _fill_crit) keeps a pair that is inside the cutoff OR that the declarative pair rule of
-// data/compute_edge.SequenceOrRandom keeps: same segment key and |i - j| < window, or a counter-based Bernoulli draw -- a 32-bit hash
-// of (seed, draw index, i, j) below a threshold.  The draw index is the number of the build: count reads rng[0], the scan (one
+// data/compute_edge.SequenceOrRandom keeps: same segment key and |i - j| < window, or a counter-based Bernoulli draw -- the 32-bit
+// pair hash of e3k_draw.h over (seed, draw index, i, j) below a threshold.  The draw index is the number of the build: count reads rng[0], the scan (one
 // workgroup, between the two passes) copies it to rng[1] and advances rng[0], fill reads rng[1] -- both passes see one draw, the
 // index goes up once per build, three launches, and stream order is the only synchronisation needed.
 #include "e3k_common.h"
+#include "e3k_draw.h"
 
 namespace e3k {
 
 constexpr int32_t NLIST_OVERFLOW = 32;      // value ORed into the persistent flag, i.e. bit 5 (values 1, 4, 8, 16: edge endpoints, one-hot types, table keys, collation)
-
-// (restated from e3k_edge.hip: the file is built with -ffp-contract=fast; the empty asm makes the rounded product a value the
-//  optimiser has to materialise, so no fmul is fused into the neighbouring fadd)
-__device__ __forceinline__ float rounded_product(float a, float b) {
-  float p = a * b;
-  asm volatile("" : "+v"(p));
-  return p;
-}
-
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // The pair rule of the criterion form.  segment_key [N] int64 (NULL or window <= 0: no sequence term); threshold = floor(p 2^32)
 // (0: no random term); keep_all: p = 1, whose threshold does not fit 32 bits; rng [2] int64 = (next draw index, draw index in use).
@@ -41,17 +32,6 @@ struct NlistCrit {
   uint32_t threshold, seed_lo, seed_hi;
   int32_t keep_all;
 };
-
-// One round of the "lowbias32" integer finaliser; the pair hash chains it over the five words (seed low, seed high, draw, src, dst)
-// from 0x9E3779B9: h = mix(h ^ word).  uint32 arithmetic: data/compute_edge.pair_hash restates it in int64 masked to 32 bits.
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x7feb352du;
-  h ^= h >> 15;
-  h *= 0x846ca68bu;
-  h ^= h >> 16;
-  return h;
-}
 
 // One wave per source node i walks its own graph's nodes 64 at a time; a ballot compacts the kept pairs in ascending j.
 // node_seg [N]: graph of every node; node_ptr [G + 2]: first node of every graph (the ghost graph is graph G: its nodes count 0).
@@ -106,18 +86,14 @@ __global__ __launch_bounds__(256) void nlist_kernel(const float* __restrict__ po
     seq_on = crit.segment_key != nullptr && crit.window > 0;
     if (seq_on) key_i = crit.segment_key[i];
     const uint32_t draw = (uint32_t)crit.rng[FILL ? 1 : 0];
-    h_i = mix32(mix32(mix32(mix32(0x9E3779B9u ^ crit.seed_lo) ^ crit.seed_hi) ^ draw) ^ (uint32_t)i);
+    h_i = mix32(draw_prefix(crit.seed_lo, crit.seed_hi, draw) ^ (uint32_t)i);
   }
   int cnt = 0;
   for (int64_t j0 = beg; j0 < end; j0 += 64) {
     const int64_t j = j0 + lane;
     bool keep = false;
     if (j < end && j != i) {
-      const float dx = px - pos[3 * j];
-      const float dy = py - pos[3 * j + 1];
-      const float dz = pz - pos[3 * j + 2];
-      const float d2 = (rounded_product(dx, dx) + rounded_product(dy, dy)) + rounded_product(dz, dz);
-      keep = sqrtf(d2) < r_max;   // (sqrtf is correctly rounded as built: no fast-math flag)
+      keep = within_cutoff(px, py, pz, pos, j, r_max);
       if constexpr (CRIT) {
         if (!keep) {
           const int64_t gap = i > j ? i - j : j - i;
@@ -197,169 +173,6 @@ __global__ __launch_bounds__(1024) void nlist_scan_kernel(const int32_t* __restr
   }
 }
 
-// velocity Verlet, first half: v += dt/2 f / m, x += dt v on the n real nodes (3n components, one per thread)
-__global__ __launch_bounds__(256) void md_drift_kernel(float* __restrict__ x, float* __restrict__ v, const float* __restrict__ f,
-                                                       const float* __restrict__ mass, int64_t n3, float dt) {
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c >= n3) return;
-  const float vn = v[c] + (0.5f * dt) * f[c] / mass[c / 3];
-  v[c] = vn;
-  x[c] = x[c] + dt * vn;
-}
-
-// second half: v += dt/2 f / m and the graphs' kinetic energies.  One wave per graph; lane l sums the nodes l, l + 64, ... of the
-// graph in ascending order, the 64 partial sums meet in a fixed butterfly: the same bits every run (no atomics).  The step's record
-// is complete in the same launch: potential[g] = energy[g] (the force graph's static output, overwritten by the next replay).
-__global__ __launch_bounds__(256) void md_kick_kernel(float* __restrict__ v, const float* __restrict__ f, const float* __restrict__ mass,
-                                                      const int64_t* __restrict__ node_ptr, int32_t G, int64_t n, float dt,
-                                                      float* __restrict__ kinetic, const float* __restrict__ energy,
-                                                      float* __restrict__ potential) {
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= G) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t beg = clampi(node_ptr[g], 0, n), end = clampi(node_ptr[g + 1], 0, n);
-  float ke = 0.f;
-  for (int64_t i = beg + lane; i < end; i += 64) {
-    const float m = mass[i], h = 0.5f * dt / m;
-    const float vx = v[3 * i] + h * f[3 * i], vy = v[3 * i + 1] + h * f[3 * i + 1], vz = v[3 * i + 2] + h * f[3 * i + 2];
-    v[3 * i] = vx;
-    v[3 * i + 1] = vy;
-    v[3 * i + 2] = vz;
-    ke += 0.5f * m * ((vx * vx + vy * vy) + vz * vz);
-  }
-  ke = wave_sum(ke);
-  if (lane == 0) {
-    if (kinetic) kinetic[g] = ke;
-    if (potential) potential[g] = energy[g];
-  }
-}
-
-// A standard normal for (seed, draw, node, word): the pair hash chain with dst = 2 word and 2 word + 1 gives u1 in (0, 1] and
-// u2 in [0, 1) (24 bits each, exact in fp32); Box-Muller's cosine branch.  h_node: the chain up to and including the node word.
-// logf, sqrtf, cospif are the precise library functions; 2 u2 is exact, so the cosine sees no argument rounding.
-// data/compute_edge.normal_draw restates it.
-__device__ __forceinline__ float normal_draw(uint32_t h_node, uint32_t word) {
-  const uint32_t h1 = mix32(h_node ^ (2u * word)), h2 = mix32(h_node ^ (2u * word + 1u));
-  const float u1 = (float)((h1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(h2 >> 8) * 0x1p-24f;
-  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-}
-
-// The thermostatted second half step: v <- c v + (s / sqrt(m)) xi, then md_kick_kernel's v += dt/2 f / m (f NULL: skipped) and
-// its records, in its walk.  c v and the noise term are rounded products that meet in a plain add: with c = 1, s = 0 the first
-// line returns v (the noise is an exact zero), whatever the compiler contracts, and the rest is md_kick_kernel's expression.
-__global__ __launch_bounds__(256) void md_kick_langevin_kernel(float* __restrict__ v, const float* __restrict__ f,
-                                                               const float* __restrict__ mass, const int64_t* __restrict__ node_ptr,
-                                                               int32_t G, int64_t n, float dt, float c, float s, uint32_t seed_lo,
-                                                               uint32_t seed_hi, uint32_t draw, uint32_t word0,
-                                                               float* __restrict__ kinetic, const float* __restrict__ energy,
-                                                               float* __restrict__ potential) {
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= G) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t beg = clampi(node_ptr[g], 0, n), end = clampi(node_ptr[g + 1], 0, n);
-  const uint32_t h_wave = mix32(mix32(mix32(0x9E3779B9u ^ seed_lo) ^ seed_hi) ^ draw);      // what does not depend on the node
-  float ke = 0.f;
-  for (int64_t i = beg + lane; i < end; i += 64) {
-    const float m = mass[i], a = s / sqrtf(m);
-    const uint32_t h_i = mix32(h_wave ^ (uint32_t)i);
-    float vx = rounded_product(c, v[3 * i]) + rounded_product(a, normal_draw(h_i, word0));
-    float vy = rounded_product(c, v[3 * i + 1]) + rounded_product(a, normal_draw(h_i, word0 + 1u));
-    float vz = rounded_product(c, v[3 * i + 2]) + rounded_product(a, normal_draw(h_i, word0 + 2u));
-    if (f) {
-      const float h = 0.5f * dt / m;
-      vx = vx + h * f[3 * i];
-      vy = vy + h * f[3 * i + 1];
-      vz = vz + h * f[3 * i + 2];
-    }
-    v[3 * i] = vx;
-    v[3 * i + 1] = vy;
-    v[3 * i + 2] = vz;
-    ke += 0.5f * m * ((vx * vx + vy * vy) + vz * vz);
-  }
-  ke = wave_sum(ke);
-  if (lane == 0) {
-    if (kinetic) kinetic[g] = ke;
-    if (potential) potential[g] = energy[g];
-  }
-}
-
-// FIRE (Bitzek et al. 2006, the step rule of ASE's optimiser) with the adaptive state PER GRAPH: one wave per graph, three
-// walks over its atoms -- the reductions, the velocity update with |dr|^2, the move.  state [G, 4] = (dt, alpha, n_pos, fmax).
-struct FireParams {
-  float ftol, dt_max, maxstep, n_min, f_inc, f_dec, alpha_start, f_alpha;
-};
-
-__global__ __launch_bounds__(256) void fire_step_kernel(float* __restrict__ x, float* __restrict__ v, const float* __restrict__ f,
-                                                        const int64_t* __restrict__ node_ptr, int32_t G, int64_t n,
-                                                        float* __restrict__ state, const FireParams p,
-                                                        const float* __restrict__ energy, float* __restrict__ energy_record,
-                                                        float* __restrict__ fmax_record) {
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= G) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t beg = clampi(node_ptr[g], 0, n), end = clampi(node_ptr[g + 1], 0, n);
-  float dt = state[4 * g], alpha = state[4 * g + 1], n_pos = state[4 * g + 2];
-  float fv = 0.f, ff = 0.f, vv = 0.f, f2max = 0.f;
-  for (int64_t i = beg + lane; i < end; i += 64) {
-    const float fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
-    const float vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
-    const float f2 = (fx * fx + fy * fy) + fz * fz;
-    fv += (fx * vx + fy * vy) + fz * vz;
-    ff += f2;
-    vv += (vx * vx + vy * vy) + vz * vz;
-    f2max = fmaxf(f2max, f2);
-  }
-  fv = wave_sum(fv);
-  ff = wave_sum(ff);
-  vv = wave_sum(vv);
-  const float fmax = sqrtf(wave_max_f(f2max));
-  const bool frozen = fmax < p.ftol;      // (wave-uniform, like every branch below: the reductions leave all lanes the same values)
-  if (frozen) {
-    for (int64_t i = beg + lane; i < end; i += 64) v[3 * i] = v[3 * i + 1] = v[3 * i + 2] = 0.f;
-  } else {
-    float keep = 0.f, mix = 0.f;      // v <- keep v + mix f
-    if (fv < 0.f) {
-      dt = dt * p.f_dec;
-      alpha = p.alpha_start;
-      n_pos = 0.f;
-    } else {
-      keep = 1.0f - alpha;
-      mix = ff > 0.f ? alpha * (sqrtf(vv) / sqrtf(ff)) : 0.f;
-      if (n_pos > p.n_min) {
-        dt = fminf(dt * p.f_inc, p.dt_max);
-        alpha = alpha * p.f_alpha;
-      }
-      n_pos = n_pos + 1.0f;
-    }
-    float v2 = 0.f;
-    for (int64_t i = beg + lane; i < end; i += 64) {
-      const float fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
-      const float vx = (keep * v[3 * i] + mix * fx) + dt * fx;
-      const float vy = (keep * v[3 * i + 1] + mix * fy) + dt * fy;
-      const float vz = (keep * v[3 * i + 2] + mix * fz) + dt * fz;
-      v[3 * i] = vx;
-      v[3 * i + 1] = vy;
-      v[3 * i + 2] = vz;
-      v2 += (vx * vx + vy * vy) + vz * vz;
-    }
-    const float norm_dr = dt * sqrtf(wave_sum(v2));
-    const float move = norm_dr > p.maxstep ? dt * (p.maxstep / norm_dr) : dt;      // dr = move v
-    for (int64_t i = beg + lane; i < end; i += 64) {
-      x[3 * i] = x[3 * i] + move * v[3 * i];
-      x[3 * i + 1] = x[3 * i + 1] + move * v[3 * i + 1];
-      x[3 * i + 2] = x[3 * i + 2] + move * v[3 * i + 2];
-    }
-  }
-  if (lane == 0) {
-    state[4 * g] = dt;
-    state[4 * g + 1] = alpha;
-    state[4 * g + 2] = n_pos;
-    state[4 * g + 3] = fmax;
-    if (energy_record) energy_record[g] = energy[g];
-    if (fmax_record) fmax_record[g] = fmax;
-  }
-}
-
 }  // namespace e3k
 
 static bool nlist_args_ok(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G) {
@@ -428,50 +241,4 @@ extern "C" int e3k_nlist_fill_crit(const float* pos, const int64_t* node_seg, co
   const e3k::NlistCrit crit{segment_key, rng, window, threshold, seed_lo, seed_hi, keep_all};
   return nlist_fill<true>(pos, node_seg, node_ptr, N, G, r_max, crit, counts, e_cap, offsets, edge_index, n_edges, edge_segment,
                           state, flag, stream);
-}
-
-extern "C" int e3k_md_drift(float* x, float* v, const float* f, const float* mass, int64_t n, float dt, void* stream) {
-  if (n < 0) return E3K_ERR_INVALID;
-  if (n == 0) return E3K_OK;
-  if (!x || !v || !f || !mass) return E3K_ERR_INVALID;
-  hipLaunchKernelGGL(e3k::md_drift_kernel, dim3((unsigned)((3 * n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, v, f, mass,
-                     3 * n, dt);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
-}
-
-extern "C" int e3k_md_kick(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt,
-                           float* kinetic, const float* energy, float* potential, void* stream) {
-  if (n < 0 || G < 0) return E3K_ERR_INVALID;
-  if (n == 0 || G == 0) return E3K_OK;
-  if (!v || !f || !mass || !node_ptr || (potential && !energy)) return E3K_ERR_INVALID;
-  hipLaunchKernelGGL(e3k::md_kick_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, f, mass, node_ptr, G, n,
-                     dt, kinetic, energy, potential);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
-}
-
-extern "C" int e3k_md_kick_langevin(float* v, const float* f, const float* mass, const int64_t* node_ptr, int32_t G, int64_t n, float dt,
-                                    float c, float s, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t word0,
-                                    float* kinetic, const float* energy, float* potential, void* stream) {
-  if (n < 0 || G < 0 || !(c >= 0.f && c <= 1.f) || !(s >= 0.f)) return E3K_ERR_INVALID;
-  if (n == 0 || G == 0) return E3K_OK;
-  if (!v || !mass || !node_ptr || (potential && !energy)) return E3K_ERR_INVALID;
-  hipLaunchKernelGGL(e3k::md_kick_langevin_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, f, mass,
-                     node_ptr, G, n, dt, c, s, seed_lo, seed_hi, draw, word0, kinetic, energy, potential);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
-}
-
-extern "C" int e3k_fire_step(float* x, float* v, const float* f, const int64_t* node_ptr, int32_t G, int64_t n, float* state,
-                             float ftol, float dt_max, float maxstep, int32_t n_min, float f_inc, float f_dec, float alpha_start,
-                             float f_alpha, const float* energy, float* energy_record, float* fmax_record, void* stream) {
-  if (n < 0 || G < 0 || !(ftol >= 0.f) || !(dt_max > 0.f) || !(maxstep > 0.f) || n_min < 0) return E3K_ERR_INVALID;
-  if (G == 0) return E3K_OK;
-  if (!node_ptr || !state || (n > 0 && (!x || !v || !f)) || (energy_record && !energy)) return E3K_ERR_INVALID;
-  const e3k::FireParams p{ftol, dt_max, maxstep, (float)n_min, f_inc, f_dec, alpha_start, f_alpha};
-  hipLaunchKernelGGL(e3k::fire_step_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, v, f, node_ptr, G, n,
-                     state, p, energy, energy_record, fmax_record);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
 }

@@ -6,28 +6,12 @@
 //   the loss mean((score std + z)^2) of get_sde_loss_fn with score = -raw / std - x_t  e3_layers/run/sde_utils.py:161-171, :176-187
 //
 // Why counter-based draws: a replayed step whose capped neighbour list overflowed is vetoed on the device and redone eagerly by
-// the host on exactly the same noised batch -- t and z are functions of (seed, draw index, graph / node, word), and the draw index
-// is a device cell the captured step reads (the step counter), so nothing about a draw lives in a generator's state.
+// the host on exactly the same noised batch -- t and z are functions of (seed, draw index, graph / node, word) in the stream of
+// e3k_draw.h (the thermostat's), and the draw index is a device cell the captured step reads (the step counter).
 #include "e3k_common.h"
+#include "e3k_draw.h"
 
 namespace e3k {
-
-// (restated from e3k_nlist.hip, which restates rounded_product of e3k_edge.hip in the same way: mix32, the pair-hash chain over
-//  (seed low, seed high, draw, src, dst) from 0x9E3779B9, and the Box-Muller normal on two 24-bit uniforms)
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x7feb352du;
-  h ^= h >> 15;
-  h *= 0x846ca68bu;
-  h ^= h >> 16;
-  return h;
-}
-
-__device__ __forceinline__ float normal_draw(uint32_t h_node, uint32_t word) {
-  const uint32_t h1 = mix32(h_node ^ (2u * word)), h2 = mix32(h_node ^ (2u * word + 1u));
-  const float u1 = (float)((h1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(h2 >> 8) * 0x1p-24f;
-  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-}
 
 // One thread per node component (and the first G + 1 threads file t).  The time of graph g is the pair hash with src = 0xFFFFFFFF
 // (no node has that index: N < 2^31) and dst = g; a node's threads recompute their graph's t (five integer rounds and two
@@ -41,9 +25,9 @@ __global__ __launch_bounds__(256) void vpsde_perturb_kernel(const float* __restr
                                                             float* __restrict__ z_out, float* __restrict__ std_out) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const uint32_t draw = (uint32_t)draw_cell[0];
-  const uint32_t h_draw = mix32(mix32(mix32(0x9E3779B9u ^ seed_lo) ^ seed_hi) ^ draw);
+  const uint32_t h_draw = draw_prefix(seed_lo, seed_hi, draw);
   const uint32_t h_time = mix32(h_draw ^ 0xFFFFFFFFu);
-  auto time_of = [&](uint32_t g) { return fmaf(span, (float)(mix32(h_time ^ g) >> 8) * 0x1p-24f, eps); };
+  auto time_of = [&](uint32_t g) { return fmaf(span, uniform24(mix32(h_time ^ g)), eps); };
   if (k <= G) t_out[k] = k < G ? time_of((uint32_t)k) : 0.5f;
   if (k >= N * D) return;
   const int64_t i = k / D;

@@ -325,6 +325,12 @@ def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def seed_words(seed: int) -> tuple:
+    """(low, high) 32-bit words of a 64-bit seed: the first two words of the counter-based draw (``csrc/e3k_draw.h``)."""
+    seed = int(seed)
+    return seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+
+
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 

@@ -1959,7 +1959,7 @@ def vpsde_perturb(x0, node_seg, n_graphs: int, beta_0: float, beta_1: float, eps
     x_t, z = torch.empty_like(x0), torch.empty_like(x0)
     std = torch.empty(n, device=x0.device, dtype=torch.float32)
     L.check(L.load().e3k_vpsde_perturb(L.ptr(x0), L.ptr(node_seg), n, d, int(n_graphs), float(beta_0), float(beta_1), float(eps), float(T),
-                                       int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, L.ptr(draw), int(word0), L.ptr(t),
+                                       *L.seed_words(seed), L.ptr(draw), int(word0), L.ptr(t),
                                        L.ptr(x_t), L.ptr(z), L.ptr(std), L.stream_ptr()), "e3k_vpsde_perturb")
     return t, x_t, z, std
 

@@ -73,7 +73,7 @@ _M32 = 0xFFFFFFFF
 
 def _mix32(h):
     """One round of the "lowbias32" finaliser on int64 values in [0, 2^32): an int64 multiply wraps and keeps the low 32 bits, the
-    mask throws the rest away -- the kernel's uint32 arithmetic (``csrc/e3k_nlist.hip: mix32``), bit for bit."""
+    mask throws the rest away -- the kernel's uint32 arithmetic (``csrc/e3k_draw.h: mix32``), bit for bit."""
     h = h ^ (h >> 16)
     h = (h * 0x7feb352d) & _M32
     h = h ^ (h >> 15)
@@ -100,7 +100,7 @@ def pair_hash(seed, draw, src, dst) -> Tensor:
 
 
 def normal_draw(seed, draw, node, word, dtype=torch.float32) -> Tensor:
-    """The counter-based standard normal of the thermostat kernel (``csrc/e3k_nlist.hip: normal_draw``) for (seed, draw index,
+    """The counter-based standard normal of the device's draw stream (``csrc/e3k_draw.h: normal_draw``) for (seed, draw index,
     node, word): ``u1 = ((h1 >> 8) + 1) 2^-24`` in (0, 1] and ``u2 = (h2 >> 8) 2^-24`` in [0, 1) from
     ``h1, h2 = pair_hash(seed, draw, node, 2 word), pair_hash(seed, draw, node, 2 word + 1)`` -- bit for bit the kernel's -- and
     ``sqrt(-2 ln u1) cos(2 pi u2)`` in ``dtype`` through torch (the kernel: fp32 ``logf``, ``sqrtf``, ``cospif``).  Component c of a
@@ -454,8 +454,7 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
                                    L.ptr(offsets), L.ptr(ei), L.ptr(n_edges), L.ptr(seg), L.ptr(state), L.ptr(flag), L.stream_ptr()),
                 "e3k_nlist_fill")
     else:
-        rule = (L.ptr(seg_key), criteria.window, criteria.threshold, int(criteria.keep_all), criteria.seed & _M32,
-                (criteria.seed >> 32) & _M32, L.ptr(rng))
+        rule = (L.ptr(seg_key), criteria.window, criteria.threshold, int(criteria.keep_all), *L.seed_words(criteria.seed), L.ptr(rng))
         L.check(lib.e3k_nlist_count_crit(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), *rule,
                                          L.ptr(counts), L.stream_ptr()), "e3k_nlist_count_crit")
         L.check(lib.e3k_nlist_fill_crit(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), *rule,

@@ -5,7 +5,7 @@ A force evaluation is forward + one backward through the force block: a hundred-
 eagerly, and the neighbour list changes as the atoms move.  ``ReplayedForceField`` pads the batch once to a bucket
 (``run/graph_step.pad_batch``), and captures ``computeEdgeIndexCapped -> model`` in ONE HIP graph (``CapturedStep``: guards,
 re-capture on a knot-table veto and flag polling come with it): the list is rebuilt on the device inside the graph, into a buffer of
-fixed capacity (``csrc/e3k_nlist.hip``).  More edges than the capacity is a REPORTED condition -- ``check()`` raises
+fixed capacity (``csrc/e3k_nlist.hip``); the integrators' kernels are ``csrc/e3k_md.hip``.  More edges than the capacity is a REPORTED condition -- ``check()`` raises
 ``EdgeCapacityExceeded``, ``grow()`` re-pads to a larger bucket and captures again.
 
     ff = ReplayedForceField(model, batch, r_max=5.0)
@@ -160,57 +160,9 @@ class ReplayedForceField:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Integrators and the minimiser.  The per-step updates are kernels of csrc/e3k_nlist.hip on device tensors; host tensors (a stub
-# force field in the rollback tests, the float64 oracle loops) take the same arithmetic in torch.
+# The minimiser's iteration and the integrators' two half steps.  The per-step updates are kernels of csrc/e3k_md.hip on device
+# tensors; host tensors (a stub force field in the rollback tests, the float64 oracle loops) take the same arithmetic in torch.
 # ---------------------------------------------------------------------------------------------------------------------
-def _drift(x, v, f, mass, dt: float) -> None:
-    if x.is_cuda:
-        L.check(L.load().e3k_md_drift(L.ptr(x), L.ptr(v), L.ptr(f), L.ptr(mass), x.shape[0], float(dt), L.stream_ptr()), "e3k_md_drift")
-        return
-    v.add_(f / mass[:, None], alpha=0.5 * dt)
-    x.add_(v, alpha=dt)
-
-
-def _kick(v, f, mass, node_ptr, dt: float, kinetic, energy=None, potential=None) -> None:
-    """``kinetic`` [G] takes the graphs' kinetic energies and ``potential`` [G] a copy of ``energy`` [G] (the force field's static
-    output) in the same launch; None: not wanted."""
-    if v.is_cuda:
-        L.check(L.load().e3k_md_kick(L.ptr(v), L.ptr(f), L.ptr(mass), L.ptr(node_ptr), node_ptr.numel() - 1, v.shape[0], float(dt),
-                                     L.ptr(kinetic), L.ptr(energy), L.ptr(potential), L.stream_ptr()), "e3k_md_kick")
-        return
-    _kick_host(v, f, mass, node_ptr, dt, kinetic, energy, potential)
-
-
-def _kick_host(v, f, mass, node_ptr, dt: float, kinetic, energy, potential) -> None:
-    if f is not None:
-        v.add_(f / mass[:, None], alpha=0.5 * dt)
-    if potential is not None:
-        potential.copy_(energy)
-    if kinetic is not None:
-        per_node = 0.5 * mass * (v * v).sum(1)
-        for g in range(node_ptr.numel() - 1):
-            kinetic[g] = per_node[int(node_ptr[g]):int(node_ptr[g + 1])].sum()
-
-
-THERMOSTAT_WORD, THERMALIZE_WORD = 0, 4      # first hash word of a step's draw and of thermalize()'s: the streams never coincide
-
-
-def _kick_langevin(v, f, mass, node_ptr, dt: float, c: float, s: float, seed: int, draw: int, word0: int, kinetic, energy=None,
-                   potential=None) -> None:
-    """``v <- c v + (s / sqrt(m)) xi``, then ``_kick`` (``f`` None: no kick, the records only).  ``xi`` is
-    ``normal_draw(seed, draw, node, word0 + component)``: counter-based, the same bits whenever the same step is done again."""
-    if v.is_cuda:
-        L.check(L.load().e3k_md_kick_langevin(L.ptr(v), L.ptr(f), L.ptr(mass), L.ptr(node_ptr), node_ptr.numel() - 1, v.shape[0],
-                                              float(dt), float(c), float(s), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
-                                              draw & 0xFFFFFFFF, int(word0), L.ptr(kinetic), L.ptr(energy), L.ptr(potential),
-                                              L.stream_ptr()), "e3k_md_kick_langevin")
-        return
-    node = torch.arange(v.shape[0], dtype=torch.int64)[:, None]
-    xi = normal_draw(seed, draw, node, word0 + torch.arange(3, dtype=torch.int64)[None, :], v.dtype)
-    v.mul_(c).add_((s / torch.sqrt(mass))[:, None] * xi)
-    _kick_host(v, f, mass, node_ptr, dt, kinetic, energy, potential)
-
-
 def _fire_step(x, v, f, node_ptr, state, fire: "Fire", energy=None, energy_record=None, fmax_record=None) -> None:
     """One FIRE iteration on every graph with the graph's own row of ``state`` [G, 4] = (dt, alpha, n_pos, fmax): the rule in
     ``Fire``'s docstring (``e3k_fire_step``; the torch path walks the graphs one by one with the same arithmetic)."""
@@ -258,7 +210,7 @@ def _fire_step_torch(x, v, f, node_ptr, state, fire, energy=None, energy_record=
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Bond-length constraints (csrc/e3k_constraint.hip): SHAKE inside the first half step, RATTLE inside the second.
+# Bond-length constraints (csrc/e3k_md.hip): SHAKE inside the first half step, RATTLE inside the second.
 # ---------------------------------------------------------------------------------------------------------------------
 MAX_SATELLITES = 4
 
@@ -413,19 +365,32 @@ def _table_args(con):
     return (L.ptr(con.star_ptr), L.ptr(con.star_atom), L.ptr(con.star_len), con.n_stars, con.n_slots, L.ptr(con.free_atom), con.n_free)
 
 
-def _drift_shake(x, v, f, mass, dt: float, con) -> None:
-    """``_drift`` with SHAKE on the stars (``e3k_md_drift_shake``).  ``f`` None: positions only -- the lengths are enforced at the
-    present positions along the present bonds, nothing else moves."""
+# ---------------------------------------------------------------------------------------------------------------------
+# The two half steps of every integrator: one function each.  On device tensors a function picks the C entry; on host tensors it
+# runs one torch sequence of the same arithmetic.
+# ---------------------------------------------------------------------------------------------------------------------
+THERMOSTAT_WORD, THERMALIZE_WORD = 0, 4      # first hash word of a step's draw and of thermalize()'s: the streams never coincide
+
+
+def _drift(x, v, f, mass, dt: float, con=None) -> None:
+    """First half: ``v += dt/2 f / m``, ``x += dt v``, with SHAKE on the stars of ``con`` (``e3k_md_drift`` /
+    ``e3k_md_drift_shake``).  ``f`` None (constrained only): positions only -- the lengths are enforced at the present positions
+    along the present bonds, nothing else moves."""
     if x.is_cuda:
-        L.check(L.load().e3k_md_drift_shake(L.ptr(x), L.ptr(v), L.ptr(f), L.ptr(mass), x.shape[0], float(dt), *_table_args(con),
-                                            con.tol, con.max_iter, L.ptr(con._shake_counter), L.stream_ptr()), "e3k_md_drift_shake")
+        if con is None:
+            L.check(L.load().e3k_md_drift(L.ptr(x), L.ptr(v), L.ptr(f), L.ptr(mass), x.shape[0], float(dt), L.stream_ptr()), "e3k_md_drift")
+        else:
+            L.check(L.load().e3k_md_drift_shake(L.ptr(x), L.ptr(v), L.ptr(f), L.ptr(mass), x.shape[0], float(dt), *_table_args(con),
+                                                con.tol, con.max_iter, L.ptr(con._shake_counter), L.stream_ptr()), "e3k_md_drift_shake")
         return
-    idx, valid = con._idx, con._valid
-    x0 = x[idx]                                         # [S, 5, 3]: the old positions, before anything moves
+    stars = con is not None and con.n_stars > 0
+    if stars:
+        idx, valid = con._idx, con._valid
+        x0 = x[idx]                                     # [S, 5, 3]: the old positions, before anything moves
     if f is not None:
         v.add_(f / mass[:, None], alpha=0.5 * dt)
         x.add_(v, alpha=dt)
-    if con.n_stars == 0:
+    if not stars:
         return
     ro = x0[:, 1:] - x0[:, :1]                          # the old bond vectors; everything below is relative to the centre's old position
     p = x0 - x0[:, :1]
@@ -461,24 +426,37 @@ def _drift_shake(x, v, f, mass, dt: float, con) -> None:
     con.counters[0] += int(fail.sum())
 
 
-def _kick_rattle(x, v, f, mass, node_ptr, dt: float, c: float, s: float, seed: int, draw: int, word0: int, con, kinetic, energy=None,
-                 potential=None) -> None:
-    """``_kick_langevin`` with RATTLE on the stars (``e3k_md_kick_rattle``): the velocities are projected along the present bonds
-    and ``kinetic`` is the energy of the projected velocities."""
+def _kick_langevin(v, f, mass, node_ptr, dt: float, c: float, s: float, seed: int, draw: int, word0: int, kinetic, energy=None,
+                   potential=None, *, con=None, x=None) -> None:
+    """Second half: ``v <- c v + (s / sqrt(m)) xi`` (``(c, s) = (1, 0)``: no thermostat, nothing is drawn), then
+    ``v += dt/2 f / m`` (``f`` None: no kick), then RATTLE on the stars of ``con`` along the present bonds in ``x``, then the
+    records: ``kinetic`` [G] takes the graphs' kinetic energies (of the projected velocities) and ``potential`` [G] a copy of
+    ``energy`` [G] (the force field's static output) in the same launch; None: not wanted.  ``xi`` is
+    ``normal_draw(seed, draw, node, word0 + component)``: counter-based, the same bits whenever the same step is done again.
+    Entries: ``e3k_md_kick_rattle`` with constraints, else ``e3k_md_kick`` for the plain kick with forces and
+    ``e3k_md_kick_langevin`` for everything else -- one kernel behind both."""
+    plain = c == 1.0 and s == 0.0
     if v.is_cuda:
-        L.check(L.load().e3k_md_kick_rattle(L.ptr(v), L.ptr(f), L.ptr(mass), L.ptr(node_ptr), node_ptr.numel() - 1, v.shape[0], float(dt),
-                                            float(c), float(s), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, draw & 0xFFFFFFFF,
-                                            int(word0), L.ptr(kinetic), L.ptr(energy), L.ptr(potential), L.ptr(x), *_table_args(con),
-                                            L.ptr(con.graph_star_ptr), L.ptr(con.graph_free_ptr), con.tol, con.max_iter,
-                                            L.ptr(con._rattle_counter), L.stream_ptr()), "e3k_md_kick_rattle")
+        lib, n_graphs = L.load(), node_ptr.numel() - 1
+        if con is None and plain and f is not None:
+            L.check(lib.e3k_md_kick(L.ptr(v), L.ptr(f), L.ptr(mass), L.ptr(node_ptr), n_graphs, v.shape[0], float(dt), L.ptr(kinetic),
+                                    L.ptr(energy), L.ptr(potential), L.stream_ptr()), "e3k_md_kick")
+            return
+        head = (L.ptr(v), L.ptr(f), L.ptr(mass), L.ptr(node_ptr), n_graphs, v.shape[0], float(dt), float(c), float(s),
+                *L.seed_words(seed), draw & 0xFFFFFFFF, int(word0), L.ptr(kinetic), L.ptr(energy), L.ptr(potential))
+        if con is None:
+            L.check(lib.e3k_md_kick_langevin(*head, L.stream_ptr()), "e3k_md_kick_langevin")
+        else:
+            L.check(lib.e3k_md_kick_rattle(*head, L.ptr(x), *_table_args(con), L.ptr(con.graph_star_ptr), L.ptr(con.graph_free_ptr),
+                                           con.tol, con.max_iter, L.ptr(con._rattle_counter), L.stream_ptr()), "e3k_md_kick_rattle")
         return
-    if not (c == 1.0 and s == 0.0):      # (the plain kick draws nothing: the NVE driver's path, bit for bit)
+    if not plain:
         node = torch.arange(v.shape[0], dtype=torch.int64)[:, None]
         xi = normal_draw(seed, draw, node, word0 + torch.arange(3, dtype=torch.int64)[None, :], v.dtype)
         v.mul_(c).add_((s / torch.sqrt(mass))[:, None] * xi)
     if f is not None:
         v.add_(f / mass[:, None], alpha=0.5 * dt)
-    if con.n_stars:
+    if con is not None and con.n_stars:
         idx, valid = con._idx, con._valid
         xs = x[idx]
         r = xs[:, 1:] - xs[:, :1]
@@ -487,7 +465,7 @@ def _kick_rattle(x, v, f, mass, node_ptr, dt: float, c: float, s: float, seed: i
         inv_m = 1.0 / mass[idx]
         on_k = valid[:, 1:]
         fail = torch.zeros(con.n_stars, dtype=torch.bool)
-        for it in range(con.max_iter + 1):      # passes as in _drift_shake
+        for it in range(con.max_iter + 1):      # passes as in _drift
             moved = False
             for k in range(con.max_sat):
                 rv = (r[:, k] * (u[:, 1 + k] - u[:, 0])).sum(-1)
@@ -505,7 +483,12 @@ def _kick_rattle(x, v, f, mass, node_ptr, dt: float, c: float, s: float, seed: i
                 break
         v[idx[valid]] = u[valid]
         con.counters[1] += int(fail.sum())
-    _kick_host(v, None, mass, node_ptr, dt, kinetic, energy, potential)
+    if potential is not None:
+        potential.copy_(energy)
+    if kinetic is not None:
+        per_node = 0.5 * mass * (v * v).sum(1)
+        for g in range(node_ptr.numel() - 1):
+            kinetic[g] = per_node[int(node_ptr[g]):int(node_ptr[g + 1])].sum()
 
 
 class _ChunkedDriver:
@@ -639,13 +622,9 @@ class VelocityVerlet(_ChunkedDriver):
         kT = getattr(self, "kT", None) if kT is None else float(kT)
         if kT is None or kT < 0:
             raise ValueError("thermalize() needs kT >= 0")
-        if self.constraints is not None:      # drawn and projected onto the constraints in the one launch
-            _kick_rattle(self.x, self.v, None, self.mass, self.ff.node_ptr, 0.0, 0.0, kT ** 0.5, self.seed, self.thermalizations,
-                         THERMALIZE_WORD, self.constraints, None)
-            self.thermalizations += 1
-            return
+        # (with constraints: drawn and projected onto them in the one launch)
         _kick_langevin(self.v, None, self.mass, self.ff.node_ptr, 0.0, 0.0, kT ** 0.5, self.seed, self.thermalizations, THERMALIZE_WORD,
-                       None)
+                       None, con=self.constraints, x=self.x)
         self.thermalizations += 1
 
     @property
@@ -662,8 +641,8 @@ class VelocityVerlet(_ChunkedDriver):
         con = self.constraints
         if con is None:
             raise ValueError("project() needs constraints")
-        _drift_shake(self.x, self.v, None, self.mass, 0.0, con)
-        _kick_rattle(self.x, self.v, None, self.mass, self.ff.node_ptr, 0.0, 1.0, 0.0, 0, 0, 0, con, None)
+        _drift(self.x, self.v, None, self.mass, 0.0, con)
+        _kick_langevin(self.v, None, self.mass, self.ff.node_ptr, 0.0, 1.0, 0.0, 0, 0, 0, None, con=con, x=self.x)
         self._forces = None      # the positions moved
         failure = self._chunk_failure(0, 0)
         if failure is not None:
@@ -699,21 +678,13 @@ class VelocityVerlet(_ChunkedDriver):
         if self.constraints is not None:
             self.constraints.counters.zero_()          # what the thrown-away steps counted
 
-    def _second_half(self, k: int, forces, energy, kinetic, potential) -> None:
-        _kick(self.v, forces, self.mass, self.ff.node_ptr, self.dt, kinetic, energy, potential)
-
     def _step(self, i: int, k: int) -> None:
         con = self.constraints
-        if con is None:
-            _drift(self.x, self.v, self._chunk_forces, self.mass, self.dt)
-            energy, self._chunk_forces = self.ff.evaluate()
-            self._second_half(k, self._chunk_forces, energy, self._kin[i], self._pot[i])
-            return
-        _drift_shake(self.x, self.v, self._chunk_forces, self.mass, self.dt, con)
+        _drift(self.x, self.v, self._chunk_forces, self.mass, self.dt, con)
         energy, self._chunk_forces = self.ff.evaluate()
         c, s = self._ou()
-        _kick_rattle(self.x, self.v, self._chunk_forces, self.mass, self.ff.node_ptr, self.dt, c, s, self.seed, k, THERMOSTAT_WORD, con,
-                     self._kin[i], energy, self._pot[i])
+        _kick_langevin(self.v, self._chunk_forces, self.mass, self.ff.node_ptr, self.dt, c, s, self.seed, k, THERMOSTAT_WORD,
+                       self._kin[i], energy, self._pot[i], con=con, x=self.x)
 
     def run(self, n_steps: int, check_every: int = 50):
         """``n_steps`` steps; returns {"potential": [n_steps, G], "kinetic": [n_steps, G]} (per graph, after every step); the state
@@ -752,10 +723,6 @@ class Langevin(VelocityVerlet):
 
     def _ou(self):
         return self.c, self.s
-
-    def _second_half(self, k: int, forces, energy, kinetic, potential) -> None:
-        _kick_langevin(self.v, forces, self.mass, self.ff.node_ptr, self.dt, self.c, self.s, self.seed, k, THERMOSTAT_WORD, kinetic,
-                       energy, potential)
 
 
 class Fire(_ChunkedDriver):

@@ -665,8 +665,8 @@ int e3k_radius_graph_fill(const float* pos, const int32_t* graph_start, const in
                           int64_t* edge_index, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Capped neighbour list (csrc/e3k_nlist.hip): the radius graph above into a buffer of FIXED size, for loops that
- * evaluate a model over and over while the atoms move inside one captured HIP graph.
+ * Capped neighbour list (csrc/e3k_nlist.hip; the integrators further down: csrc/e3k_md.hip): the radius graph above into a
+ * buffer of FIXED size, for loops that evaluate a model over and over while the atoms move inside one captured HIP graph.
  * Replaces computeEdgeIndex (e3_layers/data/compute_edge.py:38-113) where the sampling loop drops and rebuilds
  * edge_index after every update (e3_layers/run/sde_sampling.py:236-241) and where an MD driver (torchMD.ipynb) calls the
  * model on moved positions: same distance test, same edge order, no pre-existing edges, nothing read back by the host.
@@ -749,7 +749,7 @@ int e3k_fire_step(float* x, float* v, const float* f, const int64_t* node_ptr, i
                   float dt_max, float maxstep, int32_t n_min, float f_inc, float f_dec, float alpha_start, float f_alpha,
                   const float* energy, float* energy_record, float* fmax_record, void* stream);
 
-/* Bond-length constraints for the two half steps above (csrc/e3k_constraint.hip; SHAKE: Ryckaert, Ciccotti, Berendsen 1977; RATTLE:
+/* Bond-length constraints for the two half steps above (csrc/e3k_md.hip; SHAKE: Ryckaert, Ciccotti, Berendsen 1977; RATTLE:
  * Andersen 1983).  The constraints form disjoint STARS -- a centre with 1..4 satellites, every constraint centre--satellite, no atom
  * in two stars (the bonds-to-hydrogen set) -- so one thread owns a star: no atomics in the arithmetic, the same bits every run.
  * Tables, built once by the caller:
@@ -828,7 +828,7 @@ int e3k_adam_ema_step_vetoed(float* param, const float* grad, float* exp_avg, fl
  * on a capped neighbour list (run/score_step.py).  Replaces t ~ U(eps, T) and VPSDE.marginal (e3_layers/run/sde_utils.py:54-66,
  * :143-160) and the loss of get_sde_loss_fn (:161-171 with the score of :176-187), whose draws come from a torch generator: here
  * every draw is a function of (seed, draw index, graph or node, word), the pair hash and the normal xi of e3k_md_kick_langevin
- * above, so a step that has to be redone is redone on exactly the same noised batch.
+ * above (csrc/e3k_draw.h: one definition for both), so a step that has to be redone is redone on exactly the same noised batch.
  *
  * e3k_vpsde_perturb: one launch, one thread per node component.  x0, x_t, z [N, D], std [N], t [G + 1], node_seg [N] int64;
  *   draw: one DEVICE int64 read by every thread and not written (its low 32 bits are the draw index).  Per graph g < G:

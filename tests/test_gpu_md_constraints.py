@@ -1,4 +1,4 @@
-"""Bond-length constraints on the device (csrc/e3k_constraint.hip: ``e3k_md_drift_shake``, ``e3k_md_kick_rattle``): single calls
+"""Bond-length constraints on the device (csrc/e3k_md.hip: ``e3k_md_drift_shake``, ``e3k_md_kick_rattle``): single calls
 against the float64 torch path converged to 1e-12, with the float32 torch path on the CPU as the yardstick; the drivers through the
 kernels on stub fields that live on the device (the host tests' systems and bounds); and on the replayed force field against the
 float64 oracle loop."""
@@ -52,7 +52,7 @@ def test_single_calls_follow_the_converged_float64_projection(dev, masses):
                                     ("dev", torch.float32, dev, {})):
         con = _constraints(pairs, d0, x, mass, sizes, dtype, device, **kw)
         xs, vs, fs, ms = (t.to(dtype).to(device).clone().contiguous() for t in (x, v, f, mass))
-        M._drift_shake(xs, vs, fs, ms, dt, con)
+        M._drift(xs, vs, fs, ms, dt, con)
         runs[name] = [con, xs.clone(), vs.clone()]
     x_mid = runs["f64"][1].float().double()              # the common input of the second call: the converged positions in fp32
     kin = {}
@@ -60,7 +60,7 @@ def test_single_calls_follow_the_converged_float64_projection(dev, masses):
         con = runs[name][0]
         xs, vs, fs, ms = (t.to(dtype).to(device).clone().contiguous() for t in (x_mid, v, f, mass))
         kin[name] = torch.zeros(len(sizes), dtype=dtype, device=device)
-        M._kick_rattle(xs, vs, fs, ms, node_ptr_of(sizes, device), dt, 1.0, 0.0, 0, 0, 0, con, kin[name])
+        M._kick_langevin(vs, fs, ms, node_ptr_of(sizes, device), dt, 1.0, 0.0, 0, 0, 0, kin[name], con=con, x=xs)
         runs[name].append(vs.clone())
         assert con.counters.tolist() == [0, 0], (name, con.counters.tolist())
     con, x_dev, v_dev, v2_dev = runs["dev"]
@@ -99,7 +99,7 @@ def test_a_projection_leaves_every_stars_momentum_where_it_was(dev):
     con = _constraints(pairs, d0, x, mass, sizes, torch.float32, dev)
     xs, vs, ms = (t.float().to(dev).contiguous() for t in (x, v, mass))
     before = vs.clone()
-    M._kick_rattle(xs, vs, None, ms, node_ptr_of(sizes, dev), 0.0, 1.0, 0.0, 0, 0, 0, con, None)
+    M._kick_langevin(vs, None, ms, node_ptr_of(sizes, dev), 0.0, 1.0, 0.0, 0, 0, 0, None, con=con, x=xs)
     assert con.counters.tolist() == [0, 0]
     assert_constraints_hold(con, xs, vs, EPS32, "after the projection")
     assert torch.equal(vs[con.free_atom], before[con.free_atom]) and not torch.equal(vs, before)

@@ -1,4 +1,4 @@
-"""The thermostat kick and the FIRE iteration (csrc/e3k_nlist.hip: e3k_md_kick_langevin, e3k_fire_step) called directly, against
+"""The thermostat kick and the FIRE iteration (csrc/e3k_md.hip: e3k_md_kick_langevin, e3k_fire_step) called directly, against
 float64 restatements on the shapes of tests/test_gpu_md_kernels.py: graphs of one atom, more than a wave's 64 lanes, none, and rows
 behind the real nodes that must not move.
 
@@ -94,7 +94,7 @@ def test_thermostat_kick_against_float64(dev, seed):
     n_graphs, draw = len(SIZES), 41
     fd, md, ptr, ed = (t.clone().to(dev).contiguous() for t in (f, mass, node_ptr, energy))
 
-    def run(draw, forces=fd):
+    def run(draw, forces=fd, s=s):
         vd = v.clone().to(dev).contiguous()
         record = torch.full((2, n_graphs + 2), -7.0, device=dev)      # [kinetic | potential], a canary on either side of each row
         _kick_langevin(vd[:n], None if forces is None else forces[:n], md[:n], ptr, DT, c, s, SEED, draw, 0, record[0, 1:-1], ed,
@@ -126,18 +126,52 @@ def test_thermostat_kick_against_float64(dev, seed):
     vd4, _ = run(draw, None)
     v64_4 = c32 * v[:n].double() + amp[:, None] * xi
     assert bool(((vd4[:n].double().cpu() - v64_4).abs() <= 1e-6 * float(v64_4.abs().max()) + amp[:, None] * XI_BOUND).all())
+    # friction without noise: s = 0 at the case's c, with forces -- nothing is drawn, so the bound's noise term is zero
+    vd5, record5 = run(draw, fd, 0.0)
+    v64_5 = c32 * v[:n].double() + 0.5 * DT * f[:n].double() / mass[:n].double()[:, None]
+    err5 = (vd5[:n].double().cpu() - v64_5).abs()
+    print(f"friction alone seed {seed}: worst |v - v64| {float(err5.max()):.3e}, bound {1e-6 * float(v64_5.abs().max()):.3e}")
+    assert bool((err5 <= 1e-6 * float(v64_5.abs().max())).all()), float(err5.max())
+    per_node5 = 0.5 * mass[:n].double() * (v64_5 * v64_5).sum(1)
+    want5 = torch.stack([per_node5[int(node_ptr[g]):int(node_ptr[g + 1])].sum() for g in range(n_graphs)])
+    got5 = record5[0, 1:-1].double().cpu()
+    assert ((got5 - want5).abs() <= 1e-5 * want5.abs()).all(), (got5, want5)
 
 
 def test_thermostat_kick_without_thermostat_is_the_plain_kick_bit_for_bit(dev):
-    from e3_layers_amd.run.md import _kick, _kick_langevin
+    from e3_layers_amd.backend import lib as L
 
     n, _, v, f, mass, node_ptr = _state(dev, 3)
     fd, md, ptr = (t.clone().to(dev).contiguous() for t in (f, mass, node_ptr))
     va, vb = v.clone().to(dev).contiguous(), v.clone().to(dev).contiguous()
     ka, kb = torch.empty(len(SIZES), device=dev), torch.empty(len(SIZES), device=dev)
-    _kick(va[:n], fd[:n], md[:n], ptr, DT, ka)
-    _kick_langevin(vb[:n], fd[:n], md[:n], ptr, DT, 1.0, 0.0, SEED, 5, 0, kb)
+    L.check(L.load().e3k_md_kick(L.ptr(va[:n]), L.ptr(fd[:n]), L.ptr(md[:n]), L.ptr(ptr), len(SIZES), n, DT, L.ptr(ka), None, None,
+                                 L.stream_ptr()), "e3k_md_kick")
+    L.check(L.load().e3k_md_kick_langevin(L.ptr(vb[:n]), L.ptr(fd[:n]), L.ptr(md[:n]), L.ptr(ptr), len(SIZES), n, DT, 1.0, 0.0,
+                                          *L.seed_words(SEED), 5, 0, L.ptr(kb), None, None, L.stream_ptr()), "e3k_md_kick_langevin")
     assert torch.equal(va, vb) and torch.equal(ka, kb)
+
+
+@pytest.mark.parametrize("word0", [0, 4])
+def test_score_step_noise_is_the_thermostat_stream_bit_for_bit(dev, word0):
+    """``e3k_vpsde_perturb``'s z (D = 3, every node in a real graph) and ``e3k_md_kick_langevin``'s velocities at c = 0, s = 1, unit
+    masses, no forces -- 0 v + 1 xi is xi exactly -- for the same seed, draw index and first word: one stream (csrc/e3k_draw.h), so
+    ``torch.equal``.  The draw index is a device cell there and an argument here; both take it modulo 2^32."""
+    from e3_layers_amd.backend import ops
+    from e3_layers_amd.run.md import _kick_langevin
+
+    n = sum(SIZES)
+    ptr = torch.tensor([0] + list(np.cumsum(SIZES)), dtype=torch.int64, device=dev)
+    node_seg = torch.repeat_interleave(torch.arange(len(SIZES), device=dev), torch.tensor(SIZES, device=dev)).contiguous()
+    x0 = torch.randn(n, 3, generator=torch.Generator().manual_seed(11)).to(dev)
+    mass = torch.ones(n, device=dev)
+    for draw in (7, (1 << 32) + 7):
+        cell = torch.tensor([draw], dtype=torch.int64, device=dev)
+        _, _, z, _ = ops.vpsde_perturb(x0, node_seg, len(SIZES), 0.1, 20.0, 1e-3, 1.0, SEED, cell, word0)
+        v = torch.full((n, 3), 3.0, device=dev)
+        _kick_langevin(v, None, mass, ptr, 0.0, 0.0, 1.0, SEED, draw, word0, None)
+        assert float(z.abs().max()) > 1.0                       # (something was drawn)
+        assert torch.equal(z, v), (draw, float((z - v).abs().max()))
 
 
 # ---- FIRE -----------------------------------------------------------------------------------------------------------------------

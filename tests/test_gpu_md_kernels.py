@@ -1,4 +1,4 @@
-"""The velocity-Verlet half-step kernels (csrc/e3k_nlist.hip: e3k_md_drift, e3k_md_kick) called directly, against the same
+"""The velocity-Verlet half-step kernels (csrc/e3k_md.hip: e3k_md_drift, e3k_md_kick) called directly, against the same
 arithmetic in float64 torch: random masses (the per-node mass indexing), graphs of unequal sizes -- one atom, more than a wave's
 64 lanes, an empty graph -- (the per-graph placement of the kinetic energies), and rows behind the real nodes that must not move.
 
@@ -44,7 +44,7 @@ def test_drift_kernel_uses_each_nodes_mass_and_leaves_the_tail_alone(dev):
 
 
 def test_kick_kernel_files_kinetic_and_potential_energy_per_graph(dev):
-    from e3_layers_amd.run.md import _kick
+    from e3_layers_amd.run.md import _kick_langevin
 
     n, _, v, f, mass, node_ptr = _state(dev, 1)
     n_graphs = len(SIZES)
@@ -52,7 +52,7 @@ def test_kick_kernel_files_kinetic_and_potential_energy_per_graph(dev):
     energy = torch.randn(n_graphs, generator=torch.Generator().manual_seed(2)).to(dev)
     record = torch.full((2, n_graphs + 2), -7.0, device=dev)       # [kinetic | potential], a canary on either side of each row
     kin, pot = record[0, 1:-1], record[1, 1:-1]
-    _kick(vd[:n], fd[:n], md[:n], ptr, DT, kin, energy, pot)
+    _kick_langevin(vd[:n], fd[:n], md[:n], ptr, DT, 1.0, 0.0, 0, 0, 0, kin, energy, pot)
     torch.cuda.synchronize()
     v64 = v[:n].double() + 0.5 * DT * f[:n].double() / mass[:n].double()[:, None]
     per_node = 0.5 * mass[:n].double() * (v64 * v64).sum(1)
@@ -67,5 +67,5 @@ def test_kick_kernel_files_kinetic_and_potential_energy_per_graph(dev):
     # fixed summation order: the same bits on a second run from the same state
     vd2 = v.to(dev).contiguous()
     kin2 = torch.empty(n_graphs, device=dev)
-    _kick(vd2[:n], fd[:n], md[:n], ptr, DT, kin2)
+    _kick_langevin(vd2[:n], fd[:n], md[:n], ptr, DT, 1.0, 0.0, 0, 0, 0, kin2)
     assert torch.equal(kin2, kin) and torch.equal(vd2, vd)

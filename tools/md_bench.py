@@ -134,22 +134,24 @@ def replay_start(md, ff, x0, v0):
 
 
 def replay_steps(md, ff, n_steps):
-    """The launches of ``VelocityVerlet.run``'s inner loop, and nothing else: ``run`` closes a chunk with ``check()``, a host
-    synchronisation that would sit between the two events -- the caller checks after the closing event instead."""
+    """The launches of ``VelocityVerlet.run``'s inner loop (plain, thermostatted or constrained: what ``md`` is), and nothing else:
+    ``run`` closes a chunk with ``check()``, a host synchronisation that would sit between the two events -- the caller checks after
+    the closing event instead."""
     from e3_layers_amd.run import md as M
 
     n_graphs = ff.node_ptr.numel() - 1
     pot = torch.zeros(n_steps, n_graphs, device=ff.dev)
     kin = torch.zeros_like(pot)
-    forces = md._forces
+    forces, con, (c, s) = md._forces, md.constraints, md._ou()
 
     def loop():
         nonlocal forces
         t0 = time.perf_counter()
         for i in range(n_steps):
-            M._drift(ff.pos, md.v, forces, md.mass, md.dt)
+            M._drift(ff.pos, md.v, forces, md.mass, md.dt, con)
             energy, forces = ff.evaluate()
-            md._second_half(i, forces, energy, kin[i], pot[i])      # e3k_md_kick, or e3k_md_kick_langevin with draw index i
+            M._kick_langevin(md.v, forces, md.mass, ff.node_ptr, md.dt, c, s, md.seed, i, M.THERMOSTAT_WORD, kin[i], energy, pot[i],
+                             con=con, x=ff.pos)      # e3k_md_kick, e3k_md_kick_langevin or e3k_md_kick_rattle, with draw index i
         return time.perf_counter() - t0
 
     return loop
@@ -170,28 +172,6 @@ def bonds_to_hydrogen(batch, x0, ff, reach=1.3):
     return BondConstraints(pairs, pos=x0, node_ptr=ff.node_ptr, masses=mass), mass
 
 
-def constrained_steps(md, ff, n_steps):
-    """The launches of the constrained ``VelocityVerlet._step`` (``e3k_md_drift_shake``, the graph, ``e3k_md_kick_rattle``), as
-    ``replay_steps`` issues the plain ones."""
-    from e3_layers_amd.run import md as M
-
-    n_graphs = ff.node_ptr.numel() - 1
-    pot = torch.zeros(n_steps, n_graphs, device=ff.dev)
-    kin = torch.zeros_like(pot)
-    forces, con = md._forces, md.constraints
-
-    def loop():
-        nonlocal forces
-        t0 = time.perf_counter()
-        for i in range(n_steps):
-            M._drift_shake(ff.pos, md.v, forces, md.mass, md.dt, con)
-            energy, forces = ff.evaluate()
-            M._kick_rattle(ff.pos, md.v, forces, md.mass, ff.node_ptr, md.dt, 1.0, 0.0, 0, i, M.THERMOSTAT_WORD, con, kin[i], energy, pot[i])
-        return time.perf_counter() - t0
-
-    return loop
-
-
 def bench_constraints(n_mol, steps, warmup, reps, dt, dev):
     """The constrained step against the plain step of the same build on ONE force field, the same masses and the same (projected)
     start: the two differ in their two launches outside the graph."""
@@ -205,7 +185,6 @@ def bench_constraints(n_mol, steps, warmup, reps, dt, dev):
     ff.pos.copy_(x0)
     mds["constrained"].project()
     v0 = mds["constrained"].v.clone()             # both start on the constraint surface
-    loops = {"plain": replay_steps, "constrained": constrained_steps}
     rows = {k: [] for k in ("plain", "constrained", "plain_host", "constrained_host")}
     for name, md in mds.items():
         replay_start(md, ff, x0, v0)
@@ -213,7 +192,7 @@ def bench_constraints(n_mol, steps, warmup, reps, dt, dev):
     for _ in range(reps):
         for name, md in mds.items():
             replay_start(md, ff, x0, v0)
-            ms, host = timed(loops[name](md, ff, steps))
+            ms, host = timed(replay_steps(md, ff, steps))
             ff.check()
             rows[name].append(ms / steps)
             rows[name + "_host"].append(1e3 * host / steps)
