@@ -135,7 +135,16 @@ struct Seg {
     e3k_gemm_segment& sg = s[n - 1];
     sg.n_keys = n_keys; sg.perm = perm; sg.groups_dev = bounds; sg.b_key_stride = L->d.ld_m;
   }
-  int run(int wgrad, void* st) {
+  // rider (weight gradients only): the knot-table transpose that goes out WITH round 0 (e3k_wgrad_with_table_bwd), or on its own
+  // when the sets have no round at all
+  struct Rider {
+    const float *g_w, *coef;
+    const int32_t *bin_ptr, *bin_seg, *bin_perm;
+    int64_t E;
+    int32_t K, W;
+    float *ws, *g_T;
+  };
+  int run(int wgrad, void* st, const Rider* rider = nullptr) {
     for (int r = 0;; ++r) {
       e3k_gemm_segment round[SEG_MAX];
       int m = 0;
@@ -148,8 +157,13 @@ struct Seg {
         sg.n_templates = end - beg;
         round[m++] = sg;
       }
+      const Rider* rd = r == 0 ? rider : nullptr;
+      if (!m && rd)
+        return e3k_rtable_interp_bwd(rd->g_w, rd->coef, nullptr, rd->bin_ptr, rd->bin_seg, rd->bin_perm, rd->E, rd->K, rd->W, rd->ws, rd->g_T, 0, st);
       if (!m) return E3K_OK;
-      const int rc = e3k_gemm_multi(round, m, wgrad, st);
+      const int rc = rd ? e3k_wgrad_with_table_bwd(round, m, rd->g_w, rd->coef, nullptr, rd->bin_ptr, rd->bin_seg, rd->bin_perm, rd->E, rd->K,
+                                                   rd->W, rd->ws, rd->g_T, 0, st)
+                        : e3k_gemm_multi(round, m, wgrad, st);
       if (rc != E3K_OK) return rc;
     }
   }
@@ -420,7 +434,7 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
     }
     return E3K_OK;
   };
-  auto weight_grads = [&](bool with_g_conv, bool with_lin1, void* st) -> int {
+  auto weight_grads = [&](bool with_g_conv, bool with_lin1, void* st, const Seg::Rider* rider = nullptr) -> int {
     Seg g;
     if (with_g_conv && need_post) g.add(L, POST_WGRAD, a->mid, a->gb_post, const_cast<float*>(a->g_conv), a->N);
     if (with_g_conv && want_sc) {
@@ -429,7 +443,7 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       g.add_keyed(L, SC_WGRAD, a->x_cf, a->gm, const_cast<float*>(a->g_conv), a->N, a->perm, a->bounds, a->n_keys);
     }
     if (with_lin1 && need_lin1) g.add(L, LIN1_WGRAD, a->x_cf, a->gb_lin1, a->g_x1, a->N);
-    return g.run(1, st);
+    return g.run(1, st, rider);
   };
   // the weight gradients that need only g_conv start BESIDE tp_bwd_x.  (Starting all three Linears' behind it, in one call, won in
   // round 3 -- 256 molecules 5.34 -> 5.30 ms, 192: 4.51 -> 4.47 --; with round 4's kernels the early start wins again, see the
@@ -449,6 +463,12 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   // already runs beside the main stream's GEMMs, and stays
   const bool fused_xw_s = a->fuse_xw && !fused_xw && need_x1 && !in_kernel_table(d, r) && need_radial_side && a->E > 0 && a->g_w && a->x1 &&
                           r.w && side == main;
+  // One stream, the fused walk, a table: the transpose (an HBM stream without LDS) rides in the launch of the weight gradients
+  // (MFMA and LDS) at the end of the layer -- nothing before that reads g_T when the radial stack's backward takes the rows later.
+  // Forked, the two run on streams of their own; a layer profiled for the transpose keeps its own launch, which the record times.
+  const bool rtable_timed = L->prof_cap > 0 && ((L->prof_mask >> E3K_PROF_RTABLE_BWD) & 1u);
+  const bool ride = fused_xw && r.use_table && side == main && side3 == main && !rtable_timed && a->g_T && a->table_ws &&
+                    (r.have_rows || !(need_last || need_hidden || a->need_radial));
   if (need_x1) {
     if (!a->g_x1) return E3K_ERR_INVALID;
     if (!d.tp_bwd_x_overwrites && e3k::zero_fill(a->g_x1, sizeof(float) * a->N * d.d_x1, (hipStream_t)main))
@@ -480,7 +500,9 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       E3K_TRY(e3k_tp_bwd_w(d.tp, a->x1, a->sh, r.w, a->g_mid, a->src, a->dst_ptr, a->dst_perm, a->N, a->E, a->g_w, nullptr, wst));
     }
     if (wst == main) E3K_TRY(edge(L, 2, main, side));
-    if (r.use_table) {
+    if (r.use_table && ride) {
+      g_rows = a->g_T;      // (written by the weight gradients' launch below)
+    } else if (r.use_table) {
       Timed t(L, E3K_PROF_RTABLE_BWD, side, r.R, r.E);
       E3K_TRY(e3k_rtable_interp_bwd(a->g_w, r.bin_coef, nullptr, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, d.W, a->table_ws,
                                     a->g_T, 0, side));
@@ -517,8 +539,9 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       E3K_TRY(edge(L, 3, main, side3));
       E3K_TRY(weight_grads(false, true, side3));
     }
-  } else if (need_post || need_lin1 || want_sc) {
-    E3K_TRY(weight_grads(true, true, main));
+  } else if (need_post || need_lin1 || want_sc || ride) {
+    const Seg::Rider rd{a->g_w, r.bin_coef, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, d.W, a->table_ws, a->g_T};
+    E3K_TRY(weight_grads(true, true, main, ride ? &rd : nullptr));
     if (want_sc) E3K_TRY(keyed_weight_grads());
   }
   if (hipGetLastError() != hipSuccess) return E3K_ERR_LAUNCH;

@@ -258,6 +258,7 @@ SIGNATURES = {
     "e3k_rtable_interp_fwd2": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
     "e3k_rtable_bwd_workspace_floats": (C.c_int64, [_I64, _I32, _I32]),
     "e3k_rtable_interp_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I32, _P]),
+    "e3k_wgrad_with_table_bwd": (C.c_int, [C.POINTER(GemmSegment), _I32, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I32, _P]),
     "e3k_rtable_pack": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "e3k_rtable_pack_multi": (C.c_int, [_P, _I32, _P, _P, _I32, _P]),
     "e3k_rtable_interp_packed": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _P, _P]),

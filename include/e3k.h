@@ -447,6 +447,15 @@ int64_t e3k_rtable_bwd_workspace_floats(int64_t E, int32_t K, int32_t W);
 int e3k_rtable_interp_bwd(const float* g_w, const float* coef, const float* scale, const int32_t* bin_ptr,
                           const int32_t* bin_seg, const int32_t* bin_perm, int64_t E, int32_t K, int32_t W, float* workspace,
                           float* g_T, int32_t accumulate, void* stream);
+/* e3k_gemm_multi(segments, n_segments, wgrad = 1, stream) and e3k_rtable_interp_bwd(g_w .. accumulate, stream) as ONE call: the
+ * weight-gradient problems of the pipelined kernel (16-byte-loadable operands, not the outer-product form) and the transpose's first
+ * pass go out as one launch, gemm_wgrad2_with_table_bwd_kernel -- the GEMM's workgroups first, the transpose's behind them --, then
+ * the transpose's second pass.  Same results: g_T bit for bit, the weight gradients up to the order of their fp32 atomics.  Every
+ * argument error of either call is refused before anything is launched.  Without such a problem, or with E = 0, the two calls are
+ * made one after the other.  e3k_gemm_last_routes() reports the GEMM side's launches. */
+int e3k_wgrad_with_table_bwd(const e3k_gemm_segment* segments, int32_t n_segments, const float* g_w, const float* coef,
+                             const float* scale, const int32_t* bin_ptr, const int32_t* bin_seg, const int32_t* bin_perm, int64_t E,
+                             int32_t K, int32_t W, float* workspace, float* g_T, int32_t accumulate, void* stream);
 
 /* The table packed for the tensor-product kernels: 12 bytes per (knot, weight) in ONE row -- the cubic through rows i-1 .. i+2 as
  * its Taylor polynomial about the middle of knot interval i, {d0: f32, d1: f32, d2 * 2^10: f16, d3 * 2^16: f16} -- instead of four
