@@ -1,5 +1,5 @@
 // The counter-based draw: the one definition of the stream that the capped list's pair criterion (e3k_nlist.hip), the thermostat
-// and thermalize() (e3k_md.hip) and the score step's perturbation (e3k_score.hip) read.  Nothing about a draw lives in a
+// and thermalize() (e3k_md.hip), the score step's perturbation (e3k_score.hip) and the seeded sampler (e3k_sampler.hip) read.  Nothing about a draw lives in a
 // generator's state: a value is a function of five 32-bit words, so a step that is done again sees the same bits.
 //
 // The stream layout.  h = mix32(h ^ word) over the words, in this order, from 0x9E3779B9:
@@ -8,6 +8,13 @@
 //   * src is a node index (N < 2^31), or 0xFFFFFFFF for a graph's time (then dst is the graph).
 //   * a pair's Bernoulli draw: src = i, dst = j, the 32-bit hash against a threshold.
 //   * a standard normal for (node, word): src = the node, dst = 2 word and 2 word + 1 give the two uniforms of normal_draw().
+//   * the seeded sampler (e3k_sampler.hip; run/sde_utils.py restates it): D_total = the sum of the dimensions of the diffusion keys
+//     (sde.irreps, in order), a key's word0 = the sum of the dimensions before it, src = the node, and for component c of a key
+//         reverse step i (from 0), corrector noise:  draw index i,      word word0 + c
+//         reverse step i, predictor noise:           draw index i,      word D_total + word0 + c
+//         the prior x_T:                             draw index sde.N,  word word0 + c        (no step uses index sde.N)
+//     The sampler's seed is an argument of its own and should differ from the pair criterion's: with one seed a node's noise and the
+//     Bernoulli draws of its pairs at the same draw index come from one chain.
 // data/compute_edge.py (_mix32, pair_hash, normal_draw) is the host restatement, in int64 masked to 32 bits.
 #pragma once
 #include <stdint.h>

@@ -1,0 +1,185 @@
+// The seeded predictor-corrector sampler's arithmetic around the model (run/sde_sampling.get_pc_sampler(seed=...)): the step's time
+// and number from device cells, the Langevin corrector and the Euler-Maruyama step of the reverse VP-SDE, one launch each per
+// diffusion key.  (A file of its own beside e3k_score.hip, whose object keeps the training step's three kernels.)
+//
+// Replaces (paths of the reference project):
+//   score = -raw / std - x with std = sqrt(1 - exp(2 lm)) per node                  e3_layers/run/sde_utils.py:176-187
+//   LangevinCorrector.update_fn: randn, two row norms and their means, alphas[k],   e3_layers/run/sde_sampling.py:117-143
+//     x + step score + sqrt(2 step) z
+//   RSDE.sde / VPSDE.sde: the Euler-Maruyama step with dt = -1 / N                  e3_layers/run/sde_utils.py:68-81, :104-119
+//   the loop's "t = timesteps[i]" per step                                          e3_layers/run/sde_sampling.py:229-242
+//
+// Why counter-based draws: the noise of reverse step i is a function of (seed, i, node, word) in the stream of e3k_draw.h, so the
+// corrector forms both of its batch-wide norms over the REAL rows of a padded batch, recomputes the same draw for the update (no
+// noise buffer), and a replayed run and an eager run at one seed see the same bits.  The words: component c of a key whose earlier
+// keys hold word0 components draws word0 + c for the corrector and D_total + word0 + c for the predictor (the caller passes that sum);
+// the prior x_T is draw index sde.N, words word0 + c, through e3k_vpsde_perturb's z.
+#include "e3k_common.h"
+#include "e3k_draw.h"
+
+namespace e3k {
+
+// std of the perturbation kernel at time t: lm = t (q t + h), one explicit FMA and one product; sqrt(-expm1(2 lm)).
+__device__ __forceinline__ float vp_std(float t, float q, float h) {
+  const float lm = t * fmaf(q, t, h);
+  return sqrtf(-expm1f(2.0f * lm));
+}
+
+// One workgroup.  cells [2] = (next step, step in use).  Every thread reads k = cells[0] BEFORE the barrier, thread 0 writes the
+// cells after it.  k outside the table: nothing is written (a run that replays past its schedule stands still).
+__global__ __launch_bounds__(256) void sampler_begin_step_kernel(const float* __restrict__ times, int64_t n_times,
+                                                                 int64_t* __restrict__ cells, float* __restrict__ t, int32_t G1) {
+  const int64_t k = cells[0];
+  if (k < 0 || k >= n_times) return;      // (uniform: the whole workgroup leaves)
+  const float tk = times[k];
+  for (int32_t g = threadIdx.x; g < G1; g += 256) t[g] = tk;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    cells[1] = k;
+    cells[0] = k + 1;
+  }
+}
+
+// One workgroup, fixed summation order (denoise_loss_kernel's): thread j takes the rows j, j + 1024, ...; six shuffle levels;
+// sixteen partial sums added in order.  Phase 1: the mean row norms of score and z over the real rows.  Phase 2: the update, with
+// score and z recomputed.  x_out may alias x: a row is read and written by one thread, phase 1 writes nothing.
+__global__ __launch_bounds__(1024) void sampler_langevin_kernel(float* x_out, const float* x, const float* __restrict__ raw,
+                                                                const int64_t* __restrict__ node_seg, const float* __restrict__ t,
+                                                                const float* __restrict__ alphas, int64_t N, int32_t D, int32_t G,
+                                                                int32_t n_alpha, float q, float h, float T, float snr,
+                                                                uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ cells,
+                                                                uint32_t word0, float* __restrict__ norms) {
+  __shared__ float part_g[16], part_z[16];
+  __shared__ int part_n[16];
+  __shared__ float mean[2];
+  const uint32_t h_draw = draw_prefix(seed_lo, seed_hi, (uint32_t)cells[1]);
+  float acc_g = 0.f, acc_z = 0.f;
+  int acc_n = 0;
+  for (int64_t i = threadIdx.x; i < N; i += 1024) {
+    const int64_t g = node_seg[i];
+    if (g < 0 || g >= G) continue;
+    const float s = vp_std(t[g], q, h);
+    const uint32_t h_node = mix32(h_draw ^ (uint32_t)i);
+    float gg = 0.f, zz = 0.f;
+    for (int32_t c = 0; c < D; ++c) {
+      const float score = -(raw[i * D + c] / s) - x[i * D + c];
+      const float z = normal_draw(h_node, word0 + (uint32_t)c);
+      gg = fmaf(score, score, gg);
+      zz = fmaf(z, z, zz);
+    }
+    acc_g += sqrtf(gg);
+    acc_z += sqrtf(zz);
+    acc_n += 1;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    acc_g += __shfl_down(acc_g, off, 64);
+    acc_z += __shfl_down(acc_z, off, 64);
+    acc_n += __shfl_down(acc_n, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    part_g[threadIdx.x >> 6] = acc_g;
+    part_z[threadIdx.x >> 6] = acc_z;
+    part_n[threadIdx.x >> 6] = acc_n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float sg = 0.f, sz = 0.f;
+    int n_real = 0;
+    for (int k = 0; k < 16; ++k) {
+      sg += part_g[k];
+      sz += part_z[k];
+      n_real += part_n[k];
+    }
+    mean[0] = norms[0] = sg / (float)n_real;
+    mean[1] = norms[1] = sz / (float)n_real;
+  }
+  __syncthreads();
+  const float ratio = (snr * mean[1]) / mean[0];
+  const float base = ratio * ratio * 2.0f;
+  for (int64_t i = threadIdx.x; i < N; i += 1024) {
+    const int64_t g = node_seg[i];
+    if (g < 0 || g >= G) {      // the ghost graph: bit for bit
+      for (int32_t c = 0; c < D; ++c) x_out[i * D + c] = x[i * D + c];
+      continue;
+    }
+    const float tg = t[g];
+    const float s = vp_std(tg, q, h);
+    int64_t k = (int64_t)((tg * (float)(n_alpha - 1)) / T);
+    k = k < 0 ? 0 : k > n_alpha - 1 ? n_alpha - 1 : k;
+    const float step = base * alphas[k];
+    const float amp = sqrtf(step * 2.0f);
+    const uint32_t h_node = mix32(h_draw ^ (uint32_t)i);
+    for (int32_t c = 0; c < D; ++c) {
+      const float xc = x[i * D + c];
+      const float score = -(raw[i * D + c] / s) - xc;
+      const float z = normal_draw(h_node, word0 + (uint32_t)c);
+      x_out[i * D + c] = xc + step * score + amp * z;
+    }
+  }
+}
+
+// One thread per component: x' = x + (-0.5 beta x) dt + sqrt(beta) sqrt(|dt|) z - dt beta score, reverse_step's arithmetic in its
+// order; beta = fma(t, beta_1 - beta_0, beta_0).  x_out may alias x (an element is read and written by one thread).
+__global__ __launch_bounds__(256) void sampler_reverse_em_kernel(float* x_out, const float* x, const float* __restrict__ raw,
+                                                                 const int64_t* __restrict__ node_seg, const float* __restrict__ t,
+                                                                 int64_t N, int32_t D, int32_t G, float q, float h, float beta_0,
+                                                                 float dbeta, float dt, uint32_t seed_lo, uint32_t seed_hi,
+                                                                 const int64_t* __restrict__ cells, uint32_t word0) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= N * D) return;
+  const int64_t i = k / D;
+  const uint32_t c = (uint32_t)(k - i * D);
+  const int64_t g = node_seg[i];
+  const float xc = x[k];
+  if (g < 0 || g >= G) {
+    x_out[k] = xc;
+    return;
+  }
+  const float tg = t[g];
+  const float s = vp_std(tg, q, h);
+  const float score = -(raw[k] / s) - xc;
+  const float beta = fmaf(tg, dbeta, beta_0);
+  const uint32_t h_draw = draw_prefix(seed_lo, seed_hi, (uint32_t)cells[1]);
+  const float z = normal_draw(mix32(h_draw ^ (uint32_t)i), word0 + c);
+  const float mean = xc + (-0.5f * beta * xc) * dt;
+  const float noised = mean + (sqrtf(beta) * sqrtf(fabsf(dt))) * z;
+  x_out[k] = noised - (dt * beta) * score;
+}
+
+}  // namespace e3k
+
+extern "C" int e3k_sampler_begin_step(const float* times, int64_t n_times, int64_t* cells, float* t, int32_t G1, void* stream) {
+  if (!times || !cells || !t || n_times < 1 || G1 < 1) return E3K_ERR_INVALID;
+  hipLaunchKernelGGL(e3k::sampler_begin_step_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, times, n_times, cells, t, G1);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_sampler_langevin(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t,
+                                    const float* alphas, int64_t N, int32_t D, int32_t G, int32_t n_alpha, float beta_0, float beta_1,
+                                    float T, float snr, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells, uint32_t word0,
+                                    float* norms, void* stream) {
+  if (N < 1 || N >= (int64_t)1 << 31 || D < 1 || D > 1024 || G < 1 || n_alpha < 1 || !(T > 0.f) || !(snr > 0.f) || !(beta_0 >= 0.f) ||
+      !(beta_1 >= beta_0))
+    return E3K_ERR_INVALID;
+  if (!x_out || !x || !raw || !node_seg || !t || !alphas || !cells || !norms) return E3K_ERR_INVALID;
+  const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
+  hipLaunchKernelGGL(e3k::sampler_langevin_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x_out, x, raw, node_seg, t, alphas, N,
+                     D, G, n_alpha, q, h, T, snr, seed_lo, seed_hi, cells, word0, norms);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_sampler_reverse_em(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t,
+                                      int64_t N, int32_t D, int32_t G, float beta_0, float beta_1, int32_t n_sde, uint32_t seed_lo,
+                                      uint32_t seed_hi, const int64_t* cells, uint32_t word0, void* stream) {
+  if (N < 1 || N >= (int64_t)1 << 31 || D < 1 || D > 1024 || G < 0 || n_sde < 1 || !(beta_0 >= 0.f) || !(beta_1 >= beta_0) ||
+      N * D >= (int64_t)1 << 38)
+    return E3K_ERR_INVALID;
+  if (!x_out || !x || !raw || !node_seg || !t || !cells) return E3K_ERR_INVALID;
+  const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
+  hipLaunchKernelGGL(e3k::sampler_reverse_em_kernel, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_out, x,
+                     raw, node_seg, t, N, D, G, q, h, beta_0, beta_1 - beta_0, -1.0f / (float)n_sde, seed_lo, seed_hi, cells, word0);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}

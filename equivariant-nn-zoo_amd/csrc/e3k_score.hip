@@ -8,6 +8,9 @@
 // Why counter-based draws: a replayed step whose capped neighbour list overflowed is vetoed on the device and redone eagerly by
 // the host on exactly the same noised batch -- t and z are functions of (seed, draw index, graph / node, word) in the stream of
 // e3k_draw.h (the thermostat's), and the draw index is a device cell the captured step reads (the step counter).
+//
+// The sampling side of the same nets -- the seeded predictor-corrector loop's step header, Langevin corrector and reverse
+// Euler-Maruyama step, on the same stream of draws -- is e3k_sampler.hip: this object keeps the training step's three kernels.
 #include "e3k_common.h"
 #include "e3k_draw.h"
 

@@ -1998,6 +1998,65 @@ def denoise_loss(raw, x_t, z, std, w=None):
     return DenoiseLossFn.apply(raw, x_t, z, std, w)
 
 
+def _sampler_operands(name, x, raw, node_seg, t, n_graphs, cells, out):
+    L.require_cuda(x, raw, node_seg, t, cells)
+    x, raw, t = L.f32c(x.detach()), L.f32c(raw.detach()), L.f32c(t.detach()).reshape(-1)
+    if x.dim() != 2 or raw.shape != x.shape or node_seg.dtype != torch.int64 or node_seg.numel() != x.shape[0] or not node_seg.is_contiguous():
+        raise ValueError(f"{name} needs x, raw [N, D] and a contiguous int64 node_seg [N]")
+    if t.numel() < int(n_graphs):
+        raise ValueError(f"{name}: t holds {t.numel()} times for {int(n_graphs)} graphs")
+    if cells.dtype != torch.int64 or cells.numel() < 2 or not cells.is_contiguous():
+        raise ValueError(f"{name}: cells must be a contiguous int64 device tensor [2] = (next step, step in use)")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"{name}: out must be a contiguous fp32 device tensor of x's shape")
+    return x, raw, t, out
+
+
+def sampler_begin_step(times, cells, t) -> None:
+    """The seeded sampler's step header (``csrc/e3k_sampler.hip``): with ``k = cells[0]`` inside the table ``times`` [n] fp32, every
+    element of ``t`` (fp32, the ghost graph's included) becomes ``times[k]`` and ``cells`` (DEVICE int64 [2]) becomes ``(k + 1, k)``;
+    outside the table nothing is written.  One launch, in place, no host synchronisation."""
+    L.require_cuda(times, cells, t)
+    if times.dtype != torch.float32 or t.dtype != torch.float32 or not times.is_contiguous() or not t.is_contiguous():
+        raise ValueError("sampler_begin_step needs contiguous fp32 times [n] and t")
+    if cells.dtype != torch.int64 or cells.numel() < 2 or not cells.is_contiguous():
+        raise ValueError("sampler_begin_step: cells must be a contiguous int64 device tensor [2] = (next step, step in use)")
+    L.check(L.load().e3k_sampler_begin_step(L.ptr(times), times.numel(), L.ptr(cells), L.ptr(t), t.numel(), L.stream_ptr()),
+            "e3k_sampler_begin_step")
+
+
+def sampler_langevin(x, raw, node_seg, t, alphas, n_graphs: int, beta_0: float, beta_1: float, T: float, snr: float, seed: int, cells,
+                     word0: int = 0, out=None):
+    """One Langevin corrector update of a diffusion key with counter-based noise (``csrc/e3k_sampler.hip``): ``(x', norms [2])`` for
+    ``x``, ``raw`` [N, D] (the score head's output: score = -raw / std(t) - x), ``t`` per graph and the ``alphas`` table; ``norms`` =
+    (mean score row norm, mean noise row norm) over the rows of the ``n_graphs`` real graphs; the other rows (the ghost graph of a
+    padded batch) are copied through.  The noise is draw ``cells[1]``, words ``word0 + c``.  ``out`` may be ``x``.  One launch."""
+    x, raw, t, out = _sampler_operands("sampler_langevin", x, raw, node_seg, t, n_graphs, cells, out)
+    L.require_cuda(alphas)
+    alphas = L.f32c(alphas).reshape(-1)
+    n, d = x.shape
+    norms = torch.empty(2, device=x.device, dtype=torch.float32)
+    L.check(L.load().e3k_sampler_langevin(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(node_seg), L.ptr(t), L.ptr(alphas), n, d, int(n_graphs),
+                                          alphas.numel(), float(beta_0), float(beta_1), float(T), float(snr), *L.seed_words(seed),
+                                          L.ptr(cells), int(word0), L.ptr(norms), L.stream_ptr()), "e3k_sampler_langevin")
+    return out, norms
+
+
+def sampler_reverse_em(x, raw, node_seg, t, n_graphs: int, beta_0: float, beta_1: float, n_sde: int, seed: int, cells, word0: int,
+                       out=None):
+    """One Euler-Maruyama step of the reverse VP-SDE (``dt = -1 / n_sde``) of a diffusion key with counter-based noise
+    (``csrc/e3k_sampler.hip``); operands as ``sampler_langevin``'s.  ``word0``: D_total + the key's first word (the predictor's words
+    of the draw layout, ``csrc/e3k_draw.h``).  ``out`` may be ``x``.  One launch."""
+    x, raw, t, out = _sampler_operands("sampler_reverse_em", x, raw, node_seg, t, n_graphs, cells, out)
+    n, d = x.shape
+    L.check(L.load().e3k_sampler_reverse_em(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(node_seg), L.ptr(t), n, d, int(n_graphs), float(beta_0),
+                                            float(beta_1), int(n_sde), *L.seed_words(seed), L.ptr(cells), int(word0), L.stream_ptr()),
+            "e3k_sampler_reverse_em")
+    return out
+
+
 def segment_sum(x, ptr, seg_index, mean=False):
     return SegmentSumFn.apply(_c(x), ptr, seg_index, bool(mean))
 

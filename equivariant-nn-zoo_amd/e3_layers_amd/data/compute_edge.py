@@ -105,6 +105,9 @@ def normal_draw(seed, draw, node, word, dtype=torch.float32) -> Tensor:
     ``h1, h2 = pair_hash(seed, draw, node, 2 word), pair_hash(seed, draw, node, 2 word + 1)`` -- bit for bit the kernel's -- and
     ``sqrt(-2 ln u1) cos(2 pi u2)`` in ``dtype`` through torch (the kernel: fp32 ``logf``, ``sqrtf``, ``cospif``).  Component c of a
     step's thermostat draw is word c with the step number as draw index; ``thermalize`` uses words 4 + c and a counter of its own.
+    The seeded sampler (``run/sde_utils.py``): with ``word0`` the sum of the dimensions of the diffusion keys before a key and
+    ``D_total`` the sum over all of them, reverse step i draws index i -- word ``word0 + c`` for the corrector, ``D_total + word0 + c``
+    for the predictor -- and the prior draws index ``sde.N``, word ``word0 + c``.
     Arguments as ``pair_hash``'s: ints or int64 tensors, broadcasting."""
     two_w = 2 * (word if torch.is_tensor(word) else int(word))
     u1 = ((pair_hash(seed, draw, node, two_w) >> 8) + 1).to(dtype) * 2.0 ** -24
@@ -161,7 +164,9 @@ class SequenceOrRandom(PairCriterion):
     """``(segment[src] == segment[dst] and |src - dst| < window) or bernoulli(p)`` on global node indices -- the shipped protein rule
     is ``SequenceOrRandom("chain_id", 5, 0.02)``.  ``window=0`` switches the sequence term off, ``p=0`` the random one; ``p=1`` keeps
     every candidate.  The Bernoulli draw is counter-based and stateless per pair: ``pair_hash(seed, draw, src, dst) < floor(p 2^32)``,
-    where ``draw`` is the number of the list build -- the same for every pair of one build, one more for the next build."""
+    where ``draw`` is the number of the list build -- the same for every pair of one build, one more for the next build.  ``seed``
+    should differ from the seeded sampler's (``get_pc_sampler(seed=...)``): the two streams share the hash, and with one seed a node's
+    noise and the Bernoulli draws of its pairs come from one chain."""
 
     def __init__(self, segment: str = "chain_id", window: int = 5, p: float = 0.02, seed: int = 0):
         super().__init__()

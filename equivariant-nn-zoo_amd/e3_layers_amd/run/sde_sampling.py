@@ -20,6 +20,12 @@ Noise comes from ``generator`` (or an injected ``noise_fn(shape)`` — the parit
 same draws).  The reference's corrector evaluates the score ``n_steps`` times on the *unchanged* batch
 (:131-142 never writes ``x`` back inside the loop); here every inner step sees the updated positions, which
 is identical for the default ``n_steps=1``.
+
+``get_pc_sampler(seed=...)`` is the seeded form: the noise of reverse step i is counter-based (``csrc/e3k_draw.h``; the layout is
+restated in ``run/sde_utils.py``), the arithmetic around each model call is one HIP launch per diffusion key
+(``csrc/e3k_sampler.hip``), and the step's time and number live in device cells that a one-workgroup launch advances -- the host
+copies nothing per step.  The corrector forms its batch-wide norms over the real rows only, so the Langevin corrector is served on
+the capped replay too, and the eager loop, the static-edge graph and the capped replay see the same draws at one seed.
 """
 from __future__ import annotations
 
@@ -32,7 +38,8 @@ from ..backend.graph import TOPO_KEYS, EdgeCapacityExceeded
 from ..data.compute_edge import PairCriterion, computeEdgeIndex, computeEdgeIndexCapped
 from .capped import EDGE_KEYS, CappedBucket, builder_cells, edge_layer_of, replayable_criterion
 from .graph_step import CapturedStep
-from .sde_utils import VPSDE, _node_t, _randn, get_score_fn, prior_sampling, reverse_step
+from .sde_utils import (VPSDE, _node_t, _randn, get_score_fn, langevin_step_counter, prior_sampling, prior_sampling_counter,
+                        reverse_step, reverse_step_counter, sampler_begin_step)
 
 class _Registry(dict):
     """name -> class table with a decorator: ``@table.register(name="langevin")`` (bare ``@table.register`` uses the
@@ -123,8 +130,15 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                    n_steps: int = 1, continuous: bool = True, eps: float = 1e-3,
                    preprocess: Sequence[Callable] = (), static_edges: bool = False, graph: bool = False,
                    n_iter: Optional[int] = None, edge_capacity: Optional[int] = None, r_max: Optional[float] = None,
-                   criteria=None):
+                   criteria=None, seed: Optional[int] = None):
     """``pc_sampler(model, batch, generator=None, noise_fn=None) -> (batch, n_function_evaluations)``.
+
+    seed: the seeded form (at most 64 bits).  The prior and every step's noise are counter-based draws of (seed, step, node,
+        component) -- ``run/sde_utils.prior_sampling_counter``, ``langevin_step_counter``, ``reverse_step_counter`` -- instead of a
+        generator's, so ``generator`` and ``noise_fn`` are refused; the predictor and the corrector are the built-in classes (any
+        other class is refused: its ``update_fn`` draws from a generator), ``n_steps`` is 1 with the Langevin corrector (the draw
+        layout holds one corrector draw per step).  With ``edge_capacity`` the Langevin corrector is served: its norms run over the real
+        rows.  It should differ from the pair criterion's seed, or a node's noise and its pairs' Bernoulli draws share a chain.
 
     preprocess: the dataset's ``(data, attrs) -> (data, attrs)`` functions (``data_config.preprocess``) that
         rebuild ``edge_index`` when the model tree has no ``edge_index`` layer of its own.
@@ -153,12 +167,22 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
     if edge_capacity is not None:
         if not graph or static_edges:
             raise ValueError("edge_capacity belongs to graph=True on cutoff graphs (static_edges=False)")
-        if corrector is not NoneCorrector:
+        if corrector is not NoneCorrector and not (seed is not None and corrector is LangevinCorrector):
             raise ValueError("edge_capacity: the ghost graph's nodes would enter the corrector's batch-wide norms; only NoneCorrector is served")
         if r_max is None:
             raise ValueError("edge_capacity needs the cutoff of the neighbour list: pass r_max")
         if criteria is not None and not isinstance(criteria, PairCriterion):
             raise ValueError("edge_capacity: criteria must be a data.PairCriterion (the capped builder evaluates it in its kernels)")
+    seeded = seed is not None
+    if seeded:
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed: at most 64 bits")
+        if predictor not in (EulerMaruyamaPredictor, NonePredictor) or corrector not in (LangevinCorrector, NoneCorrector):
+            raise ValueError("seed: only the built-in predictors and correctors draw counter-based noise "
+                             f"(got {predictor.__name__}, {corrector.__name__})")
+        if corrector is LangevinCorrector and n_steps != 1:
+            raise ValueError("seed: the draw layout holds one corrector draw per reverse step, and the capped loop would rebuild the "
+                             "list between inner corrector steps where the eager loop does not: n_steps must be 1")
 
     def rebuild_edges(batch):
         for k in SAMPLER_EDGE_KEYS:
@@ -172,10 +196,12 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
     steps = sde.N if n_iter is None else min(int(n_iter), sde.N)
 
     def pc_sampler(model, batch, generator=None, noise_fn=None):
+        if seeded and (generator is not None or noise_fn is not None):
+            raise ValueError("seed: the noise is counter-based; generator and noise_fn have nothing to feed")
         batch = batch.clone()
         dev = batch["_n_nodes"].device
         batch.attrs["t"] = ("graph", "1x0e")
-        batch = prior_sampling(sde, batch, generator, noise_fn)
+        batch = prior_sampling_counter(sde, batch, seed) if seeded else prior_sampling(sde, batch, generator, noise_fn)
         sde.alphas = sde.alphas.to(dev)      # resident before any capture (no pageable host copy inside a graph)
         timesteps = torch.linspace(sde.T, eps, sde.N, device=dev)
         score_fn = get_score_fn(sde, model, train=False)
@@ -204,17 +230,27 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                 return b
             return rebuild_edges(b)
 
+        if seeded:
+            # the step's time and number: device cells (next step, step in use) that the step's first launch advances
+            cells = torch.zeros(2, dtype=torch.int64, device=dev)
+            times = timesteps.contiguous()
+            same = lambda b: b      # noqa: E731  (the None classes)
+            corr_fn = partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=snr) if corrector is LangevinCorrector else same
+            pred_fn = partial(reverse_step_counter, sde, model, seed=seed, draw=cells) if predictor is EulerMaruyamaPredictor else same
+        else:
+            corr_fn = lambda b: corr.update_fn(b, generator, noise_fn)      # noqa: E731
+            pred_fn = lambda b: pred.update_fn(b, generator, noise_fn)      # noqa: E731
+
         def one_step(b):
-            b = moved(corr.update_fn(b, generator, noise_fn))
-            return moved(pred.update_fn(b, generator, noise_fn))
+            return moved(pred_fn(moved(corr_fn(b))))
 
         def capped_updates():
-            return [lambda b: corr.update_fn(b, generator, noise_fn), lambda b: pred.update_fn(b, generator, noise_fn)]
+            return [corr_fn, pred_fn]
 
         with torch.no_grad():
             if graph and edge_capacity is not None:
                 loop = CappedLoop(batch, model, capped_updates(), keys, float(timesteps[0]), int(edge_capacity), float(r_max),
-                                  criteria)
+                                  criteria, seeded=(times, cells) if seeded else None)
                 loop.rewind()
                 loop.run(timesteps, steps)
                 batch = loop.result()
@@ -227,6 +263,8 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                     for k in keys:
                         work[k] = state[k]
                     work["t"] = t_dev
+                    if seeded:
+                        sampler_begin_step(times, cells, t_dev)
                     work = one_step(work)
                     for k in keys:
                         state[k].copy_(work[k])
@@ -239,6 +277,8 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                     captured()                     # warm-up (allocations, plan creation) outside the capture
                     for k in keys:
                         state[k].copy_(saved[k])
+                    if seeded:
+                        cells.zero_()              # (the warm-up was step 0: the run starts there again)
                 torch.cuda.current_stream().wait_stream(side)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
@@ -246,13 +286,17 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                 for k in keys:                     # the capture pass itself does not execute; restore anyway
                     state[k].copy_(saved[k])
                 for i in range(steps):
-                    t_dev.copy_(timesteps[i].expand_as(t_dev))
+                    if not seeded:
+                        t_dev.copy_(timesteps[i].expand_as(t_dev))
                     g.replay()
                 for k in keys:
                     batch[k] = state[k]
             else:
                 for i in range(steps):
-                    t_dev.copy_(timesteps[i].expand_as(t_dev))
+                    if seeded:
+                        sampler_begin_step(times, cells, t_dev)
+                    else:
+                        t_dev.copy_(timesteps[i].expand_as(t_dev))
                     batch["t"] = t_dev
                     batch = one_step(batch)
         return inverse_scaler(batch), steps * (n_steps + 1)
@@ -269,7 +313,9 @@ class CappedLoop:
     Construction sizes, pads and captures (``t0``: the time of the warm-up step); ``rewind()`` puts the state and the draw index
     back on the start, ``run()`` replays, ``result()`` checks the capacity and unpads (``tools/sample_bench.py`` times ``run`` alone)."""
 
-    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None):
+    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None, seeded=None):
+        """``seeded``: ``(times, cells)`` of the seeded sampler -- the captured step then begins with ``e3k_sampler_begin_step``, which
+        sets the time from the table and advances the cells, and ``run`` is replays only."""
         dev = batch["_n_nodes"].device
         own = edge_layer_of(model)
         if own is not None:
@@ -306,12 +352,15 @@ class CappedLoop:
             return fresh
 
         def captured():
+            if seeded is not None:
+                sampler_begin_step(seeded[0], seeded[1], padded["t"])
             work = padded.view()
             for update in updates:
                 work = relisted(update(work))
             for k in keys:
                 state[k][:n].copy_(work[k][:n])
 
+        self.seeded = seeded
         self.padded, self.state, self.rng, self.keys, self.n, self.first_edges = padded, state, rng, keys, n, e
         self.t_dev = padded["t"]
         self.saved = {k: v.clone() for k, v in state.items()}
@@ -323,8 +372,14 @@ class CappedLoop:
         for k in self.keys:
             self.state[k].copy_(self.saved[k])
         self.rng.zero_()
+        if self.seeded is not None:
+            self.seeded[1].zero_()
 
     def run(self, timesteps, steps: int) -> None:
+        if self.seeded is not None:      # the time comes from the table inside the graph: bare replays
+            for _ in range(steps):
+                self.step()
+            return
         t_dev = self.t_dev
         for i in range(steps):
             t_dev.copy_(timesteps[i].expand_as(t_dev))

@@ -189,6 +189,176 @@ def sde_perturb_counter(sde: VPSDE, batch, seed: int, draw, eps: float = 1e-5, d
     return pert, {"zs": zs, "std": s}
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The seeded predictor-corrector sampler's steps (run/sde_sampling.get_pc_sampler(seed=...)): counter-based noise in the draw layout
+# of csrc/e3k_draw.h.  D_total = the sum of the dimensions of sde.irreps; a key's word0 = the sum of the dimensions before it.
+#   reverse step i (from 0), corrector noise of component c:  normal_draw(seed, i, node, word0 + c)
+#   reverse step i, predictor noise:                          normal_draw(seed, i, node, D_total + word0 + c)
+#   the prior x_T:                                            normal_draw(seed, sde.N, node, word0 + c)      (no step has index sde.N)
+# The sampler's seed should not be the pair criterion's (data.SequenceOrRandom(seed=...)): a node's noise and the Bernoulli draws of
+# its pairs would come from one chain.
+# ---------------------------------------------------------------------------------------------------------------------
+def draw_words(sde: VPSDE):
+    """({key: word0}, D_total) of the sampler's draw layout."""
+    words, total = {}, 0
+    for key, dim in sde.irreps.items():
+        words[key] = total
+        total += int(dim)
+    return words, total
+
+
+def _real_graphs(batch) -> int:
+    """(a padded batch -- ``_graph_weight`` present -- ends with the ghost graph)"""
+    return len(batch) - 1 if "_graph_weight" in batch else len(batch)
+
+
+def _sampler_cells(draw, dev):
+    """The kernels read the step in use from element 1 of the sampler's cells (next step, step in use)."""
+    if torch.is_tensor(draw):
+        return draw
+    return torch.tensor([int(draw) + 1, int(draw)], dtype=torch.int64, device=dev)
+
+
+def _step_in_use(draw) -> int:
+    if torch.is_tensor(draw):
+        flat = draw.reshape(-1)
+        return int(flat[1] if flat.numel() > 1 else flat[0])
+    return int(draw)
+
+
+def _raw_scores(sde: VPSDE, model, batch, train: bool = False):
+    """The score heads' outputs per diffusion key, before ``get_score_fn``'s ``-raw / std - x``."""
+    model.train(train)
+    result = model(batch)
+    return {key: result[f"score_{key}"] if f"score_{key}" in result else result["score"] for key in sde.irreps}
+
+
+def _host_terms(sde: VPSDE, batch, dtype):
+    """(t per node, std per node, real-row mask [N, 1], node index [N, 1]) of the CPU restatements, in ``dtype``"""
+    seg = batch.nodeSegment()
+    t = batch["t"].reshape(-1).to(dtype)
+    q, h = -0.25 * (sde.beta_1 - sde.beta_0), -0.5 * sde.beta_0
+    lm = t * (q * t + h)
+    s = torch.sqrt(-torch.expm1(2.0 * lm))
+    real = (torch.arange(len(batch)) < _real_graphs(batch))[seg].reshape(-1, 1)
+    node = torch.arange(seg.shape[0], dtype=torch.int64).reshape(-1, 1)
+    return t[seg].reshape(-1, 1), s[seg].reshape(-1, 1), real, node
+
+
+def sampler_begin_step(times, cells, t) -> None:
+    """The seeded loops' step header: with ``k = cells[0]`` inside the table ``times``, ``t`` (every graph's, the ghost graph's
+    included) becomes ``times[k]`` and ``cells`` (int64 [2]) becomes ``(k + 1, k)``; outside the table nothing moves.  Device tensors:
+    one ``e3k_sampler_begin_step`` launch, no host synchronisation.  CPU tensors: the same in torch."""
+    if t.is_cuda:
+        from ..backend import ops
+
+        return ops.sampler_begin_step(times, cells, t)
+    k = int(cells[0])
+    if 0 <= k < times.numel():
+        t.fill_(float(times[k]))
+        cells[1] = k
+        cells[0] = k + 1
+
+
+def prior_sampling_counter(sde: VPSDE, batch, seed: int, draw=None, dtype=None):
+    """``prior_sampling`` with counter-based draws: ``x_T = normal_draw(seed, draw, node, word0 + c)`` per diffused key; ``draw``
+    defaults to ``sde.N``, the index no reverse step uses.  The ghost rows of a padded batch keep what they hold (zeros where the key
+    is new).  Device: one ``e3k_vpsde_perturb`` launch per key (its z output; fp32).  CPU: torch, in ``dtype`` (default: torch's)."""
+    from ..data.compute_edge import normal_draw
+
+    dev = batch["_n_nodes"].device
+    seg = batch.nodeSegment()
+    n, n_real = int(seg.shape[0]), _real_graphs(batch)
+    padded = n_real != len(batch)
+    draw = sde.N if draw is None else draw
+    words, _ = draw_words(sde)
+    if dev.type == "cuda":
+        from ..backend import ops
+
+        cell = draw if torch.is_tensor(draw) else torch.tensor([int(draw)], dtype=torch.int64, device=dev)
+        real = (seg < n_real).reshape(-1, 1) if padded else None
+        for key, dim in sde.irreps.items():
+            zero = torch.zeros(n, dim, device=dev)
+            z = ops.vpsde_perturb(zero, seg, n_real, sde.beta_0, sde.beta_1, 0.0, sde.T, seed, cell, words[key])[2]
+            batch[key] = torch.where(real, z, batch[key].float()) if padded and key in batch else z
+        return batch
+    dtype = torch.get_default_dtype() if dtype is None else dtype
+    real = (torch.arange(len(batch)) < n_real)[seg].reshape(-1, 1)
+    node = torch.arange(n, dtype=torch.int64).reshape(-1, 1)
+    for key, dim in sde.irreps.items():
+        z = normal_draw(seed, _step_in_use(draw), node, words[key] + torch.arange(dim, dtype=torch.int64).reshape(1, -1), dtype)
+        old = batch[key].to(dtype) if key in batch else torch.zeros(n, dim, dtype=dtype)
+        batch[key] = torch.where(real, z, old)
+    return batch
+
+
+def langevin_step_counter(sde: VPSDE, model, batch, seed: int, draw, snr: float, dtype=None, train: bool = False):
+    """One ``LangevinCorrector`` update (``n_steps = 1``) with counter-based noise: per key, ``z = normal_draw(seed, draw, node,
+    word0 + c)``, the mean row norms of score and z over the REAL rows, ``step = (snr |z| / |score|)^2 2 alphas[k]`` and
+    ``x + step score + sqrt(2 step) z``; the rows of a padded batch's ghost graph stay as they are and enter no norm.
+
+    ``draw``: the reverse step's number, an int, or the sampler's DEVICE cells (int64 [2]: next step, step in use -- read by the kernel,
+    no host synchronisation).  Device tensors: the model call and one ``e3k_sampler_langevin`` launch per key (fp32).  CPU tensors: the
+    torch restatement of the same hashes and formulas in ``dtype`` (default: the key's) -- float64 is the kernel tests' reference."""
+    raw = _raw_scores(sde, model, batch, train)
+    words, _ = draw_words(sde)
+    dev = batch[next(iter(sde.irreps))].device
+    if dev.type == "cuda":
+        from ..backend import ops
+
+        cells, seg, n_real = _sampler_cells(draw, dev), batch.nodeSegment(), _real_graphs(batch)
+        for key in sde.irreps:
+            batch[key], _ = ops.sampler_langevin(batch[key], raw[key], seg, batch["t"], sde.alphas, n_real, sde.beta_0, sde.beta_1,
+                                                 sde.T, snr, seed, cells, words[key])
+        return batch
+    from ..data.compute_edge import normal_draw
+
+    step_no = _step_in_use(draw)
+    for key, dim in sde.irreps.items():
+        x = batch[key] if dtype is None else batch[key].to(dtype)
+        t, s, real, node = _host_terms(sde, batch, x.dtype)
+        n_alpha = int(sde.alphas.numel())
+        k = ((t * (n_alpha - 1)) / sde.T).long().clamp(0, n_alpha - 1)
+        alpha = sde.alphas.to(x.dtype)[k]
+        score = -(raw[key].to(x.dtype) / s) - x
+        z = normal_draw(seed, step_no, node, words[key] + torch.arange(dim, dtype=torch.int64).reshape(1, -1), x.dtype)
+        rows = real.reshape(-1)
+        grad_norm, noise_norm = torch.norm(score[rows], dim=-1).mean(), torch.norm(z[rows], dim=-1).mean()
+        step = ((snr * noise_norm) / grad_norm) ** 2 * 2 * alpha
+        batch[key] = torch.where(real, x + step * score + torch.sqrt(step * 2) * z, x)
+    return batch
+
+
+def reverse_step_counter(sde: VPSDE, model, batch, seed: int, draw, dtype=None, train: bool = False):
+    """``reverse_step`` with counter-based noise: ``z = normal_draw(seed, draw, node, D_total + word0 + c)`` -- the predictor's words,
+    not the corrector's of the same step.  ``draw``, devices, ``dtype`` and the ghost rows as ``langevin_step_counter``'s; device
+    tensors: the model call and one ``e3k_sampler_reverse_em`` launch per key."""
+    raw = _raw_scores(sde, model, batch, train)
+    words, total = draw_words(sde)
+    dev = batch[next(iter(sde.irreps))].device
+    if dev.type == "cuda":
+        from ..backend import ops
+
+        cells, seg, n_real = _sampler_cells(draw, dev), batch.nodeSegment(), _real_graphs(batch)
+        for key in sde.irreps:
+            batch[key] = ops.sampler_reverse_em(batch[key], raw[key], seg, batch["t"], n_real, sde.beta_0, sde.beta_1, sde.N, seed, cells,
+                                                total + words[key])
+        return batch
+    from ..data.compute_edge import normal_draw
+
+    step_no, dt = _step_in_use(draw), -1.0 / sde.N
+    for key, dim in sde.irreps.items():
+        x = batch[key] if dtype is None else batch[key].to(dtype)
+        t, s, real, node = _host_terms(sde, batch, x.dtype)
+        score = -(raw[key].to(x.dtype) / s) - x
+        beta = t * (sde.beta_1 - sde.beta_0) + sde.beta_0
+        z = normal_draw(seed, step_no, node, total + words[key] + torch.arange(dim, dtype=torch.int64).reshape(1, -1), x.dtype)
+        x_mean = x + (-0.5 * beta * x) * dt
+        noised = x_mean + (torch.sqrt(beta) * (abs(dt) ** 0.5)) * z
+        batch[key] = torch.where(real, noised - (dt * beta) * score, x)
+    return batch
+
+
 def sde_loss_of(sde: VPSDE, model, pert, misc, train: bool = True, node_weight=None) -> Tuple[torch.Tensor, dict]:
     """Second half of ``sde_loss``: the score network on the noised batch and the denoising loss."""
     scores = get_score_fn(sde, model, train)(pert)

@@ -862,6 +862,37 @@ int e3k_denoise_loss(const float* raw, const float* x_t, const float* z, const f
 int e3k_score_step_record(const float* loss, const int64_t* overflow, int64_t* cells, float* ring, int32_t W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The seeded predictor-corrector sampler's arithmetic around the model (csrc/e3k_sampler.hip; run/sde_sampling.py
+ * get_pc_sampler(seed=...)).  Replaces the per-step "t = timesteps[i]", get_score_fn's score = -raw / std - x
+ * (e3_layers/run/sde_utils.py:176-187), LangevinCorrector.update_fn (e3_layers/run/sde_sampling.py:117-143) and the reverse
+ * Euler-Maruyama step (e3_layers/run/sde_utils.py:68-81, :104-119), whose noise came from a torch generator: here the noise of
+ * reverse step i is xi(seed, i, node, word) of csrc/e3k_draw.h.  Operands fp32; node_seg [N] int64, a row whose segment is
+ * outside [0, G) is a ghost row (e3k_vpsde_perturb's convention): it is copied through bit for bit and enters no sum.
+ * cells [2] DEVICE int64 = (next step, step in use).  s(t) = sqrtf(-expm1f(2 lm)), lm = t fma(q, t, h) as e3k_vpsde_perturb.
+ *
+ * e3k_sampler_begin_step: one workgroup.  k = cells[0]; if 0 <= k < n_times: t[g] = times[k] for every g < G1 (the ghost graph
+ *   included), then cells = (k + 1, k).  k outside the table: nothing is written.
+ * e3k_sampler_langevin: one workgroup, fixed summation order; x_out may alias x.  Per real row i of graph g:
+ *     score_c = -(raw_c / s(t_g)) - x_c;   z_c = xi(seed, cells[1], i, word0 + c);
+ *   norms[0] = mean_i sqrtf(sum_c score_c^2), norms[1] = mean_i sqrtf(sum_c z_c^2) over the real rows;
+ *     k_i = (int64)((t_g (float)(n_alpha - 1)) / T) clamped to the table;   step_i = ((snr norms[1]) / norms[0])^2 * 2 * alphas[k_i];
+ *     x_out_c = x_c + step_i score_c + sqrtf(step_i * 2) z_c.
+ *   A zero mean score norm divides by zero, as the reference does.
+ * e3k_sampler_reverse_em: one thread per component; x_out may alias x.  dt = -1 / n_sde, beta = fma(t_g, beta_1 - beta_0, beta_0),
+ *     z = xi(seed, cells[1], i, word0 + c)   (the caller passes D_total + the key's first word: not the corrector's words);
+ *     x_out = x + (-0.5 beta x) dt + sqrtf(beta) sqrtf(|dt|) z - dt beta score.
+ * Null pointers, N < 1, D outside [1, 1024], n_times, G1, n_alpha, n_sde < 1, T <= 0, snr <= 0, beta_1 < beta_0: invalid.
+ * ------------------------------------------------------------------------------------------ */
+int e3k_sampler_begin_step(const float* times, int64_t n_times, int64_t* cells, float* t, int32_t G1, void* stream);
+int e3k_sampler_langevin(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t,
+                         const float* alphas, int64_t N, int32_t D, int32_t G, int32_t n_alpha, float beta_0, float beta_1, float T,
+                         float snr, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells, uint32_t word0, float* norms,
+                         void* stream);
+int e3k_sampler_reverse_em(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t, int64_t N,
+                           int32_t D, int32_t G, float beta_0, float beta_1, int32_t n_sde, uint32_t seed_lo, uint32_t seed_hi,
+                           const int64_t* cells, uint32_t word0, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A convolution layer as ONE call (csrc/e3k_layer.hip): FactorizedConvolution + Gate
  * (e3_layers/nn/message_passing.py:91-124, 249) forward and backward -- the launch sequence of
  * backend/conv_block.py issued from native code on the caller's streams, with the library's own events

@@ -10,12 +10,18 @@ Proteins (``--protein``): config_diffusion_CA as shipped but built with the decl
 eager sampler loop on the same tree and start -- the only way to sample these nets before.
 
     python tools/sample_bench.py --protein --steps 100 --out profiles/protein_sampler_replay.json
+    python tools/sample_bench.py --protein --seed 7 --corrector langevin --steps 100      (-> profiles/protein_sampler_pc.json)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/sample_bench.py --protein --trace-steps 40
     python tools/sample_bench.py --launches DIR_A/..._kernel_stats.csv 10 DIR_B/..._kernel_stats.csv 40    (launches per replayed step)
 
 Protocol (tools/md_bench.py's): device events around ``--steps`` reverse steps after a warm-up, the two variants alternating in one
 process, ``--reps`` repetitions each (min / median / max); host-busy time is the wall time of the enqueue loop before the closing
-synchronisation.  No threshold is asserted: the numbers are quoted in README.md and DESIGN.md."""
+synchronisation.  No threshold is asserted: the numbers are quoted in README.md and DESIGN.md.
+
+``--seed S`` times the seeded form (``get_pc_sampler(seed=S)``: counter-based noise, one launch per key around each model call, the
+time and the step number in device cells): the seeded replay against the seeded eager loop and -- with ``--corrector none``, the only
+corrector the unseeded replay serves -- against the unseeded replay, the three alternating in one process.  ``--trace-steps`` and
+``--launches`` then count the seeded replay's launches."""
 import argparse, csv, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
@@ -118,6 +124,56 @@ def replay_loop(model, sde, batch, timesteps, slack):
         return CappedLoop(b, model, [lambda w: w, lambda w: pred.update_fn(w)], ["CA"], float(timesteps[0]), e_cap, None), e_cap
 
 
+def seeded_updates(model, sde, seed, cells, corrector):
+    """[corrector, predictor] of the seeded form, as get_pc_sampler builds them"""
+    from functools import partial
+
+    from e3_layers_amd.run.sde_utils import langevin_step_counter, reverse_step_counter
+
+    corr = partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=0.16) if corrector == "langevin" else (lambda w: w)
+    return [corr, partial(reverse_step_counter, sde, model, seed=seed, draw=cells)]
+
+
+def seeded_replay_loop(model, sde, batch, timesteps, e_cap, seed, corrector):
+    from e3_layers_amd.run.sde_sampling import CappedLoop
+
+    b = batch.clone()
+    b.attrs["t"] = ("graph", "1x0e")
+    cells = torch.zeros(2, dtype=torch.int64, device=timesteps.device)
+    with torch.no_grad():
+        return CappedLoop(b, model, seeded_updates(model, sde, seed, cells, corrector), ["CA"], float(timesteps[0]), e_cap, None,
+                          seeded=(timesteps, cells))
+
+
+def seeded_eager_loop(model, sde, batch, timesteps, crit, n_steps, seed, corrector):
+    """pc_sampler's eager path with a seed: the step header, corrector, predictor; the per-edge keys dropped after each"""
+    from e3_layers_amd.run.sde_sampling import SAMPLER_EDGE_KEYS
+    from e3_layers_amd.run.sde_utils import sampler_begin_step
+
+    cells = torch.zeros(2, dtype=torch.int64, device=timesteps.device)
+    updates = seeded_updates(model, sde, seed, cells, corrector)
+    state = {"b": batch.clone()}
+    state["b"].attrs["t"] = ("graph", "1x0e")
+    state["b"]["t"] = torch.empty(len(batch), 1, device=timesteps.device)
+    crit.reset()
+
+    def loop():
+        b = state["b"]
+        t_dev = b["t"]
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            for i in range(n_steps):
+                sampler_begin_step(timesteps, cells, t_dev)
+                for update in updates:
+                    b = update(b)
+                    for k in SAMPLER_EDGE_KEYS:
+                        b.pop(k)
+        state["b"] = b
+        return time.perf_counter() - t0
+
+    return loop
+
+
 def timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -144,9 +200,15 @@ def protein(argv):
     ap.add_argument("--slack", type=float, default=1.15, help="edge capacity = slack x the first list, rounded up to 1024")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
+    ap.add_argument("--seed", type=int, default=None, help="time the seeded form (get_pc_sampler(seed=...)) as well")
+    ap.add_argument("--corrector", choices=("none", "langevin"), default="none", help="with --seed: the corrector of the seeded loops")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     model, sde, batch, timesteps, crit = protein_setup(args.proteins, args.residues, dev)
+    if args.seed is not None:
+        return protein_seeded(args, model, sde, batch, timesteps, crit)
+    if args.corrector != "none":
+        raise SystemExit("--corrector langevin needs --seed: the unseeded replay serves NoneCorrector only")
     loop, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
 
     def replay(n):
@@ -195,6 +257,67 @@ def protein(argv):
     if args.out:
         with open(args.out, "w") as f:
             f.write(text + "\n")
+
+
+def protein_seeded(args, model, sde, batch, timesteps, crit):
+    """The seeded replay, the seeded eager loop and (NoneCorrector only) the unseeded replay, alternating."""
+    plain, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
+    if args.corrector == "langevin":      # (two model calls per step, and the corrector moves the nodes before the second list)
+        e_cap = -(-int(1.1 * e_cap) // 1024) * 1024
+    loop = seeded_replay_loop(model, sde, batch, timesteps, e_cap, args.seed, args.corrector)
+
+    def replay(which, n):
+        def run():
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                which.run(timesteps, n)
+            return time.perf_counter() - t0
+        return run
+
+    if args.trace_steps:
+        loop.rewind()
+        replay(loop, args.trace_steps)()
+        torch.cuda.synchronize()
+        print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
+                          "corrector": args.corrector}))
+        return
+    variants = {"seeded_replay": lambda n: (loop.rewind(), replay(loop, n))[1],
+                "seeded_eager": lambda n: seeded_eager_loop(model, sde, batch, timesteps, crit, n, args.seed, args.corrector)}
+    if args.corrector == "none":
+        variants["replay"] = lambda n: (plain.rewind(), replay(plain, n))[1]
+    for make in variants.values():
+        make(args.warmup)()
+    rows = {name: [] for name in variants}
+    host = {name: [] for name in variants}
+    for _ in range(args.reps):
+        for name, make in variants.items():
+            ms, busy = timed(make(args.steps))
+            if name == "seeded_replay":
+                loop.result()                       # (after the closing event: an overflowed repetition would raise here)
+            elif name == "replay":
+                plain.result()
+            rows[name].append(ms / args.steps)
+            host[name].append(1e3 * busy / args.steps)
+
+    def mmm(v):
+        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
+
+    doc = {"workload": f"reverse diffusion (Euler-Maruyama, corrector {args.corrector}, first steps of N=1000) on config_diffusion_CA as "
+                       "shipped, built with pair_criterion(); synth_protein; seeded form",
+           "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
+           "corrector": args.corrector, "nodes": int(batch["CA"].shape[0]), "edges_first_list": loop.first_edges, "e_cap": e_cap,
+           "n_cap": loop.bucket.n_cap, "steps": args.steps, "reps": args.reps, "recaptures": loop.step.recaptures}
+    for name in variants:
+        doc[f"{name}_ms_per_step"] = mmm(rows[name])
+        doc[f"{name}_host_busy_ms_per_step"] = mmm(host[name])
+    if "replay" not in variants:
+        doc["replay_ms_per_step"] = "not measured: the unseeded replay refuses the Langevin corrector"
+    doc["speedup_median_seeded_replay_over_seeded_eager"] = round(statistics.median(rows["seeded_eager"]) / statistics.median(rows["seeded_replay"]), 3)
+    text = json.dumps(doc, indent=1)
+    print(text)
+    out = args.out or os.path.join(ROOT, "profiles", "protein_sampler_pc.json")
+    with open(out, "w") as f:
+        f.write(text + "\n")
 
 
 if __name__ == "__main__":
