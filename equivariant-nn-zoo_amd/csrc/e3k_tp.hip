@@ -74,13 +74,49 @@ __device__ __forceinline__ void load_y_full(YRegs& y, const float* __restrict__ 
   for (int j = 0; j < 5; ++j) y.y2[j] = yr[4 + j];
 }
 
-// MODE 1 (table): the edge's path weights are not read from w[e] but interpolated here from the four rows of the radial knot
-// table around the edge's radius with the edge's weights coef[e, 0..3] (same products, same order as
-// rtable_interp_fwd_kernel): w[E, W] is never written or read; the table (2-4 MB a layer) is served by L2.
-// MODE 2 (table, second-order forms of force training): a second operand set (x2, sh2, s2) rides along and the kernel forms
-// the sum of the three terms in which exactly one of (x, sh, w) is replaced by its partner -- x2, sh2, and s2[e] * dw/dr[e]
-// with dw/dr interpolated from the slope table D (a.w2) by the same four weights: the derivative of the trilinear product
-// along (x2, sh2, s2 in r) -- in one walk over the edges instead of three.
+// ---- kernel variants: the MODE template parameter of tp_fwd_kernel / tp_fwd_body* and of tp_bwd_x_kernel / tp_bwd_x_body* --------
+// (plain ints: the number is part of the kernels' mangled names, of the route strings and of every committed profile, and the rest
+//  of the project speaks it -- "MODE 5")
+// Where the path weights w[e] come from:
+//   streamed  a.w = w [E, W], one row per edge (every plan; the other two: channel-complete (FULL) plans only)
+//   table     a.w = the radial knot table T [K + 1, W]; w[e] is interpolated here from the four rows around the edge's radius with
+//             the edge's weights coef[e, 0..3] (same products, same order as rtable_interp_fwd_kernel): w [E, W] is never written
+//             or read; the table (2-4 MB a layer) is served by L2
+//   packed    a.w = the packed table [K + 1, 3 W] (see PackedRec below), walked by edge records (a.erec: they carry nbr, bin, coef, sh)
+// Second-order forms of force training (FULL plans): a second operand set (x2, sh2, s2) rides along; dw/dr[e] comes from a.w2, the
+// slope table D interpolated by the same four weights (table) or the materialised rows dw [E, W] (streamed).
+//   forward              weights   reads beside x, sh, w         writes
+//   kFwdStream       0   streamed                                out = TP(x, sh, w)
+//   kFwdTable        1   table     bin, coef                     out
+//   kFwdJvpTable     2   table     bin, coef, D, x2, sh2, s2     out = TP(x2, sh, w) + TP(x, sh2, w) + TP(x, sh, s2 dw/dr)       (a)
+//   kFwdJvp          3   streamed  dw, x2, sh2, s2               the same
+//   kFwdPacked       4   packed    erec                          out
+//   input gradient       weights   reads beside sh, w, g_out     writes
+//   kBwdXStream      0   streamed                                g_x
+//   kBwdXTable       1   table     bin, coef                     g_x
+//   kBwdXDualTable   2   table     bin, coef, D, sh2, s2         g_x = yg(sh2, g, w) + yg(sh, g, s2 dw/dr)                       (b)
+//   kBwdXDual        3   streamed  dw, sh2, s2                   the same
+//   kBwdXPacked      4   packed    erec                          g_x
+//   kBwdXwPacked     5   packed    erec, x                       g_x, g_w                                                        (c)
+//   kBwdXw           6   streamed  x                             g_x, g_w: force training's rows, and plans that are not FULL
+//   kBwdXwDual       7   streamed  dw, sh2, s2, x, x2            kBwdXDual's g_x, g_w, optionally g_w2                           (d)
+//   kBwdXe           8   streamed  dw, x                         kBwdXw's g_x and (optionally) g_w, g_sh, g_r                    (e)
+// (a) the sum of the three terms in which exactly one of (x, sh, w) is replaced by its partner -- x2, sh2, and s2[e] * dw/dr[e]: the
+//     derivative of the trilinear product along (x2, sh2, s2 in r) -- in one walk over the edges instead of three
+// (b) the node-feature gradient of the product's derivative along (sh2, s2 in r)
+// (c) ... and the WEIGHT gradient of every edge beside it.  Both gradients contract the same sums t[m1] = sum CG sh[m2] g[m3] of an
+//     edge and a path: g_x[src] += w t, g_w[e] = <x[src], t> -- with the source's own rows resident (2 l1 + 1 registers) the second
+//     costs 2 l1 + 1 FMAs and one 256-byte store per path, against a whole second walk of the edges (tp_bwd_w_kernel: the sh, x[src]
+//     and g[dst] gathers again) -- and the 0.5 GB of g_w [E, W] leave through HBM while this kernel waits on its L2 gathers
+// (d) ... + the weight gradients that share its sums -- the dual one, g_w[e] = <x2, t(sh)> + <x, t(sh2)> (what tp_bwd_w_dual forms in
+//     a walk of its own), and optionally the plain one, g_w2[e] = <x, t(sh)> (tp_bwd_w): the u-sweep of force training wants all three
+// (e) force training's first backward: kBwdXw + the EDGE gradients of tp_bwd_e in the same walk -- g_sh[e] += xg(x[src], g[dst], w)
+//     (nine values: butterfly + one atomic per wave), g_r[e] += <g_w[e], dw/dr[e]> (one value) -- every operand of both is already in
+//     this walk's registers; g_w is stored only when asked for
+constexpr int kFwdStream = 0, kFwdTable = 1, kFwdJvpTable = 2, kFwdJvp = 3, kFwdPacked = 4;
+constexpr int kBwdXStream = 0, kBwdXTable = 1, kBwdXDualTable = 2, kBwdXDual = 3, kBwdXPacked = 4, kBwdXwPacked = 5, kBwdXw = 6,
+              kBwdXwDual = 7, kBwdXe = 8;
+
 struct KnotRows {
   __amdgpu_buffer_rsrc_t ra, rb, rc, rd;
   float c0, c1, c2, c3;
@@ -115,7 +151,7 @@ __device__ __forceinline__ float knot_mix(float c0, float c1, float c2, float c3
   return fmaf(c3, vd, fmaf(c2, vc, fmaf(c1, vb, c0 * va)));
 }
 
-// MODE 4 (packed table, round 5): the same cubic from 12 bytes per (knot, weight) in ONE table row -- {d0, d1: f32; d2 * 2^10,
+// The packed table (round 5): the same cubic from 12 bytes per (knot, weight) in ONE table row -- {d0, d1: f32; d2 * 2^10,
 // d3 * 2^16: f16}, the Taylor coefficients about the middle of the knot interval (e3k_rtable_pack; a row = its W (d0, d1) pairs, then
 // its W f16 pairs) -- one dwordx2 + one dword load per slot instead of four dword loads out of four rows: 23 instead of 31 KB of
 // table per edge through L1, half the table's VMEM instructions.  a.w is then the packed table [K + 1, 3 W] (dwords).
@@ -181,8 +217,8 @@ template <int L1, int L3MAX, int MODE, int PART>
 __device__ __forceinline__ void tp_fwd_body_full(const TpArgs& a, const e3k_tp_group& g, const int node, const int u) {
   using S = Slots<L1>;
   constexpr int D1 = 2 * L1 + 1;
-  constexpr bool TABLE = MODE == 1 || MODE == 2, JVP = MODE == 2 || MODE == 3;      // MODE 3: the JVP form on STREAMED w[e], dw/dr[e] rows
-  constexpr bool PACKED = MODE == 4;
+  constexpr bool TABLE = MODE == kFwdTable || MODE == kFwdJvpTable, JVP = MODE == kFwdJvpTable || MODE == kFwdJvp;
+  constexpr bool PACKED = MODE == kFwdPacked;
   const int u4 = u * 4;
   const int xoff4 = uniform(g.x_off * 4), mul4 = uniform(g.mul * 4);
   int woff4[S::NQ];
@@ -311,7 +347,7 @@ __device__ __forceinline__ void tp_fwd_body_full(const TpArgs& a, const e3k_tp_g
 // across lanes l and l ^ 32 once per node.
 template <int L1, int L3MAX, int MODE, int PART, bool FULL, bool HALF = false>
 __device__ __forceinline__ void tp_fwd_body(const TpArgs& a, const e3k_tp_group& g, const int node, const int u) {
-  static_assert(FULL || MODE == 0, "the table forms exist for FULL plans only");
+  static_assert(FULL || MODE == kFwdStream, "the table forms exist for FULL plans only");
   if constexpr (FULL) {
     tp_fwd_body_full<L1, L3MAX, MODE, PART>(a, g, node, u);
     return;
@@ -679,26 +715,14 @@ __device__ __forceinline__ void tp_bwd_e_body(const TpArgs& a, const e3k_tp_grou
 // ------------------------------------------------------------------------------------------
 // backward wrt the node features: walk the out-edges of a source node
 // ------------------------------------------------------------------------------------------
-// MODE 0: w streamed; 1: w interpolated from the knot table; 2 (table, DUAL): g_x = yg(sh2, g, w) + yg(sh, g, s2 * dw/dr) --
-// the node-feature gradient of the product's derivative along (sh2, s2 in r) (second-order term of force training)
 template <int L1, int L3MAX, int MODE, int PART>
 __device__ __forceinline__ void tp_bwd_x_body_full(const TpArgs& a, const e3k_tp_group& g, const int node, const int u) {
   using S = Slots<L1>;
   constexpr int D1 = 2 * L1 + 1;
-  constexpr bool TABLE = MODE == 1 || MODE == 2, DUAL = MODE == 2 || MODE == 3 || MODE == 7;     // MODE 3: the DUAL form on STREAMED w[e], dw/dr[e] rows
-  // MODE 7: MODE 3 + the weight gradients that share its sums -- the DUAL one, g_w[e] = <x2, t(sh)> + <x, t(sh2)> (what tp_bwd_w_dual
-  // forms in a walk of its own), and optionally the plain one, g_w2[e] = <x, t(sh)> (tp_bwd_w): the u-sweep of force training wants all three
-  constexpr bool GW2 = MODE == 7;
-  constexpr bool PACKED = MODE == 4 || MODE == 5;                                   // MODE 4: w from the packed table (see tp_fwd_body_full)
-  // MODE 5: ... and the WEIGHT gradient of every edge beside it.  Both gradients contract the same sums t[m1] = sum CG sh[m2] g[m3]
-  // of an edge and a path: g_x[src] += w t, g_w[e] = <x[src], t> -- with the source's own rows resident (2 l1 + 1 registers) the
-  // second costs 2 l1 + 1 FMAs and one 256-byte store per path, against a whole second walk of the edges (tp_bwd_w_kernel: the
-  // sh, x[src] and g[dst] gathers again) -- and the 0.5 GB of g_w [E, W] leave through HBM while this kernel waits on its L2 gathers
-  constexpr bool GW = MODE == 5 || MODE == 6;      // (MODE 6: the same with the weights STREAMED from w[E, W] -- force training's rows)
-  // MODE 8 (streamed rows w, dw/dr [E, W]; force training's first backward): MODE 6 + the EDGE gradients of tp_bwd_e in the same walk --
-  // g_sh[e] += xg(x[src], g[dst], w) (nine values: butterfly + one atomic per wave), g_r[e] += <g_w[e], dw/dr[e]> (one value) -- every
-  // operand of both is already in this walk's registers; g_w is stored only when asked for
-  constexpr bool GE = MODE == 8;
+  constexpr bool TABLE = MODE == kBwdXTable || MODE == kBwdXDualTable;
+  constexpr bool DUAL = MODE == kBwdXDualTable || MODE == kBwdXDual || MODE == kBwdXwDual;
+  constexpr bool PACKED = MODE == kBwdXPacked || MODE == kBwdXwPacked;
+  constexpr bool GW = MODE == kBwdXwPacked || MODE == kBwdXw, GW2 = MODE == kBwdXwDual, GE = MODE == kBwdXe;
   const int mul = g.mul;
   const int u4 = u * 4;
   int goff4[S::NQ], gstr4[S::NQ], woff4[S::NQ];
@@ -857,7 +881,7 @@ __device__ __forceinline__ void tp_bwd_x_body_full(const TpArgs& a, const e3k_tp
         const float sa = wn[Q] * cf[Q], sb = w2[Q] * cf[Q];
         float dd = 0.0f, dp = 0.0f;
 #pragma unroll
-        for (int i = 0; i < D1; ++i) gx[i] = fmaf(sa, ta[i], gx[i]);      // (the order and the bits of the two CG::yg calls of MODE 3)
+        for (int i = 0; i < D1; ++i) gx[i] = fmaf(sa, ta[i], gx[i]);      // (the order and the bits of the two CG::yg calls of kBwdXDual)
 #pragma unroll
         for (int i = 0; i < D1; ++i) {
           gx[i] = fmaf(sb, tb[i], gx[i]);
@@ -877,7 +901,7 @@ __device__ __forceinline__ void tp_bwd_x_body_full(const TpArgs& a, const e3k_tp
         float dot = 0.0f;
 #pragma unroll
         for (int i = 0; i < D1; ++i) {
-          gx[i] = fmaf(sw, tq[i], gx[i]);      // (the bits of CG::yg: MODE 4 and MODE 5 give the same g_x)
+          gx[i] = fmaf(sw, tq[i], gx[i]);      // (the bits of CG::yg: kBwdXPacked and kBwdXwPacked give the same g_x)
           dot = fmaf(xs[i], tq[i], dot);
         }
         buf_st_stream(dot * cf[Q], rgw, u4, woff4[Q]);
@@ -916,12 +940,12 @@ __device__ __forceinline__ void tp_bwd_x_body_full(const TpArgs& a, const e3k_tp
 
 template <int L1, int L3MAX, int MODE, int PART, bool FULL, bool HALF = false>
 __device__ __forceinline__ void tp_bwd_x_body(const TpArgs& a, const e3k_tp_group& g, const int node, const int u) {
-  static_assert(FULL || MODE == 0 || MODE == 6, "the table forms exist for FULL plans only");
+  static_assert(FULL || MODE == kBwdXStream || MODE == kBwdXw, "the table forms exist for FULL plans only");
   if constexpr (FULL) {
     tp_bwd_x_body_full<L1, L3MAX, MODE, PART>(a, g, node, u);
     return;
   }
-  constexpr bool GW = MODE == 6;      // ... with the per-edge weight gradient in the same walk (see tp_bwd_x_body_full)
+  constexpr bool GW = MODE == kBwdXw;      // ... with the per-edge weight gradient in the same walk (see tp_bwd_x_body_full)
   using S = Slots<L1>;
   constexpr int D1 = 2 * L1 + 1;
   const int mul = g.mul;
@@ -1073,12 +1097,10 @@ __device__ __forceinline__ void tp_bwd_w_dual_body(const TpArgs& a, const e3k_tp
   tp_bwd_w_body<L1, false, L3MAX, PART, FULL, true>(a, g, node, u);
 }
 
-// MODE: 0 = per-edge weights streamed from w[E, W]; 1 = interpolated from the knot table inside the kernel; 2 = the table
-// form's second-order (JVP / DUAL) variant -- FULL plans only for 1 and 2
 // (packed form, l_max <= 2 plans: 67 VGPRs as the compiler first allocates them -- one step over the 64 of eight waves per SIMD; asked
 //  for eight, it fits without spilling)
-#define E3K_TP_FWD_WAVES(MODE, MAXL, L3MAX) ((MODE == 4 && MAXL <= 2 && L3MAX <= 2) ? 8 : 1)
-template <int MAXL, int L3MAX, bool SPLIT, bool FULL, int MODE = 0>
+#define E3K_TP_FWD_WAVES(MODE, MAXL, L3MAX) ((MODE == kFwdPacked && MAXL <= 2 && L3MAX <= 2) ? 8 : 1)
+template <int MAXL, int L3MAX, bool SPLIT, bool FULL, int MODE = kFwdStream>
 __global__ __launch_bounds__(256, E3K_TP_FWD_WAVES(MODE, MAXL, L3MAX)) void tp_fwd_kernel(TpArgs a, const e3k_tp_group* __restrict__ groups,
                                                      const int2* __restrict__ gc, int n_gc) {
   E3K_TP_PROLOGUE
@@ -1092,12 +1114,12 @@ __global__ __launch_bounds__(256) void tp_bwd_w_kernel(TpArgs a, const e3k_tp_gr
   E3K_TP_DISPATCH(tp_bwd_w_body, WITH_SH, L3MAX)
 }
 
-#define E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX) ((MODE == 5 && MAXL <= 2 && L3MAX <= 2) ? 8 : 1)
-template <int MAXL, int L3MAX, bool SPLIT, bool FULL, int MODE = 0>
+#define E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX) ((MODE == kBwdXwPacked && MAXL <= 2 && L3MAX <= 2) ? 8 : 1)
+template <int MAXL, int L3MAX, bool SPLIT, bool FULL, int MODE = kBwdXStream>
 __global__ __launch_bounds__(256, E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX)) void tp_bwd_x_kernel(TpArgs a, const e3k_tp_group* __restrict__ groups,
                                                        const int2* __restrict__ gc, int n_gc) {
   E3K_TP_PROLOGUE
-  if constexpr (MODE == 8) {      // (e_store: this work item's slices of the edge-gradient partials)
+  if constexpr (MODE == kBwdXe) {      // (e_store: this work item's slices of the edge-gradient partials)
     TpArgs ap = a;
     if (a.e_store) {
       if (a.g_sh) ap.g_sh = a.g_sh + (int64_t)gci * a.e_edges * a.d_sh;
@@ -1172,60 +1194,199 @@ extern "C" void e3k_tp_limits(int* l1max, int* l2max, int* l3max) {
 }
 
 namespace {
-template <int L1>
-int max_l3_of(unsigned mask) {
-  int m = 0;
-  for (int q = 0; q < e3k::Slots<L1>::NQ; ++q)
-    if ((mask & (1u << q)) && e3k::Slots<L1>::L3[q] > m) m = e3k::Slots<L1>::L3[q];
-  return m;
-}
-template <int L1>
-void slot_counts_of(unsigned mask, int& n_acc, int& lo, int& hi) {
-  using S = e3k::Slots<L1>;
-  for (int q = 0; q < S::NQ; ++q) {
-    if (!(mask & (1u << q))) continue;
-    const int d = 2 * S::L3[q] + 1;
-    n_acc += d;
-    if (q < e3k::SplitAt<L1>::Q) lo += d; else hi += d;
-  }
-}
-void plan_slot_counts(const e3k_tp_group& g, int& n_acc, int& lo, int& hi) {
-  switch (g.l1) {
-    case 0: slot_counts_of<0>(g.mask, n_acc, lo, hi); break;
-    case 1: slot_counts_of<1>(g.mask, n_acc, lo, hi); break;
-    case 2: slot_counts_of<2>(g.mask, n_acc, lo, hi); break;
-    default: slot_counts_of<3>(g.mask, n_acc, lo, hi); break;
-  }
-}
-template <int L1>
-unsigned full_mask_of(int l3max) {
-  unsigned m = 0;
-  for (int q = 0; q < e3k::Slots<L1>::NQ; ++q)
-    if (e3k::Slots<L1>::L3[q] <= l3max) m |= 1u << q;
-  return m;
-}
-unsigned plan_full_mask(int l1, int l3max) {
+// f(std::integral_constant<int, l1>{}): a group's input degree as a compile-time constant (Slots<L1>, SplitAt<L1>)
+template <class F>
+auto with_l1(int l1, F&& f) {
+  static_assert(E3K_L1MAX == 3, "one case per input degree");
   switch (l1) {
-    case 0: return full_mask_of<0>(l3max);
-    case 1: return full_mask_of<1>(l3max);
-    case 2: return full_mask_of<2>(l3max);
-    default: return full_mask_of<3>(l3max);
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
   }
 }
+// accumulators of the group's enabled slots: all of them, and those of the two slot parts
+void plan_slot_counts(const e3k_tp_group& g, int& n_acc, int& lo, int& hi) {
+  with_l1(g.l1, [&](auto l1) {
+    using S = e3k::Slots<decltype(l1)::value>;
+    for (int q = 0; q < S::NQ; ++q) {
+      if (!(g.mask & (1u << q))) continue;
+      const int d = 2 * S::L3[q] + 1;
+      n_acc += d;
+      if (q < e3k::SplitAt<decltype(l1)::value>::Q) lo += d; else hi += d;
+    }
+  });
+}
+// every slot of input degree l1 with an output degree up to l3max
+unsigned plan_full_mask(int l1, int l3max) {
+  return with_l1(l1, [&](auto l1c) {
+    using S = e3k::Slots<decltype(l1c)::value>;
+    unsigned m = 0;
+    for (int q = 0; q < S::NQ; ++q)
+      if (S::L3[q] <= l3max) m |= 1u << q;
+    return m;
+  });
+}
+int plan_max_l3(const e3k_tp_group& g) {
+  return with_l1(g.l1, [&](auto l1) {
+    using S = e3k::Slots<decltype(l1)::value>;
+    int m = 0;
+    for (int q = 0; q < S::NQ; ++q)
+      if ((g.mask & (1u << q)) && S::L3[q] > m) m = S::L3[q];
+    return m;
+  });
+}
+
+// ---- plan -> kernel cell -> kernel ------------------------------------------------------------------------------------------
+// The cell (MAXL, L3MAX, SPLIT, FULL) whose kernels serve a plan.  Instantiations exist per largest input degree with outputs up
+// to the same degree (l_max-limited models) or up to 3, the latter also in the split form (two waves per group).
+struct TpCell {
+  int maxl, l3max;
+  bool split, full;
+};
+TpCell plan_cell(const e3k_tp_plan* p) {
+  return {p->max_l1, (p->max_l3 <= p->max_l1 && !p->split) ? p->max_l1 : 3, p->split != 0, p->full64 != 0};
+}
+
+// What the C ABI can ask of a plan, one kind per (kernel family, variant).  *_TABLE / *_PACKED: the path weights come from the knot
+// table / the packed table instead of streamed rows.  TP_BWD_XW_DUAL and TP_BWD_XE exist on streamed rows only (their entry points
+// take no table).
+enum TpKind { TP_FWD, TP_BWD_W, TP_BWD_W_SH, TP_BWD_X, TP_BWD_XW,                                  // every plan
+              TP_FWD_TABLE, TP_BWD_X_TABLE, TP_FWD_PACKED, TP_BWD_X_PACKED, TP_BWD_XW_PACKED,      // channel-complete plans
+              // second-order forms of force training: channel-complete plans; walked by one wave per group (the l_max <= 2 models),
+              // or by two (SPLIT: l_max 3) with the weights STREAMED (w[e], dw/dr[e] materialised -- what the force block does by default)
+              TP_FWD_JVP, TP_BWD_X_DUAL, TP_BWD_E, TP_BWD_W_DUAL, TP_BWD_XW_DUAL, TP_BWD_XE,
+              TP_FWD_JVP_TABLE, TP_BWD_X_DUAL_TABLE, TP_BWD_E_TABLE };
+
 // A group whose enabled slots hold more than kSplitAcc accumulators (l_max = 3 models) is walked by two waves, one per slot part.
 constexpr int kSplitAcc = 24;
 // Every slot up to output degree 3 of an input degree l1 >= 1 is more than that (Slots<L1>::TOTAL: 27, 36, 34).  A channel-complete
-// plan enables every slot up to its instantiation's L3MAX in every group, so a channel-complete plan with L3MAX == 3 and an l1 >= 1
-// group is always split: launch_all has no FULL && !SPLIT && L3MAX == 3 && MAXL >= 1 instantiation.
+// plan enables every slot up to its cell's L3MAX in every group, so a channel-complete plan with L3MAX == 3 and an l1 >= 1
+// group is always split: tp_has_kernel leaves the cells FULL && !SPLIT && L3MAX == 3 && MAXL >= 1 empty.
 static_assert(e3k::Slots<1>::TOTAL > kSplitAcc && e3k::Slots<2>::TOTAL > kSplitAcc && e3k::Slots<3>::TOTAL > kSplitAcc,
-              "launch_all omits the unsplit channel-complete l3 <= 3 kernels of l1 >= 1 because no plan reaches them");
-int plan_max_l3(const e3k_tp_group& g) {
-  switch (g.l1) {
-    case 0: return max_l3_of<0>(g.mask);
-    case 1: return max_l3_of<1>(g.mask);
-    case 2: return max_l3_of<2>(g.mask);
-    default: return max_l3_of<3>(g.mask);
+              "tp_has_kernel omits the unsplit channel-complete l3 <= 3 kernels of l1 >= 1 because no plan reaches them");
+// Is there a kernel for this kind in this cell?  The only statement of it: launch_kind instantiates exactly the pairs that pass, and
+// every other pair refuses with E3K_ERR_UNSUPPORTED.
+constexpr bool tp_has_kernel(int MAXL, int L3MAX, bool SPLIT, bool FULL, TpKind kind) {
+  if (FULL && !SPLIT && L3MAX == 3 && MAXL >= 1) return false;      // (no plan reaches it: see kSplitAcc)
+  const bool every_plan = kind == TP_FWD || kind == TP_BWD_W || kind == TP_BWD_W_SH || kind == TP_BWD_X || kind == TP_BWD_XW;
+  const bool table2 = kind == TP_FWD_JVP_TABLE || kind == TP_BWD_X_DUAL_TABLE || kind == TP_BWD_E_TABLE;
+  if (!FULL) return every_plan;      // the table, packed and second-order forms are built without idle-lane handling
+  return !(SPLIT && table2);         // split plans: second-order forms on streamed rows only
+}
+
+// the calling thread's most recent TP launch: the kernel family and its template arguments as the launch site spells them
+struct TpRoute {
+  const char* family;
+  int n;
+  int value[5];
+  bool is_bool[5];
+};
+thread_local TpRoute tp_route{};
+thread_local char tp_route_buf[128];
+
+struct TpLaunch {
+  const e3k::TpArgs& args;
+  const e3k_tp_plan* p;
+  dim3 grid;
+  hipStream_t st;
+};
+using TpKernel = void (*)(e3k::TpArgs, const e3k_tp_group*, const int2*, int);
+template <class... P>
+int tp_go(const TpLaunch& l, TpKernel kernel, const char* family, P... params) {
+  static_assert(sizeof...(P) <= 5, "TpRoute holds five template arguments");
+  tp_route = TpRoute{family, (int)sizeof...(P), {(int)params...}, {std::is_same<P, bool>::value...}};
+  hipLaunchKernelGGL(kernel, l.grid, dim3(256), 0, l.st, l.args, l.p->d_groups, l.p->d_gc, l.p->n_gc);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+// launches e3k::FAMILY<arguments> and records it as the route
+#define E3K_TP_GO(FAMILY, ...) tp_go(l, e3k::FAMILY<__VA_ARGS__>, #FAMILY, __VA_ARGS__)
+
+template <int ML, int L3, bool SP, bool FU>
+int launch_kind(TpKind kind, const TpLaunch& l) {
+  using namespace e3k;
+  constexpr auto has = [](TpKind k) { return tp_has_kernel(ML, L3, SP, FU, k); };
+  switch (kind) {
+    case TP_FWD: if constexpr (has(TP_FWD)) return E3K_TP_GO(tp_fwd_kernel, ML, L3, SP, FU, kFwdStream); break;
+    case TP_FWD_TABLE: if constexpr (has(TP_FWD_TABLE)) return E3K_TP_GO(tp_fwd_kernel, ML, L3, SP, FU, kFwdTable); break;
+    case TP_FWD_JVP_TABLE: if constexpr (has(TP_FWD_JVP_TABLE)) return E3K_TP_GO(tp_fwd_kernel, ML, L3, SP, FU, kFwdJvpTable); break;
+    case TP_FWD_JVP: if constexpr (has(TP_FWD_JVP)) return E3K_TP_GO(tp_fwd_kernel, ML, L3, SP, FU, kFwdJvp); break;
+    case TP_FWD_PACKED: if constexpr (has(TP_FWD_PACKED)) return E3K_TP_GO(tp_fwd_kernel, ML, L3, SP, FU, kFwdPacked); break;
+    case TP_BWD_W: if constexpr (has(TP_BWD_W)) return E3K_TP_GO(tp_bwd_w_kernel, false, ML, L3, SP, FU); break;
+    case TP_BWD_W_SH: if constexpr (has(TP_BWD_W_SH)) return E3K_TP_GO(tp_bwd_w_kernel, true, ML, L3, SP, FU); break;
+    case TP_BWD_W_DUAL: if constexpr (has(TP_BWD_W_DUAL)) return E3K_TP_GO(tp_bwd_w_dual_kernel, ML, L3, SP); break;
+    case TP_BWD_E: if constexpr (has(TP_BWD_E)) return E3K_TP_GO(tp_bwd_e_kernel, ML, L3, true, SP); break;
+    case TP_BWD_E_TABLE: if constexpr (has(TP_BWD_E_TABLE)) return E3K_TP_GO(tp_bwd_e_kernel, ML, L3, false, SP); break;
+    case TP_BWD_X: if constexpr (has(TP_BWD_X)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXStream); break;
+    case TP_BWD_X_TABLE: if constexpr (has(TP_BWD_X_TABLE)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXTable); break;
+    case TP_BWD_X_DUAL_TABLE: if constexpr (has(TP_BWD_X_DUAL_TABLE)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXDualTable); break;
+    case TP_BWD_X_DUAL: if constexpr (has(TP_BWD_X_DUAL)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXDual); break;
+    case TP_BWD_X_PACKED: if constexpr (has(TP_BWD_X_PACKED)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXPacked); break;
+    case TP_BWD_XW_PACKED: if constexpr (has(TP_BWD_XW_PACKED)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXwPacked); break;
+    case TP_BWD_XW: if constexpr (has(TP_BWD_XW)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXw); break;
+    case TP_BWD_XW_DUAL: if constexpr (has(TP_BWD_XW_DUAL)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXwDual); break;
+    case TP_BWD_XE: if constexpr (has(TP_BWD_XE)) return E3K_TP_GO(tp_bwd_x_kernel, ML, L3, SP, FU, kBwdXe); break;
   }
+  return E3K_ERR_UNSUPPORTED;
+}
+#undef E3K_TP_GO
+template <int ML, int L3, bool SP>
+int launch_cell(bool full, TpKind kind, const TpLaunch& l) {
+  return full ? launch_kind<ML, L3, SP, true>(kind, l) : launch_kind<ML, L3, SP, false>(kind, l);
+}
+constexpr int cell_key(int maxl, int l3max, bool split) { return (maxl * 4 + l3max) * 2 + (split ? 1 : 0); }
+
+int launch_all(TpKind kind, const e3k::TpArgs& a, const e3k_tp_plan* p, int64_t N, hipStream_t st) {
+  static_assert(E3K_L1MAX == 3, "extend the degree switch in the kernels when the CG tables grow");
+  const int n_gc = p->n_gc;
+  if (!n_gc || N <= 0) return E3K_OK;
+  e3k::TpArgs args = a;
+  args.n_items = N * n_gc;
+  int64_t blocks = (args.n_items + 3) / 4;
+  // (packed table, layer 3 of config_energy at 256 molecules, isolated: forward 163 -> 151 us, input gradient 221 -> 215; inside the
+  //  step 124 -> 118 and 194 -> 187; the four-row form, whose 3.9 MB table stays in L2 either way, gains nothing: 187 / 188 us)
+  args.order = ((kind == TP_FWD_PACKED || kind == TP_BWD_X_PACKED || kind == TP_BWD_XW_PACKED) && N >= 64) ? 1 : 0;
+  if (args.order) blocks = 8 * ((((N + 7) / 8) * n_gc + 3) / 4);      // eight equal sub-grids, one per XCD (blocks b, b + 8, .. share one)
+  if (blocks > 0x7fffffffLL) return E3K_ERR_INVALID;
+  const TpLaunch l{args, p, dim3((unsigned)blocks), st};
+  const TpCell c = plan_cell(p);
+  // the cells plan_cell can name: L3MAX is MAXL or 3, and only plans with an l1 >= 1 group split (then with L3MAX == 3)
+  switch (cell_key(c.maxl, c.l3max, c.split)) {
+    case cell_key(0, 0, false): return launch_cell<0, 0, false>(c.full, kind, l);
+    case cell_key(0, 3, false): return launch_cell<0, 3, false>(c.full, kind, l);
+    case cell_key(1, 1, false): return launch_cell<1, 1, false>(c.full, kind, l);
+    case cell_key(1, 3, false): return launch_cell<1, 3, false>(c.full, kind, l);
+    case cell_key(1, 3, true): return launch_cell<1, 3, true>(c.full, kind, l);
+    case cell_key(2, 2, false): return launch_cell<2, 2, false>(c.full, kind, l);
+    case cell_key(2, 3, false): return launch_cell<2, 3, false>(c.full, kind, l);
+    case cell_key(2, 3, true): return launch_cell<2, 3, true>(c.full, kind, l);
+    case cell_key(3, 3, false): return launch_cell<3, 3, false>(c.full, kind, l);
+    case cell_key(3, 3, true): return launch_cell<3, 3, true>(c.full, kind, l);
+    default: return E3K_ERR_UNSUPPORTED;
+  }
+}
+
+// A call's arguments start from its plan (the row widths) ...
+e3k::TpArgs plan_args(const e3k_tp_plan* plan) {
+  e3k::TpArgs a{};
+  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  return a;
+}
+// ... and its walk.  Over a node's in-edges (CSR by destination; an edge's neighbour is its source): the forward and the weight /
+// edge gradients ...
+e3k::TpArgs walk_in_edges(const e3k_tp_plan* plan, const int32_t* src, const int32_t* dst_ptr, const int32_t* dst_perm) {
+  e3k::TpArgs a = plan_args(plan);
+  a.nbr = src; a.ptr = dst_ptr; a.perm = dst_perm;
+  return a;
+}
+// ... or over its out-edges (CSR by source; the neighbour is the destination): the input gradients, which need to know whether g_x
+// takes atomics.  (The packed forms pass the row pointers alone: their edge records carry the neighbours and the edge ids.)
+e3k::TpArgs walk_out_edges(const e3k_tp_plan* plan, const int32_t* dst, const int32_t* src_ptr, const int32_t* src_perm) {
+  e3k::TpArgs a = plan_args(plan);
+  a.nbr = dst; a.ptr = src_ptr; a.perm = src_perm;
+  a.x_shared = plan->x_shared;
+  return a;
 }
 }  // namespace
 
@@ -1312,9 +1473,8 @@ extern "C" int e3k_tp_plan_create(const e3k_tp_group* groups, int32_t n_groups, 
       p->max_l1 = groups[i].l1 > p->max_l1 ? groups[i].l1 : p->max_l1;
       p->max_l3 = plan_max_l3(groups[i]) > p->max_l3 ? plan_max_l3(groups[i]) : p->max_l3;
     }
-    // ... and every slot the kernel instantiation visits is enabled in every group (see launch_all: outputs up to the
-    // largest input degree when the model stops there, else up to 3)
-    const int l3_inst = (p->max_l3 <= p->max_l1 && !p->split) ? p->max_l1 : 3;   // the predicate of launch_all
+    // ... and every slot the plan's cell visits is enabled in every group
+    const int l3_inst = plan_cell(p).l3max;
     for (int i = 0; i < n_groups; ++i) {
       if (groups[i].mask != plan_full_mask(groups[i].l1, l3_inst)) p->full64 = 0;
       // FULL kernels read sh[e] at fixed columns: degrees 0, 1, 2 at 0, 1, 4 of a 9-wide row
@@ -1337,167 +1497,18 @@ extern "C" void e3k_tp_plan_destroy(e3k_tp_plan* p) {
   delete p;
 }
 
-namespace {
-// the instantiation of the calling thread's most recent TP launch, as the launch site spells it: "(e3k::tp_..._kernel<...>)"
-thread_local const char* tp_route = nullptr;
-thread_local char tp_route_buf[128];
-}  // namespace
-#define E3K_TP_GO(K, ...)                   \
-  do {                                      \
-    tp_route = #K;                          \
-    hipLaunchKernelGGL(K, __VA_ARGS__);     \
-  } while (0)
-
 extern "C" const char* e3k_tp_last_route(void) {
-  if (!tp_route) return nullptr;
-  const char* s = tp_route + (sizeof("(e3k::") - 1);
-  const int n = (int)strlen(s) - 1;      // (without the closing parenthesis)
-  snprintf(tp_route_buf, sizeof(tp_route_buf), "%.*s", n, s);
+  const TpRoute& r = tp_route;
+  if (!r.family) return nullptr;
+  int len = snprintf(tp_route_buf, sizeof(tp_route_buf), "%s<", r.family);
+  for (int i = 0; i < r.n; ++i) {
+    const char* sep = i ? ", " : "";
+    if (r.is_bool[i]) len += snprintf(tp_route_buf + len, sizeof(tp_route_buf) - len, "%s%s", sep, r.value[i] ? "true" : "false");
+    else len += snprintf(tp_route_buf + len, sizeof(tp_route_buf) - len, "%s%d", sep, r.value[i]);
+  }
+  snprintf(tp_route_buf + len, sizeof(tp_route_buf) - len, ">");
   return tp_route_buf;
 }
-
-namespace {
-enum TpKind { TP_FWD, TP_BWD_W, TP_BWD_W_SH, TP_BWD_X, TP_FWD_TABLE, TP_BWD_X_TABLE, TP_FWD_JVP, TP_BWD_X_DUAL, TP_BWD_E, TP_BWD_W_DUAL,
-              TP_FWD_PACKED, TP_BWD_X_PACKED, TP_BWD_XW_PACKED, TP_BWD_XW, TP_BWD_XW_DUAL, TP_BWD_XE };
-
-int launch_all(TpKind kind, const e3k::TpArgs& a, const e3k_tp_plan* p, int64_t N, hipStream_t st) {
-  static_assert(E3K_L1MAX == 3, "extend the degree switch in the kernels when the CG tables grow");
-  const int n_gc = p->n_gc;
-  if (!n_gc || N <= 0) return E3K_OK;
-  e3k::TpArgs args = a;
-  args.n_items = N * n_gc;
-  int64_t blocks = (args.n_items + 3) / 4;
-  // (packed table, layer 3 of config_energy at 256 molecules, isolated: forward 163 -> 151 us, input gradient 221 -> 215; inside the
-  //  step 124 -> 118 and 194 -> 187; the four-row form, whose 3.9 MB table stays in L2 either way, gains nothing: 187 / 188 us)
-  args.order = ((kind == TP_FWD_PACKED || kind == TP_BWD_X_PACKED || kind == TP_BWD_XW_PACKED) && N >= 64) ? 1 : 0;
-  if (args.order) blocks = 8 * ((((N + 7) / 8) * n_gc + 3) / 4);      // eight equal sub-grids, one per XCD (blocks b, b + 8, .. share one)
-  if (blocks > 0x7fffffffLL) return E3K_ERR_INVALID;
-  dim3 grid((unsigned)blocks), block(256);
-  if (kind == TP_FWD_JVP || kind == TP_BWD_X_DUAL || kind == TP_BWD_E || kind == TP_BWD_W_DUAL || kind == TP_BWD_XW_DUAL || kind == TP_BWD_XE) {
-    // second-order forms of force training: channel-complete plans; walked by one wave per group (the l_max <= 2 models), or by two
-    // (SPLIT: l_max 3) with the weights STREAMED (w[e], dw/dr[e] materialised -- what the force block does by default)
-    if (!p->full64) return E3K_ERR_UNSUPPORTED;
-    const bool lo = p->max_l3 <= p->max_l1;
-    const bool streamed = args.bin == nullptr;      // w[e] / dw[e] rows in a.w / a.w2 instead of the tables + per-edge knots
-    if ((kind == TP_BWD_XW_DUAL || kind == TP_BWD_XE) && !streamed) return E3K_ERR_UNSUPPORTED;
-    if (p->split) {
-      if (!streamed) return E3K_ERR_UNSUPPORTED;
-#define E3K_TP_LAUNCH_2S(ML)                                                                                                            \
-  switch (kind) {                                                                                                                       \
-    case TP_FWD_JVP: E3K_TP_GO((e3k::tp_fwd_kernel<ML, 3, true, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;      \
-    case TP_BWD_X_DUAL: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, 3, true, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    case TP_BWD_XW_DUAL: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, 3, true, true, 7>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    case TP_BWD_XE: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, 3, true, true, 8>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    case TP_BWD_E: E3K_TP_GO((e3k::tp_bwd_e_kernel<ML, 3, true, true>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;         \
-    default: E3K_TP_GO((e3k::tp_bwd_w_dual_kernel<ML, 3, true>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;                \
-  }
-      switch (p->max_l1) {
-        case 1: E3K_TP_LAUNCH_2S(1) break;
-        case 2: E3K_TP_LAUNCH_2S(2) break;
-        default: E3K_TP_LAUNCH_2S(3) break;
-      }
-#undef E3K_TP_LAUNCH_2S
-      E3K_CHECK_LAUNCH();
-      return E3K_OK;
-    }
-#define E3K_TP_LAUNCH_2(ML, L3)                                                                                                         \
-  switch (kind) {                                                                                                                       \
-    case TP_FWD_JVP:                                                                                                                    \
-      if (streamed) E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, false, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);   \
-      else E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, false, true, 2>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
-      break;                                                                                                                            \
-    case TP_BWD_X_DUAL:                                                                                                                 \
-      if (streamed) E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 3>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); \
-      else E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 2>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);          \
-      break;                                                                                                                            \
-    case TP_BWD_XW_DUAL:                                                                                                                \
-      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 7>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);         \
-      break;                                                                                                                            \
-    case TP_BWD_XE:                                                                                                                     \
-      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, false, true, 8>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);         \
-      break;                                                                                                                            \
-    case TP_BWD_E:                                                                                                                      \
-      if (streamed) E3K_TP_GO((e3k::tp_bwd_e_kernel<ML, L3, true, false>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);           \
-      else E3K_TP_GO((e3k::tp_bwd_e_kernel<ML, L3, false, false>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);                   \
-      break;                                                                                                                            \
-    default: E3K_TP_GO((e3k::tp_bwd_w_dual_kernel<ML, L3, false>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break;      \
-  }
-    // (l1 >= 1 with outputs up to 3 is split: see kSplitAcc)
-    switch (p->max_l1) {
-      case 0: if (lo) { E3K_TP_LAUNCH_2(0, 0) } else { E3K_TP_LAUNCH_2(0, 3) } break;
-      case 1: if (!lo) return E3K_ERR_UNSUPPORTED; E3K_TP_LAUNCH_2(1, 1) break;
-      case 2: if (!lo) return E3K_ERR_UNSUPPORTED; E3K_TP_LAUNCH_2(2, 2) break;
-      default: return E3K_ERR_UNSUPPORTED;
-    }
-#undef E3K_TP_LAUNCH_2
-    E3K_CHECK_LAUNCH();
-    return E3K_OK;
-  }
-  if (kind == TP_FWD_TABLE || kind == TP_BWD_X_TABLE || kind == TP_FWD_PACKED || kind == TP_BWD_X_PACKED || kind == TP_BWD_XW_PACKED) {      // channel-complete (FULL) plans, split or not
-    if (!p->full64) return E3K_ERR_UNSUPPORTED;
-    const bool lo = p->max_l3 <= p->max_l1, spl = p->split != 0;
-#define E3K_TP_LAUNCH_T(ML, L3, SP)                                                                                                     \
-  {                                                                                                                                     \
-    if (kind == TP_FWD_TABLE)                                                                                                           \
-      E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, SP, true, 1>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);              \
-    else if (kind == TP_FWD_PACKED)                                                                                                     \
-      E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, SP, true, 4>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);              \
-    else if (kind == TP_BWD_X_PACKED)                                                                                                   \
-      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 4>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
-    else if (kind == TP_BWD_XW_PACKED)                                                                                                  \
-      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 5>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
-    else                                                                                                                                \
-      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, true, 1>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);            \
-  }
-    // (l1 >= 1 with outputs up to 3 is split: see kSplitAcc)
-    switch (p->max_l1) {
-      case 0: if (lo) E3K_TP_LAUNCH_T(0, 0, false) else E3K_TP_LAUNCH_T(0, 3, false) break;
-      case 1: if (!spl && !lo) return E3K_ERR_UNSUPPORTED; if (!spl) E3K_TP_LAUNCH_T(1, 1, false) else E3K_TP_LAUNCH_T(1, 3, true) break;
-      case 2: if (!spl && !lo) return E3K_ERR_UNSUPPORTED; if (!spl) E3K_TP_LAUNCH_T(2, 2, false) else E3K_TP_LAUNCH_T(2, 3, true) break;
-      default: if (!spl) return E3K_ERR_UNSUPPORTED; E3K_TP_LAUNCH_T(3, 3, true) break;
-    }
-#undef E3K_TP_LAUNCH_T
-    E3K_CHECK_LAUNCH();
-    return E3K_OK;
-  }
-#define E3K_TP_LAUNCH_F(ML, L3, SP, FU)                                                                                      \
-  switch (kind) {                                                                                                   \
-    case TP_BWD_XW:                                                                                                 \
-      E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, FU, 6>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); \
-      break;                                                                                                        \
-    case TP_FWD: E3K_TP_GO((e3k::tp_fwd_kernel<ML, L3, SP, FU, 0>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    case TP_BWD_W:                                                                                                  \
-      E3K_TP_GO((e3k::tp_bwd_w_kernel<false, ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);  \
-      break;                                                                                                        \
-    case TP_BWD_W_SH:                                                                                               \
-      E3K_TP_GO((e3k::tp_bwd_w_kernel<true, ML, L3, SP, FU>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc);   \
-      break;                                                                                                        \
-    case TP_BWD_X: E3K_TP_GO((e3k::tp_bwd_x_kernel<ML, L3, SP, FU, 0>), grid, block, 0, st, args, p->d_groups, p->d_gc, n_gc); break; \
-    default: break;                                                                                                 \
-  }
-#define E3K_TP_LAUNCH(ML, L3, SP)                  \
-  if (p->full64) { E3K_TP_LAUNCH_F(ML, L3, SP, true) } \
-  else { E3K_TP_LAUNCH_F(ML, L3, SP, false) }
-#define E3K_TP_LAUNCH_NF(ML, L3, SP)               \
-  if (p->full64) return E3K_ERR_UNSUPPORTED;       \
-  E3K_TP_LAUNCH_F(ML, L3, SP, false)
-  // instantiations per input degree: outputs up to the same degree (l_max-limited models) or up to 3, the latter
-  // also in the split form (two waves per group); unsplit with outputs up to 3 and l1 >= 1: never channel-complete (see kSplitAcc)
-  const bool low = p->max_l3 <= p->max_l1;
-  const bool sp = p->split != 0;
-  switch (p->max_l1) {
-    case 0: if (low) { E3K_TP_LAUNCH(0, 0, false) } else { E3K_TP_LAUNCH(0, 3, false) } break;
-    case 1: if (low && !sp) { E3K_TP_LAUNCH(1, 1, false) } else if (!sp) { E3K_TP_LAUNCH_NF(1, 3, false) } else { E3K_TP_LAUNCH(1, 3, true) } break;
-    case 2: if (low && !sp) { E3K_TP_LAUNCH(2, 2, false) } else if (!sp) { E3K_TP_LAUNCH_NF(2, 3, false) } else { E3K_TP_LAUNCH(2, 3, true) } break;
-    default: if (!sp) { E3K_TP_LAUNCH_NF(3, 3, false) } else { E3K_TP_LAUNCH(3, 3, true) } break;
-  }
-#undef E3K_TP_LAUNCH_NF
-#undef E3K_TP_LAUNCH
-#undef E3K_TP_LAUNCH_F
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
-}
-}  // namespace
 
 extern "C" int e3k_tp_fwd(const e3k_tp_plan* plan, const float* x, const float* sh, const float* w,
                           const int32_t* src, const int32_t* dst_ptr, const int32_t* dst_perm, int64_t N, int64_t E,
@@ -1505,9 +1516,8 @@ extern "C" int e3k_tp_fwd(const e3k_tp_plan* plan, const float* x, const float* 
   if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N == 0) return E3K_OK;
   if (!x || !out || !dst_ptr || (E > 0 && (!sh || !w || !src || !dst_perm))) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
-  a.x = x; a.sh = sh; a.w = w; a.out = out; a.nbr = src; a.ptr = dst_ptr; a.perm = dst_perm;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_in_edges(plan, src, dst_ptr, dst_perm);
+  a.x = x; a.sh = sh; a.w = w; a.out = out;
   return launch_all(TP_FWD, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1518,10 +1528,8 @@ extern "C" int e3k_tp_bwd_w(const e3k_tp_plan* plan, const float* x, const float
   if (N == 0 || E == 0) return E3K_OK;
   if (!x || !sh || !g_out || !src || !dst_ptr || !dst_perm || (!g_w && !g_sh)) return E3K_ERR_INVALID;
   if (g_sh && !w) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
+  e3k::TpArgs a = walk_in_edges(plan, src, dst_ptr, dst_perm);
   a.x = x; a.sh = sh; a.w = w; a.g_out = g_out; a.g_w = g_w; a.g_sh = g_sh;
-  a.nbr = src; a.ptr = dst_ptr; a.perm = dst_perm;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
   return launch_all(g_sh ? TP_BWD_W_SH : TP_BWD_W, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1531,10 +1539,8 @@ extern "C" int e3k_tp_bwd_x(const e3k_tp_plan* plan, const float* sh, const floa
   if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N == 0) return E3K_OK;
   if (!g_out || !g_x || !src_ptr || (E > 0 && (!sh || !w || !dst || !src_perm))) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
-  a.sh = sh; a.w = w; a.g_out = g_out; a.g_x = g_x; a.nbr = dst; a.ptr = src_ptr; a.perm = src_perm;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_out_edges(plan, dst, src_ptr, src_perm);
+  a.sh = sh; a.w = w; a.g_out = g_out; a.g_x = g_x;
   return launch_all(TP_BWD_X, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1559,9 +1565,8 @@ extern "C" int e3k_tp_fwd_table(const e3k_tp_plan* plan, const float* x, const f
   if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N == 0) return E3K_OK;
   if (!x || !out || !dst_ptr || (E > 0 && (!sh || !T || !bin || !coef || !src || !dst_perm))) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
-  a.x = x; a.sh = sh; a.w = T; a.bin = bin; a.coef = coef; a.out = out; a.nbr = src; a.ptr = dst_ptr; a.perm = dst_perm;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_in_edges(plan, src, dst_ptr, dst_perm);
+  a.x = x; a.sh = sh; a.w = T; a.bin = bin; a.coef = coef; a.out = out;
   return launch_all(TP_FWD_TABLE, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1571,10 +1576,8 @@ extern "C" int e3k_tp_bwd_x_table(const e3k_tp_plan* plan, const float* sh, cons
   if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N == 0) return E3K_OK;
   if (!g_out || !g_x || !src_ptr || (E > 0 && (!sh || !T || !bin || !coef || !dst || !src_perm))) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
-  a.sh = sh; a.w = T; a.bin = bin; a.coef = coef; a.g_out = g_out; a.g_x = g_x; a.nbr = dst; a.ptr = src_ptr; a.perm = src_perm;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_out_edges(plan, dst, src_ptr, src_perm);
+  a.sh = sh; a.w = T; a.bin = bin; a.coef = coef; a.g_out = g_out; a.g_x = g_x;
   return launch_all(TP_BWD_X_TABLE, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1586,9 +1589,8 @@ extern "C" int e3k_tp_fwd_ptable(const e3k_tp_plan* plan, const float* x, const 
   if (N == 0) return E3K_OK;
   if (!x || !out || !dst_ptr || (E > 0 && (!P || !erec_dst))) return E3K_ERR_INVALID;
   if ((int64_t)plan->w_numel * 12 > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(erec_dst) & 63)) return E3K_ERR_UNSUPPORTED;
-  e3k::TpArgs a{};
-  a.x = x; a.w = static_cast<const float*>(P); a.erec = erec_dst; a.out = out; a.ptr = dst_ptr;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_in_edges(plan, nullptr, dst_ptr, nullptr);
+  a.x = x; a.w = static_cast<const float*>(P); a.erec = erec_dst; a.out = out;
   return launch_all(TP_FWD_PACKED, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1598,10 +1600,8 @@ extern "C" int e3k_tp_bwd_x_ptable(const e3k_tp_plan* plan, const void* P, const
   if (N == 0) return E3K_OK;
   if (!g_out || !g_x || !src_ptr || (E > 0 && (!P || !erec_src))) return E3K_ERR_INVALID;
   if (reinterpret_cast<uintptr_t>(erec_src) & 63) return E3K_ERR_UNSUPPORTED;
-  e3k::TpArgs a{};
-  a.w = static_cast<const float*>(P); a.erec = erec_src; a.g_out = g_out; a.g_x = g_x; a.ptr = src_ptr;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_out_edges(plan, nullptr, src_ptr, nullptr);
+  a.w = static_cast<const float*>(P); a.erec = erec_src; a.g_out = g_out; a.g_x = g_x;
   return launch_all(TP_BWD_X_PACKED, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1613,10 +1613,8 @@ extern "C" int e3k_tp_bwd_xw_ptable(const e3k_tp_plan* plan, const float* x, con
   if (N == 0) return E3K_OK;
   if (!x || !g_out || !g_x || !src_ptr || (E > 0 && (!P || !erec_src || !g_w))) return E3K_ERR_INVALID;
   if (reinterpret_cast<uintptr_t>(erec_src) & 63) return E3K_ERR_UNSUPPORTED;
-  e3k::TpArgs a{};
-  a.x = x; a.w = static_cast<const float*>(P); a.erec = erec_src; a.g_out = g_out; a.g_x = g_x; a.g_w = g_w; a.ptr = src_ptr;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_out_edges(plan, nullptr, src_ptr, nullptr);
+  a.x = x; a.w = static_cast<const float*>(P); a.erec = erec_src; a.g_out = g_out; a.g_x = g_x; a.g_w = g_w;
   return launch_all(TP_BWD_XW_PACKED, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1628,10 +1626,8 @@ extern "C" int e3k_tp_bwd_xw(const e3k_tp_plan* plan, const float* x, const floa
   if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N == 0) return E3K_OK;
   if (!x || !g_out || !g_x || !src_ptr || (E > 0 && (!sh || !w || !dst || !src_perm || !g_w))) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
-  a.x = x; a.sh = sh; a.w = w; a.g_out = g_out; a.g_x = g_x; a.g_w = g_w; a.nbr = dst; a.ptr = src_ptr; a.perm = src_perm;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_out_edges(plan, dst, src_ptr, src_perm);
+  a.x = x; a.sh = sh; a.w = w; a.g_out = g_out; a.g_x = g_x; a.g_w = g_w;
   return launch_all(TP_BWD_XW, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1673,13 +1669,11 @@ extern "C" int e3k_tp_bwd_e_table(const e3k_tp_plan* plan, const float* x, const
   if (N == 0 || E == 0) return E3K_OK;
   if (!x || !sh || !T || !D || (bin != nullptr) != (coef != nullptr) || !g_out || !src || !dst_ptr || !dst_perm || (!g_sh && !g_r && !g_w))
     return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
+  e3k::TpArgs a = walk_in_edges(plan, src, dst_ptr, dst_perm);
   a.x = x; a.sh = sh; a.w = T; a.w2 = D; a.bin = bin; a.coef = coef; a.g_out = g_out; a.g_sh = g_sh; a.g_r = g_r; a.g_w = g_w;
-  a.nbr = src; a.ptr = dst_ptr; a.perm = dst_perm;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
   const bool part = e_partials && (g_sh || g_r);
   if (part) edge_partials_args(a, plan, E, e_partials);
-  const int rc = launch_all(TP_BWD_E, a, plan, N, (hipStream_t)stream);
+  const int rc = launch_all(bin ? TP_BWD_E_TABLE : TP_BWD_E, a, plan, N, (hipStream_t)stream);
   if (rc != E3K_OK || !part) return rc;
   return edge_partials_combine(plan, E, e_partials, g_sh, g_r, (hipStream_t)stream);
 }
@@ -1692,11 +1686,9 @@ extern "C" int e3k_tp_fwd_jvp_table(const e3k_tp_plan* plan, const float* x, con
   if (N == 0) return E3K_OK;
   if (!x || !x2 || !out || !dst_ptr || (E > 0 && (!sh || !sh2 || !T || !D || (bin != nullptr) != (coef != nullptr) || !s2 || !src || !dst_perm)))
     return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
+  e3k::TpArgs a = walk_in_edges(plan, src, dst_ptr, dst_perm);
   a.x = x; a.x2 = x2; a.sh = sh; a.sh2 = sh2; a.w = T; a.w2 = D; a.bin = bin; a.coef = coef; a.s2 = s2; a.out = out;
-  a.nbr = src; a.ptr = dst_ptr; a.perm = dst_perm;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
-  return launch_all(TP_FWD_JVP, a, plan, N, (hipStream_t)stream);
+  return launch_all(bin ? TP_FWD_JVP_TABLE : TP_FWD_JVP, a, plan, N, (hipStream_t)stream);
 }
 
 extern "C" int e3k_tp_bwd_x_dual_table(const e3k_tp_plan* plan, const float* sh, const float* sh2, const float* T, const float* D,
@@ -1706,12 +1698,9 @@ extern "C" int e3k_tp_bwd_x_dual_table(const e3k_tp_plan* plan, const float* sh,
   if (N == 0) return E3K_OK;
   if (!g_out || !g_x || !src_ptr || (E > 0 && (!sh || !sh2 || !T || !D || (bin != nullptr) != (coef != nullptr) || !s2 || !dst || !src_perm)))
     return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
+  e3k::TpArgs a = walk_out_edges(plan, dst, src_ptr, src_perm);
   a.sh = sh; a.sh2 = sh2; a.w = T; a.w2 = D; a.bin = bin; a.coef = coef; a.s2 = s2; a.g_out = g_out; a.g_x = g_x;
-  a.nbr = dst; a.ptr = src_ptr; a.perm = src_perm;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
-  return launch_all(TP_BWD_X_DUAL, a, plan, N, (hipStream_t)stream);
+  return launch_all(bin ? TP_BWD_X_DUAL_TABLE : TP_BWD_X_DUAL, a, plan, N, (hipStream_t)stream);
 }
 
 // the first backward of a force evaluation in ONE walk of the source CSR (streamed rows w, dw [E, W]): g_x (e3k_tp_bwd_x), g_sh and g_r
@@ -1722,11 +1711,8 @@ extern "C" int e3k_tp_bwd_xe(const e3k_tp_plan* plan, const float* x, const floa
   if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N == 0) return E3K_OK;
   if (!x || !g_out || !g_x || !src_ptr || (E > 0 && (!sh || !w || !dw || !dst || !src_perm || (!g_sh && !g_r)))) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
+  e3k::TpArgs a = walk_out_edges(plan, dst, src_ptr, src_perm);
   a.x = x; a.sh = sh; a.w = w; a.w2 = dw; a.g_out = g_out; a.g_x = g_x; a.g_sh = g_sh; a.g_r = g_r; a.g_w = g_w;
-  a.nbr = dst; a.ptr = src_ptr; a.perm = src_perm;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
   const bool part = e_partials && E > 0;
   if (part) edge_partials_args(a, plan, E, e_partials);
   const int rc = launch_all(TP_BWD_XE, a, plan, N, (hipStream_t)stream);
@@ -1746,11 +1732,8 @@ extern "C" int e3k_tp_bwd_xw_dual(const e3k_tp_plan* plan, const float* x, const
   if (N == 0) return E3K_OK;
   if (!x || !x2 || !g_out || !g_x || !src_ptr || (E > 0 && (!sh || !sh2 || !w || !dw || !s2 || !dst || !src_perm || !g_w)))
     return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
+  e3k::TpArgs a = walk_out_edges(plan, dst, src_ptr, src_perm);
   a.x = x; a.x2 = x2; a.sh = sh; a.sh2 = sh2; a.w = w; a.w2 = dw; a.s2 = s2; a.g_out = g_out; a.g_x = g_x; a.g_w = g_w; a.g_w2 = g_w_plain;
-  a.nbr = dst; a.ptr = src_ptr; a.perm = src_perm;
-  a.x_shared = plan->x_shared;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
   return launch_all(TP_BWD_XW_DUAL, a, plan, N, (hipStream_t)stream);
 }
 
@@ -1760,8 +1743,7 @@ extern "C" int e3k_tp_bwd_w_dual(const e3k_tp_plan* plan, const float* x, const 
   if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N == 0 || E == 0) return E3K_OK;
   if (!x || !x2 || !sh || !sh2 || !g_out || !src || !dst_ptr || !dst_perm || !g_w) return E3K_ERR_INVALID;
-  e3k::TpArgs a{};
-  a.x = x; a.x2 = x2; a.sh = sh; a.sh2 = sh2; a.g_out = g_out; a.g_w = g_w; a.nbr = src; a.ptr = dst_ptr; a.perm = dst_perm;
-  a.d_in = plan->d_in; a.d_sh = plan->d_sh; a.W = plan->w_numel; a.d_mid = plan->d_mid;
+  e3k::TpArgs a = walk_in_edges(plan, src, dst_ptr, dst_perm);
+  a.x = x; a.x2 = x2; a.sh = sh; a.sh2 = sh2; a.g_out = g_out; a.g_w = g_w;
   return launch_all(TP_BWD_W_DUAL, a, plan, N, (hipStream_t)stream);
 }
