@@ -214,6 +214,16 @@ int radial_fwd(const e3k_layer* L, const e3k_layer_radial& r, void* st) {
 extern "C" int e3k_layer_create(const e3k_layer_desc* desc, e3k_layer** out) {
   if (!desc || !out || !desc->tp) return E3K_ERR_INVALID;
   if (desc->n_hidden < 1 || desc->n_hidden > 4) return E3K_ERR_UNSUPPORTED;
+  if (desc->w_live < 0 || desc->n_live < 0 || desc->n_live > 8 || (desc->w_live > 0) != (desc->n_live > 0)) return E3K_ERR_INVALID;
+  if (desc->w_live > 0) {      // a narrow layer: a scalar-output plan on the dense layer's weight row
+    if (!e3k_tp_scalar_supported(desc->tp) || (desc->w_live % 4) || desc->w_live > desc->W) return E3K_ERR_UNSUPPORTED;
+    int sum = 0;
+    for (int i = 0; i < desc->n_live; ++i) {
+      if (desc->live_col[i] < 0 || desc->live_len[i] <= 0 || desc->live_col[i] + desc->live_len[i] > desc->W) return E3K_ERR_INVALID;
+      sum += desc->live_len[i];
+    }
+    if (sum != desc->w_live) return E3K_ERR_INVALID;
+  }
   e3k_layer* L = new (std::nothrow) e3k_layer();
   if (!L) return E3K_ERR_LAUNCH;
   L->d = *desc;
@@ -310,6 +320,7 @@ extern "C" int e3k_layer_profile_read(e3k_layer* L, int32_t kind, float* ms, int
 extern "C" int e3k_layer_fwd(const e3k_layer* L, const e3k_layer_fwd_args* a) {
   if (!L || !a || a->N < 0 || a->E < 0) return E3K_ERR_INVALID;
   const e3k_layer_desc& d = L->d;
+  if (d.w_live > 0) return E3K_ERR_UNSUPPORTED;      // (a narrow layer describes a backward)
   const bool has_sc = !L->sets[SC_FWD].empty();
   void* main = a->main;
   void* side = a->fork ? a->side : main;
@@ -402,6 +413,21 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   const bool want_sc = has_sc && (a->have_m ? a->gm != nullptr : (a->gb_sc || a->need_attrs));
   const bool need_x1 = a->need_x || need_lin1;
   if (!a->gy || !a->g_conv || !a->g_mid || !a->conv) return E3K_ERR_INVALID;
+  // packed table + both gradients wanted: ONE walk of the source CSR forms g_x1 and g_w [E, W] (csrc/e3k_tp.hip, MODE 5): the
+  // weight-gradient pass re-gathered sh, x[src] and g_mid[dst] of every edge for a dot product with sums the input gradient
+  // already holds (layer 3 of config_energy at 256 molecules: 213 + 104 us -> 258 us isolated; 217 + 169 -> 261 in the replayed step)
+  const bool fused_xw = a->fuse_xw && need_x1 && in_kernel_table(d, r) && r.P && need_radial_side && a->E > 0 && a->g_w && a->x1;
+  // A narrow layer (d.w_live > 0: gy zero outside the columns its sets were pruned for) exists on that route only: its walk is the
+  // scalar-output one, its g_w and the transposed table gradient are w_live wide, and g_T -- what the radial stack's backward reads --
+  // is the compact gradient spread over the dense columns.  Dead columns of g_mid and g_w are neither written nor read.
+  const bool narrow = d.w_live > 0;
+  const int32_t w_rows = narrow ? d.w_live : d.W;      // columns of g_w and of the table gradient the transpose forms
+  // (refused here, from the arguments and the descriptor alone: nothing has been launched or written.  The caller decides the
+  //  same thing before it picks the narrow layer -- backend/conv_native.py, NativeConvBlockFn.backward, "narrow = cand" -- and falls
+  //  back to the dense layer there: keep the two conditions in step)
+  if (narrow && !(fused_xw && r.use_table && r.have_rows && a->g_T && a->g_T_live && a->table_ws && !need_last && !need_hidden &&
+                  !a->need_radial))
+    return E3K_ERR_UNSUPPORTED;
 
   // gate' -> gradient of the convolution output; both readers of it in one call
   E3K_TRY(e3k_gate_bwd(a->conv, a->gy, nullptr, a->N, d.d_conv, d.d_out, L->gate.data(), (int32_t)L->gate.size(), a->out_cf,
@@ -453,11 +479,7 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
     E3K_TRY(weight_grads(true, false, side3));
     if (want_sc) E3K_TRY(keyed_weight_grads());
   }
-  // tensor product
-  // packed table + both gradients wanted: ONE walk of the source CSR forms g_x1 and g_w [E, W] (csrc/e3k_tp.hip, MODE 5): the
-  // weight-gradient pass re-gathered sh, x[src] and g_mid[dst] of every edge for a dot product with sums the input gradient
-  // already holds (layer 3 of config_energy at 256 molecules: 213 + 104 us -> 258 us isolated; 217 + 169 -> 261 in the replayed step)
-  const bool fused_xw = a->fuse_xw && need_x1 && in_kernel_table(d, r) && r.P && need_radial_side && a->E > 0 && a->g_w && a->x1;
+  // tensor product (fused_xw: decided above, before the first launch)
   // ... the same for layers whose weights are streamed from w [E, W] (per-edge radial MLP, 32-channel plans), where the replayed /
   // one-stream step gains what the packed layers gain; with the backward forked over streams the separate weight-gradient pass
   // already runs beside the main stream's GEMMs, and stays
@@ -467,6 +489,16 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   // (MFMA and LDS) at the end of the layer -- nothing before that reads g_T when the radial stack's backward takes the rows later.
   // Forked, the two run on streams of their own; a layer profiled for the transpose keeps its own launch, which the record times.
   const bool rtable_timed = L->prof_cap > 0 && ((L->prof_mask >> E3K_PROF_RTABLE_BWD) & 1u);
+  float* const g_T_rows = narrow ? a->g_T_live : a->g_T;
+  auto spread_table_gradient = [&](void* st) -> int {
+    if (!narrow) return E3K_OK;
+    int32_t src_col[8];
+    for (int i = 0, pos = 0; i < d.n_live; ++i) {
+      src_col[i] = pos;
+      pos += d.live_len[i];
+    }
+    return e3k_expand_columns(a->g_T_live, r.R, d.w_live, d.W, src_col, d.live_col, d.live_len, d.n_live, a->g_T, st);
+  };
   const bool ride = fused_xw && r.use_table && side == main && side3 == main && !rtable_timed && a->g_T && a->table_ws &&
                     (r.have_rows || !(need_last || need_hidden || a->need_radial));
   if (need_x1) {
@@ -474,7 +506,10 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
     if (!d.tp_bwd_x_overwrites && e3k::zero_fill(a->g_x1, sizeof(float) * a->N * d.d_x1, (hipStream_t)main))
       return E3K_ERR_LAUNCH;
     Timed t(L, E3K_PROF_TP_BWD_X, main, a->N, a->E);
-    if (fused_xw) {      // ... and the per-edge weight gradient in the same walk: no tp_bwd_w pass below
+    if (narrow) {
+      E3K_TRY(e3k_tp_bwd_xw_scalar_ptable(d.tp, a->x1, r.P, d.W, d.live_col, r.erec_src, a->g_mid, a->src_ptr, a->N, a->E, a->g_x1, a->g_w,
+                                          main));
+    } else if (fused_xw) {      // ... and the per-edge weight gradient in the same walk: no tp_bwd_w pass below
       E3K_TRY(e3k_tp_bwd_xw_ptable(d.tp, a->x1, r.P, r.erec_src, a->g_mid, a->src_ptr, a->N, a->E, a->g_x1, a->g_w, main));
     } else if (fused_xw_s) {
       E3K_TRY(e3k_tp_bwd_xw(d.tp, a->x1, a->sh, r.w, a->g_mid, a->dst, a->src_ptr, a->src_perm, a->N, a->E, a->g_x1, a->g_w, main));
@@ -504,8 +539,9 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       g_rows = a->g_T;      // (written by the weight gradients' launch below)
     } else if (r.use_table) {
       Timed t(L, E3K_PROF_RTABLE_BWD, side, r.R, r.E);
-      E3K_TRY(e3k_rtable_interp_bwd(a->g_w, r.bin_coef, nullptr, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, d.W, a->table_ws,
-                                    a->g_T, 0, side));
+      E3K_TRY(e3k_rtable_interp_bwd(a->g_w, r.bin_coef, nullptr, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, w_rows, a->table_ws,
+                                    g_T_rows, 0, side));
+      E3K_TRY(spread_table_gradient(side));
       g_rows = a->g_T;
     }
     }
@@ -540,8 +576,9 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
       E3K_TRY(weight_grads(false, true, side3));
     }
   } else if (need_post || need_lin1 || want_sc || ride) {
-    const Seg::Rider rd{a->g_w, r.bin_coef, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, d.W, a->table_ws, a->g_T};
+    const Seg::Rider rd{a->g_w, r.bin_coef, r.bin_ptr, r.bin_seg, r.bin_perm, r.E, r.knots, w_rows, a->table_ws, g_T_rows};
     E3K_TRY(weight_grads(true, true, main, ride ? &rd : nullptr));
+    if (ride) E3K_TRY(spread_table_gradient(main));
     if (want_sc) E3K_TRY(keyed_weight_grads());
   }
   if (hipGetLastError() != hipSuccess) return E3K_ERR_LAUNCH;

@@ -26,18 +26,6 @@
 
 #include "e3k_tp_body.h"
 
-// the per-edge weights are read once per pass and the weight gradients written once: streamed past the caches
-// (the cache lines stay for the gathered node rows)
-#ifdef E3K_NO_NT
-#define E3K_STREAM_LOAD(p) (*(p))
-#define E3K_STREAM_STORE(v, p) (*(p) = (v))
-#define E3K_STREAM_AUX 0
-#else
-#define E3K_STREAM_AUX 2   // buffer-load cache policy bit 1 = nt
-#define E3K_STREAM_LOAD(p) __builtin_nontemporal_load(p)
-#define E3K_STREAM_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#endif
-
 namespace e3k {
 
 // FULL: every group of the plan has a multiple of 64 channels and every (l2, l3) slot its degrees allow (all output
@@ -54,18 +42,6 @@ namespace e3k {
 // registers -- 37-74 spilled to VGPR lanes and read back with v_readlane inside the edge loop -- and the k > 0 rows were
 // formed with 64-bit VECTOR adds.  sh[e] is nine unconditional scalar loads (FULL plans keep the degrees 0, 1, 2 at columns
 // 0, 1, 4 of a 9-wide row: checked when the plan is built), no branch on y_off inside the loop.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const float* base, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ float buf_ld_stream(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, E3K_STREAM_AUX));
-}
-__device__ __forceinline__ void buf_st_stream(float v, __amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, E3K_STREAM_AUX);
-}
 __device__ __forceinline__ void load_y_full(YRegs& y, const float* __restrict__ yr) {
   y.y0[0] = yr[0];
 #pragma unroll
@@ -151,67 +127,6 @@ __device__ __forceinline__ float knot_mix(float c0, float c1, float c2, float c3
   return fmaf(c3, vd, fmaf(c2, vc, fmaf(c1, vb, c0 * va)));
 }
 
-// The packed table (round 5): the same cubic from 12 bytes per (knot, weight) in ONE table row -- {d0, d1: f32; d2 * 2^10,
-// d3 * 2^16: f16}, the Taylor coefficients about the middle of the knot interval (e3k_rtable_pack; a row = its W (d0, d1) pairs, then
-// its W f16 pairs) -- one dwordx2 + one dword load per slot instead of four dword loads out of four rows: 23 instead of 31 KB of
-// table per edge through L1, half the table's VMEM instructions.  a.w is then the packed table [K + 1, 3 W] (dwords).
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-struct PackedRec {
-  float d0, d1;
-  unsigned int pk;
-};
-struct KnotPacked {
-  __amdgpu_buffer_rsrc_t r;
-  float s, s2, s3;
-};
-// the t-th edge of the walk as one aligned 64-byte record (e3k_edge_records): a single s_load_dwordx16 whose address follows from
-// the loop counter -- the packed-table kernels fetch edge t + 1's record while edge t is computed
-struct EdgeRec {
-  int nbr, bin;
-  float c0, c1, c2, c3;
-  float y[9];
-  int e;
-};
-__device__ __forceinline__ EdgeRec load_rec(const int32_t* __restrict__ erec, int t) {
-  const int32_t* __restrict__ p = static_cast<const int32_t*>(__builtin_assume_aligned(erec + 16 * (int64_t)t, 64));
-  EdgeRec r;
-  r.nbr = uniform(p[0]);
-  r.bin = uniform(p[1]);
-  r.c0 = __int_as_float(uniform(p[2])); r.c1 = __int_as_float(uniform(p[3]));
-  r.c2 = __int_as_float(uniform(p[4])); r.c3 = __int_as_float(uniform(p[5]));
-#pragma unroll
-  for (int j = 0; j < 9; ++j) r.y[j] = __int_as_float(uniform(p[6 + j]));
-  r.e = uniform(p[15]);
-  return r;
-}
-__device__ __forceinline__ void rec_y(YRegs& y, const EdgeRec& r) {
-  y.y0[0] = r.y[0];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) y.y1[j] = r.y[1 + j];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) y.y2[j] = r.y[4 + j];
-}
-__device__ __forceinline__ KnotPacked knot_packed_rec(const TpArgs& a, const EdgeRec& r, int row_p) {
-  KnotPacked k;
-  k.r = row_rsrc(a.w + 3 * (int64_t)r.bin * a.W, row_p);
-  k.s = fmaf(2.f, r.c3, r.c2 - r.c0) - 0.5f;      // t = sum_k x_k L_k(t), x = (-1, 0, 1, 2); s = t - 1/2
-  k.s2 = k.s * (1.f / 1024.f);
-  k.s3 = k.s * (1.f / 64.f);
-  return k;
-}
-// slot at weight offset woff4 (bytes of a 4-byte column) of the row, lane channel u4 = 4 u; pk_base = 8 W (bytes)
-__device__ __forceinline__ PackedRec buf_ld_rec(__amdgpu_buffer_rsrc_t r, int u4, int woff4, int pk_base) {
-  const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, u4 * 2, woff4 * 2, 0);
-  PackedRec p;
-  p.d0 = __uint_as_float(v[0]);
-  p.d1 = __uint_as_float(v[1]);
-  p.pk = __builtin_amdgcn_raw_buffer_load_b32(r, u4, pk_base + woff4, 0);
-  return p;
-}
-__device__ __forceinline__ float packed_mix(const KnotPacked& k, const PackedRec& v) {      // the order of e3k::packed_eval (e3k_rtable.hip)
-  const f16x2 h = __builtin_bit_cast(f16x2, v.pk);
-  return fmaf(k.s, fmaf(k.s2, fmaf(k.s3, (float)h.y, (float)h.x), v.d1), v.d0);
-}
 
 template <int L1, int L3MAX, int MODE, int PART>
 __device__ __forceinline__ void tp_fwd_body_full(const TpArgs& a, const e3k_tp_group& g, const int node, const int u) {
@@ -1042,33 +957,6 @@ __device__ __forceinline__ void tp_bwd_x_body(const TpArgs& a, const e3k_tp_grou
 // ------------------------------------------------------------------------------------------
 // one launch per pass: a wave looks up its work item and branches (wave-uniformly) on the input degree
 // ------------------------------------------------------------------------------------------
-// Work order.  0: node-major -- XCD x owns a contiguous slice of the (node, group-chunk) list, a workgroup = four consecutive items
-// (mostly the groups of ONE node).  1 (table forms): group-major inside the XCD's node slice -- XCD x owns nodes [x N / 8, (x + 1) N / 8)
-// and walks them group-chunk by group-chunk, a workgroup = four consecutive NODES of one group-chunk: at any time an XCD's L2 then
-// holds the table columns of ONE group (2.4 of the packed table's 11.8 MB) beside that group's feature columns of its own nodes.
-#define E3K_TP_PROLOGUE                                                        \
-  int node_, gci_;                                                             \
-  if (a.order == 0) {                                                          \
-    const int b = xcd_remap(blockIdx.x, gridDim.x);                            \
-    const int64_t item = (int64_t)b * 4 + (threadIdx.x >> 6);                  \
-    if (item >= a.n_items) return;                                             \
-    node_ = (int)(item / n_gc);                                                \
-    gci_ = (int)(item % n_gc);                                                 \
-  } else {                                                                     \
-    const int64_t n_nodes = a.n_items / n_gc;                                  \
-    const int xcd = blockIdx.x & 7;                                            \
-    const int64_t n0 = xcd * n_nodes / 8, nx = (xcd + 1) * n_nodes / 8 - n0;   \
-    const int64_t j = (int64_t)(blockIdx.x >> 3) * 4 + (threadIdx.x >> 6);     \
-    if (j >= nx * n_gc) return;                                                \
-    gci_ = (int)(j / nx);                                                      \
-    node_ = (int)(n0 + j % nx);                                                \
-  }                                                                            \
-  const int node = uniform(node_);                                             \
-  const int gci = uniform(gci_);                                               \
-  const int2 gcv = gc[gci];                                                    \
-  const e3k_tp_group& g = groups[uniform(gcv.x)];                              \
-  const int part = uniform(gcv.y) >> 16;                                        \
-  const int u = (uniform(gcv.y) & 0xffff) * 64 + (threadIdx.x & 63);
 
 // MAXL = largest input degree of the plan: the register allocation of a kernel is the maximum over the branches of
 // the degree switch, so an l_max = 2 model must not carry the l1 = 3 body (63 accumulators) it never runs.
@@ -1407,8 +1295,11 @@ extern "C" int e3k_tp_plan_create(const e3k_tp_group* groups, int32_t n_groups, 
   p->d_groups = nullptr;
   p->d_gc = nullptr;
   p->n_gc = 0;
+  p->h_groups = new e3k_tp_group[n_groups];      // (host copy: what e3k_tp_scalar.hip checks a plan by)
+  memcpy(p->h_groups, groups, sizeof(e3k_tp_group) * n_groups);
   if (hipMalloc(&p->d_groups, sizeof(e3k_tp_group) * n_groups) != hipSuccess) {
-    delete p;
+    p->d_groups = nullptr;
+    e3k_tp_plan_destroy(p);
     return E3K_ERR_LAUNCH;
   }
   if (hipMemcpy(p->d_groups, groups, sizeof(e3k_tp_group) * n_groups, hipMemcpyHostToDevice) != hipSuccess) {
@@ -1494,12 +1385,20 @@ extern "C" void e3k_tp_plan_destroy(e3k_tp_plan* p) {
   if (!p) return;
   if (p->d_groups) (void)hipFree(p->d_groups);
   if (p->d_gc) (void)hipFree(p->d_gc);
+  delete[] p->h_groups;
   delete p;
 }
+
+// (e3k_tp_scalar.hip's launch: a family with one template-free name)
+void e3k::tp_record_route(const char* family) { tp_route = TpRoute{family, 0, {}, {}}; }
 
 extern "C" const char* e3k_tp_last_route(void) {
   const TpRoute& r = tp_route;
   if (!r.family) return nullptr;
+  if (!r.n) {      // (a kernel without template arguments)
+    snprintf(tp_route_buf, sizeof(tp_route_buf), "%s", r.family);
+    return tp_route_buf;
+  }
   int len = snprintf(tp_route_buf, sizeof(tp_route_buf), "%s<", r.family);
   for (int i = 0; i < r.n; ++i) {
     const char* sep = i ? ", " : "";

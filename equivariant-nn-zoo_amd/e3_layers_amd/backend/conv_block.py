@@ -48,6 +48,22 @@ class ConvBlockPlan:
         self.prefetched = None     # radial branch of THIS layer issued by the previous layer's forward (look-ahead)
         self.guard_key = None      # the radial MLP's last-layer Parameter: key of its knot-table guard (radial_table.guard)
 
+    def replace(self, **fields) -> "ConvBlockPlan":
+        """A NEW plan with the named constructor fields substituted (``conv_native.NativeLayer.narrow``: the same layer with pruned
+        specs).  Built through the constructor: per-object state and caches (``prefetched``, the executor's layer object, whatever
+        is cached on a plan later) start empty."""
+        args = dict(in_blocks=self.in_blocks, lin1_spec=self.lin1_spec, mlp_alphas=self.mlp_alphas, mlp_act=self.mlp_act,
+                    mlp_cst=self.mlp_cst, mlp_k0=self.mlp_k0, last_spec=self.last_spec, tp_plan=self.tp_plan, post_spec=self.post_spec,
+                    scale=self.scale, sc_spec=self.sc_spec, sc_m_off=self.sc_m_off, sc_ld_m=self.sc_ld_m, gate_spec=self.gate_spec,
+                    addend=self.addend)
+        unknown = set(fields) - set(args)
+        if unknown:
+            raise TypeError(f"ConvBlockPlan.replace: no such field {sorted(unknown)}")
+        args.update(fields)
+        new = ConvBlockPlan(**args)
+        new.guard_key = self.guard_key
+        return new
+
 
 class _on:
     """``with _on(stream, main)``: launches go to ``stream`` (no-op when it is ``main``)."""

@@ -13,7 +13,8 @@ against the same sequence issued from Python.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List
+import dataclasses
+from typing import List, Optional
 
 import torch
 
@@ -21,7 +22,7 @@ from .tuning import knob as _knob
 from torch.autograd.function import once_differentiable
 
 from . import lib as L
-from . import ops, radial_table
+from . import memo, ops, radial_table
 
 # bench.py reads these three to describe the path it measured; the executor, the packed table and the fused
 # tensor-product backward are the only forms there are
@@ -31,17 +32,51 @@ _LAYERS: List["NativeLayer"] = []      # every layer object created (bench.py ar
 
 
 MAX_ROUNDS = 4
+# 1: a layer whose incoming gradient carries a valid "live_cols" mark (ops.StridedLinearFn.backward puts it on the input gradient of
+# a Linear that reads only some blocks of its input: the o3.Linear to 1x0e of an energy head) runs the backward of the paths that
+# end in those columns only -- NativeLayer.narrow; everything else about the mark's absence or the layer's shape falls back to the
+# dense backward.  0: always dense (reference runs, tests)
+LIVE_GRAD = _knob("E3K_LIVE_GRAD")
+NARROW_MAX_GROUPS = 8      # (e3k_layer_desc.live_col)
+
+
+def _hits(lo: int, hi: int, ranges) -> bool:
+    return any(lo < b and a < hi for a, b in ranges)
+
+
+def _covers(instr, width: int) -> bool:
+    """The input blocks of these instructions tile a row of ``width`` columns."""
+    return sum(w for _, w in {(ins.in_off, ins.mul_in * ins.dim) for ins in instr}) == width
+
+
+@dataclasses.dataclass
+class LiveSets:
+    """What of a layer's backward is not zero by construction when gy is zero outside ``cols`` (``NativeLayer.live_sets``)."""
+    cols: tuple            # live column ranges (lo, hi) of the layer output
+    conv: list             # ... of the pre-gate row
+    post: list             # instructions of the trailing Linear that end in a live block
+    sc: list               # (index, instruction) of the self-connection likewise
+    mid: list              # live column ranges of the tensor product's output
+    slots: list            # (group index, slot) of the live tensor-product paths
+    w: list                # their weight columns (offset, channels), in slot order
+    x1: list               # live column ranges of the tensor product's input
+    lin1: list             # instructions of linear_1 that end in a live block
 
 
 class NativeLayer:
     """The static description of one layer handed to ``e3k_layer_create`` (the ctypes arrays stay referenced here)."""
 
-    def __init__(self, plan):
+    def __init__(self, plan, narrow_of: Optional["NativeLayer"] = None):
         self.plan = plan
         self.handles = {}          # device index -> e3k_layer*
         self.keep = []             # ctypes arrays referenced by the descriptor until create() has copied them
         self.desc = self._describe(plan)      # (NotImplementedError: the executor does not take this layer)
-        _LAYERS.append(self)
+        self.narrows = {}          # live columns -> the narrow form of this layer's backward, or None (narrow())
+        self.prof = (0, 0xFFFFFFFF)      # the per-kernel timers as last armed (a narrow form built later is armed alike)
+        if narrow_of is None:
+            _LAYERS.append(self)
+        else:
+            self.prof = narrow_of.prof
 
     def _set(self, rounds) -> L.GemmSet:
         """``rounds``: [(ctypes problem array, n)] -- concatenated round-major (problems of one round write distinct
@@ -137,20 +172,111 @@ class NativeLayer:
             with torch.cuda.device(idx):
                 L.check(L.load().e3k_layer_create(C.byref(self.desc), C.byref(out)), "e3k_layer_create")
             h = self.handles[idx] = out.value
+            if self.prof[0]:
+                L.check(L.load().e3k_layer_profile_mask(h, *self.prof), "e3k_layer_profile_mask")
         return h
+
+    # ---- the backward for a gradient that is zero outside some columns ----
+    def live_sets(self, cols) -> LiveSets:
+        """Propagates "gy is zero outside the column ranges ``cols``" through the layer's own descriptors, output to input: gate
+        segments -> blocks of the pre-gate row; trailing Linear and self-connection instructions that end in one of those -> blocks
+        of the tensor product's output and of the layer input; path slots that write into one of those -> their weight columns and
+        the input blocks of their groups; linear_1 instructions that end in one of those.  Everything outside the returned sets
+        has gradient exactly zero (tests/test_live_columns_host.py checks the claim against the float64 layer)."""
+        from ..nn.core import tp_slots
+
+        plan = self.plan
+        conv = []
+        for kind, in_off, gate_off, out_off, mul, dim, _, _ in plan.gate_spec.segs:
+            if _hits(out_off, out_off + mul * dim, cols):
+                conv.append((in_off, in_off + mul * dim))
+                if kind == 1:
+                    conv.append((gate_off, gate_off + mul))
+        post = [ins for ins in plan.post_spec.instr if _hits(ins.out_off, ins.out_off + ins.mul_out * ins.dim, conv)]
+        sc = [] if plan.sc_spec is None else [(j, ins) for j, ins in enumerate(plan.sc_spec.instr)
+                                              if _hits(ins.out_off, ins.out_off + ins.mul_out * ins.dim, conv)]
+        mid = sorted({(ins.in_off, ins.in_off + ins.mul_in * ins.dim) for ins in post})
+        slots, w, x1 = [], [], []
+        for gi, g in enumerate(plan.tp_plan.groups):
+            pairs = tp_slots(g.l1)
+            live_q = [q for q in range(len(pairs)) if (g.mask >> q) & 1 and any(
+                _hits(g.out_off[q] + k * g.out_stride[q], g.out_off[q] + k * g.out_stride[q] + g.mul, mid) for k in range(2 * pairs[q][1] + 1))]
+            slots += [(gi, q) for q in live_q]
+            w += [(g.w_off[q], g.mul) for q in live_q]
+            if live_q:
+                x1.append((g.x_off, g.x_off + (2 * g.l1 + 1) * g.mul))
+        lin1 = [ins for ins in plan.lin1_spec.instr if _hits(ins.out_off, ins.out_off + ins.mul_out * ins.dim, x1)]
+        return LiveSets(tuple(cols), conv, post, sc, mid, slots, w, sorted(set(x1)), lin1)
+
+    def narrow(self, cols) -> Optional["NativeLayer"]:
+        """The layer object whose backward computes only what ``live_sets(cols)`` names, or None when the executor has no such form:
+        every live path must be a slot (l2 = l1, l3 = 0) with l1 <= 2 (``csrc/e3k_tp_scalar.hip``).  Built once per column set."""
+        cols = tuple(cols)
+        if cols in self.narrows:
+            return self.narrows[cols]
+        from ..nn.core import tp_slots
+
+        plan, nl = self.plan, None
+        ls = self.live_sets(cols)
+        groups = plan.tp_plan.groups
+        fits = (0 < len(ls.slots) <= NARROW_MAX_GROUPS and len({gi for gi, _ in ls.slots}) == len(ls.slots) and not plan.addend
+                and all(tp_slots(groups[gi].l1)[q] == (groups[gi].l1, 0) and groups[gi].l1 <= 2 and groups[gi].mul % 64 == 0
+                        for gi, q in ls.slots))
+        if fits:
+            live_groups, pos = [], 0
+            for gi, q in ls.slots:
+                g, n = groups[gi], L.TpGroup()
+                n.l1, n.x_off, n.mul, n.mask = g.l1, g.x_off, g.mul, 1 << q
+                for t in range(4):
+                    n.y_off[t] = g.y_off[t]
+                n.w_off[q], n.out_off[q], n.out_stride[q], n.coeff[q] = pos, g.out_off[q], g.out_stride[q], g.coeff[q]
+                pos += g.mul
+                live_groups.append(n)
+            tp = plan.tp_plan
+            # the same layer with the dead instructions and paths taken out
+            pruned = dict(tp_plan=ops.TpPlan(live_groups, tp.d_in, tp.d_sh, pos, tp.d_mid),
+                          post_spec=dataclasses.replace(plan.post_spec, instr=ls.post, in_covered=_covers(ls.post, plan.post_spec.d_in)),
+                          lin1_spec=dataclasses.replace(plan.lin1_spec, instr=ls.lin1, in_covered=_covers(ls.lin1, plan.lin1_spec.d_in)))
+            if plan.sc_spec is not None:
+                live_sc = [ins for _, ins in ls.sc]
+                pruned.update(sc_spec=dataclasses.replace(plan.sc_spec, instr=live_sc, in_covered=_covers(live_sc, plan.sc_spec.d_in)),
+                              sc_m_off=tuple(plan.sc_m_off[j] for j, _ in ls.sc))
+            np_ = plan.replace(**pruned)
+            try:
+                nl = NativeLayer(np_, narrow_of=self)
+            except NotImplementedError:
+                nl = None
+        if nl is not None:
+            d = nl.desc
+            if plan.sc_spec is not None:      # the per-key weights M and their gradient keep the dense layer's layout
+                kw = ops._kw_array(plan.sc_spec, plan.sc_m_off)
+                nl.keep.append(kw)
+                d.kw, d.n_kw = kw, len(plan.sc_spec.instr)
+            d.post_in_covered = 1      # (no fill: the walk reads only the columns of g_mid the live instructions write)
+            d.w_live, d.n_live = pos, len(ls.slots)
+            for i, (off, mul) in enumerate(ls.w):
+                d.live_col[i], d.live_len[i] = off, mul
+            nl.live = ls
+        self.narrows[cols] = nl
+        return nl
+
+    def _all(self):
+        return [self] + [n for n in self.narrows.values() if n is not None]
 
     # ---- per-kernel timers (bench.py) ----
     def profile(self, capacity: int, kinds=None) -> None:
         """Arms ``capacity`` event pairs per kernel kind (0 disarms); ``kinds``: only these (names of ``PROF_KINDS``)."""
         mask = 0xFFFFFFFF if kinds is None else sum(1 << PROF_KINDS[k] for k in kinds)
-        for h in self.handles.values():
-            L.check(L.load().e3k_layer_profile_mask(h, capacity, mask), "e3k_layer_profile_mask")
+        for lay in self._all():
+            lay.prof = (capacity, mask)
+            for h in lay.handles.values():
+                L.check(L.load().e3k_layer_profile_mask(h, capacity, mask), "e3k_layer_profile_mask")
 
     def profile_read(self, kind: str):
         out = []
         cap = 4096
         ms, n, e = (C.c_float * cap)(), (C.c_int64 * cap)(), (C.c_int64 * cap)()
-        for h in self.handles.values():
+        for h in [h for lay in self._all() for h in lay.handles.values()]:
             cnt = L.load().e3k_layer_profile_read(h, PROF_KINDS[kind], ms, n, e, cap)
             if cnt < 0:
                 L.check(cnt, "e3k_layer_profile_read")
@@ -751,6 +877,7 @@ class NativeConvBlockFn(torch.autograd.Function):
         from . import conv_block
 
         plan, topo, groups, in_cf, out_cf, fork, n_hidden, table, carve, rcarve, need_relayout = ctx.cfg
+        live_cols = memo.recall(gy, "live_cols") if (LIVE_GRAD and gy is not None) else None      # (before anything touches gy)
         saved = ctx.saved_tensors
         x_in, edge_radial, sh, buf, rbuf, w, w_lin1, w_post, w_sc, w_last, t_keep, m_pre = saved[:12]
         conv_ext = None
@@ -778,14 +905,29 @@ class NativeConvBlockFn(torch.autograd.Function):
                 "if this was reached another way")
         has_sc = plan.sc_spec is not None
         dev = gy.device
-        layer = native_layer(plan).handle(dev)
+        n, e, r = gy.shape[0], sh.shape[0], edge_radial.shape[0]
+        # gy marked zero outside some columns, on the route the narrow form exists for (the executor's fused packed-table walk with
+        # the rows from the radial stack): the backward of the live paths only.  Anything else: the dense layer.
+        narrow = None
+        if live_cols is not None:
+            # (built, and its device objects made, at the first marked gradient whichever route that call takes: the eager warm-up of
+            #  a step that is captured afterwards may fork where the capture does not, and nothing may be created while capturing)
+            cand = native_layer(plan).narrow(live_cols)
+            if cand is not None:
+                cand.handle(dev)
+                # (the executor states the same condition from its side -- csrc/e3k_layer.hip, e3k_layer_bwd: "if (narrow && !(fused_xw
+                #  && ...": it refuses a narrow layer off this route with E3K_ERR_UNSUPPORTED before its first launch.  Keep the two
+                #  in step: a route this gate lets through and the executor refuses raises instead of running the dense layer.)
+                if (stack and need_pre and table is not None and p_tab is not None and w is None and (need_x or need_lin1) and e > 0
+                        and gy.dtype == torch.float32 and gy.is_contiguous()):
+                    narrow = cand
+        layer = (narrow or native_layer(plan)).handle(dev)
         main = ops.current_stream(dev)
         fork = fork and not torch.cuda.is_current_stream_capturing()
         side = ops.side_stream(dev, 0) if fork else main
         side2 = ops.side_stream(dev, 1) if fork else main
         side3 = ops.side_stream(dev, 2) if (fork and ops.WGRAD_SIDE) else main
         gy = L.f32c(gy)
-        n, e, r = gy.shape[0], sh.shape[0], edge_radial.shape[0]
         lin1, post, last, sc = plan.lin1_spec, plan.post_spec, plan.last_spec, plan.sc_spec
         off = carve.off
         a = L.LayerBwdArgs()
@@ -859,6 +1001,7 @@ class NativeConvBlockFn(torch.autograd.Function):
                     g_m = torch.empty(groups.n_keys, plan.sc_ld_m, device=dev, dtype=torch.float32)
             a.gm = g_m.data_ptr()
         # ---- scratch: one allocation
+        w_cols = last.d_out if narrow is None else int(narrow.desc.w_live)      # columns of g_w and of the transposed table gradient
         sc_ = _Carve()
         sc_.add("g_conv", n * post.d_out)
         sc_.add("g_mid", n * post.d_in)
@@ -875,14 +1018,16 @@ class NativeConvBlockFn(torch.autograd.Function):
             if stack and table is None:
                 g_pre = torch.empty(e, last.d_out, device=dev, dtype=torch.float32)      # g_w IS the gradient of the layer's rows
             else:
-                sc_.add("g_w", e * last.d_out)
+                sc_.add("g_w", e * w_cols)
             if table is not None:
                 if stack:
                     with conv_block._on(side, main):
                         g_pre = torch.empty(r, last.d_out, device=dev, dtype=torch.float32)
                 else:
                     sc_.add("g_T", r * last.d_out)
-                sc_.add("table_ws", int(L.load().e3k_rtable_bwd_workspace_floats(e, table.knots, last.d_out)))
+                if narrow is not None:
+                    sc_.add("g_T_live", r * w_cols)
+                sc_.add("table_ws", int(L.load().e3k_rtable_bwd_workspace_floats(e, table.knots, w_cols)))
             if need_radial or any(need_hidden):
                 sc_.add("g_h", r * last.d_in)
         if want_sc:
@@ -904,7 +1049,7 @@ class NativeConvBlockFn(torch.autograd.Function):
                 a.g_xcf, a.g_x = _ptr(work, so["g_xcf"]), g_x.data_ptr()
             else:
                 a.g_xcf = g_x.data_ptr()
-        for k in ("g_w", "g_T", "table_ws", "g_h", "gm", "ga", "kw_ws"):
+        for k in ("g_w", "g_T", "g_T_live", "table_ws", "g_h", "gm", "ga", "kw_ws"):
             if k in so:
                 setattr(a, k, _ptr(work, so[k]))
         if g_pre is not None:

@@ -83,7 +83,9 @@ class LayerDesc(C.Structure):
                    ("k0", C.c_int32), ("h", C.c_int32), ("n_hidden", C.c_int32), ("act", C.c_int32), ("cst", C.c_float),
                    ("alphas", C.c_float * 4)]
                 + [(k, C.c_int32) for k in ("d_in", "d_x1", "d_mid", "d_conv", "d_out", "W", "post_in_covered", "sc_in_covered",
-                                            "lin1_in_covered", "sc_out_covered", "post_out_covered", "tp_bwd_x_overwrites")])
+                                            "lin1_in_covered", "sc_out_covered", "post_out_covered", "tp_bwd_x_overwrites",
+                                            "w_live", "n_live")]
+                + [("live_col", C.c_int32 * 8), ("live_len", C.c_int32 * 8)])
 
 
 class LayerRadial(C.Structure):
@@ -142,7 +144,7 @@ class LayerBwdArgs(C.Structure):
                 + [(k, C.c_void_p) for k in ("gb_lin1", "gb_post", "gb_sc", "gb_last")]
                 + [("gb_hidden", C.c_void_p * 4)]
                 + [(k, C.c_void_p) for k in ("g_x", "g_attrs", "g_radial", "g_conv", "g_mid", "g_x1", "g_xcf", "g_w", "g_T",
-                                             "table_ws", "g_h", "gm", "ga", "kw_ws")])
+                                             "table_ws", "g_h", "gm", "ga", "kw_ws", "g_T_live")])
 
 
 # name -> (restype, argtypes); every symbol include/e3k.h declares must appear here (tests check it)
@@ -233,6 +235,9 @@ SIGNATURES = {
     "e3k_tp_fwd_ptable": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "e3k_tp_bwd_x_ptable": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "e3k_tp_bwd_xw_ptable": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "e3k_tp_scalar_supported": (C.c_int, [_P]),
+    "e3k_tp_bwd_xw_scalar_ptable": (C.c_int, [_P, _P, _P, _I32, C.POINTER(_I32), _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "e3k_expand_columns": (C.c_int, [_P, _I64, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _I32, _P, _P]),
     "e3k_tp_bwd_xw": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "e3k_tp_bwd_xe": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
     "e3k_tp_edge_partials_floats": (C.c_int64, [_P, _I64]),

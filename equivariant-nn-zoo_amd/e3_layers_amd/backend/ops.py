@@ -28,6 +28,7 @@ from torch.autograd.function import once_differentiable
 import weakref
 
 from . import lib as L
+from . import memo
 from .graph import GraphTopo
 
 # bench.py sets this to a dict to collect, per named kernel, (start_event, end_event, meta) of every launch: HIP
@@ -584,6 +585,11 @@ class StridedLinearFn(torch.autograd.Function):
                 _lin_wgrad_raw(x, gy, gw, spec, scale)
         if need[0]:
             gx = _lin_dgrad_raw(gy, weight, spec, scale)
+            if not spec.in_covered and not ctx.act:
+                # gx was zero-filled and only the instructions' input blocks written: everything else IS zero, by construction.  The
+                # mark lives on this tensor object (backend/memo.py: void once the tensor is written to); a consumer that receives
+                # another tensor -- autograd summed two gradients, a hook replaced it -- finds none (conv_native.NativeLayer.narrow)
+                memo.remember(gx, "live_cols", tuple(sorted({(ins.in_off, ins.in_off + ins.mul_in * ins.dim) for ins in spec.instr})))
         if sunk:
             gw = None   # already accumulated into the flat gradient buffer
         if ctx.has_bias and need[2]:

@@ -277,6 +277,26 @@ int e3k_tp_bwd_x_ptable(const e3k_tp_plan* plan, const void* P, const int32_t* e
  * g_w [E, W] row e = d F / d w[e] (written once each: no zero-fill).  g_x carries the bits of e3k_tp_bwd_x_ptable. */
 int e3k_tp_bwd_xw_ptable(const e3k_tp_plan* plan, const float* x, const void* P, const int32_t* erec_src, const float* g_out,
                          const int32_t* src_ptr, int64_t N, int64_t E, float* g_x, float* g_w, void* stream);
+/* ... and for plans whose every group enables exactly the slot (l2 = l1, l3 = 0), l1 <= 2, groups of a multiple of 64 channels on
+ * distinct input blocks, d_sh = 9 (e3k_tp_scalar_supported; else E3K_ERR_UNSUPPORTED, nothing written) -- what is left of a layer's
+ * product when only the 0e block of its output carries a gradient (the last convolution in front of an o3.Linear to 1x0e,
+ * nn/message_passing.py:104-109 under autograd) -- csrc/e3k_tp_scalar.hip:
+ *   g_x[s, x_off + i mul + u] = sum_{e: src(e) = s} coeff w[e, u] C_ii0 sh[e, i] g_out[dst(e), out_off + u]     (the groups' blocks only:
+ *                                                                         the caller zero-fills what no group owns)
+ *   g_w[e, w_off + u]         = coeff g_out[dst(e), out_off + u] sum_i C_ii0 x[s, x_off + i mul + u] sh[e, i]   (g_w [E, plan w_numel])
+ * The plan numbers its weight columns compactly (w_off, w_numel); the packed table may be a wider layer's: P [K + 1, 3 table_w] with
+ * group i's column at table_off[i] (HOST array, n_groups entries).  table_off = NULL, table_w = 0: the table has the plan's own
+ * columns.  Of g_out only the columns out_off .. out_off + mul of the groups are read.  Same bits as e3k_tp_bwd_xw_ptable gives for
+ * these slots on a dense plan when the rest of g_out is zero. */
+int e3k_tp_scalar_supported(const e3k_tp_plan* plan);
+int e3k_tp_bwd_xw_scalar_ptable(const e3k_tp_plan* plan, const float* x, const void* P, int32_t table_w, const int32_t* table_off,
+                                const int32_t* erec_src, const float* g_out, const int32_t* src_ptr, int64_t N, int64_t E, float* g_x,
+                                float* g_w, void* stream);
+/* dst [rows, w_dst] = 0, except dst[r, dst_col[k] + c] = src[r, src_col[k] + c] for c < len[k], k < n_ranges <= 8 (HOST arrays;
+ * columns, widths and lengths multiples of 4, src and dst 16-byte aligned, the ranges of dst disjoint): a compact knot-table
+ * gradient spread over the dense table's columns.  One launch, every element of dst written. */
+int e3k_expand_columns(const float* src, int64_t rows, int32_t w_src, int32_t w_dst, const int32_t* src_col, const int32_t* dst_col,
+                       const int32_t* len, int32_t n_ranges, float* dst, void* stream);
 /* ... the same pair of gradients with the weights streamed from w [E, W] (every plan): replaces e3k_tp_bwd_x + e3k_tp_bwd_w where
  * both are wanted (layers whose radial MLP runs per edge; force training's materialised rows). */
 int e3k_tp_bwd_xw(const e3k_tp_plan* plan, const float* x, const float* sh, const float* w, const float* g_out, const int32_t* dst,
@@ -931,6 +951,15 @@ typedef struct {
   float alphas[4];
   int32_t d_in, d_x1, d_mid, d_conv, d_out, W;
   int32_t post_in_covered, sc_in_covered, lin1_in_covered, sc_out_covered, post_out_covered, tp_bwd_x_overwrites;
+  /* A NARROW layer (w_live > 0; backward only): the same layer for a gy that is zero outside some columns, so that only n_live path
+   * slots, all of the form (l2 = l1, l3 = 0), carry a gradient.  `tp` is then a plan of e3k_tp_scalar_supported with one group per
+   * live slot and the weight columns numbered compactly (w_numel = w_live: group i's live_len[i] = mul columns behind those of the
+   * groups before it); group i's column in the DENSE weight row (W wide: the packed table, g_T) is live_col[i].  The backward template sets hold only the problems that end in a live block.  g_w is then
+   * [E, w_live], g_mid is written (and read) on the live slots' columns only, the table gradient is formed compactly in g_T_live
+   * [knots + 1, w_live] and spread into the dense, zero-filled g_T.  e3k_layer_bwd takes such a layer on the fused packed-table
+   * route with the rows from the radial stack only (E3K_ERR_UNSUPPORTED otherwise); e3k_layer_fwd refuses it. */
+  int32_t w_live, n_live;
+  int32_t live_col[8], live_len[8];
 } e3k_layer_desc;
 
 typedef struct e3k_layer e3k_layer;
@@ -1011,6 +1040,7 @@ typedef struct {
   float *g_radial;   /* [R, k0] (need_radial) */
   /* scratch */
   float *g_conv, *g_mid, *g_x1, *g_xcf, *g_w, *g_T, *table_ws, *g_h, *gm, *ga, *kw_ws;
+  float *g_T_live;   /* narrow layers: [knots + 1, w_live] scratch */
 } e3k_layer_bwd_args;
 int e3k_layer_bwd(const e3k_layer* layer, const e3k_layer_bwd_args* a);
 
