@@ -13,6 +13,11 @@
 //         reverse step i (from 0), corrector noise:  draw index i,      word word0 + c
 //         reverse step i, predictor noise:           draw index i,      word D_total + word0 + c
 //         the prior x_T:                             draw index sde.N,  word word0 + c        (no step uses index sde.N)
+//       and, for the rows that conditional sampling keeps on known values (get_pc_sampler(fixed=...)), the replacement's noise:
+//         reverse step i, after the corrector:       draw index i,      word 2 D_total + word0 + c
+//         reverse step i, after the predictor:       draw index i,      word 3 D_total + word0 + c
+//       (the prior's fixed rows use the prior's own draw: m(T) x0 + s(T) z).  Blocks 0 and 1 and the prior are where they were, so an
+//       unconditioned seeded run keeps its bits.
 //     The sampler's seed is an argument of its own and should differ from the pair criterion's: with one seed a node's noise and the
 //     Bernoulli draws of its pairs at the same draw index come from one chain.
 // data/compute_edge.py (_mix32, pair_hash, normal_draw) is the host restatement, in int64 masked to 32 bits.

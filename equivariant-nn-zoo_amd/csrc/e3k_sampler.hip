@@ -14,6 +14,12 @@
 // noise buffer), and a replayed run and an eager run at one seed see the same bits.  The words: component c of a key whose earlier
 // keys hold word0 components draws word0 + c for the corrector and D_total + word0 + c for the predictor (the caller passes that sum);
 // the prior x_T is draw index sde.N, words word0 + c, through e3k_vpsde_perturb's z.
+//
+// Conditional sampling (get_pc_sampler(fixed=...), the replacement method of Song et al. 2021, section I.2): the FIXED forms of the two
+// update kernels overwrite the rows whose mask byte is not zero with the known clean value perturbed to the step's own noise level,
+// fmaf(m(t), x0, s(t) z) with m = expf(lm), in the launch that made the update -- no launch joins the replayed step.  z is the same
+// draw index's word 2 D_total + word0 + c after the corrector and 3 D_total + word0 + c after the predictor (word_fixed: the caller
+// passes the sum).  The unconditioned entry points are the FIXED = false instances of the same bodies.
 #include "e3k_common.h"
 #include "e3k_draw.h"
 
@@ -23,6 +29,12 @@ namespace e3k {
 __device__ __forceinline__ float vp_std(float t, float q, float h) {
   const float lm = t * fmaf(q, t, h);
   return sqrtf(-expm1f(2.0f * lm));
+}
+
+// its mean coefficient exp(lm), the same lm (e3k_vpsde_perturb's a)
+__device__ __forceinline__ float vp_mean(float t, float q, float h) {
+  const float lm = t * fmaf(q, t, h);
+  return expf(lm);
 }
 
 // One workgroup.  cells [2] = (next step, step in use).  Every thread reads k = cells[0] BEFORE the barrier, thread 0 writes the
@@ -43,12 +55,16 @@ __global__ __launch_bounds__(256) void sampler_begin_step_kernel(const float* __
 // One workgroup, fixed summation order (denoise_loss_kernel's): thread j takes the rows j, j + 1024, ...; six shuffle levels;
 // sixteen partial sums added in order.  Phase 1: the mean row norms of score and z over the real rows.  Phase 2: the update, with
 // score and z recomputed.  x_out may alias x: a row is read and written by one thread, phase 1 writes nothing.
+// FIXED: a real row whose mask byte is set takes the replacement in phase 2 instead of the update; phase 1 is the same code, so both
+// norms run over all real rows, the fixed ones included (the corrector ran on the whole state).  known never aliases x_out.
+template <bool FIXED>
 __global__ __launch_bounds__(1024) void sampler_langevin_kernel(float* x_out, const float* x, const float* __restrict__ raw,
+                                                                const float* __restrict__ known, const uint8_t* __restrict__ fixed,
                                                                 const int64_t* __restrict__ node_seg, const float* __restrict__ t,
                                                                 const float* __restrict__ alphas, int64_t N, int32_t D, int32_t G,
                                                                 int32_t n_alpha, float q, float h, float T, float snr,
                                                                 uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ cells,
-                                                                uint32_t word0, float* __restrict__ norms) {
+                                                                uint32_t word0, uint32_t word_fixed, float* __restrict__ norms) {
   __shared__ float part_g[16], part_z[16];
   __shared__ int part_n[16];
   __shared__ float mean[2];
@@ -104,6 +120,14 @@ __global__ __launch_bounds__(1024) void sampler_langevin_kernel(float* x_out, co
     }
     const float tg = t[g];
     const float s = vp_std(tg, q, h);
+    if constexpr (FIXED) {
+      if (fixed[i] != 0) {
+        const float m = vp_mean(tg, q, h);
+        const uint32_t h_fixed = mix32(h_draw ^ (uint32_t)i);
+        for (int32_t c = 0; c < D; ++c) x_out[i * D + c] = fmaf(m, known[i * D + c], s * normal_draw(h_fixed, word_fixed + (uint32_t)c));
+        continue;
+      }
+    }
     int64_t k = (int64_t)((tg * (float)(n_alpha - 1)) / T);
     k = k < 0 ? 0 : k > n_alpha - 1 ? n_alpha - 1 : k;
     const float step = base * alphas[k];
@@ -120,11 +144,14 @@ __global__ __launch_bounds__(1024) void sampler_langevin_kernel(float* x_out, co
 
 // One thread per component: x' = x + (-0.5 beta x) dt + sqrt(beta) sqrt(|dt|) z - dt beta score, reverse_step's arithmetic in its
 // order; beta = fma(t, beta_1 - beta_0, beta_0).  x_out may alias x (an element is read and written by one thread).
+// FIXED: the component of a real row whose mask byte is set is the replacement at the same t[g] instead.
+template <bool FIXED>
 __global__ __launch_bounds__(256) void sampler_reverse_em_kernel(float* x_out, const float* x, const float* __restrict__ raw,
+                                                                 const float* __restrict__ known, const uint8_t* __restrict__ fixed,
                                                                  const int64_t* __restrict__ node_seg, const float* __restrict__ t,
                                                                  int64_t N, int32_t D, int32_t G, float q, float h, float beta_0,
                                                                  float dbeta, float dt, uint32_t seed_lo, uint32_t seed_hi,
-                                                                 const int64_t* __restrict__ cells, uint32_t word0) {
+                                                                 const int64_t* __restrict__ cells, uint32_t word0, uint32_t word_fixed) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= N * D) return;
   const int64_t i = k / D;
@@ -137,6 +164,13 @@ __global__ __launch_bounds__(256) void sampler_reverse_em_kernel(float* x_out, c
   }
   const float tg = t[g];
   const float s = vp_std(tg, q, h);
+  if constexpr (FIXED) {
+    if (fixed[i] != 0) {
+      const uint32_t h_fixed = mix32(draw_prefix(seed_lo, seed_hi, (uint32_t)cells[1]) ^ (uint32_t)i);
+      x_out[k] = fmaf(vp_mean(tg, q, h), known[k], s * normal_draw(h_fixed, word_fixed + c));
+      return;
+    }
+  }
   const float score = -(raw[k] / s) - xc;
   const float beta = fmaf(tg, dbeta, beta_0);
   const uint32_t h_draw = draw_prefix(seed_lo, seed_hi, (uint32_t)cells[1]);
@@ -155,31 +189,70 @@ extern "C" int e3k_sampler_begin_step(const float* times, int64_t n_times, int64
   return E3K_OK;
 }
 
-extern "C" int e3k_sampler_langevin(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t,
-                                    const float* alphas, int64_t N, int32_t D, int32_t G, int32_t n_alpha, float beta_0, float beta_1,
-                                    float T, float snr, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells, uint32_t word0,
-                                    float* norms, void* stream) {
+// The two forms of each update share their checks and their launch: FIXED adds the known values and the mask.
+template <bool FIXED>
+static int launch_langevin(float* x_out, const float* x, const float* raw, const float* known, const uint8_t* fixed,
+                           const int64_t* node_seg, const float* t, const float* alphas, int64_t N, int32_t D, int32_t G, int32_t n_alpha,
+                           float beta_0, float beta_1, float T, float snr, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells,
+                           uint32_t word0, uint32_t word_fixed, float* norms, void* stream) {
   if (N < 1 || N >= (int64_t)1 << 31 || D < 1 || D > 1024 || G < 1 || n_alpha < 1 || !(T > 0.f) || !(snr > 0.f) || !(beta_0 >= 0.f) ||
       !(beta_1 >= beta_0))
     return E3K_ERR_INVALID;
   if (!x_out || !x || !raw || !node_seg || !t || !alphas || !cells || !norms) return E3K_ERR_INVALID;
+  if (FIXED && (!known || !fixed || known == x_out)) return E3K_ERR_INVALID;
   const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
-  hipLaunchKernelGGL(e3k::sampler_langevin_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x_out, x, raw, node_seg, t, alphas, N,
-                     D, G, n_alpha, q, h, T, snr, seed_lo, seed_hi, cells, word0, norms);
+  hipLaunchKernelGGL(e3k::sampler_langevin_kernel<FIXED>, dim3(1), dim3(1024), 0, (hipStream_t)stream, x_out, x, raw, known, fixed,
+                     node_seg, t, alphas, N, D, G, n_alpha, q, h, T, snr, seed_lo, seed_hi, cells, word0, word_fixed, norms);
   E3K_CHECK_LAUNCH();
   return E3K_OK;
+}
+
+template <bool FIXED>
+static int launch_reverse_em(float* x_out, const float* x, const float* raw, const float* known, const uint8_t* fixed,
+                             const int64_t* node_seg, const float* t, int64_t N, int32_t D, int32_t G, float beta_0, float beta_1,
+                             int32_t n_sde, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells, uint32_t word0, uint32_t word_fixed,
+                             void* stream) {
+  if (N < 1 || N >= (int64_t)1 << 31 || D < 1 || D > 1024 || G < 0 || n_sde < 1 || !(beta_0 >= 0.f) || !(beta_1 >= beta_0) ||
+      N * D >= (int64_t)1 << 38)
+    return E3K_ERR_INVALID;
+  if (!x_out || !x || !raw || !node_seg || !t || !cells) return E3K_ERR_INVALID;
+  if (FIXED && (!known || !fixed || known == x_out)) return E3K_ERR_INVALID;
+  const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
+  hipLaunchKernelGGL(e3k::sampler_reverse_em_kernel<FIXED>, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     x_out, x, raw, known, fixed, node_seg, t, N, D, G, q, h, beta_0, beta_1 - beta_0, -1.0f / (float)n_sde, seed_lo,
+                     seed_hi, cells, word0, word_fixed);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_sampler_langevin(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t,
+                                    const float* alphas, int64_t N, int32_t D, int32_t G, int32_t n_alpha, float beta_0, float beta_1,
+                                    float T, float snr, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells, uint32_t word0,
+                                    float* norms, void* stream) {
+  return launch_langevin<false>(x_out, x, raw, nullptr, nullptr, node_seg, t, alphas, N, D, G, n_alpha, beta_0, beta_1, T, snr, seed_lo,
+                                seed_hi, cells, word0, 0u, norms, stream);
+}
+
+extern "C" int e3k_sampler_langevin_fixed(float* x_out, const float* x, const float* raw, const float* known, const uint8_t* fixed,
+                                          const int64_t* node_seg, const float* t, const float* alphas, int64_t N, int32_t D, int32_t G,
+                                          int32_t n_alpha, float beta_0, float beta_1, float T, float snr, uint32_t seed_lo,
+                                          uint32_t seed_hi, const int64_t* cells, uint32_t word0, uint32_t word_fixed, float* norms,
+                                          void* stream) {
+  return launch_langevin<true>(x_out, x, raw, known, fixed, node_seg, t, alphas, N, D, G, n_alpha, beta_0, beta_1, T, snr, seed_lo,
+                               seed_hi, cells, word0, word_fixed, norms, stream);
 }
 
 extern "C" int e3k_sampler_reverse_em(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t,
                                       int64_t N, int32_t D, int32_t G, float beta_0, float beta_1, int32_t n_sde, uint32_t seed_lo,
                                       uint32_t seed_hi, const int64_t* cells, uint32_t word0, void* stream) {
-  if (N < 1 || N >= (int64_t)1 << 31 || D < 1 || D > 1024 || G < 0 || n_sde < 1 || !(beta_0 >= 0.f) || !(beta_1 >= beta_0) ||
-      N * D >= (int64_t)1 << 38)
-    return E3K_ERR_INVALID;
-  if (!x_out || !x || !raw || !node_seg || !t || !cells) return E3K_ERR_INVALID;
-  const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
-  hipLaunchKernelGGL(e3k::sampler_reverse_em_kernel, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_out, x,
-                     raw, node_seg, t, N, D, G, q, h, beta_0, beta_1 - beta_0, -1.0f / (float)n_sde, seed_lo, seed_hi, cells, word0);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
+  return launch_reverse_em<false>(x_out, x, raw, nullptr, nullptr, node_seg, t, N, D, G, beta_0, beta_1, n_sde, seed_lo, seed_hi, cells,
+                                  word0, 0u, stream);
+}
+
+extern "C" int e3k_sampler_reverse_em_fixed(float* x_out, const float* x, const float* raw, const float* known, const uint8_t* fixed,
+                                            const int64_t* node_seg, const float* t, int64_t N, int32_t D, int32_t G, float beta_0,
+                                            float beta_1, int32_t n_sde, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells,
+                                            uint32_t word0, uint32_t word_fixed, void* stream) {
+  return launch_reverse_em<true>(x_out, x, raw, known, fixed, node_seg, t, N, D, G, beta_0, beta_1, n_sde, seed_lo, seed_hi, cells,
+                                 word0, word_fixed, stream);
 }

@@ -291,6 +291,11 @@ SIGNATURES = {
     "e3k_sampler_begin_step": (C.c_int, [_P, _I64, _P, _P, _I32, _P]),
     "e3k_sampler_langevin": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _F, _F, _F, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P]),
     "e3k_sampler_reverse_em": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _I32, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P]),
+    # (the FIXED forms: known and the mask behind raw, word_fixed behind word0)
+    "e3k_sampler_langevin_fixed": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _F, _F, _F, C.c_uint32, C.c_uint32, _P,
+                                             C.c_uint32, C.c_uint32, _P, _P]),
+    "e3k_sampler_reverse_em_fixed": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _I32, C.c_uint32, C.c_uint32, _P, C.c_uint32,
+                                               C.c_uint32, _P]),
     "e3k_segment_sum": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 

@@ -2063,6 +2063,50 @@ def sampler_reverse_em(x, raw, node_seg, t, n_graphs: int, beta_0: float, beta_1
     return out
 
 
+def _fixed_operands(name, x, known, fixed, out):
+    """known [N, D] fp32 and the mask [N] uint8 of the FIXED forms, refused as their siblings' operands are"""
+    L.require_cuda(known, fixed)
+    known = L.f32c(known.detach())
+    if known.shape != x.shape:
+        raise ValueError(f"{name}: known must have x's shape {tuple(x.shape)} (got {tuple(known.shape)})")
+    if fixed.dtype != torch.uint8 or fixed.numel() != x.shape[0] or not fixed.is_contiguous():
+        raise ValueError(f"{name}: fixed must be a contiguous uint8 device tensor [N] (not zero: the row is fixed)")
+    if known.data_ptr() == out.data_ptr():
+        raise ValueError(f"{name}: out must not be the known values")
+    return known
+
+
+def sampler_langevin_fixed(x, raw, known, fixed, node_seg, t, alphas, n_graphs: int, beta_0: float, beta_1: float, T: float, snr: float,
+                           seed: int, cells, word0: int, word_fixed: int, out=None):
+    """``sampler_langevin`` for conditional sampling (``e3k_sampler_langevin_fixed``): the real rows whose ``fixed`` byte (uint8 [N]) is
+    not zero become ``exp(lm(t)) known + std(t) z`` instead, z the draw ``cells[1]``'s words ``word_fixed + c`` (2 D_total + the key's
+    first word); the norms run over all real rows, as its sibling's.  Still one launch."""
+    x, raw, t, out = _sampler_operands("sampler_langevin_fixed", x, raw, node_seg, t, n_graphs, cells, out)
+    known = _fixed_operands("sampler_langevin_fixed", x, known, fixed, out)
+    L.require_cuda(alphas)
+    alphas = L.f32c(alphas).reshape(-1)
+    n, d = x.shape
+    norms = torch.empty(2, device=x.device, dtype=torch.float32)
+    L.check(L.load().e3k_sampler_langevin_fixed(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(known), L.ptr(fixed), L.ptr(node_seg), L.ptr(t),
+                                                L.ptr(alphas), n, d, int(n_graphs), alphas.numel(), float(beta_0), float(beta_1), float(T),
+                                                float(snr), *L.seed_words(seed), L.ptr(cells), int(word0), int(word_fixed), L.ptr(norms),
+                                                L.stream_ptr()), "e3k_sampler_langevin_fixed")
+    return out, norms
+
+
+def sampler_reverse_em_fixed(x, raw, known, fixed, node_seg, t, n_graphs: int, beta_0: float, beta_1: float, n_sde: int, seed: int, cells,
+                             word0: int, word_fixed: int, out=None):
+    """``sampler_reverse_em`` for conditional sampling (``e3k_sampler_reverse_em_fixed``): the fixed rows become ``exp(lm(t)) known +
+    std(t) z`` at the step's own t, z at words ``word_fixed + c`` (3 D_total + the key's first word).  Still one launch."""
+    x, raw, t, out = _sampler_operands("sampler_reverse_em_fixed", x, raw, node_seg, t, n_graphs, cells, out)
+    known = _fixed_operands("sampler_reverse_em_fixed", x, known, fixed, out)
+    n, d = x.shape
+    L.check(L.load().e3k_sampler_reverse_em_fixed(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(known), L.ptr(fixed), L.ptr(node_seg), L.ptr(t), n, d,
+                                                  int(n_graphs), float(beta_0), float(beta_1), int(n_sde), *L.seed_words(seed), L.ptr(cells),
+                                                  int(word0), int(word_fixed), L.stream_ptr()), "e3k_sampler_reverse_em_fixed")
+    return out
+
+
 def segment_sum(x, ptr, seg_index, mean=False):
     return SegmentSumFn.apply(_c(x), ptr, seg_index, bool(mean))
 

@@ -26,6 +26,11 @@ restated in ``run/sde_utils.py``), the arithmetic around each model call is one 
 (``csrc/e3k_sampler.hip``), and the step's time and number live in device cells that a one-workgroup launch advances -- the host
 copies nothing per step.  The corrector forms its batch-wide norms over the real rows only, so the Langevin corrector is served on
 the capped replay too, and the eager loop, the static-edge graph and the capped replay see the same draws at one seed.
+
+``get_pc_sampler(fixed="name")`` samples conditionally (inpainting; the replacement method of Song et al. 2021, section I.2): the nodes
+whose per-node field ``name`` is not zero keep the values the batch holds on entry.  After the prior and after every corrector and
+predictor update their rows are overwritten with the known values perturbed to the step's noise level, and with the known values
+themselves when the run ends.  Seeded, the replacement is a branch of the update's own kernel: the replayed step has no launch more.
 """
 from __future__ import annotations
 
@@ -38,8 +43,8 @@ from ..backend.graph import TOPO_KEYS, EdgeCapacityExceeded
 from ..data.compute_edge import PairCriterion, computeEdgeIndex, computeEdgeIndexCapped
 from .capped import EDGE_KEYS, CappedBucket, builder_cells, edge_layer_of, replayable_criterion
 from .graph_step import CapturedStep
-from .sde_utils import (VPSDE, _node_t, _randn, get_score_fn, langevin_step_counter, prior_sampling, prior_sampling_counter,
-                        reverse_step, reverse_step_counter, sampler_begin_step)
+from .sde_utils import (VPSDE, _node_t, _randn, fixed_rows, get_score_fn, langevin_step_counter, prior_sampling,
+                        prior_sampling_counter, replace_fixed, reverse_step, reverse_step_counter, sampler_begin_step)
 
 class _Registry(dict):
     """name -> class table with a decorator: ``@table.register(name="langevin")`` (bare ``@table.register`` uses the
@@ -130,7 +135,7 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                    n_steps: int = 1, continuous: bool = True, eps: float = 1e-3,
                    preprocess: Sequence[Callable] = (), static_edges: bool = False, graph: bool = False,
                    n_iter: Optional[int] = None, edge_capacity: Optional[int] = None, r_max: Optional[float] = None,
-                   criteria=None, seed: Optional[int] = None):
+                   criteria=None, seed: Optional[int] = None, fixed: Optional[str] = None):
     """``pc_sampler(model, batch, generator=None, noise_fn=None) -> (batch, n_function_evaluations)``.
 
     seed: the seeded form (at most 64 bits).  The prior and every step's noise are counter-based draws of (seed, step, node,
@@ -139,6 +144,17 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
         other class is refused: its ``update_fn`` draws from a generator), ``n_steps`` is 1 with the Langevin corrector (the draw
         layout holds one corrector draw per step).  With ``edge_capacity`` the Langevin corrector is served: its norms run over the real
         rows.  It should differ from the pair criterion's seed, or a node's noise and its pairs' Bernoulli draws share a chain.
+
+    fixed: conditional sampling.  The name of a per-node field of the batch (``("node", "1x0e")``, any dtype): a node whose entry is
+        not zero is FIXED.  The known clean values x0 are the batch's own values of the diffused keys on entry, in the model's scaled
+        space.  With m(t) = exp(lm(t)), s(t) = sqrt(-expm1(2 lm(t))): the prior's fixed rows are m(T) x0 + s(T) z with the prior's
+        own z; after the corrector's and after the predictor's update of step i (time t_i) they become m(t_i) x0 + s(t_i) z with a
+        fresh z each (a ``None`` class does nothing, so nothing is replaced after it); when the run ends they are x0, bit for bit.
+        The Langevin norms run over all real rows, the fixed ones included.  Served by every loop, seeded (one launch per key, as
+        without: the draw layout's blocks 2 and 3) or not (``noise_fn`` sees the prior per key, then per step: corrector per key,
+        replacement per key, predictor per key, replacement per key; custom classes included).  The mask and x0 travel in the
+        working copy of the batch as node fields (``fixed`` as uint8, ``known_<key>``), so the capped loop pads them with the rest;
+        the result carries the caller's fields only.  None: nothing changes, in bits or in launches.
 
     preprocess: the dataset's ``(data, attrs) -> (data, attrs)`` functions (``data_config.preprocess``) that
         rebuild ``edge_index`` when the model tree has no ``edge_index`` layer of its own.
@@ -201,7 +217,18 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
         batch = batch.clone()
         dev = batch["_n_nodes"].device
         batch.attrs["t"] = ("graph", "1x0e")
-        batch = prior_sampling_counter(sde, batch, seed) if seeded else prior_sampling(sde, batch, generator, noise_fn)
+        given = None if fixed is None else _condition(sde, batch, fixed)
+        if seeded:
+            batch = prior_sampling_counter(sde, batch, seed, fixed=fixed)
+        else:
+            batch = prior_sampling(sde, batch, generator, noise_fn)
+            if fixed is not None:      # m(T) x0 + s(T) z with the prior's own z
+                lm = sde.log_mean_coeff(torch.tensor(float(sde.T)))
+                m, s = torch.exp(lm), torch.sqrt(1.0 - torch.exp(2.0 * lm))
+                rows = fixed_rows(batch, fixed)
+                for key in sde.irreps:
+                    z = batch[key]
+                    batch[key] = torch.where(rows, m * batch[f"known_{key}"].to(z.dtype) + s * z, z)
         sde.alphas = sde.alphas.to(dev)      # resident before any capture (no pageable host copy inside a graph)
         timesteps = torch.linspace(sde.T, eps, sde.N, device=dev)
         score_fn = get_score_fn(sde, model, train=False)
@@ -235,11 +262,21 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
             cells = torch.zeros(2, dtype=torch.int64, device=dev)
             times = timesteps.contiguous()
             same = lambda b: b      # noqa: E731  (the None classes)
-            corr_fn = partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=snr) if corrector is LangevinCorrector else same
-            pred_fn = partial(reverse_step_counter, sde, model, seed=seed, draw=cells) if predictor is EulerMaruyamaPredictor else same
+            corr_fn = (partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=snr, fixed=fixed)
+                       if corrector is LangevinCorrector else same)
+            pred_fn = partial(reverse_step_counter, sde, model, seed=seed, draw=cells, fixed=fixed) if predictor is EulerMaruyamaPredictor else same
         else:
             corr_fn = lambda b: corr.update_fn(b, generator, noise_fn)      # noqa: E731
             pred_fn = lambda b: pred.update_fn(b, generator, noise_fn)      # noqa: E731
+            if fixed is not None:      # the replacement follows every update that is one (a None class draws nothing)
+                def replaced(update):
+                    def fn(b):
+                        b = update(b)
+                        return replace_fixed(sde, b, fixed, {k: b[f"known_{k}"] for k in keys}, generator, noise_fn)
+                    return fn
+
+                corr_fn = corr_fn if corrector is NoneCorrector else replaced(corr_fn)
+                pred_fn = pred_fn if predictor is NonePredictor else replaced(pred_fn)
 
         def one_step(b):
             return moved(pred_fn(moved(corr_fn(b))))
@@ -250,7 +287,7 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
         with torch.no_grad():
             if graph and edge_capacity is not None:
                 loop = CappedLoop(batch, model, capped_updates(), keys, float(timesteps[0]), int(edge_capacity), float(r_max),
-                                  criteria, seeded=(times, cells) if seeded else None)
+                                  criteria, seeded=(times, cells) if seeded else None, fixed=fixed)
                 loop.rewind()
                 loop.run(timesteps, steps)
                 batch = loop.result()
@@ -299,9 +336,49 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                         t_dev.copy_(timesteps[i].expand_as(t_dev))
                     batch["t"] = t_dev
                     batch = one_step(batch)
+        if fixed is not None:
+            batch = _release(sde, batch, fixed, given)
         return inverse_scaler(batch), steps * (n_steps + 1)
 
     return pc_sampler
+
+
+def _condition(sde: VPSDE, batch, fixed: str):
+    """Conditional sampling's fields in the sampler's working copy of the batch: ``known_<key>`` = the diffused keys' values on entry
+    (with the key's attrs) and the mask ``fixed`` as uint8 [N, 1], the form the kernels read.  -> what the caller held under those
+    names, for ``_release``."""
+    if fixed not in batch:
+        raise ValueError(f"fixed: the batch has no field {fixed!r}")
+    if batch.attrs.get(fixed, ("",))[0] != "node":
+        raise ValueError(f"fixed: {fixed!r} is not a per-node field (attrs {batch.attrs.get(fixed)!r})")
+    missing = [k for k in sde.irreps if k not in batch]
+    if missing:
+        raise ValueError(f"fixed: the batch holds no known values for {missing}")
+    mask = batch[fixed]
+    n = int(batch[next(iter(sde.irreps))].shape[0])
+    if mask.dim() < 1 or mask.shape[0] != n or mask.numel() != n:
+        raise ValueError(f"fixed: {fixed!r} has shape {tuple(mask.shape)} for {n} nodes (one entry per node)")
+    names = [fixed] + [f"known_{k}" for k in sde.irreps]
+    given = {name: (batch[name], batch.attrs.get(name)) for name in names if name in batch}
+    for key in sde.irreps:
+        batch.attrs[f"known_{key}"] = batch.attrs[key]
+        batch[f"known_{key}"] = batch[key].float() if batch[key].is_cuda else batch[key].clone()
+    batch[fixed] = (mask.reshape(-1, 1) != 0).to(torch.uint8)
+    return given
+
+
+def _release(sde: VPSDE, batch, fixed: str, given):
+    """The end of a conditioned run: the fixed rows are the known values, bit for bit (one ``torch.where`` per key, outside any
+    graph), and the batch carries under ``fixed`` / ``known_<key>`` what the caller put there, nothing else."""
+    rows = fixed_rows(batch, fixed)
+    for key in sde.irreps:
+        batch[key] = torch.where(rows, batch[f"known_{key}"].to(batch[key].dtype), batch[key])
+        batch.pop(f"known_{key}")
+    for name, (value, attrs) in given.items():
+        if attrs is not None:
+            batch.attrs[name] = attrs
+        batch[name] = value
+    return batch
 
 
 class CappedLoop:
@@ -313,9 +390,11 @@ class CappedLoop:
     Construction sizes, pads and captures (``t0``: the time of the warm-up step); ``rewind()`` puts the state and the draw index
     back on the start, ``run()`` replays, ``result()`` checks the capacity and unpads (``tools/sample_bench.py`` times ``run`` alone)."""
 
-    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None, seeded=None):
+    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None, seeded=None, fixed=None):
         """``seeded``: ``(times, cells)`` of the seeded sampler -- the captured step then begins with ``e3k_sampler_begin_step``, which
-        sets the time from the table and advances the cells, and ``run`` is replays only."""
+        sets the time from the table and advances the cells, and ``run`` is replays only.  ``fixed``: the name of conditional
+        sampling's mask field; padding collates integers as int64, so the padded mask is made uint8 again here, once -- the form the
+        kernels read, and no conversion joins the replayed step."""
         dev = batch["_n_nodes"].device
         own = edge_layer_of(model)
         if own is not None:
@@ -339,6 +418,8 @@ class CappedLoop:
         batch["t"] = torch.full((len(batch), 1), float(t0), device=dev)
         bucket = self.bucket = CappedBucket.around_list(batch, e_cap, pos_key, rng=rng)      # (the cells the sizing build read)
         padded = bucket.padded
+        if fixed is not None:
+            padded.data[fixed] = (padded[fixed] != 0).to(torch.uint8)
         state = {k: padded[k] for k in keys}
 
         def relisted(b):

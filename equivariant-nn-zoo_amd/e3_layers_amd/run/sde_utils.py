@@ -29,8 +29,9 @@ class VPSDE:
         t = batch["t"][batch.nodeSegment()]
         return torch.sqrt(1.0 - torch.exp(2.0 * self.log_mean_coeff(t)))
 
-    def marginal(self, batch, return_std: bool = False, generator=None):
-        """x_t = exp(log_mean) x_0 + std z per diffused key, with the per-graph time broadcast to nodes."""
+    def marginal(self, batch, return_std: bool = False, generator=None, noise_fn=None):
+        """x_t = exp(log_mean) x_0 + std z per diffused key, with the per-graph time broadcast to nodes (``noise_fn(shape)``: an
+        injected z, as the sampler's)."""
         if return_std:
             return self.std(batch)
         t = batch["t"][batch.nodeSegment()]
@@ -39,7 +40,7 @@ class VPSDE:
         zs = {}
         for key in self.irreps:
             x = batch[key]
-            z = torch.randn(x.shape, device=x.device, dtype=x.dtype, generator=generator)
+            z = _randn(x, generator, noise_fn)
             batch[key] = torch.exp(lm) * x + std * z
             zs[key] = z
         return batch, {"zs": zs, "std": std}
@@ -53,6 +54,29 @@ def _randn(like: torch.Tensor, generator=None, noise_fn=None) -> torch.Tensor:
 
 def _node_t(batch) -> torch.Tensor:
     return batch["t"].reshape(-1, 1)[batch.nodeSegment()]
+
+
+def fixed_rows(batch, fixed) -> torch.Tensor:
+    """The conditional sampler's mask as bool [N, 1]: ``fixed`` names a per-node field of the batch (or is the tensor itself), not
+    zero = fixed; the rows of a padded batch's ghost graph are never fixed, whatever their bytes hold."""
+    m = (batch[fixed] if isinstance(fixed, str) else fixed).reshape(-1, 1) != 0
+    if "_graph_weight" in batch:
+        m = m & (batch.nodeSegment() < len(batch) - 1).reshape(-1, 1)
+    return m
+
+
+def replace_fixed(sde: VPSDE, batch, fixed, known, generator=None, noise_fn=None):
+    """The replacement step of conditional sampling (Song et al. 2021, section I.2) for the unseeded sampler: the fixed rows of every
+    diffused key become the known clean values ``known[key]`` perturbed to the batch's time by ``VPSDE.marginal``, one draw per key
+    (all rows of it: the draw does not depend on the mask)."""
+    noised = batch.view()
+    for key in sde.irreps:
+        noised[key] = known[key].to(batch[key].dtype)
+    noised, _ = sde.marginal(noised, generator=generator, noise_fn=noise_fn)
+    rows = fixed_rows(batch, fixed)
+    for key in sde.irreps:
+        batch[key] = torch.where(rows, noised[key], batch[key])
+    return batch
 
 
 def vpsde_sde(sde: VPSDE, batch, dt=None, generator=None, noise_fn=None):
@@ -195,6 +219,11 @@ def sde_perturb_counter(sde: VPSDE, batch, seed: int, draw, eps: float = 1e-5, d
 #   reverse step i (from 0), corrector noise of component c:  normal_draw(seed, i, node, word0 + c)
 #   reverse step i, predictor noise:                          normal_draw(seed, i, node, D_total + word0 + c)
 #   the prior x_T:                                            normal_draw(seed, sde.N, node, word0 + c)      (no step has index sde.N)
+# Conditional sampling (``fixed=``: the rows kept on known values x0) adds two blocks of the same draw index; blocks 0 and 1 and the
+# prior stay where they are, so an unconditioned seeded run keeps its bits:
+#   reverse step i, the replacement after the corrector:      normal_draw(seed, i, node, 2 D_total + word0 + c)
+#   reverse step i, the replacement after the predictor:      normal_draw(seed, i, node, 3 D_total + word0 + c)
+#   the prior's fixed rows:                                   m(T) x0 + s(T) z with the prior's own z
 # The sampler's seed should not be the pair criterion's (data.SequenceOrRandom(seed=...)): a node's noise and the Bernoulli draws of
 # its pairs would come from one chain.
 # ---------------------------------------------------------------------------------------------------------------------
@@ -245,6 +274,30 @@ def _host_terms(sde: VPSDE, batch, dtype):
     return t[seg].reshape(-1, 1), s[seg].reshape(-1, 1), real, node
 
 
+def _known_of(batch, known, key):
+    """(the known clean values travel in the batch as ``known_<key>`` unless the caller hands them in)"""
+    return batch[f"known_{key}"] if known is None else known[key]
+
+
+def _device_mask(batch, fixed) -> torch.Tensor:
+    """The mask as the kernels read it, uint8 [N]: the field itself when it already is that (no launch joins a replayed step)."""
+    m = (batch[fixed] if isinstance(fixed, str) else fixed).reshape(-1)
+    return m if m.dtype == torch.uint8 and m.is_contiguous() else (m != 0).to(torch.uint8)
+
+
+def _host_replaced(sde: VPSDE, batch, new, terms, fixed, x0, seed: int, draw: int, words):
+    """The CPU restatement of the kernels' FIXED branch: the fixed real rows of ``new`` become ``exp(lm) x0 + s z`` with
+    ``z = normal_draw(seed, draw, node, words)``; ``terms``: ``_host_terms``' tuple."""
+    from ..data.compute_edge import normal_draw
+
+    t, s, real, node = terms
+    q, h = -0.25 * (sde.beta_1 - sde.beta_0), -0.5 * sde.beta_0
+    m = torch.exp(t * (q * t + h))
+    z = normal_draw(seed, draw, node, words, new.dtype)
+    mask = (batch[fixed] if isinstance(fixed, str) else fixed).reshape(-1, 1) != 0
+    return torch.where(real & mask, m * x0.to(new.dtype) + s * z, new)
+
+
 def sampler_begin_step(times, cells, t) -> None:
     """The seeded loops' step header: with ``k = cells[0]`` inside the table ``times``, ``t`` (every graph's, the ghost graph's
     included) becomes ``times[k]`` and ``cells`` (int64 [2]) becomes ``(k + 1, k)``; outside the table nothing moves.  Device tensors:
@@ -260,10 +313,14 @@ def sampler_begin_step(times, cells, t) -> None:
         cells[0] = k + 1
 
 
-def prior_sampling_counter(sde: VPSDE, batch, seed: int, draw=None, dtype=None):
+def prior_sampling_counter(sde: VPSDE, batch, seed: int, draw=None, dtype=None, *, fixed=None, known=None):
     """``prior_sampling`` with counter-based draws: ``x_T = normal_draw(seed, draw, node, word0 + c)`` per diffused key; ``draw``
     defaults to ``sde.N``, the index no reverse step uses.  The ghost rows of a padded batch keep what they hold (zeros where the key
-    is new).  Device: one ``e3k_vpsde_perturb`` launch per key (its z output; fp32).  CPU: torch, in ``dtype`` (default: torch's)."""
+    is new).  Device: one ``e3k_vpsde_perturb`` launch per key (its z output; fp32).  CPU: torch, in ``dtype`` (default: torch's).
+
+    ``fixed`` (conditional sampling: a per-node field's name or the mask itself, not zero = fixed; ``known``: ``{key: x0}``, default
+    the batch's ``known_<key>``): the fixed real rows start from ``m(T) x0 + s(T) z`` with the same z -- on the device the same
+    launch's ``x_t`` output at ``t = T``."""
     from ..data.compute_edge import normal_draw
 
     dev = batch["_n_nodes"].device
@@ -277,10 +334,16 @@ def prior_sampling_counter(sde: VPSDE, batch, seed: int, draw=None, dtype=None):
 
         cell = draw if torch.is_tensor(draw) else torch.tensor([int(draw)], dtype=torch.int64, device=dev)
         real = (seg < n_real).reshape(-1, 1) if padded else None
+        rows = None if fixed is None else fixed_rows(batch, fixed)
         for key, dim in sde.irreps.items():
-            zero = torch.zeros(n, dim, device=dev)
-            z = ops.vpsde_perturb(zero, seg, n_real, sde.beta_0, sde.beta_1, 0.0, sde.T, seed, cell, words[key])[2]
-            batch[key] = torch.where(real, z, batch[key].float()) if padded and key in batch else z
+            if rows is None:
+                zero = torch.zeros(n, dim, device=dev)
+                z = ops.vpsde_perturb(zero, seg, n_real, sde.beta_0, sde.beta_1, 0.0, sde.T, seed, cell, words[key])[2]
+            else:      # eps = T: every graph's time is T, x_t = fma(m(T), x0, s(T) z)
+                _, x_t, z, _ = ops.vpsde_perturb(_known_of(batch, known, key), seg, n_real, sde.beta_0, sde.beta_1, sde.T, sde.T, seed, cell,
+                                                 words[key])
+            free = torch.where(real, z, batch[key].float()) if padded and key in batch else z
+            batch[key] = free if rows is None else torch.where(rows, x_t, free)
         return batch
     dtype = torch.get_default_dtype() if dtype is None else dtype
     real = (torch.arange(len(batch)) < n_real)[seg].reshape(-1, 1)
@@ -288,28 +351,45 @@ def prior_sampling_counter(sde: VPSDE, batch, seed: int, draw=None, dtype=None):
     for key, dim in sde.irreps.items():
         z = normal_draw(seed, _step_in_use(draw), node, words[key] + torch.arange(dim, dtype=torch.int64).reshape(1, -1), dtype)
         old = batch[key].to(dtype) if key in batch else torch.zeros(n, dim, dtype=dtype)
-        batch[key] = torch.where(real, z, old)
+        new = torch.where(real, z, old)
+        if fixed is not None:
+            q, h = -0.25 * (sde.beta_1 - sde.beta_0), -0.5 * sde.beta_0
+            lm = torch.tensor(sde.T * (q * sde.T + h), dtype=dtype)
+            noised = torch.exp(lm) * _known_of(batch, known, key).to(dtype) + torch.sqrt(-torch.expm1(2.0 * lm)) * z
+            new = torch.where(fixed_rows(batch, fixed), noised, new)
+        batch[key] = new
     return batch
 
 
-def langevin_step_counter(sde: VPSDE, model, batch, seed: int, draw, snr: float, dtype=None, train: bool = False):
+def langevin_step_counter(sde: VPSDE, model, batch, seed: int, draw, snr: float, dtype=None, train: bool = False, *, fixed=None,
+                          known=None):
     """One ``LangevinCorrector`` update (``n_steps = 1``) with counter-based noise: per key, ``z = normal_draw(seed, draw, node,
     word0 + c)``, the mean row norms of score and z over the REAL rows, ``step = (snr |z| / |score|)^2 2 alphas[k]`` and
     ``x + step score + sqrt(2 step) z``; the rows of a padded batch's ghost graph stay as they are and enter no norm.
 
     ``draw``: the reverse step's number, an int, or the sampler's DEVICE cells (int64 [2]: next step, step in use -- read by the kernel,
     no host synchronisation).  Device tensors: the model call and one ``e3k_sampler_langevin`` launch per key (fp32).  CPU tensors: the
-    torch restatement of the same hashes and formulas in ``dtype`` (default: the key's) -- float64 is the kernel tests' reference."""
+    torch restatement of the same hashes and formulas in ``dtype`` (default: the key's) -- float64 is the kernel tests' reference.
+
+    ``fixed`` / ``known`` (conditional sampling, as ``prior_sampling_counter``'s): after the update the fixed real rows become
+    ``m(t) x0 + s(t) z'`` with ``z' = normal_draw(seed, draw, node, 2 D_total + word0 + c)``; both norms still run over all real rows.
+    Device: ``e3k_sampler_langevin_fixed``, still one launch per key -- the mask is read as it is when it is uint8."""
     raw = _raw_scores(sde, model, batch, train)
-    words, _ = draw_words(sde)
+    words, total = draw_words(sde)
     dev = batch[next(iter(sde.irreps))].device
     if dev.type == "cuda":
         from ..backend import ops
 
         cells, seg, n_real = _sampler_cells(draw, dev), batch.nodeSegment(), _real_graphs(batch)
+        mask = None if fixed is None else _device_mask(batch, fixed)
         for key in sde.irreps:
-            batch[key], _ = ops.sampler_langevin(batch[key], raw[key], seg, batch["t"], sde.alphas, n_real, sde.beta_0, sde.beta_1,
-                                                 sde.T, snr, seed, cells, words[key])
+            if mask is None:
+                batch[key], _ = ops.sampler_langevin(batch[key], raw[key], seg, batch["t"], sde.alphas, n_real, sde.beta_0, sde.beta_1,
+                                                     sde.T, snr, seed, cells, words[key])
+            else:
+                batch[key], _ = ops.sampler_langevin_fixed(batch[key], raw[key], _known_of(batch, known, key), mask, seg, batch["t"],
+                                                           sde.alphas, n_real, sde.beta_0, sde.beta_1, sde.T, snr, seed, cells, words[key],
+                                                           2 * total + words[key])
         return batch
     from ..data.compute_edge import normal_draw
 
@@ -325,14 +405,21 @@ def langevin_step_counter(sde: VPSDE, model, batch, seed: int, draw, snr: float,
         rows = real.reshape(-1)
         grad_norm, noise_norm = torch.norm(score[rows], dim=-1).mean(), torch.norm(z[rows], dim=-1).mean()
         step = ((snr * noise_norm) / grad_norm) ** 2 * 2 * alpha
-        batch[key] = torch.where(real, x + step * score + torch.sqrt(step * 2) * z, x)
+        new = torch.where(real, x + step * score + torch.sqrt(step * 2) * z, x)
+        if fixed is not None:
+            new = _host_replaced(sde, batch, new, (t, s, real, node), fixed, _known_of(batch, known, key), seed, step_no,
+                                 2 * total + words[key] + torch.arange(dim, dtype=torch.int64).reshape(1, -1))
+        batch[key] = new
     return batch
 
 
-def reverse_step_counter(sde: VPSDE, model, batch, seed: int, draw, dtype=None, train: bool = False):
+def reverse_step_counter(sde: VPSDE, model, batch, seed: int, draw, dtype=None, train: bool = False, *, fixed=None, known=None):
     """``reverse_step`` with counter-based noise: ``z = normal_draw(seed, draw, node, D_total + word0 + c)`` -- the predictor's words,
     not the corrector's of the same step.  ``draw``, devices, ``dtype`` and the ghost rows as ``langevin_step_counter``'s; device
-    tensors: the model call and one ``e3k_sampler_reverse_em`` launch per key."""
+    tensors: the model call and one ``e3k_sampler_reverse_em`` launch per key.
+
+    ``fixed`` / ``known``: after the update the fixed real rows become ``m(t) x0 + s(t) z''`` at the step's own t, with
+    ``z'' = normal_draw(seed, draw, node, 3 D_total + word0 + c)`` (device: ``e3k_sampler_reverse_em_fixed``, one launch per key)."""
     raw = _raw_scores(sde, model, batch, train)
     words, total = draw_words(sde)
     dev = batch[next(iter(sde.irreps))].device
@@ -340,9 +427,15 @@ def reverse_step_counter(sde: VPSDE, model, batch, seed: int, draw, dtype=None, 
         from ..backend import ops
 
         cells, seg, n_real = _sampler_cells(draw, dev), batch.nodeSegment(), _real_graphs(batch)
+        mask = None if fixed is None else _device_mask(batch, fixed)
         for key in sde.irreps:
-            batch[key] = ops.sampler_reverse_em(batch[key], raw[key], seg, batch["t"], n_real, sde.beta_0, sde.beta_1, sde.N, seed, cells,
-                                                total + words[key])
+            if mask is None:
+                batch[key] = ops.sampler_reverse_em(batch[key], raw[key], seg, batch["t"], n_real, sde.beta_0, sde.beta_1, sde.N, seed,
+                                                    cells, total + words[key])
+            else:
+                batch[key] = ops.sampler_reverse_em_fixed(batch[key], raw[key], _known_of(batch, known, key), mask, seg, batch["t"], n_real,
+                                                          sde.beta_0, sde.beta_1, sde.N, seed, cells, total + words[key],
+                                                          3 * total + words[key])
         return batch
     from ..data.compute_edge import normal_draw
 
@@ -355,7 +448,11 @@ def reverse_step_counter(sde: VPSDE, model, batch, seed: int, draw, dtype=None, 
         z = normal_draw(seed, step_no, node, total + words[key] + torch.arange(dim, dtype=torch.int64).reshape(1, -1), x.dtype)
         x_mean = x + (-0.5 * beta * x) * dt
         noised = x_mean + (torch.sqrt(beta) * (abs(dt) ** 0.5)) * z
-        batch[key] = torch.where(real, noised - (dt * beta) * score, x)
+        new = torch.where(real, noised - (dt * beta) * score, x)
+        if fixed is not None:
+            new = _host_replaced(sde, batch, new, (t, s, real, node), fixed, _known_of(batch, known, key), seed, step_no,
+                                 3 * total + words[key] + torch.arange(dim, dtype=torch.int64).reshape(1, -1))
+        batch[key] = new
     return batch
 
 

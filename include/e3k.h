@@ -902,6 +902,17 @@ int e3k_score_step_record(const float* loss, const int64_t* overflow, int64_t* c
  *     z = xi(seed, cells[1], i, word0 + c)   (the caller passes D_total + the key's first word: not the corrector's words);
  *     x_out = x + (-0.5 beta x) dt + sqrtf(beta) sqrtf(|dt|) z - dt beta score.
  * Null pointers, N < 1, D outside [1, 1024], n_times, G1, n_alpha, n_sde < 1, T <= 0, snr <= 0, beta_1 < beta_0: invalid.
+ *
+ * Conditional sampling (get_pc_sampler(fixed=...): the replacement method of Song et al. 2021, section I.2).
+ * e3k_sampler_langevin_fixed, e3k_sampler_reverse_em_fixed: the same kernels' FIXED instances, still one launch.  known [N, D]
+ *   fp32 (the known clean values x0, in the model's scaled space), fixed [N] uint8 (not zero: the row is fixed).  A real row i of
+ *   graph g with fixed[i] != 0 becomes, instead of the update,
+ *     x_out_c = fmaf(expf(lm(t_g)), known_c, s(t_g) * xi(seed, cells[1], i, word_fixed + c))
+ *   at the t_g the update read (the caller passes word_fixed = 2 D_total + the key's first word after the corrector,
+ *   3 D_total + it after the predictor).  Every other row is what the unconditioned entry point writes, bit for bit: an all-zero
+ *   mask reproduces it.  The Langevin norms run over ALL real rows, the fixed ones included, as in e3k_sampler_langevin (the
+ *   corrector ran on the whole state; the fixed rows are replaced afterwards).  Ghost rows are copied through whatever their mask
+ *   byte holds.  x_out may alias x.  Additionally invalid: null known or fixed, known == x_out.
  * ------------------------------------------------------------------------------------------ */
 int e3k_sampler_begin_step(const float* times, int64_t n_times, int64_t* cells, float* t, int32_t G1, void* stream);
 int e3k_sampler_langevin(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t,
@@ -911,6 +922,14 @@ int e3k_sampler_langevin(float* x_out, const float* x, const float* raw, const i
 int e3k_sampler_reverse_em(float* x_out, const float* x, const float* raw, const int64_t* node_seg, const float* t, int64_t N,
                            int32_t D, int32_t G, float beta_0, float beta_1, int32_t n_sde, uint32_t seed_lo, uint32_t seed_hi,
                            const int64_t* cells, uint32_t word0, void* stream);
+int e3k_sampler_langevin_fixed(float* x_out, const float* x, const float* raw, const float* known, const uint8_t* fixed,
+                               const int64_t* node_seg, const float* t, const float* alphas, int64_t N, int32_t D, int32_t G,
+                               int32_t n_alpha, float beta_0, float beta_1, float T, float snr, uint32_t seed_lo, uint32_t seed_hi,
+                               const int64_t* cells, uint32_t word0, uint32_t word_fixed, float* norms, void* stream);
+int e3k_sampler_reverse_em_fixed(float* x_out, const float* x, const float* raw, const float* known, const uint8_t* fixed,
+                                 const int64_t* node_seg, const float* t, int64_t N, int32_t D, int32_t G, float beta_0, float beta_1,
+                                 int32_t n_sde, uint32_t seed_lo, uint32_t seed_hi, const int64_t* cells, uint32_t word0,
+                                 uint32_t word_fixed, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A convolution layer as ONE call (csrc/e3k_layer.hip): FactorizedConvolution + Gate

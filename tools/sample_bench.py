@@ -21,7 +21,14 @@ synchronisation.  No threshold is asserted: the numbers are quoted in README.md 
 ``--seed S`` times the seeded form (``get_pc_sampler(seed=S)``: counter-based noise, one launch per key around each model call, the
 time and the step number in device cells): the seeded replay against the seeded eager loop and -- with ``--corrector none``, the only
 corrector the unseeded replay serves -- against the unseeded replay, the three alternating in one process.  ``--trace-steps`` and
-``--launches`` then count the seeded replay's launches."""
+``--launches`` then count the seeded replay's launches.
+
+``--fixed FRACTION`` (with ``--seed``) adds the conditioned replay (``get_pc_sampler(fixed=...)``: inpainting): the middle FRACTION of
+every chain is kept on its known coordinates, the rest is sampled around it.  The conditioned seeded replay then alternates with the
+unconditioned seeded replay of the same tree (and the other variants), ``--trace-steps`` counts ITS launches, and the result goes to
+profiles/protein_sampler_fixed.json:
+
+    python tools/sample_bench.py --protein --seed 7 --corrector langevin --fixed 0.25 --steps 100"""
 import argparse, csv, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
@@ -69,10 +76,10 @@ def protein_setup(n_prot, n_res, dev):
     model = build(config_diffusion_CA.get_config(edge_criteria=crit).model_config).to(dev).eval()
     sde = VPSDE({"CA": 3}, N=1000)
     sde.alphas = sde.alphas.to(dev)
-    batch = synth_protein(1, n_prot, n_res=n_res).to(dev)
-    batch = prior_sampling(sde, batch, torch.Generator(device=dev).manual_seed(1))      # x_T: where the sampler starts
+    clean = synth_protein(1, n_prot, n_res=n_res).to(dev)
+    batch = prior_sampling(sde, clean.clone(), torch.Generator(device=dev).manual_seed(1))      # x_T: where the sampler starts
     timesteps = torch.linspace(sde.T, 1e-3, sde.N, device=dev)
-    return model, sde, batch, timesteps, crit
+    return model, sde, batch, timesteps, crit, clean
 
 
 def predictor(model, sde):
@@ -124,25 +131,47 @@ def replay_loop(model, sde, batch, timesteps, slack):
         return CappedLoop(b, model, [lambda w: w, lambda w: pred.update_fn(w)], ["CA"], float(timesteps[0]), e_cap, None), e_cap
 
 
-def seeded_updates(model, sde, seed, cells, corrector):
-    """[corrector, predictor] of the seeded form, as get_pc_sampler builds them"""
+def seeded_updates(model, sde, seed, cells, corrector, fixed=None):
+    """[corrector, predictor] of the seeded form, as get_pc_sampler builds them (``fixed``: the mask field's name, or None)"""
     from functools import partial
 
     from e3_layers_amd.run.sde_utils import langevin_step_counter, reverse_step_counter
 
-    corr = partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=0.16) if corrector == "langevin" else (lambda w: w)
-    return [corr, partial(reverse_step_counter, sde, model, seed=seed, draw=cells)]
+    corr = (partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=0.16, fixed=fixed) if corrector == "langevin"
+            else (lambda w: w))
+    return [corr, partial(reverse_step_counter, sde, model, seed=seed, draw=cells, fixed=fixed)]
 
 
-def seeded_replay_loop(model, sde, batch, timesteps, e_cap, seed, corrector):
+def seeded_replay_loop(model, sde, batch, timesteps, e_cap, seed, corrector, fixed=None):
     from e3_layers_amd.run.sde_sampling import CappedLoop
 
     b = batch.clone()
     b.attrs["t"] = ("graph", "1x0e")
     cells = torch.zeros(2, dtype=torch.int64, device=timesteps.device)
+    extra = {} if fixed is None else {"fixed": fixed}      # (the unconditioned call: as before)
     with torch.no_grad():
-        return CappedLoop(b, model, seeded_updates(model, sde, seed, cells, corrector), ["CA"], float(timesteps[0]), e_cap, None,
-                          seeded=(timesteps, cells))
+        return CappedLoop(b, model, seeded_updates(model, sde, seed, cells, corrector, fixed), ["CA"], float(timesteps[0]), e_cap, None,
+                          seeded=(timesteps, cells), **extra)
+
+
+def conditioned(sde, batch, clean, fraction):
+    """``batch`` (at x_T = z) with conditional sampling's fields, as get_pc_sampler(fixed="fixed") sets them up: the middle ``fraction``
+    of every chain of every protein is fixed (a contiguous stretch, chosen by the chain's length alone), ``known_CA`` = the clean
+    coordinates, and the fixed rows of x_T are m(T) x0 + s(T) z.  -> (batch, fixed rows)"""
+    b = batch.clone()
+    chain = clean["chain_id"].reshape(-1) + (int(clean["chain_id"].max()) + 1) * clean.nodeSegment()
+    mask = torch.zeros_like(chain, dtype=torch.bool)
+    for c in torch.unique(chain).tolist():
+        rows = torch.nonzero(chain == c).reshape(-1)
+        k = int(round(fraction * rows.numel()))
+        start = (rows.numel() - k) // 2
+        mask[rows[start:start + k]] = True
+    b.attrs["fixed"], b.attrs["known_CA"] = ("node", "1x0e"), b.attrs["CA"]
+    b["fixed"] = mask.reshape(-1, 1).to(torch.uint8)
+    b["known_CA"] = clean["CA"].float()
+    lm = sde.log_mean_coeff(torch.tensor(float(sde.T)))
+    b["CA"] = torch.where(mask.reshape(-1, 1), torch.exp(lm) * b["known_CA"] + torch.sqrt(-torch.expm1(2.0 * lm)) * b["CA"], b["CA"])
+    return b, int(mask.sum())
 
 
 def seeded_eager_loop(model, sde, batch, timesteps, crit, n_steps, seed, corrector):
@@ -202,11 +231,14 @@ def protein(argv):
     ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
     ap.add_argument("--seed", type=int, default=None, help="time the seeded form (get_pc_sampler(seed=...)) as well")
     ap.add_argument("--corrector", choices=("none", "langevin"), default="none", help="with --seed: the corrector of the seeded loops")
+    ap.add_argument("--fixed", type=float, default=0.0, help="with --seed: the conditioned replay too, this fraction of every chain fixed")
     args = ap.parse_args(argv)
+    if not 0.0 <= args.fixed < 1.0 or (args.fixed and args.seed is None):
+        raise SystemExit("--fixed FRACTION: in [0, 1), with --seed (the conditioned replay is the seeded form's)")
     dev = torch.device("cuda:0")
-    model, sde, batch, timesteps, crit = protein_setup(args.proteins, args.residues, dev)
+    model, sde, batch, timesteps, crit, clean = protein_setup(args.proteins, args.residues, dev)
     if args.seed is not None:
-        return protein_seeded(args, model, sde, batch, timesteps, crit)
+        return protein_seeded(args, model, sde, batch, timesteps, crit, clean)
     if args.corrector != "none":
         raise SystemExit("--corrector langevin needs --seed: the unseeded replay serves NoneCorrector only")
     loop, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
@@ -259,12 +291,17 @@ def protein(argv):
             f.write(text + "\n")
 
 
-def protein_seeded(args, model, sde, batch, timesteps, crit):
-    """The seeded replay, the seeded eager loop and (NoneCorrector only) the unseeded replay, alternating."""
+def protein_seeded(args, model, sde, batch, timesteps, crit, clean):
+    """The seeded replay, the seeded eager loop and (NoneCorrector only) the unseeded replay, alternating; with ``--fixed`` the
+    conditioned seeded replay as well."""
     plain, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
     if args.corrector == "langevin":      # (two model calls per step, and the corrector moves the nodes before the second list)
         e_cap = -(-int(1.1 * e_cap) // 1024) * 1024
     loop = seeded_replay_loop(model, sde, batch, timesteps, e_cap, args.seed, args.corrector)
+    cond = n_fixed = None
+    if args.fixed:      # (the same capacity: the fixed rows start near their clean places, the rest as before)
+        cond_batch, n_fixed = conditioned(sde, batch, clean, args.fixed)
+        cond = seeded_replay_loop(model, sde, cond_batch, timesteps, e_cap, args.seed, args.corrector, fixed="fixed")
 
     def replay(which, n):
         def run():
@@ -275,14 +312,17 @@ def protein_seeded(args, model, sde, batch, timesteps, crit):
         return run
 
     if args.trace_steps:
-        loop.rewind()
-        replay(loop, args.trace_steps)()
+        traced = loop if cond is None else cond
+        traced.rewind()
+        replay(traced, args.trace_steps)()
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
-                          "corrector": args.corrector}))
+                          "corrector": args.corrector, "fixed": args.fixed}))
         return
     variants = {"seeded_replay": lambda n: (loop.rewind(), replay(loop, n))[1],
                 "seeded_eager": lambda n: seeded_eager_loop(model, sde, batch, timesteps, crit, n, args.seed, args.corrector)}
+    if cond is not None:
+        variants["fixed_replay"] = lambda n: (cond.rewind(), replay(cond, n))[1]
     if args.corrector == "none":
         variants["replay"] = lambda n: (plain.rewind(), replay(plain, n))[1]
     for make in variants.values():
@@ -294,6 +334,8 @@ def protein_seeded(args, model, sde, batch, timesteps, crit):
             ms, busy = timed(make(args.steps))
             if name == "seeded_replay":
                 loop.result()                       # (after the closing event: an overflowed repetition would raise here)
+            elif name == "fixed_replay":
+                cond.result()
             elif name == "replay":
                 plain.result()
             rows[name].append(ms / args.steps)
@@ -313,9 +355,15 @@ def protein_seeded(args, model, sde, batch, timesteps, crit):
     if "replay" not in variants:
         doc["replay_ms_per_step"] = "not measured: the unseeded replay refuses the Langevin corrector"
     doc["speedup_median_seeded_replay_over_seeded_eager"] = round(statistics.median(rows["seeded_eager"]) / statistics.median(rows["seeded_replay"]), 3)
+    if cond is not None:
+        lo, hi = min(rows["seeded_replay"]), max(rows["seeded_replay"])
+        med = statistics.median(rows["fixed_replay"])
+        doc.update(fixed_fraction=args.fixed, fixed_nodes=n_fixed, fixed_recaptures=cond.step.recaptures,
+                   fixed_replay_median_inside_seeded_replay_min_max=bool(lo <= med <= hi),
+                   fixed_replay_over_seeded_replay_median=round(med / statistics.median(rows["seeded_replay"]), 4))
     text = json.dumps(doc, indent=1)
     print(text)
-    out = args.out or os.path.join(ROOT, "profiles", "protein_sampler_pc.json")
+    out = args.out or os.path.join(ROOT, "profiles", "protein_sampler_fixed.json" if cond is not None else "protein_sampler_pc.json")
     with open(out, "w") as f:
         f.write(text + "\n")
 
