@@ -20,6 +20,9 @@
 // fmaf(m(t), x0, s(t) z) with m = expf(lm), in the launch that made the update -- no launch joins the replayed step.  z is the same
 // draw index's word 2 D_total + word0 + c after the corrector and 3 D_total + word0 + c after the predictor (word_fixed: the caller
 // passes the sum).  The unconditioned entry points are the FIXED = false instances of the same bodies.
+//
+// The probability-flow ODE sampler (run/sde_sampling.get_ode_sampler) shares the step header and vp_std: its two kernels, the Euler
+// step / Heun's stage A and Heun's stage B, stand below the predictor-corrector ones.
 #include "e3k_common.h"
 #include "e3k_draw.h"
 
@@ -180,6 +183,70 @@ __global__ __launch_bounds__(256) void sampler_reverse_em_kernel(float* x_out, c
   x_out[k] = noised - (dt * beta) * score;
 }
 
+// The probability-flow ODE of the VP-SDE, dx/dt = -0.5 beta (x + score): with score = -raw / s - x the x terms cancel and the drift
+// is d(raw, t) = (0.5 beta(t)) (raw / s(t)) -- the collapsed form, which never forms x + (-raw / s - x).
+// Both kernels read the step k = cells[1] and the times t_k = times[k], t_{k+1} = times[k + 1] from the table, never the batch's t:
+// hs = t_{k+1} - t_k (negative) is one subtraction of the two table entries.  k < 0 or k + 1 >= n_times: nothing moves.
+//
+// Euler step / Heun stage A, one thread per component: d1 = d(raw, t_k), x_out = fmaf(hs, d1, x).  x_out may alias x.  d_out (nullable)
+// takes d1, zero on ghost rows and outside the table.  t_out (nullable): block 0 writes t_{k+1} into t_out[0 .. G1) -- the time the
+// model's next call sees; no thread of this kernel reads it.
+__global__ __launch_bounds__(256) void sampler_ode_euler_kernel(float* x_out, float* __restrict__ d_out, const float* x,
+                                                                const float* __restrict__ raw, const int64_t* __restrict__ node_seg,
+                                                                const float* __restrict__ times, int64_t n_times,
+                                                                const int64_t* __restrict__ cells, float* __restrict__ t_out, int32_t G1,
+                                                                int64_t N, int32_t D, int32_t G, float q, float h, float beta_0,
+                                                                float dbeta) {
+  const int64_t step = cells[1];
+  const bool inside = step >= 0 && step + 1 < n_times;      // (uniform)
+  float tk = 0.f, tn = 0.f;
+  if (inside) {
+    tk = times[step];
+    tn = times[step + 1];
+    if (t_out != nullptr && blockIdx.x == 0)
+      for (int32_t g = threadIdx.x; g < G1; g += 256) t_out[g] = tn;
+  }
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= N * D) return;
+  const int64_t i = k / D;
+  const int64_t g = node_seg[i];
+  const float xc = x[k];
+  if (!inside || g < 0 || g >= G) {
+    x_out[k] = xc;
+    if (d_out != nullptr) d_out[k] = 0.f;
+    return;
+  }
+  const float s = vp_std(tk, q, h);
+  const float beta = fmaf(tk, dbeta, beta_0);
+  const float d1 = (0.5f * beta) * (raw[k] / s);
+  x_out[k] = fmaf(tn - tk, d1, xc);
+  if (d_out != nullptr) d_out[k] = d1;
+}
+
+// Heun stage B at t_{k+1}, one thread per component: d2 = d(raw2, t_{k+1}), x_out = fmaf(0.5 hs, d1 + d2, x0).  x_out may alias x0
+// (never d1: another launch's operand, refused by the entry point).  Ghost rows and steps outside the table: x_out = x0.
+__global__ __launch_bounds__(256) void sampler_ode_heun_kernel(float* x_out, const float* x0, const float* __restrict__ d1,
+                                                               const float* __restrict__ raw2, const int64_t* __restrict__ node_seg,
+                                                               const float* __restrict__ times, int64_t n_times,
+                                                               const int64_t* __restrict__ cells, int64_t N, int32_t D, int32_t G,
+                                                               float q, float h, float beta_0, float dbeta) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= N * D) return;
+  const int64_t step = cells[1];
+  const int64_t i = k / D;
+  const int64_t g = node_seg[i];
+  const float xc = x0[k];
+  if (step < 0 || step + 1 >= n_times || g < 0 || g >= G) {
+    x_out[k] = xc;
+    return;
+  }
+  const float tk = times[step], tn = times[step + 1];
+  const float s = vp_std(tn, q, h);
+  const float beta = fmaf(tn, dbeta, beta_0);
+  const float d2 = (0.5f * beta) * (raw2[k] / s);
+  x_out[k] = fmaf(0.5f * (tn - tk), d1[k] + d2, xc);
+}
+
 }  // namespace e3k
 
 extern "C" int e3k_sampler_begin_step(const float* times, int64_t n_times, int64_t* cells, float* t, int32_t G1, void* stream) {
@@ -255,4 +322,36 @@ extern "C" int e3k_sampler_reverse_em_fixed(float* x_out, const float* x, const 
                                             uint32_t word0, uint32_t word_fixed, void* stream) {
   return launch_reverse_em<true>(x_out, x, raw, known, fixed, node_seg, t, N, D, G, beta_0, beta_1, n_sde, seed_lo, seed_hi, cells,
                                  word0, word_fixed, stream);
+}
+
+// The ODE sampler's two launches (run/sde_sampling.get_ode_sampler): checks as launch_reverse_em's, the table in place of t.
+static bool ode_args_ok(int64_t N, int32_t D, int32_t G, int64_t n_times, float beta_0, float beta_1) {
+  return !(N < 1 || N >= (int64_t)1 << 31 || D < 1 || D > 1024 || G < 0 || n_times < 2 || !(beta_0 >= 0.f) || !(beta_1 >= beta_0) ||
+           N * D >= (int64_t)1 << 38);
+}
+
+extern "C" int e3k_sampler_ode_euler(float* x_out, float* d_out, const float* x, const float* raw, const int64_t* node_seg,
+                                     const float* times, int64_t n_times, const int64_t* cells, float* t_out, int32_t G1, int64_t N,
+                                     int32_t D, int32_t G, float beta_0, float beta_1, void* stream) {
+  if (!ode_args_ok(N, D, G, n_times, beta_0, beta_1)) return E3K_ERR_INVALID;
+  if (!x_out || !x || !raw || !node_seg || !times || !cells) return E3K_ERR_INVALID;
+  if (d_out && (d_out == x_out || d_out == x || d_out == raw)) return E3K_ERR_INVALID;
+  if (t_out && G1 < 1) return E3K_ERR_INVALID;
+  const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
+  hipLaunchKernelGGL(e3k::sampler_ode_euler_kernel, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_out,
+                     d_out, x, raw, node_seg, times, n_times, cells, t_out, G1, N, D, G, q, h, beta_0, beta_1 - beta_0);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_sampler_ode_heun(float* x_out, const float* x0, const float* d1, const float* raw2, const int64_t* node_seg,
+                                    const float* times, int64_t n_times, const int64_t* cells, int64_t N, int32_t D, int32_t G,
+                                    float beta_0, float beta_1, void* stream) {
+  if (!ode_args_ok(N, D, G, n_times, beta_0, beta_1)) return E3K_ERR_INVALID;
+  if (!x_out || !x0 || !d1 || !raw2 || !node_seg || !times || !cells || d1 == x_out) return E3K_ERR_INVALID;
+  const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
+  hipLaunchKernelGGL(e3k::sampler_ode_heun_kernel, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_out, x0,
+                     d1, raw2, node_seg, times, n_times, cells, N, D, G, q, h, beta_0, beta_1 - beta_0);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
 }

@@ -296,6 +296,9 @@ SIGNATURES = {
                                              C.c_uint32, C.c_uint32, _P, _P]),
     "e3k_sampler_reverse_em_fixed": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _I32, C.c_uint32, C.c_uint32, _P, C.c_uint32,
                                                C.c_uint32, _P]),
+    # (the ODE sampler: x_out, d_out | x0, d1 first; the time table and the cells in place of t)
+    "e3k_sampler_ode_euler": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _I32, _I64, _I32, _I32, _F, _F, _P]),
+    "e3k_sampler_ode_heun": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _F, _F, _P]),
     "e3k_segment_sum": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 

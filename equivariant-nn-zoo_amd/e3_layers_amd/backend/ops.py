@@ -2107,6 +2107,57 @@ def sampler_reverse_em_fixed(x, raw, known, fixed, node_seg, t, n_graphs: int, b
     return out
 
 
+def _ode_operands(name, x, raw, node_seg, times, n_graphs, cells, out):
+    """``_sampler_operands`` with the time table where its siblings take t: contiguous fp32 ``times`` [n >= 2] on the device"""
+    L.require_cuda(times)
+    x, raw, _, out = _sampler_operands(name, x, raw, node_seg, times, 0, cells, out)
+    if times.dtype != torch.float32 or not times.is_contiguous() or times.dim() != 1 or times.numel() < 2:
+        raise ValueError(f"{name}: times must be a contiguous fp32 device tensor [n_steps + 1]")
+    if int(n_graphs) < 0:
+        raise ValueError(f"{name}: n_graphs = {int(n_graphs)}")
+    return x, raw, out
+
+
+def sampler_ode_euler(x, raw, node_seg, times, cells, n_graphs: int, beta_0: float, beta_1: float, t_out=None, want_d: bool = True,
+                      out=None):
+    """One Euler step of the probability-flow ODE of a diffusion key, which is Heun's stage A (``e3k_sampler_ode_euler``):
+    ``(x + h d1, d1)`` with ``d1 = (0.5 beta(t_k)) (raw / s(t_k))``, ``k = cells[1]``, ``t_k = times[k]``, ``h = times[k + 1] - t_k``
+    read from the table on the device; ``d1`` is None without ``want_d``.  ``t_out`` (contiguous fp32, the batch's t): every element
+    becomes ``times[k + 1]`` in the same launch.  Rows outside the ``n_graphs`` real graphs are copied through (``d1 = 0``), and so is
+    everything when ``k`` or ``k + 1`` is outside the table.  ``out`` may be ``x``.  One launch."""
+    x, raw, out = _ode_operands("sampler_ode_euler", x, raw, node_seg, times, n_graphs, cells, out)
+    g1 = 0
+    if t_out is not None:
+        L.require_cuda(t_out)
+        if t_out.dtype != torch.float32 or not t_out.is_contiguous() or t_out.numel() < 1:
+            raise ValueError("sampler_ode_euler: t_out must be a contiguous fp32 device tensor")
+        g1 = t_out.numel()
+    d = torch.empty_like(x) if want_d else None
+    n, dim = x.shape
+    L.check(L.load().e3k_sampler_ode_euler(L.ptr(out), L.ptr(d), L.ptr(x), L.ptr(raw), L.ptr(node_seg), L.ptr(times),
+                                           times.numel(), L.ptr(cells), L.ptr(t_out), g1, n, dim,
+                                           int(n_graphs), float(beta_0), float(beta_1), L.stream_ptr()), "e3k_sampler_ode_euler")
+    return out, d
+
+
+def sampler_ode_heun(x0, d1, raw2, node_seg, times, cells, n_graphs: int, beta_0: float, beta_1: float, out=None):
+    """Heun's stage B of the same step (``e3k_sampler_ode_heun``): ``x0 + (0.5 h) (d1 + d2)`` with ``d2 = (0.5 beta(t_{k+1}))
+    (raw2 / s(t_{k+1}))``; ``x0``, ``d1``: the state before stage A and its drift, ``raw2``: the model's output at the stage-A state.
+    Ghost rows and steps outside the table: ``x0``.  ``out`` may be ``x0``, never ``d1``.  One launch."""
+    x0, raw2, out = _ode_operands("sampler_ode_heun", x0, raw2, node_seg, times, n_graphs, cells, out)
+    L.require_cuda(d1)
+    d1 = L.f32c(d1.detach())
+    if d1.shape != x0.shape:
+        raise ValueError(f"sampler_ode_heun: d1 must have x0's shape {tuple(x0.shape)} (got {tuple(d1.shape)})")
+    if d1.data_ptr() == out.data_ptr():
+        raise ValueError("sampler_ode_heun: out must not be d1")
+    n, dim = x0.shape
+    L.check(L.load().e3k_sampler_ode_heun(L.ptr(out), L.ptr(x0), L.ptr(d1), L.ptr(raw2), L.ptr(node_seg), L.ptr(times), times.numel(),
+                                          L.ptr(cells), n, dim, int(n_graphs), float(beta_0), float(beta_1), L.stream_ptr()),
+            "e3k_sampler_ode_heun")
+    return out
+
+
 def segment_sum(x, ptr, seg_index, mean=False):
     return SegmentSumFn.apply(_c(x), ptr, seg_index, bool(mean))
 

@@ -31,6 +31,10 @@ the capped replay too, and the eager loop, the static-edge graph and the capped 
 whose per-node field ``name`` is not zero keep the values the batch holds on entry.  After the prior and after every corrector and
 predictor update their rows are overwritten with the known values perturbed to the step's noise level, and with the known values
 themselves when the run ends.  Seeded, the replacement is a branch of the update's own kernel: the replayed step has no launch more.
+
+``get_ode_sampler(method="heun" | "euler", n_steps=K)`` integrates the probability-flow ODE of the same SDE on a fixed grid of K steps
+instead (the ``"ode"`` method the reference's ``get_sampling_fn`` dispatches to and never defines, :247-286): no noise after the prior,
+one launch per key and stage around each model call, the same three loops -- ``_run_loop`` drives them for both samplers.
 """
 from __future__ import annotations
 
@@ -43,8 +47,8 @@ from ..backend.graph import TOPO_KEYS, EdgeCapacityExceeded
 from ..data.compute_edge import PairCriterion, computeEdgeIndex, computeEdgeIndexCapped
 from .capped import EDGE_KEYS, CappedBucket, builder_cells, edge_layer_of, replayable_criterion
 from .graph_step import CapturedStep
-from .sde_utils import (VPSDE, _node_t, _randn, fixed_rows, get_score_fn, langevin_step_counter, prior_sampling,
-                        prior_sampling_counter, replace_fixed, reverse_step, reverse_step_counter, sampler_begin_step)
+from .sde_utils import (VPSDE, _node_t, _randn, fixed_rows, get_score_fn, langevin_step_counter, ode_euler_step, ode_heun_finish,
+                        prior_sampling, prior_sampling_counter, replace_fixed, reverse_step, reverse_step_counter, sampler_begin_step)
 
 class _Registry(dict):
     """name -> class table with a decorator: ``@table.register(name="langevin")`` (bare ``@table.register`` uses the
@@ -178,17 +182,8 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
     inverse_scaler = inverse_scaler or (lambda b: b)
     predictor = predictor or NonePredictor
     corrector = corrector or NoneCorrector
-    if graph and not static_edges and edge_capacity is None:
-        raise ValueError("graph capture needs static_edges=True (a changing edge count changes every launch)")
-    if edge_capacity is not None:
-        if not graph or static_edges:
-            raise ValueError("edge_capacity belongs to graph=True on cutoff graphs (static_edges=False)")
-        if corrector is not NoneCorrector and not (seed is not None and corrector is LangevinCorrector):
-            raise ValueError("edge_capacity: the ghost graph's nodes would enter the corrector's batch-wide norms; only NoneCorrector is served")
-        if r_max is None:
-            raise ValueError("edge_capacity needs the cutoff of the neighbour list: pass r_max")
-        if criteria is not None and not isinstance(criteria, PairCriterion):
-            raise ValueError("edge_capacity: criteria must be a data.PairCriterion (the capped builder evaluates it in its kernels)")
+    _check_loop_args(graph, static_edges, edge_capacity, r_max, criteria,
+                     norms_served=corrector is NoneCorrector or (seed is not None and corrector is LangevinCorrector))
     seeded = seed is not None
     if seeded:
         if not 0 <= int(seed) < 1 << 64:
@@ -200,15 +195,7 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
             raise ValueError("seed: the draw layout holds one corrector draw per reverse step, and the capped loop would rebuild the "
                              "list between inner corrector steps where the eager loop does not: n_steps must be 1")
 
-    def rebuild_edges(batch):
-        for k in SAMPLER_EDGE_KEYS:
-            batch.pop(k)
-        for fn in preprocess:
-            new, attrs = fn(batch.data, batch.attrs)
-            batch.attrs.update(attrs)
-            batch.update(new)
-        return batch
-
+    rebuild_edges, moved = _edge_plumbing(preprocess, static_edges)
     steps = sde.N if n_iter is None else min(int(n_iter), sde.N)
 
     def pc_sampler(model, batch, generator=None, noise_fn=None):
@@ -235,27 +222,10 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
         pred, corr = predictor(sde, score_fn), corrector(sde, score_fn, snr, n_steps)
         batch["t"] = torch.empty(len(batch), 1, device=dev)
         if static_edges:
-            from ..backend.graph import build_topology
-
-            if "edge_index" not in batch:
-                rebuild_edges(batch)
-            if "_e3k_dst_ptr" not in batch and batch["edge_index"].is_cuda:
-                batch.update(build_topology(batch["edge_index"], batch.n_nodes).as_dict())
+            _static_topology(batch, rebuild_edges)
         t_dev = batch["t"]
         keys = list(sde.irreps)
-        own = edge_layer_of(model)
-        for crit in (criteria, own and own.criterion):
-            if isinstance(crit, PairCriterion):
-                crit.reset()      # build k of this run draws with index k
-
-        def moved(b):
-            # positions changed: the geometry cached in the batch by the model's first layer is stale
-            # (the reference pops edge_index / edge_vector here, :236-241)
-            if static_edges:
-                b.pop("edge_vector")
-                b.pop("edge_length")
-                return b
-            return rebuild_edges(b)
+        _reset_criteria(model, criteria)
 
         if seeded:
             # the step's time and number: device cells (next step, step in use) that the step's first launch advances
@@ -278,69 +248,208 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
                 corr_fn = corr_fn if corrector is NoneCorrector else replaced(corr_fn)
                 pred_fn = pred_fn if predictor is NonePredictor else replaced(pred_fn)
 
-        def one_step(b):
-            return moved(pred_fn(moved(corr_fn(b))))
-
-        def capped_updates():
-            return [corr_fn, pred_fn]
-
         with torch.no_grad():
-            if graph and edge_capacity is not None:
-                loop = CappedLoop(batch, model, capped_updates(), keys, float(timesteps[0]), int(edge_capacity), float(r_max),
-                                  criteria, seeded=(times, cells) if seeded else None, fixed=fixed)
-                loop.rewind()
-                loop.run(timesteps, steps)
-                batch = loop.result()
-            elif graph:
-                # static buffers: the diffused tensors and t; the step writes its result back into them
-                state = {k: batch[k].clone() for k in keys}
-
-                def captured():
-                    work = batch.clone()           # model layers add keys: work on a copy, keep `batch` pristine
-                    for k in keys:
-                        work[k] = state[k]
-                    work["t"] = t_dev
-                    if seeded:
-                        sampler_begin_step(times, cells, t_dev)
-                    work = one_step(work)
-                    for k in keys:
-                        state[k].copy_(work[k])
-
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    saved = {k: v.clone() for k, v in state.items()}
-                    t_dev.fill_(float(timesteps[0]))
-                    captured()                     # warm-up (allocations, plan creation) outside the capture
-                    for k in keys:
-                        state[k].copy_(saved[k])
-                    if seeded:
-                        cells.zero_()              # (the warm-up was step 0: the run starts there again)
-                torch.cuda.current_stream().wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    captured()
-                for k in keys:                     # the capture pass itself does not execute; restore anyway
-                    state[k].copy_(saved[k])
-                for i in range(steps):
-                    if not seeded:
-                        t_dev.copy_(timesteps[i].expand_as(t_dev))
-                    g.replay()
-                for k in keys:
-                    batch[k] = state[k]
-            else:
-                for i in range(steps):
-                    if seeded:
-                        sampler_begin_step(times, cells, t_dev)
-                    else:
-                        t_dev.copy_(timesteps[i].expand_as(t_dev))
-                    batch["t"] = t_dev
-                    batch = one_step(batch)
+            batch = _run_loop(batch, model, [corr_fn, pred_fn], keys, timesteps, steps, moved, t_dev, graph=graph,
+                              edge_capacity=edge_capacity, r_max=r_max, criteria=criteria, header=(times, cells) if seeded else None,
+                              fixed=fixed)
         if fixed is not None:
             batch = _release(sde, batch, fixed, given)
         return inverse_scaler(batch), steps * (n_steps + 1)
 
     return pc_sampler
+
+
+def get_ode_sampler(sde: VPSDE, inverse_scaler: Callable = None, method: str = "heun", *, n_steps: int, eps: float = 1e-3,
+                    preprocess: Sequence[Callable] = (), static_edges: bool = False, graph: bool = False,
+                    n_iter: Optional[int] = None, edge_capacity: Optional[int] = None, r_max: Optional[float] = None,
+                    criteria=None, seed: Optional[int] = None):
+    """``ode_sampler(model, batch, generator=None, noise_fn=None) -> (batch, n_function_evaluations)``: fixed-step integration of the
+    probability-flow ODE of the VP-SDE, ``dx/dt = -0.5 beta(t) [x + score(x, t)]`` -- the deterministic flow with the reverse SDE's
+    marginals.  With the head convention ``score = -raw / s(t) - x`` the drift is ``d(raw, t) = (0.5 beta(t)) (raw / s(t))``
+    (``run/sde_utils.ode_euler_step``, ``ode_heun_finish``; ``csrc/e3k_sampler.hip``).
+
+    method: ``"euler"`` (``x + h d1``; one model call per step) or ``"heun"`` (stage A as Euler's, stage B ``x + (0.5 h) (d1 + d2)`` with
+        ``d2`` at the stage-A state and ``t_{k+1}``; two model calls per step, every step, the last included: ``s(eps) > 0``).
+    n_steps: the steps of the run, required: the grid is ``linspace(sde.T, eps, n_steps + 1)``, step k goes from ``t_k`` to
+        ``t_{k+1}``.  It has nothing to do with ``sde.N``, which only names the prior's draw index.  How many steps a trained network
+        needs for a given sample quality is not assessed here.
+    seed: selects only the prior.  Seeded: ``prior_sampling_counter`` -- the ``x_T`` bits of ``get_pc_sampler(seed=...)`` at the same
+        seed; ``generator`` and ``noise_fn`` are refused.  Unseeded: ``prior_sampling`` from ``generator`` / ``noise_fn`` (one draw per
+        key).  After the prior the loop is deterministic and the same either way: the step's time and number live in device cells,
+        the update is one launch per key and stage.
+    preprocess, static_edges, graph, edge_capacity, r_max, criteria, n_iter: the loops of ``get_pc_sampler``, with its meaning and
+        its refusals (``n_iter`` stops after this many of the ``n_steps`` steps).  The neighbour list is rebuilt from the moved
+        positions after stage A and again after stage B, as that loop does after its corrector and its predictor.  Ghost rows of a
+        padded batch never move.
+
+    Out of scope: conditional sampling (there is no ``fixed`` argument: a deterministic replacement rule for the fixed rows is a design
+    question of its own) and likelihood evaluation (the divergence of the drift)."""
+    inverse_scaler = inverse_scaler or (lambda b: b)
+    if method not in ("euler", "heun"):
+        raise ValueError(f"ODE method {method!r} unknown (euler, heun)")
+    if int(n_steps) < 1:
+        raise ValueError(f"n_steps: at least one step (got {n_steps})")
+    n_steps = int(n_steps)
+    _check_loop_args(graph, static_edges, edge_capacity, r_max, criteria)
+    if seed is not None and not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed: at most 64 bits")
+    rebuild_edges, moved = _edge_plumbing(preprocess, static_edges)
+    steps = n_steps if n_iter is None else min(int(n_iter), n_steps)
+
+    def ode_sampler(model, batch, generator=None, noise_fn=None):
+        if seed is not None and (generator is not None or noise_fn is not None):
+            raise ValueError("seed: the prior is counter-based; generator and noise_fn have nothing to feed")
+        batch = batch.clone()
+        dev = batch["_n_nodes"].device
+        batch.attrs["t"] = ("graph", "1x0e")
+        if seed is not None:
+            batch = prior_sampling_counter(sde, batch, seed)
+        else:
+            batch = prior_sampling(sde, batch, generator, noise_fn)
+        # fp32 on the device (what the kernels read); torch's default dtype on the host, where float64 is the tests' reference
+        times = torch.linspace(sde.T, eps, n_steps + 1, device=dev, dtype=torch.float32 if dev.type == "cuda" else None)
+        batch["t"] = torch.empty(len(batch), 1, device=dev, dtype=times.dtype)
+        if static_edges:
+            _static_topology(batch, rebuild_edges)
+        _reset_criteria(model, criteria)
+        cells = torch.zeros(2, dtype=torch.int64, device=dev)
+        if method == "euler":
+            updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells)]
+        else:
+            kept = {}      # stage A's (x, d1) per key: made and used inside one step (one captured step on the replays)
+            updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells, keep=kept),
+                       partial(ode_heun_finish, sde, model, kept=kept, times=times, cells_or_step=cells)]
+        with torch.no_grad():
+            # the step header walks the first n_steps entries: a run replayed past its schedule stands still
+            batch = _run_loop(batch, model, updates, list(sde.irreps), times, steps, moved, batch["t"], graph=graph,
+                              edge_capacity=edge_capacity, r_max=r_max, criteria=criteria, header=(times[:n_steps], cells))
+        return inverse_scaler(batch), steps * len(updates)
+
+    return ode_sampler
+
+
+def _check_loop_args(graph, static_edges, edge_capacity, r_max, criteria, norms_served: bool = True) -> None:
+    """The refusals every sampler shares for the arguments that choose the loop.  ``norms_served``: whether the updates' batch-wide
+    reductions (the corrector's norms), if any, skip the ghost graph's rows."""
+    if graph and not static_edges and edge_capacity is None:
+        raise ValueError("graph capture needs static_edges=True (a changing edge count changes every launch)")
+    if edge_capacity is not None:
+        if not graph or static_edges:
+            raise ValueError("edge_capacity belongs to graph=True on cutoff graphs (static_edges=False)")
+        if not norms_served:
+            raise ValueError("edge_capacity: the ghost graph's nodes would enter the corrector's batch-wide norms; only NoneCorrector is served")
+        if r_max is None:
+            raise ValueError("edge_capacity needs the cutoff of the neighbour list: pass r_max")
+        if criteria is not None and not isinstance(criteria, PairCriterion):
+            raise ValueError("edge_capacity: criteria must be a data.PairCriterion (the capped builder evaluates it in its kernels)")
+
+
+def _edge_plumbing(preprocess, static_edges: bool):
+    """-> (rebuild_edges, moved): what the loops do to a batch's neighbour list, with the dataset's ``preprocess`` functions"""
+    def rebuild_edges(batch):
+        for k in SAMPLER_EDGE_KEYS:
+            batch.pop(k)
+        for fn in preprocess:
+            new, attrs = fn(batch.data, batch.attrs)
+            batch.attrs.update(attrs)
+            batch.update(new)
+        return batch
+
+    def moved(b):
+        # positions changed: the geometry cached in the batch by the model's first layer is stale
+        # (the reference pops edge_index / edge_vector here, :236-241)
+        if static_edges:
+            b.pop("edge_vector")
+            b.pop("edge_length")
+            return b
+        return rebuild_edges(b)
+
+    return rebuild_edges, moved
+
+
+def _static_topology(batch, rebuild_edges) -> None:
+    """(``static_edges``: the list and the CSR topology on it are built once, before the loop)"""
+    from ..backend.graph import build_topology
+
+    if "edge_index" not in batch:
+        rebuild_edges(batch)
+    if "_e3k_dst_ptr" not in batch and batch["edge_index"].is_cuda:
+        batch.update(build_topology(batch["edge_index"], batch.n_nodes).as_dict())
+
+
+def _reset_criteria(model, criteria) -> None:
+    own = edge_layer_of(model)
+    for crit in (criteria, own and own.criterion):
+        if isinstance(crit, PairCriterion):
+            crit.reset()      # build k of this run draws with index k
+
+
+def _run_loop(batch, model, updates, keys, timesteps, steps: int, moved, t_dev, *, graph: bool, edge_capacity, r_max, criteria,
+              header=None, fixed=None):
+    """The three loop drivers of the samplers: ``steps`` steps, each the ``updates`` (``batch -> batch``: corrector and predictor, or the
+    ODE's stages) in order with ``moved`` after every one -- eager; one captured step replayed (``graph``: the edge set is static);
+    ``CappedLoop`` (``graph`` with ``edge_capacity``: cutoff graphs, the list rebuilt inside the captured step, which does ``moved``'s
+    work itself).  ``keys``: the tensors the updates move; ``t_dev``: the batch's time tensor.
+
+    ``header``: ``(times, cells)`` -- every step begins with ``sampler_begin_step(times, cells, t_dev)`` on the device, and replays
+    are bare.  None: the host copies ``timesteps[i]`` into ``t_dev`` before step i.  -> the batch after the last step."""
+    def one_step(b):
+        for update in updates:
+            b = moved(update(b))
+        return b
+
+    if graph and edge_capacity is not None:
+        loop = CappedLoop(batch, model, updates, keys, float(timesteps[0]), int(edge_capacity), float(r_max), criteria, seeded=header,
+                          fixed=fixed)
+        loop.rewind()
+        loop.run(timesteps, steps)
+        return loop.result()
+    if graph:
+        # static buffers: the diffused tensors and t; the step writes its result back into them
+        state = {k: batch[k].clone() for k in keys}
+
+        def captured():
+            work = batch.clone()           # model layers add keys: work on a copy, keep `batch` pristine
+            for k in keys:
+                work[k] = state[k]
+            work["t"] = t_dev
+            if header is not None:
+                sampler_begin_step(header[0], header[1], t_dev)
+            work = one_step(work)
+            for k in keys:
+                state[k].copy_(work[k])
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            saved = {k: v.clone() for k, v in state.items()}
+            t_dev.fill_(float(timesteps[0]))
+            captured()                     # warm-up (allocations, plan creation) outside the capture
+            for k in keys:
+                state[k].copy_(saved[k])
+            if header is not None:
+                header[1].zero_()          # (the warm-up was step 0: the run starts there again)
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            captured()
+        for k in keys:                     # the capture pass itself does not execute; restore anyway
+            state[k].copy_(saved[k])
+        for i in range(steps):
+            if header is None:
+                t_dev.copy_(timesteps[i].expand_as(t_dev))
+            g.replay()
+        for k in keys:
+            batch[k] = state[k]
+        return batch
+    for i in range(steps):
+        if header is not None:
+            sampler_begin_step(header[0], header[1], t_dev)
+        else:
+            t_dev.copy_(timesteps[i].expand_as(t_dev))
+        batch["t"] = t_dev
+        batch = one_step(batch)
+    return batch
 
 
 def _condition(sde: VPSDE, batch, fixed: str):
@@ -475,8 +584,15 @@ class CappedLoop:
 
 
 def get_sampling_fn(config, sde: VPSDE, inverse_scaler, eps: float, **kwargs):
-    """``config.sampling.{method, predictor, corrector, snr, n_steps_each}`` → sampler (:247-286; only 'pc')."""
+    """``config.sampling.{method, predictor, corrector, snr, n_steps_each}`` → sampler (:247-286: 'pc'; 'ode', which the reference
+    dispatches to a sampler it never defines: ``config.sampling.ode_steps`` (required) and ``ode_method`` (default 'heun'))."""
     name = config.sampling.method.lower()
+    if name == "ode":
+        n_steps = getattr(config.sampling, "ode_steps", None)
+        if n_steps is None:
+            raise ValueError("config.sampling.ode_steps is required with sampling.method = 'ode' (the steps of the ODE run)")
+        return get_ode_sampler(sde=sde, inverse_scaler=inverse_scaler, method=str(getattr(config.sampling, "ode_method", "heun")).lower(),
+                               n_steps=n_steps, eps=eps, **kwargs)
     if name != "pc":
         raise ValueError(f"Sampler name {config.sampling.method} unknown.")
     return get_pc_sampler(sde=sde, predictor=get_predictor(config.sampling.predictor.lower()),

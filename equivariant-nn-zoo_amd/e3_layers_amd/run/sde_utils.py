@@ -456,6 +456,97 @@ def reverse_step_counter(sde: VPSDE, model, batch, seed: int, draw, dtype=None, 
     return batch
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The probability-flow ODE sampler's steps (run/sde_sampling.get_ode_sampler): fixed-step Euler and Heun on
+#   dx/dt = -0.5 beta(t) [x + score(x, t)],   score = -raw / s(t) - x   =>   d(raw, t) = (0.5 beta(t)) (raw / s(t))
+# -- the collapsed drift: the x terms cancel, so it is never formed as x + (-raw / s - x).  ``times`` = linspace(T, eps, n_steps + 1);
+# step k goes from t_k = times[k] to t_{k+1} = times[k + 1], h = t_{k+1} - t_k < 0, both read from the table (not from the batch's t):
+#   Euler / Heun stage A:  d1 = d(raw(x, t_k), t_k),           x~ = x + h d1,                and the batch's t becomes t_{k+1}
+#   Heun stage B:          d2 = d(raw(x~, t_{k+1}), t_{k+1}),  x' = x + (0.5 h) (d1 + d2)
+# Ghost rows of a padded batch: x~ = x' = x bit for bit, d1 = 0.  k or k + 1 outside the table: nothing moves.
+# ---------------------------------------------------------------------------------------------------------------------
+def _ode_host_terms(sde: VPSDE, batch, times, k: int, dtype):
+    """(beta(t) / 2, s(t)) at t = times[k] in ``dtype``, the real-row mask [N, 1]: the CPU restatement's terms"""
+    t = times[k].to(dtype)
+    q, h = -0.25 * (sde.beta_1 - sde.beta_0), -0.5 * sde.beta_0
+    lm = t * (q * t + h)
+    seg = batch.nodeSegment()
+    real = (torch.arange(len(batch)) < _real_graphs(batch))[seg].reshape(-1, 1)
+    return 0.5 * (t * (sde.beta_1 - sde.beta_0) + sde.beta_0), torch.sqrt(-torch.expm1(2.0 * lm)), real
+
+
+def ode_euler_step(sde: VPSDE, model, batch, times, cells_or_step, dtype=None, keep=None, train: bool = False):
+    """One Euler step of the probability-flow ODE, which is Heun's stage A: the model call at the batch's state and time, then per
+    diffusion key ``x + h d1`` with ``d1 = (0.5 beta(t_k)) (raw / s(t_k))`` (the formulas above); the batch's ``t`` becomes
+    ``t_{k+1}``, what the model's next call sees.
+
+    ``times``: the run's table [n_steps + 1].  ``cells_or_step``: the step k as an int, or the sampler's cells (int64 [2]: next step,
+    step in use; on device tensors DEVICE cells, read by the kernel without a host synchronisation).  ``keep``: a dict that receives
+    ``{key: (x, d1)}`` for ``ode_heun_finish`` (None: the Euler method, nothing is kept and the key is updated in place where it can
+    be).  Device tensors: one ``e3k_sampler_ode_euler`` launch per key (fp32); the first key's launch writes the time.  CPU tensors:
+    the torch restatement in ``dtype`` (default: the key's) -- float64 is the kernel tests' reference."""
+    raw = _raw_scores(sde, model, batch, train)
+    keys = list(sde.irreps)
+    dev = batch[keys[0]].device
+    if dev.type == "cuda":
+        from ..backend import ops
+
+        cells, seg, n_real = _sampler_cells(cells_or_step, dev), batch.nodeSegment(), _real_graphs(batch)
+        for key in keys:
+            x = batch[key]
+            in_place = keep is None and x.dtype == torch.float32 and x.is_contiguous()
+            batch[key], d1 = ops.sampler_ode_euler(x, raw[key], seg, times, cells, n_real, sde.beta_0, sde.beta_1,
+                                                   t_out=batch["t"] if key == keys[0] else None, want_d=keep is not None,
+                                                   out=x if in_place else None)
+            if keep is not None:
+                keep[key] = (x, d1)
+        return batch
+    k = _step_in_use(cells_or_step)
+    if not 0 <= k < times.numel() - 1:
+        if keep is not None:
+            keep.update({key: (batch[key], torch.zeros_like(batch[key])) for key in keys})
+        return batch
+    for key in keys:
+        x = batch[key] if dtype is None else batch[key].to(dtype)
+        half_beta, s, real = _ode_host_terms(sde, batch, times, k, x.dtype)
+        h = (times[k + 1] - times[k]).to(x.dtype)
+        d1 = torch.where(real, half_beta * (raw[key].to(x.dtype) / s), torch.zeros((), dtype=x.dtype))
+        batch[key] = torch.where(real, x + h * d1, x)
+        if keep is not None:
+            keep[key] = (x, d1)
+    batch["t"].fill_(float(times[k + 1]))
+    return batch
+
+
+def ode_heun_finish(sde: VPSDE, model, batch, kept, times, cells_or_step, dtype=None, train: bool = False):
+    """Heun's stage B: the model call at the stage-A state ``x~`` and ``t_{k+1}``, then per diffusion key ``x + (0.5 h) (d1 + d2)``
+    with ``d2 = (0.5 beta(t_{k+1})) (raw2 / s(t_{k+1}))`` and ``(x, d1) = kept[key]`` from ``ode_euler_step(keep=kept)`` of the same
+    step.  ``times``, ``cells_or_step``, devices and ``dtype`` as there; device tensors: one ``e3k_sampler_ode_heun`` launch per key."""
+    raw2 = _raw_scores(sde, model, batch, train)
+    keys = list(sde.irreps)
+    dev = batch[keys[0]].device
+    if dev.type == "cuda":
+        from ..backend import ops
+
+        cells, seg, n_real = _sampler_cells(cells_or_step, dev), batch.nodeSegment(), _real_graphs(batch)
+        for key in keys:
+            x0, d1 = kept[key]
+            batch[key] = ops.sampler_ode_heun(x0, d1, raw2[key], seg, times, cells, n_real, sde.beta_0, sde.beta_1)
+        return batch
+    k = _step_in_use(cells_or_step)
+    for key in keys:
+        x0, d1 = kept[key]
+        x0 = x0 if dtype is None else x0.to(dtype)
+        if not 0 <= k < times.numel() - 1:
+            batch[key] = x0
+            continue
+        half_beta, s, real = _ode_host_terms(sde, batch, times, k + 1, x0.dtype)
+        h = (times[k + 1] - times[k]).to(x0.dtype)
+        d2 = half_beta * (raw2[key].to(x0.dtype) / s)
+        batch[key] = torch.where(real, x0 + (0.5 * h) * (d1.to(x0.dtype) + d2), x0)
+    return batch
+
+
 def sde_loss_of(sde: VPSDE, model, pert, misc, train: bool = True, node_weight=None) -> Tuple[torch.Tensor, dict]:
     """Second half of ``sde_loss``: the score network on the noised batch and the denoising loss."""
     scores = get_score_fn(sde, model, train)(pert)

@@ -932,6 +932,34 @@ int e3k_sampler_reverse_em_fixed(float* x_out, const float* x, const float* raw,
                                  uint32_t word_fixed, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The probability-flow ODE sampler's arithmetic around the model (csrc/e3k_sampler.hip; run/sde_sampling.py get_ode_sampler):
+ * fixed-step Euler and Heun on dx/dt = -0.5 beta(t) [x + score(x, t)].  With the head convention score = -raw / s(t) - x the
+ * x terms cancel and the drift is
+ *     d(raw, t) = (0.5f * beta(t)) * (raw / s(t)),   beta(t) = fma(t, beta_1 - beta_0, beta_0),   s(t) as above
+ * -- the collapsed form the kernels evaluate (no x + (-raw / s - x)).  Operands fp32, ghost rows as above.
+ * times [n_times] DEVICE fp32: the run's grid, linspace(T, eps, n_steps + 1).  cells [2] DEVICE int64 (next step, step in use),
+ * read and never written.  With k = cells[1]: t_k = times[k], t_n = times[k + 1], hs = t_n - t_k (one fp32 subtraction, negative);
+ * the batch's own t is not read.  k < 0 or k + 1 >= n_times: nothing moves (below).
+ *
+ * e3k_sampler_ode_euler (the Euler step and Heun's stage A): one thread per component.  Real rows inside the table:
+ *     d1 = d(raw, t_k);   x_out = fmaf(hs, d1, x);   d_out = d1 (d_out nullable).
+ *   Ghost rows, and every row outside the table: x_out = x bit for bit, d_out = 0.  x_out may alias x; d_out aliases nothing.
+ *   t_out nullable: inside the table t_out[g] = t_n for every g < G1 (the time of the model's next call; the ghost graph included);
+ *   outside it t_out is untouched.  G1 is not read when t_out is null.
+ * e3k_sampler_ode_heun (Heun's stage B, at t_n): one thread per component.  Real rows inside the table:
+ *     d2 = d(raw2, t_n);   x_out = fmaf(0.5f * hs, d1 + d2, x0).
+ *   Ghost rows and every row outside the table: x_out = x0 bit for bit.  x_out may alias x0.
+ * Invalid: null pointers (but d_out, t_out), N < 1, N >= 2^31, D outside [1, 1024], G < 0, n_times < 2, beta_0 < 0,
+ *   beta_1 < beta_0, N D >= 2^38, t_out with G1 < 1, d_out == x_out, x or raw, d1 == x_out.
+ * ------------------------------------------------------------------------------------------ */
+int e3k_sampler_ode_euler(float* x_out, float* d_out, const float* x, const float* raw, const int64_t* node_seg, const float* times,
+                          int64_t n_times, const int64_t* cells, float* t_out, int32_t G1, int64_t N, int32_t D, int32_t G,
+                          float beta_0, float beta_1, void* stream);
+int e3k_sampler_ode_heun(float* x_out, const float* x0, const float* d1, const float* raw2, const int64_t* node_seg,
+                         const float* times, int64_t n_times, const int64_t* cells, int64_t N, int32_t D, int32_t G, float beta_0,
+                         float beta_1, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A convolution layer as ONE call (csrc/e3k_layer.hip): FactorizedConvolution + Gate
  * (e3_layers/nn/message_passing.py:91-124, 249) forward and backward -- the launch sequence of
  * backend/conv_block.py issued from native code on the caller's streams, with the library's own events

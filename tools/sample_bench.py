@@ -28,7 +28,17 @@ every chain is kept on its known coordinates, the rest is sampled around it.  Th
 unconditioned seeded replay of the same tree (and the other variants), ``--trace-steps`` counts ITS launches, and the result goes to
 profiles/protein_sampler_fixed.json:
 
-    python tools/sample_bench.py --protein --seed 7 --corrector langevin --fixed 0.25 --steps 100"""
+    python tools/sample_bench.py --protein --seed 7 --corrector langevin --fixed 0.25 --steps 100
+
+``--ode euler|heun --ode-steps K`` (with ``--protein --seed S``) times the probability-flow ODE sampler's replayed step
+(``get_ode_sampler(graph=True, edge_capacity=...)``: a grid of K steps from T to 1e-3) beside the seeded Euler-Maruyama + Langevin
+replay of the same tree: the Heun replay, the Euler replay and the predictor-corrector replay alternate in one process, every
+repetition from x_T over the first ``--steps`` (<= K) steps of its schedule.  ``--ode`` names the method ``--trace-steps`` replays
+under rocprofv3.  What is timed is a STEP; how many steps a trained network needs is not assessed.  -> profiles/protein_sampler_ode.json
+
+    python tools/sample_bench.py --protein --seed 7 --ode heun --ode-steps 100 --steps 100
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/sample_bench.py --protein --seed 7 --ode heun \
+        --ode-steps 100 --trace-steps 40"""
 import argparse, csv, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
@@ -154,6 +164,29 @@ def seeded_replay_loop(model, sde, batch, timesteps, e_cap, seed, corrector, fix
                           seeded=(timesteps, cells), **extra)
 
 
+def ode_replay_loop(model, sde, batch, method, n_steps, e_cap):
+    """The capped loop of get_ode_sampler(graph=True, edge_capacity=...), built as it builds it: the updates are the ODE's stages, the
+    step header walks the first n_steps entries of the table."""
+    from functools import partial
+
+    from e3_layers_amd.run.sde_sampling import CappedLoop
+    from e3_layers_amd.run.sde_utils import ode_euler_step, ode_heun_finish
+
+    dev = batch["CA"].device
+    b = batch.clone()
+    b.attrs["t"] = ("graph", "1x0e")
+    times = torch.linspace(sde.T, 1e-3, n_steps + 1, device=dev, dtype=torch.float32)
+    cells = torch.zeros(2, dtype=torch.int64, device=dev)
+    if method == "euler":
+        updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells)]
+    else:
+        kept = {}
+        updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells, keep=kept),
+                   partial(ode_heun_finish, sde, model, kept=kept, times=times, cells_or_step=cells)]
+    with torch.no_grad():
+        return CappedLoop(b, model, updates, ["CA"], float(times[0]), e_cap, None, seeded=(times[:n_steps], cells))
+
+
 def conditioned(sde, batch, clean, fraction):
     """``batch`` (at x_T = z) with conditional sampling's fields, as get_pc_sampler(fixed="fixed") sets them up: the middle ``fraction``
     of every chain of every protein is fixed (a contiguous stretch, chosen by the chain's length alone), ``known_CA`` = the clean
@@ -232,11 +265,18 @@ def protein(argv):
     ap.add_argument("--seed", type=int, default=None, help="time the seeded form (get_pc_sampler(seed=...)) as well")
     ap.add_argument("--corrector", choices=("none", "langevin"), default="none", help="with --seed: the corrector of the seeded loops")
     ap.add_argument("--fixed", type=float, default=0.0, help="with --seed: the conditioned replay too, this fraction of every chain fixed")
+    ap.add_argument("--ode", choices=("euler", "heun"), default=None, help="with --seed: the ODE sampler's replays beside the seeded "
+                    "Euler-Maruyama + Langevin replay; the method --trace-steps replays")
+    ap.add_argument("--ode-steps", type=int, default=None, help="with --ode: the steps of the ODE grid (required)")
     args = ap.parse_args(argv)
+    if args.ode is not None and (args.seed is None or args.ode_steps is None or args.fixed):
+        raise SystemExit("--ode METHOD: with --seed and --ode-steps K, without --fixed")
     if not 0.0 <= args.fixed < 1.0 or (args.fixed and args.seed is None):
         raise SystemExit("--fixed FRACTION: in [0, 1), with --seed (the conditioned replay is the seeded form's)")
     dev = torch.device("cuda:0")
     model, sde, batch, timesteps, crit, clean = protein_setup(args.proteins, args.residues, dev)
+    if args.ode is not None:
+        return protein_ode(args, model, sde, batch, timesteps)
     if args.seed is not None:
         return protein_seeded(args, model, sde, batch, timesteps, crit, clean)
     if args.corrector != "none":
@@ -365,6 +405,70 @@ def protein_seeded(args, model, sde, batch, timesteps, crit, clean):
     print(text)
     out = args.out or os.path.join(ROOT, "profiles", "protein_sampler_fixed.json" if cond is not None else "protein_sampler_pc.json")
     with open(out, "w") as f:
+        f.write(text + "\n")
+
+
+def protein_ode(args, model, sde, batch, timesteps):
+    """The Heun replay, the Euler replay and the seeded Euler-Maruyama + Langevin replay, alternating, each repetition from x_T."""
+    n_timed = args.trace_steps or args.steps
+    if not 1 <= n_timed <= args.ode_steps or args.warmup > args.ode_steps:
+        raise SystemExit(f"--steps / --trace-steps / --warmup: at most --ode-steps = {args.ode_steps} (a replay past the grid stands still)")
+    _, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
+    e_cap = -(-int(1.1 * e_cap) // 1024) * 1024      # (the seeded Langevin replay's capacity; the same for every loop here)
+    loops = {"ode_heun_replay": ode_replay_loop(model, sde, batch, "heun", args.ode_steps, e_cap),
+             "ode_euler_replay": ode_replay_loop(model, sde, batch, "euler", args.ode_steps, e_cap)}
+
+    def replay(which, n):
+        which.rewind()      # (outside the timed region)
+
+        def run():
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                which.run(timesteps, n)
+            return time.perf_counter() - t0
+        return run
+
+    if args.trace_steps:
+        replay(loops[f"ode_{args.ode}_replay"], args.trace_steps)()
+        torch.cuda.synchronize()
+        print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
+                          "ode": args.ode, "ode_steps": args.ode_steps}))
+        return
+    loops["pc_langevin_replay"] = seeded_replay_loop(model, sde, batch, timesteps, e_cap, args.seed, "langevin")
+    for loop in loops.values():
+        replay(loop, args.warmup)()
+    rows = {name: [] for name in loops}
+    host = {name: [] for name in loops}
+    edges = {name: [] for name in loops}
+    for _ in range(args.reps):
+        for name, loop in loops.items():
+            ms, busy = timed(replay(loop, args.steps))
+            edges[name].append(int(loop.bucket.state[0]))
+            loop.result()                                   # (after the closing event: an overflowed repetition would raise here)
+            rows[name].append(ms / args.steps)
+            host[name].append(1e3 * busy / args.steps)
+
+    def mmm(v):
+        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
+
+    doc = {"workload": f"probability-flow ODE (Heun, Euler; grid of {args.ode_steps} steps) beside reverse diffusion (Euler-Maruyama + "
+                       "Langevin, first steps of N=1000, seeded) on config_diffusion_CA as shipped, built with pair_criterion(); "
+                       "synth_protein; capped replays, every repetition from x_T",
+           "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
+           "ode_steps": args.ode_steps, "nodes": int(batch["CA"].shape[0]), "e_cap": e_cap, "steps": args.steps, "reps": args.reps,
+           "model_calls_per_step": {"ode_heun_replay": 2, "ode_euler_replay": 1, "pc_langevin_replay": 2},
+           "sample_quality": "not assessed: untrained weights; only the time of a step is measured"}
+    for name, loop in loops.items():
+        doc[f"{name}_ms_per_step"] = mmm(rows[name])
+        doc[f"{name}_host_busy_ms_per_step"] = mmm(host[name])
+        doc[f"{name}_edges_last_list"] = edges[name]
+        doc[f"{name}_recaptures"] = loop.step.recaptures
+    pc = statistics.median(rows["pc_langevin_replay"])
+    doc["ode_heun_step_over_pc_step_median"] = round(statistics.median(rows["ode_heun_replay"]) / pc, 4)
+    doc["ode_euler_step_over_pc_step_median"] = round(statistics.median(rows["ode_euler_replay"]) / pc, 4)
+    text = json.dumps(doc, indent=1)
+    print(text)
+    with open(args.out or os.path.join(ROOT, "profiles", "protein_sampler_ode.json"), "w") as f:
         f.write(text + "\n")
 
 
