@@ -18,6 +18,10 @@
 //         reverse step i, after the predictor:       draw index i,      word 3 D_total + word0 + c
 //       (the prior's fixed rows use the prior's own draw: m(T) x0 + s(T) z).  Blocks 0 and 1 and the prior are where they were, so an
 //       unconditioned seeded run keeps its bits.
+//       and, for the likelihood (run/likelihood.py; e3k_sampler_probe), the Hutchinson probes, fixed for a whole run:
+//         probe p (from 0) of component c:           draw index sde.N + 1 + p,  word word0 + c
+//       (no step and not the prior uses an index above sde.N).  A Rademacher probe is +1 when bit 31 of mix32(h_node ^ (2 word)) is
+//       clear and -1 when it is set -- the hash normal_draw() makes its first uniform of; a Gaussian probe is normal_draw() itself.
 //     The sampler's seed is an argument of its own and should differ from the pair criterion's: with one seed a node's noise and the
 //     Bernoulli draws of its pairs at the same draw index come from one chain.
 // data/compute_edge.py (_mix32, pair_hash, normal_draw) is the host restatement, in int64 masked to 32 bits.

@@ -247,6 +247,96 @@ __global__ __launch_bounds__(256) void sampler_ode_heun_kernel(float* x_out, con
   x_out[k] = fmaf(0.5f * (tn - tk), d1[k] + d2, xc);
 }
 
+// The log-likelihood through the same flow (run/likelihood.get_likelihood_fn): on an ASCENDING table, per real graph,
+//   log p(x(eps)) = log N(x(T); 0, I) + integral of div f dt,   div f = c(t) tr(d raw / d x),   c(t) = (0.5 beta(t)) / s(t),
+// the trace by Hutchinson's estimate probe . vjp (vjp = the model's backward of probe . raw with respect to x).  Three kernels: the
+// probe, the quadrature term of one model call, the prior's log-density.  The two sums are in double: a run adds thousands of
+// terms of both signs into one number per graph, and the prior term is orders of magnitude above the integral.
+//
+// The probe of one key, one thread per component: draw index `draw` (sde.N + 1 + p for probe p), word word0 + c (e3k_draw.h).
+// kind 0: Rademacher, +1 when bit 31 of mix32(h_node ^ (2 word)) is clear, else -1; kind 1: normal_draw.  Ghost rows: 0.
+__global__ __launch_bounds__(256) void sampler_probe_kernel(float* __restrict__ out, const int64_t* __restrict__ node_seg, int64_t N,
+                                                            int32_t D, int32_t G, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw,
+                                                            uint32_t word0, int32_t kind) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= N * D) return;
+  const int64_t i = k / D;
+  const uint32_t word = word0 + (uint32_t)(k - i * D);
+  const int64_t g = node_seg[i];
+  if (g < 0 || g >= G) {
+    out[k] = 0.f;
+    return;
+  }
+  const uint32_t h_node = mix32(draw_prefix(seed_lo, seed_hi, draw) ^ (uint32_t)i);
+  out[k] = kind == 0 ? ((mix32(h_node ^ (2u * word)) >> 31) == 0u ? 1.0f : -1.0f) : normal_draw(h_node, word);
+}
+
+// The sum of a 256-thread workgroup's doubles in a fixed order: six shuffle levels inside a wavefront, the four wave partials added
+// in order by thread 0, which alone holds the result.
+__device__ __forceinline__ double block_sum_256(double v, double* part) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double total = 0.0;
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 4; ++k) total += part[k];
+  return total;
+}
+
+// (the rows [beg, end) of graph g from the int32 row pointers, clamped to the tensor's N rows: a bad pointer table reads nothing
+// outside it)
+__device__ __forceinline__ void graph_rows(const int32_t* __restrict__ row_ptr, int64_t N, int64_t* beg, int64_t* end) {
+  int64_t b = row_ptr[blockIdx.x], e = row_ptr[blockIdx.x + 1];
+  e = e < 0 ? 0 : e > N ? N : e;
+  b = b < 0 ? 0 : b > e ? e : b;
+  *beg = b, *end = e;
+}
+
+// One workgroup per real graph g: acc[g] = fma(coef, S, acc[g]) with S = sum over the graph's rows and components of probe * vjp
+// (thread j takes the elements j, j + 256, ... of the graph's contiguous range; products and sums in double) and
+// coef = (w c(t)) scale.  stage 0 (Euler): w = h, t = t_k; 1 (Heun A): w = h / 2, t = t_k; 2 (Heun B): w = h / 2, t = t_{k+1};
+// h = t_{k+1} - t_k and c(t) in double from the fp32 table entries; qd, hd, beta_0, dbeta: the doubles of the fp32 parameters.
+// k = cells[1] outside the table: nothing is written.  One writer per acc[g], no atomics; a graph of no rows adds 0.
+__global__ __launch_bounds__(256) void sampler_ode_div_kernel(double* __restrict__ acc, const float* __restrict__ probe,
+                                                              const float* __restrict__ vjp, const int32_t* __restrict__ row_ptr,
+                                                              const float* __restrict__ times, int64_t n_times,
+                                                              const int64_t* __restrict__ cells, int64_t N, int32_t D, int32_t stage,
+                                                              double scale, double qd, double hd, double beta_0, double dbeta) {
+  __shared__ double part[4];
+  const int64_t step = cells[1];
+  if (step < 0 || step + 1 >= n_times) return;      // (uniform)
+  int64_t beg, end;
+  graph_rows(row_ptr, N, &beg, &end);
+  double sum = 0.0;
+  for (int64_t k = beg * D + threadIdx.x; k < end * D; k += 256) sum += (double)probe[k] * (double)vjp[k];
+  sum = block_sum_256(sum, part);
+  if (threadIdx.x != 0) return;
+  const double tk = (double)times[step], tn = (double)times[step + 1];
+  const double w = stage == 0 ? tn - tk : 0.5 * (tn - tk);
+  const double t = stage == 2 ? tn : tk;
+  const double lm = t * (qd * t + hd);
+  const double c = (0.5 * (t * dbeta + beta_0)) / sqrt(-expm1(2.0 * lm));
+  acc[blockIdx.x] = fma((w * c) * scale, sum, acc[blockIdx.x]);
+}
+
+// One workgroup per real graph g, the same order of summation: out[g] += -0.5 sum x^2 - (0.5 n_g D) ln(2 pi), the log-density of
+// the graph's rows of one key under N(0, I).
+__global__ __launch_bounds__(256) void sampler_prior_logp_kernel(double* __restrict__ out, const float* __restrict__ x,
+                                                                 const int32_t* __restrict__ row_ptr, int64_t N, int32_t D) {
+  __shared__ double part[4];
+  int64_t beg, end;
+  graph_rows(row_ptr, N, &beg, &end);
+  double sum = 0.0;
+  for (int64_t k = beg * D + threadIdx.x; k < end * D; k += 256) {
+    const double v = (double)x[k];
+    sum += v * v;
+  }
+  sum = block_sum_256(sum, part);
+  if (threadIdx.x != 0) return;
+  const double norm = (0.5 * (double)((end - beg) * D)) * 1.8378770664093454835606594728112;      // ln(2 pi)
+  out[blockIdx.x] = out[blockIdx.x] + (-0.5 * sum - norm);
+}
+
 }  // namespace e3k
 
 extern "C" int e3k_sampler_begin_step(const float* times, int64_t n_times, int64_t* cells, float* t, int32_t G1, void* stream) {
@@ -352,6 +442,41 @@ extern "C" int e3k_sampler_ode_heun(float* x_out, const float* x0, const float* 
   const float q = -0.25f * (beta_1 - beta_0), h = -0.5f * beta_0;
   hipLaunchKernelGGL(e3k::sampler_ode_heun_kernel, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_out, x0,
                      d1, raw2, node_seg, times, n_times, cells, N, D, G, q, h, beta_0, beta_1 - beta_0);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+// The likelihood's three launches (run/likelihood.get_likelihood_fn).
+extern "C" int e3k_sampler_probe(float* out, const int64_t* node_seg, int64_t N, int32_t D, int32_t G, uint32_t seed_lo,
+                                 uint32_t seed_hi, uint32_t draw, uint32_t word0, int32_t kind, void* stream) {
+  if (!out || !node_seg || N < 1 || N >= (int64_t)1 << 31 || D < 1 || D > 1024 || G < 0 || N * D >= (int64_t)1 << 38 ||
+      (kind != 0 && kind != 1))
+    return E3K_ERR_INVALID;
+  hipLaunchKernelGGL(e3k::sampler_probe_kernel, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, node_seg,
+                     N, D, G, seed_lo, seed_hi, draw, word0, kind);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_sampler_ode_div(double* acc, const float* probe, const float* vjp, const int32_t* row_ptr, const float* times,
+                                   int64_t n_times, const int64_t* cells, int64_t N, int32_t D, int32_t G, int32_t stage, double scale,
+                                   float beta_0, float beta_1, void* stream) {
+  if (!acc || !probe || !vjp || !row_ptr || !times || !cells || stage < 0 || stage > 2 || !(scale > 0.0) ||
+      !ode_args_ok(N, D, G, n_times, beta_0, beta_1))
+    return E3K_ERR_INVALID;
+  if (G == 0) return E3K_OK;
+  const double b0 = (double)beta_0, db = (double)beta_1 - (double)beta_0;
+  hipLaunchKernelGGL(e3k::sampler_ode_div_kernel, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, acc, probe, vjp, row_ptr, times,
+                     n_times, cells, N, D, stage, scale, -0.25 * db, -0.5 * b0, b0, db);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
+extern "C" int e3k_sampler_prior_logp(double* out, const float* x, const int32_t* row_ptr, int64_t N, int32_t D, int32_t G,
+                                      void* stream) {
+  if (!out || !x || !row_ptr || !ode_args_ok(N, D, G, 2, 0.f, 0.f)) return E3K_ERR_INVALID;
+  if (G == 0) return E3K_OK;
+  hipLaunchKernelGGL(e3k::sampler_prior_logp_kernel, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, out, x, row_ptr, N, D);
   E3K_CHECK_LAUNCH();
   return E3K_OK;
 }

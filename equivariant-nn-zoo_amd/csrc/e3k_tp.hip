@@ -999,7 +999,16 @@ template <bool WITH_SH, int MAXL, int L3MAX, bool SPLIT, bool FULL>
 __global__ __launch_bounds__(256) void tp_bwd_w_kernel(TpArgs a, const e3k_tp_group* __restrict__ groups,
                                                        const int2* __restrict__ gc, int n_gc) {
   E3K_TP_PROLOGUE
-  E3K_TP_DISPATCH(tp_bwd_w_body, WITH_SH, L3MAX)
+  if constexpr (WITH_SH) {      // (e_store: this work item's slice of the harmonics' gradient partials -- e3k_tp_bwd_w_ordered)
+    TpArgs ap = a;
+    if (a.e_store) ap.g_sh = a.g_sh + (int64_t)gci * a.e_edges * a.d_sh;
+    {
+      const TpArgs& a = ap;
+      E3K_TP_DISPATCH(tp_bwd_w_body, WITH_SH, L3MAX)
+    }
+  } else {
+    E3K_TP_DISPATCH(tp_bwd_w_body, WITH_SH, L3MAX)
+  }
 }
 
 #define E3K_TP_BWDX_WAVES(MODE, MAXL, L3MAX) ((MODE == kBwdXwPacked && MAXL <= 2 && L3MAX <= 2) ? 8 : 1)
@@ -1550,6 +1559,24 @@ int edge_partials_combine(const e3k_tp_plan* plan, int64_t E, const float* parti
   return E3K_OK;
 }
 }  // namespace
+
+// e3k_tp_bwd_w with the harmonics' gradient summed in a FIXED order: every (node, group) work item stores its share of an edge's
+// g_sh into its own slice of e_partials [n_gc, E, d_sh] (the caller ZERO-FILLS e3k_tp_edge_partials_floats(plan, E) floats: a group
+// writes only the degrees it reads) and the slices are added in item order -- the same bits run to run, where e3k_tp_bwd_w adds
+// the shares of an edge that several work items visit with float atomics.  g_w as e3k_tp_bwd_w (may be NULL).
+extern "C" int e3k_tp_bwd_w_ordered(const e3k_tp_plan* plan, const float* x, const float* sh, const float* w, const float* g_out,
+                                    const int32_t* src, const int32_t* dst_ptr, const int32_t* dst_perm, int64_t N, int64_t E,
+                                    float* g_w, float* g_sh, float* e_partials, void* stream) {
+  if (!plan || N < 0 || E < 0) return E3K_ERR_INVALID;
+  if (N == 0 || E == 0) return E3K_OK;
+  if (!x || !sh || !w || !g_out || !src || !dst_ptr || !dst_perm || !g_sh || !e_partials) return E3K_ERR_INVALID;
+  e3k::TpArgs a = walk_in_edges(plan, src, dst_ptr, dst_perm);
+  a.x = x; a.sh = sh; a.w = w; a.g_out = g_out; a.g_w = g_w; a.g_sh = g_sh;
+  edge_partials_args(a, plan, E, e_partials);
+  const int rc = launch_all(TP_BWD_W_SH, a, plan, N, (hipStream_t)stream);
+  if (rc != E3K_OK) return rc;
+  return edge_partials_combine(plan, E, e_partials, g_sh, nullptr, (hipStream_t)stream);
+}
 
 // ---- force training on the table (plans with e3k_tp_table2_supported) ------------------------------------------------------
 // With F = <g, TP(x[src], sh, w(T, coef))> (linear in each of g, x, sh, T, coef):

@@ -226,6 +226,7 @@ SIGNATURES = {
     "e3k_tp_plan_destroy": (None, [_P]),
     "e3k_tp_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "e3k_tp_bwd_w": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "e3k_tp_bwd_w_ordered": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "e3k_tp_bwd_x_overwrites": (C.c_int, [_P]),
     "e3k_tp_last_route": (C.c_char_p, []),
     "e3k_gemm_last_routes": (C.c_char_p, []),
@@ -299,6 +300,10 @@ SIGNATURES = {
     # (the ODE sampler: x_out, d_out | x0, d1 first; the time table and the cells in place of t)
     "e3k_sampler_ode_euler": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _I32, _I64, _I32, _I32, _F, _F, _P]),
     "e3k_sampler_ode_heun": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _F, _F, _P]),
+    # (the likelihood: the probe; the quadrature term into the double accumulators; the prior's log-density)
+    "e3k_sampler_probe": (C.c_int, [_P, _P, _I64, _I32, _I32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _I32, _P]),
+    "e3k_sampler_ode_div": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, C.c_double, _F, _F, _P]),
+    "e3k_sampler_prior_logp": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P]),
     "e3k_segment_sum": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 

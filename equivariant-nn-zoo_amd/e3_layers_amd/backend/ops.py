@@ -192,6 +192,16 @@ INPUTS_ONLY = _Mode("INPUTS_ONLY")
 PARAMS_ONLY = _Mode("PARAMS_ONLY")
 
 
+# Inside ``with ops.ordered_edge_gradients():`` the tensor product's backward sums the harmonics' gradient of an edge in a fixed
+# order (``e3k_tp_bwd_w_ordered``) instead of with float atomics: a vector-Jacobian product with respect to positions is then the
+# same bits run to run.  The likelihood (run/likelihood.py) asks for it: its probes' estimates are compared and averaged across runs.
+ORDERED_EDGE_GRADS = _Mode("ORDERED_EDGE_GRADS")
+
+
+def ordered_edge_gradients() -> _Mode:
+    return ORDERED_EDGE_GRADS
+
+
 def inputs_only_backward() -> _Mode:
     """``with ops.inputs_only_backward(): torch.autograd.grad(y, data_tensor, ...)``: gradients of Parameters (and of
     tensors computed from Parameters alone) are skipped inside the e3k backward functions."""
@@ -1433,8 +1443,18 @@ def _tp_bwd_w_raw(x, sh, w, g_out, topo: GraphTopo, plan: TpPlan, want_sh: bool,
     n, e = topo.num_nodes, topo.num_edges
     assert want_w or want_sh
     gw = torch.empty(e, plan.w_numel, device=x.device, dtype=torch.float32) if want_w else None
-    gsh = torch.zeros(e, plan.d_sh, device=x.device, dtype=torch.float32) if want_sh else None
     handle = plan.handle(x.device)
+    if want_sh and ORDERED_EDGE_GRADS:
+        # the harmonics' gradient in a fixed order: per-item slices (zero-filled: a group writes only the degrees it reads) and
+        # an ordered combine, where e3k_tp_bwd_w adds the shares of an edge that several work items visit with float atomics
+        gsh = torch.empty(e, plan.d_sh, device=x.device, dtype=torch.float32)
+        part = torch.zeros(max(int(L.load().e3k_tp_edge_partials_floats(handle, e)), 1), device=x.device, dtype=torch.float32)
+        with timed_launch("tp_bwd_w_sh", (n, e, plan)):
+            L.check(L.load().e3k_tp_bwd_w_ordered(handle, L.ptr(x), L.ptr(sh), L.ptr(w), L.ptr(g_out), L.ptr(topo.src),
+                                                  L.ptr(topo.dst_ptr), L.ptr(topo.dst_perm), n, e, L.ptr(gw), L.ptr(gsh), L.ptr(part),
+                                                  L.stream_ptr()), "e3k_tp_bwd_w_ordered")
+        return gw, gsh
+    gsh = torch.zeros(e, plan.d_sh, device=x.device, dtype=torch.float32) if want_sh else None
     with timed_launch("tp_bwd_w_sh" if want_sh else "tp_bwd_w", (n, e, plan)):
         L.check(L.load().e3k_tp_bwd_w(handle, L.ptr(x), L.ptr(sh), L.ptr(w), L.ptr(g_out), L.ptr(topo.src),
                                       L.ptr(topo.dst_ptr), L.ptr(topo.dst_perm), n, e, L.ptr(gw), L.ptr(gsh),
@@ -2156,6 +2176,70 @@ def sampler_ode_heun(x0, d1, raw2, node_seg, times, cells, n_graphs: int, beta_0
                                           L.ptr(cells), n, dim, int(n_graphs), float(beta_0), float(beta_1), L.stream_ptr()),
             "e3k_sampler_ode_heun")
     return out
+
+
+def graph_row_pointers(counts) -> torch.Tensor:
+    """int32 [G + 1] row pointers of per-graph node counts (contiguous int64 on the device): one ``e3k_counts_to_ptr`` launch"""
+    L.require_cuda(counts)
+    n = counts.reshape(-1)
+    if n.dtype != torch.int64 or not n.is_contiguous():
+        raise ValueError("graph_row_pointers needs contiguous int64 counts")
+    ptr = torch.empty(n.numel() + 1, dtype=torch.int32, device=n.device)
+    L.check(L.load().e3k_counts_to_ptr(L.ptr(n), n.numel(), L.ptr(ptr), L.stream_ptr()), "e3k_counts_to_ptr")
+    return ptr
+
+
+def sampler_probe(node_seg, dim: int, n_graphs: int, seed: int, draw: int, word0: int, kind: int) -> torch.Tensor:
+    """The Hutchinson probe of one diffusion key (``e3k_sampler_probe``): fp32 [N, dim], component c of node i from draw index
+    ``draw``, word ``word0 + c`` of the stream of ``csrc/e3k_draw.h`` -- ``kind`` 0: Rademacher (``data.compute_edge.rademacher_draw``),
+    1: ``normal_draw``; rows outside the ``n_graphs`` real graphs are 0.  One launch."""
+    L.require_cuda(node_seg)
+    if node_seg.dtype != torch.int64 or node_seg.dim() != 1 or not node_seg.is_contiguous():
+        raise ValueError("sampler_probe needs a contiguous int64 node_seg [N]")
+    out = torch.empty(node_seg.numel(), int(dim), device=node_seg.device, dtype=torch.float32)
+    L.check(L.load().e3k_sampler_probe(L.ptr(out), L.ptr(node_seg), node_seg.numel(), int(dim), int(n_graphs), *L.seed_words(seed),
+                                       int(draw) & 0xFFFFFFFF, int(word0), int(kind), L.stream_ptr()), "e3k_sampler_probe")
+    return out
+
+
+def _per_graph_operands(name, acc, x, row_ptr, n_graphs):
+    L.require_cuda(acc, x, row_ptr)
+    x = L.f32c(x.detach())
+    if x.dim() != 2:
+        raise ValueError(f"{name} needs [N, D] operands")
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.numel() < int(n_graphs):
+        raise ValueError(f"{name}: the accumulator must be a contiguous float64 device tensor of at least {int(n_graphs)} entries")
+    if row_ptr.dtype != torch.int32 or not row_ptr.is_contiguous() or row_ptr.numel() < int(n_graphs) + 1 or int(n_graphs) < 0:
+        raise ValueError(f"{name}: row_ptr must be a contiguous int32 device tensor [n_graphs + 1]")
+    return x
+
+
+def sampler_ode_div(acc, probe, vjp, row_ptr, times, cells, n_graphs: int, stage: int, scale: float, beta_0: float, beta_1: float) -> None:
+    """One quadrature term of the likelihood's integral, in place (``e3k_sampler_ode_div``): ``acc[g] += w c(t) scale sum(probe vjp)``
+    over the rows of each of the ``n_graphs`` real graphs; ``acc`` float64 on the device, ``row_ptr`` int32 ``[n_graphs + 1]``, the step
+    ``k = cells[1]`` and its times from the table.  ``stage`` 0: ``w = h``, ``t = t_k``; 1: ``h / 2``, ``t_k``; 2: ``h / 2``,
+    ``t_{k+1}``; ``c(t) = (0.5 beta(t)) / s(t)`` in double.  Outside the table nothing is written.  One launch."""
+    vjp = _per_graph_operands("sampler_ode_div", acc, vjp, row_ptr, n_graphs)
+    L.require_cuda(probe, times, cells)
+    probe = L.f32c(probe.detach())
+    if probe.shape != vjp.shape:
+        raise ValueError(f"sampler_ode_div: probe {tuple(probe.shape)} and vjp {tuple(vjp.shape)} differ in shape")
+    if times.dtype != torch.float32 or not times.is_contiguous() or times.dim() != 1 or times.numel() < 2:
+        raise ValueError("sampler_ode_div: times must be a contiguous fp32 device tensor [n_steps + 1]")
+    if cells.dtype != torch.int64 or cells.numel() < 2 or not cells.is_contiguous():
+        raise ValueError("sampler_ode_div: cells must be a contiguous int64 device tensor [2] = (next step, step in use)")
+    n, dim = vjp.shape
+    L.check(L.load().e3k_sampler_ode_div(L.ptr(acc), L.ptr(probe), L.ptr(vjp), L.ptr(row_ptr), L.ptr(times), times.numel(), L.ptr(cells), n,
+                                         dim, int(n_graphs), int(stage), float(scale), float(beta_0), float(beta_1), L.stream_ptr()),
+            "e3k_sampler_ode_div")
+
+
+def sampler_prior_logp(out, x, row_ptr, n_graphs: int) -> None:
+    """``out[g] += log N(x_g; 0, I)`` over the rows of each real graph, in place (``e3k_sampler_prior_logp``; ``out`` float64)."""
+    x = _per_graph_operands("sampler_prior_logp", out, x, row_ptr, n_graphs)
+    n, dim = x.shape
+    L.check(L.load().e3k_sampler_prior_logp(L.ptr(out), L.ptr(x), L.ptr(row_ptr), n, dim, int(n_graphs), L.stream_ptr()),
+            "e3k_sampler_prior_logp")
 
 
 def segment_sum(x, ptr, seg_index, mean=False):

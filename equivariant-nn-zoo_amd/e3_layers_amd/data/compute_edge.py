@@ -115,6 +115,16 @@ def normal_draw(seed, draw, node, word, dtype=torch.float32) -> Tensor:
     return torch.sqrt(-2.0 * torch.log(u1)) * torch.cos((2.0 * math.pi) * u2)
 
 
+def rademacher_draw(seed, draw, node, word, dtype=torch.float32) -> Tensor:
+    """The counter-based Rademacher draw of the device's stream (``csrc/e3k_draw.h``; ``e3k_sampler_probe`` kind 0) for (seed, draw
+    index, node, word): ``+1`` when bit 31 of ``pair_hash(seed, draw, node, 2 word)`` is clear, ``-1`` when it is set -- bit for bit
+    the kernel's.  The likelihood's Hutchinson probes (``run/likelihood.py``): probe p of component c of a diffusion key draws index
+    ``sde.N + 1 + p``, word ``word0 + c`` (no step and not the prior, index ``sde.N``, uses these indices); the Gaussian probe is
+    ``normal_draw`` at the same index and word.  Arguments as ``pair_hash``'s."""
+    two_w = 2 * (word if torch.is_tensor(word) else int(word))
+    return (1 - 2 * (pair_hash(seed, draw, node, two_w) >> 31)).to(dtype)
+
+
 class PairCriterion:
     """A pair rule both edge builders recognise.  As a callable it is a ``criteria`` callback of ``computeEdgeIndex``
     (``(data, edge_index) -> bool mask`` over the ordered candidate pairs, global node indices); ``computeEdgeIndexCapped`` does not

@@ -282,8 +282,11 @@ def get_ode_sampler(sde: VPSDE, inverse_scaler: Callable = None, method: str = "
         positions after stage A and again after stage B, as that loop does after its corrector and its predictor.  Ghost rows of a
         padded batch never move.
 
+    The log-likelihood of a batch under the same flow -- the divergence of this drift integrated along it, from the data to the prior --
+    is ``run/likelihood.get_likelihood_fn``, which drives these loops and step kernels on the ascending grid.
+
     Out of scope: conditional sampling (there is no ``fixed`` argument: a deterministic replacement rule for the fixed rows is a design
-    question of its own) and likelihood evaluation (the divergence of the drift)."""
+    question of its own)."""
     inverse_scaler = inverse_scaler or (lambda b: b)
     if method not in ("euler", "heun"):
         raise ValueError(f"ODE method {method!r} unknown (euler, heun)")
@@ -385,14 +388,16 @@ def _reset_criteria(model, criteria) -> None:
 
 
 def _run_loop(batch, model, updates, keys, timesteps, steps: int, moved, t_dev, *, graph: bool, edge_capacity, r_max, criteria,
-              header=None, fixed=None):
+              header=None, fixed=None, zero=()):
     """The three loop drivers of the samplers: ``steps`` steps, each the ``updates`` (``batch -> batch``: corrector and predictor, or the
     ODE's stages) in order with ``moved`` after every one -- eager; one captured step replayed (``graph``: the edge set is static);
     ``CappedLoop`` (``graph`` with ``edge_capacity``: cutoff graphs, the list rebuilt inside the captured step, which does ``moved``'s
     work itself).  ``keys``: the tensors the updates move; ``t_dev``: the batch's time tensor.
 
     ``header``: ``(times, cells)`` -- every step begins with ``sampler_begin_step(times, cells, t_dev)`` on the device, and replays
-    are bare.  None: the host copies ``timesteps[i]`` into ``t_dev`` before step i.  -> the batch after the last step."""
+    are bare.  None: the host copies ``timesteps[i]`` into ``t_dev`` before step i.  ``zero``: tensors the updates accumulate into
+    (the likelihood's integral): a replayed loop's warm-up step added to them, so they go back to zero with the cells.
+    -> the batch after the last step."""
     def one_step(b):
         for update in updates:
             b = moved(update(b))
@@ -400,7 +405,7 @@ def _run_loop(batch, model, updates, keys, timesteps, steps: int, moved, t_dev, 
 
     if graph and edge_capacity is not None:
         loop = CappedLoop(batch, model, updates, keys, float(timesteps[0]), int(edge_capacity), float(r_max), criteria, seeded=header,
-                          fixed=fixed)
+                          fixed=fixed, zero=zero)
         loop.rewind()
         loop.run(timesteps, steps)
         return loop.result()
@@ -429,6 +434,8 @@ def _run_loop(batch, model, updates, keys, timesteps, steps: int, moved, t_dev, 
                 state[k].copy_(saved[k])
             if header is not None:
                 header[1].zero_()          # (the warm-up was step 0: the run starts there again)
+            for acc in zero:
+                acc.zero_()
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -499,11 +506,13 @@ class CappedLoop:
     Construction sizes, pads and captures (``t0``: the time of the warm-up step); ``rewind()`` puts the state and the draw index
     back on the start, ``run()`` replays, ``result()`` checks the capacity and unpads (``tools/sample_bench.py`` times ``run`` alone)."""
 
-    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None, seeded=None, fixed=None):
+    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None, seeded=None, fixed=None,
+                 zero=()):
         """``seeded``: ``(times, cells)`` of the seeded sampler -- the captured step then begins with ``e3k_sampler_begin_step``, which
         sets the time from the table and advances the cells, and ``run`` is replays only.  ``fixed``: the name of conditional
         sampling's mask field; padding collates integers as int64, so the padded mask is made uint8 again here, once -- the form the
-        kernels read, and no conversion joins the replayed step."""
+        kernels read, and no conversion joins the replayed step.  ``zero``: the tensors the updates accumulate into; ``rewind()`` zeroes
+        them."""
         dev = batch["_n_nodes"].device
         own = edge_layer_of(model)
         if own is not None:
@@ -550,7 +559,7 @@ class CappedLoop:
             for k in keys:
                 state[k][:n].copy_(work[k][:n])
 
-        self.seeded = seeded
+        self.seeded, self.zero = seeded, tuple(zero)
         self.padded, self.state, self.rng, self.keys, self.n, self.first_edges = padded, state, rng, keys, n, e
         self.t_dev = padded["t"]
         self.saved = {k: v.clone() for k, v in state.items()}
@@ -564,6 +573,8 @@ class CappedLoop:
         self.rng.zero_()
         if self.seeded is not None:
             self.seeded[1].zero_()
+        for acc in self.zero:
+            acc.zero_()
 
     def run(self, timesteps, steps: int) -> None:
         if self.seeded is not None:      # the time comes from the table inside the graph: bare replays

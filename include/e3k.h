@@ -240,6 +240,14 @@ int e3k_tp_fwd(const e3k_tp_plan* plan, const float* x, const float* sh, const f
 int e3k_tp_bwd_w(const e3k_tp_plan* plan, const float* x, const float* sh, const float* w, const float* g_out,
                  const int32_t* src, const int32_t* dst_ptr, const int32_t* dst_perm, int64_t N, int64_t E,
                  float* g_w, float* g_sh, void* stream);
+/* e3k_tp_bwd_w with g_sh (required; needs w) summed in a FIXED order, bit-reproducible run to run: every (node, group) work item
+ * stores its share of an edge's g_sh into its own slice of e_partials [n_gc, E, d_sh], which the CALLER ZERO-FILLS
+ * (e3k_tp_edge_partials_floats(plan, E) floats: a group writes only the degrees it reads), and the slices are added in item order
+ * into g_sh [E,d_sh], which is overwritten.  g_w as above (may be NULL).  The likelihood's vector-Jacobian products use it
+ * (ops.ordered_edge_gradients()). */
+int e3k_tp_bwd_w_ordered(const e3k_tp_plan* plan, const float* x, const float* sh, const float* w, const float* g_out,
+                         const int32_t* src, const int32_t* dst_ptr, const int32_t* dst_perm, int64_t N, int64_t E,
+                         float* g_w, float* g_sh, float* e_partials, void* stream);
 /* g_x [N,d_in]: the CALLER ZERO-FILLS it; plans whose groups are walked by two waves (l_max = 3: more than 24
  * accumulators per group) add their two partial sums with atomics (order independent), the others store.
  * CSR by source (src_ptr, src_perm), dst [E]. */
@@ -958,6 +966,34 @@ int e3k_sampler_ode_euler(float* x_out, float* d_out, const float* x, const floa
 int e3k_sampler_ode_heun(float* x_out, const float* x0, const float* d1, const float* raw2, const int64_t* node_seg,
                          const float* times, int64_t n_times, const int64_t* cells, int64_t N, int32_t D, int32_t G, float beta_0,
                          float beta_1, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The log-likelihood through the probability-flow ODE (csrc/e3k_sampler.hip; run/likelihood.py get_likelihood_fn; Song et al.
+ * 2021, section 4.3 and appendix D.2).  The table ASCENDS (linspace(eps, T, n_steps + 1), hs > 0: data to prior); the two step
+ * kernels above run it unchanged.  Per real graph g
+ *     log p(x_g(eps)) = log N(x_g(T); 0, I) + integral of div f dt,   div f = c(t) tr(d raw / d x),   c(t) = (0.5 beta(t)) / s(t),
+ * the trace by Hutchinson's estimate probe . vjp, vjp = d (probe . raw) / d x from the model's backward.
+ * row_ptr [G + 1] DEVICE int32: the graphs' row pointers (e3k_counts_to_ptr), rows sorted by graph; clamped to [0, N].
+ *
+ * e3k_sampler_probe: one thread per component, out [N, D] fp32.  h_node = the chain of csrc/e3k_draw.h over (seed, draw, i),
+ *   word = word0 + c.  kind 0 (Rademacher): +1 if bit 31 of mix32(h_node ^ (2 word)) is clear, else -1; kind 1: xi(seed, draw, i,
+ *   word).  Ghost rows (segment outside [0, G)): 0.  draw is a value, not a cell: sde.N + 1 + p for probe p.
+ * e3k_sampler_ode_div: one workgroup per real graph, fixed summation order, one writer per acc[g] (DEVICE double [G]):
+ *     S = sum over the graph's rows and components of (double)probe * (double)vjp;   acc[g] = fma((w c(t)) scale, S, acc[g]).
+ *   k = cells[1], t_k = times[k], t_n = times[k + 1], h = (double)t_n - (double)t_k;  stage 0 (Euler): w = h, t = t_k; 1 (Heun A):
+ *   w = h / 2, t = t_k; 2 (Heun B): w = h / 2, t = t_n.  c(t) in double: lm = t (q t + hh) with q = -(beta_1 - beta_0) / 4,
+ *   hh = -beta_0 / 2 from the doubles of the fp32 arguments, s = sqrt(-expm1(2 lm)), beta = t (beta_1 - beta_0) + beta_0.
+ *   k < 0 or k + 1 >= n_times: acc is untouched.  A graph of no rows adds 0.  Several keys: consecutive launches into one acc.
+ * e3k_sampler_prior_logp: the same shape of work: out[g] += -0.5 sum x^2 - (0.5 n_g D) ln(2 pi), double.
+ * Invalid: null pointers, N < 1, N >= 2^31, D outside [1, 1024], G < 0, N D >= 2^38, kind outside {0, 1}, stage outside {0, 1, 2},
+ *   scale <= 0, n_times < 2, beta_0 < 0, beta_1 < beta_0.  G = 0: nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+int e3k_sampler_probe(float* out, const int64_t* node_seg, int64_t N, int32_t D, int32_t G, uint32_t seed_lo, uint32_t seed_hi,
+                      uint32_t draw, uint32_t word0, int32_t kind, void* stream);
+int e3k_sampler_ode_div(double* acc, const float* probe, const float* vjp, const int32_t* row_ptr, const float* times,
+                        int64_t n_times, const int64_t* cells, int64_t N, int32_t D, int32_t G, int32_t stage, double scale,
+                        float beta_0, float beta_1, void* stream);
+int e3k_sampler_prior_logp(double* out, const float* x, const int32_t* row_ptr, int64_t N, int32_t D, int32_t G, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A convolution layer as ONE call (csrc/e3k_layer.hip): FactorizedConvolution + Gate

@@ -38,7 +38,17 @@ under rocprofv3.  What is timed is a STEP; how many steps a trained network need
 
     python tools/sample_bench.py --protein --seed 7 --ode heun --ode-steps 100 --steps 100
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/sample_bench.py --protein --seed 7 --ode heun \
-        --ode-steps 100 --trace-steps 40"""
+        --ode-steps 100 --trace-steps 40
+
+``--likelihood heun|euler --ode-steps K`` (with ``--protein --seed S``) times the replayed step of the log-likelihood
+(``run/likelihood.get_likelihood_fn(graph=True, edge_capacity=...)``: each model call is a forward AND a backward with respect to the
+positions, plus one quadrature launch) beside the ODE sampler's replayed Heun step of the same process, alternating, both from the same
+state so that both walk lists of one size.  The weights are untrained: the value of logp says nothing about a model and is not reported.
+-> profiles/protein_likelihood.json
+
+    python tools/sample_bench.py --protein --seed 7 --likelihood heun --ode-steps 100 --steps 100
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/sample_bench.py --protein --seed 7 \
+        --likelihood heun --ode-steps 100 --trace-steps 40"""
 import argparse, csv, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
@@ -187,6 +197,26 @@ def ode_replay_loop(model, sde, batch, method, n_steps, e_cap):
         return CappedLoop(b, model, updates, ["CA"], float(times[0]), e_cap, None, seeded=(times[:n_steps], cells))
 
 
+def likelihood_replay_loop(model, sde, batch, method, n_steps, e_cap, seed):
+    """The capped loop of get_likelihood_fn(graph=True, edge_capacity=...), built as it builds it: the probes ride in the batch, the
+    table ascends, the accumulators go back to zero with the cells.  -> (loop, acc)"""
+    from e3_layers_amd.backend import ops
+    from e3_layers_amd.run.likelihood import attach_probes, frozen_parameters, stage_updates
+    from e3_layers_amd.run.sde_sampling import CappedLoop
+
+    dev = batch["CA"].device
+    b = batch.clone()
+    b.attrs["t"] = ("graph", "1x0e")
+    attach_probes(sde, b, seed, "rademacher", 1)
+    times = torch.linspace(1e-3, sde.T, n_steps + 1, device=dev, dtype=torch.float32)
+    cells = torch.zeros(2, dtype=torch.int64, device=dev)
+    acc = torch.zeros(len(b), dtype=torch.float64, device=dev)
+    row_ptr = ops.graph_row_pointers(b["_n_nodes"].reshape(-1).contiguous())
+    updates = stage_updates(sde, model, method, times, cells, acc, 1, row_ptr)
+    with torch.no_grad(), frozen_parameters(model):      # (the capture records the backward: what it walks is decided here)
+        return CappedLoop(b, model, updates, ["CA"], float(times[0]), e_cap, None, seeded=(times[:n_steps], cells), zero=(acc,)), acc
+
+
 def conditioned(sde, batch, clean, fraction):
     """``batch`` (at x_T = z) with conditional sampling's fields, as get_pc_sampler(fixed="fixed") sets them up: the middle ``fraction``
     of every chain of every protein is fixed (a contiguous stretch, chosen by the chain's length alone), ``known_CA`` = the clean
@@ -267,14 +297,20 @@ def protein(argv):
     ap.add_argument("--fixed", type=float, default=0.0, help="with --seed: the conditioned replay too, this fraction of every chain fixed")
     ap.add_argument("--ode", choices=("euler", "heun"), default=None, help="with --seed: the ODE sampler's replays beside the seeded "
                     "Euler-Maruyama + Langevin replay; the method --trace-steps replays")
-    ap.add_argument("--ode-steps", type=int, default=None, help="with --ode: the steps of the ODE grid (required)")
+    ap.add_argument("--ode-steps", type=int, default=None, help="with --ode / --likelihood: the steps of the ODE grid (required)")
+    ap.add_argument("--likelihood", choices=("euler", "heun"), default=None, help="with --seed: the likelihood's replays beside the ODE "
+                    "sampler's Heun replays")
     args = ap.parse_args(argv)
+    if args.likelihood is not None and (args.seed is None or args.ode_steps is None or args.fixed or args.ode is not None):
+        raise SystemExit("--likelihood METHOD: with --seed and --ode-steps K, without --fixed and --ode")
     if args.ode is not None and (args.seed is None or args.ode_steps is None or args.fixed):
         raise SystemExit("--ode METHOD: with --seed and --ode-steps K, without --fixed")
     if not 0.0 <= args.fixed < 1.0 or (args.fixed and args.seed is None):
         raise SystemExit("--fixed FRACTION: in [0, 1), with --seed (the conditioned replay is the seeded form's)")
     dev = torch.device("cuda:0")
     model, sde, batch, timesteps, crit, clean = protein_setup(args.proteins, args.residues, dev)
+    if args.likelihood is not None:
+        return protein_likelihood(args, model, sde, batch, timesteps)
     if args.ode is not None:
         return protein_ode(args, model, sde, batch, timesteps)
     if args.seed is not None:
@@ -469,6 +505,75 @@ def protein_ode(args, model, sde, batch, timesteps):
     text = json.dumps(doc, indent=1)
     print(text)
     with open(args.out or os.path.join(ROOT, "profiles", "protein_sampler_ode.json"), "w") as f:
+        f.write(text + "\n")
+
+
+def protein_likelihood(args, model, sde, batch, timesteps):
+    """The likelihood's replayed step and the ODE sampler's replayed Heun step, alternating, each repetition from the same state."""
+    n_timed = args.trace_steps or args.steps
+    if not 1 <= n_timed <= args.ode_steps or args.warmup > args.ode_steps:
+        raise SystemExit(f"--steps / --trace-steps / --warmup: at most --ode-steps = {args.ode_steps} (a replay past the grid stands still)")
+    _, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
+    e_cap = -(-int(1.1 * e_cap) // 1024) * 1024
+    name = f"likelihood_{args.likelihood}_replay"
+    lik, acc = likelihood_replay_loop(model, sde, batch, args.likelihood, args.ode_steps, e_cap, args.seed)
+
+    def replay(which, n):
+        which.rewind()      # (outside the timed region)
+
+        def run():
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                which.run(timesteps, n)
+            return time.perf_counter() - t0
+        return run
+
+    if args.trace_steps:
+        replay(lik, args.trace_steps)()
+        torch.cuda.synchronize()
+        print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
+                          "likelihood": args.likelihood, "ode_steps": args.ode_steps}))
+        return
+    loops = {name: lik, "ode_heun_replay": ode_replay_loop(model, sde, batch, "heun", args.ode_steps, e_cap)}
+    for loop in loops.values():
+        replay(loop, args.warmup)()
+    rows = {k: [] for k in loops}
+    host = {k: [] for k in loops}
+    edges = {k: [] for k in loops}
+    for _ in range(args.reps):
+        for k, loop in loops.items():
+            ms, busy = timed(replay(loop, args.steps))
+            edges[k].append(int(loop.bucket.state[0]))
+            loop.result()
+            rows[k].append(ms / args.steps)
+            host[k].append(1e3 * busy / args.steps)
+    finite = bool(torch.isfinite(acc).all()) and bool((acc != 0).all())
+
+    def mmm(v):
+        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
+
+    calls = 2 if args.likelihood == "heun" else 1
+    doc = {"workload": f"log-likelihood through the probability-flow ODE ({args.likelihood}; grid of {args.ode_steps} steps, one Rademacher "
+                       "probe) beside the ODE sampler's Heun step on config_diffusion_CA as shipped, built with pair_criterion(); "
+                       "synth_protein; capped replays, every repetition from the same state (the ODE loop's x_T, so that both loops "
+                       "walk lists of one size)",
+           "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
+           "ode_steps": args.ode_steps, "nodes": int(batch["CA"].shape[0]), "e_cap": e_cap, "steps": args.steps, "reps": args.reps,
+           "model_calls_per_step": {name: f"{calls} (each a forward and one backward with respect to the positions)", "ode_heun_replay": 2},
+           "logp": "not reported: untrained weights, the value says nothing about a model; the closed forms of "
+                   "tests/test_likelihood_host.py pin that the number is a log-density",
+           "delta_logp_finite_and_nonzero": finite}
+    for k, loop in loops.items():
+        doc[f"{k}_ms_per_step"] = mmm(rows[k])
+        doc[f"{k}_host_busy_ms_per_step"] = mmm(host[k])
+        doc[f"{k}_edges_last_list"] = edges[k]
+        doc[f"{k}_recaptures"] = loop.step.recaptures
+    ode = statistics.median(rows["ode_heun_replay"])
+    doc["likelihood_step_over_ode_heun_step_median"] = round(statistics.median(rows[name]) / ode, 4)
+    doc["likelihood_model_call_over_ode_model_call_median"] = round((statistics.median(rows[name]) / calls) / (ode / 2), 4)
+    text = json.dumps(doc, indent=1)
+    print(text)
+    with open(args.out or os.path.join(ROOT, "profiles", "protein_likelihood.json"), "w") as f:
         f.write(text + "\n")
 
 
