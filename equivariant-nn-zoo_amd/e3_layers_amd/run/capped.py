@@ -1,4 +1,4 @@
-"""What the clients of the capped neighbour list share (``run/md.ReplayedForceField``, ``run/sde_sampling.CappedLoop``,
+"""What the clients of the capped neighbour list share (``run/md.ReplayedForceField``, ``run/loops.CappedLoop``,
 ``run/score_step.ReplayedScoreStep``; DESIGN.md section 4, "Capped neighbour list"): the names of the keys a rebuilt list touches,
 the model's own ``edge_index`` layer read once, and the padded batch that carries the capped builder's device cells."""
 from __future__ import annotations

@@ -18,8 +18,8 @@ whole run (draw index ``sde.N + 1 + p`` of the stream of ``csrc/e3k_draw.h``), `
 
 Device tensors: the step kernels ``e3k_sampler_ode_euler`` / ``e3k_sampler_ode_heun`` unchanged on the ascending table, and three
 kernels of ``csrc/e3k_sampler.hip`` -- ``e3k_sampler_probe``, ``e3k_sampler_ode_div`` (the quadrature term into double accumulators, one
-launch per key, probe and model call) and ``e3k_sampler_prior_logp``; the loops are the samplers' (``run/sde_sampling._run_loop``: eager,
-the static-edge graph, the capped replay).  The model's backward runs under ``ops.inputs_only_backward()``: with the harmonics
+launch per key, probe and model call) and ``e3k_sampler_prior_logp``; the loops are the samplers' (``run/loops``: eager, the
+static-edge graph, the capped replay), on the plan ``likelihood_plan`` sets up.  The model's backward runs under ``ops.inputs_only_backward()``: with the harmonics
 requiring grad a layer takes the force block where its structure is served and the composed per-op path otherwise (the score nets:
 un-keyed attributes, composite edge embeddings), inside ``ops.ordered_edge_gradients()``: the harmonics' gradient of an edge is summed
 in a fixed order, so a vector-Jacobian product is the same bits run to run (probes' estimates are compared and averaged across runs).
@@ -37,7 +37,7 @@ from typing import Callable, Optional, Sequence
 
 import torch
 
-from .sde_sampling import _check_loop_args, _edge_plumbing, _reset_criteria, _run_loop, _static_topology
+from .loops import StepPlan, check_loop_args, edge_plumbing, make_loop, static_topology
 from .sde_utils import VPSDE, _real_graphs, _step_in_use, draw_words, ode_euler_step, ode_heun_finish
 
 _PROBES = {"rademacher": 0, "gaussian": 1}
@@ -217,7 +217,7 @@ def attach_probes(sde: VPSDE, batch, seed: int, kind: str, n_probes: int) -> Non
 
 
 def stage_updates(sde: VPSDE, model, method: str, times, cells, acc, n_probes: int, row_ptr=None):
-    """The updates of one step for ``_run_loop`` / ``CappedLoop``: ``div_stage`` (the model call, its backwards, the quadrature term
+    """The updates of one step of the likelihood's plan: ``div_stage`` (the model call, its backwards, the quadrature term
     into ``acc``) in front of the sampler's own step function, which takes the model's output from it."""
     def first_stage(b, keep=None):
         done = div_stage(sde, model, b, acc, times, cells, 0 if keep is None else 1, n_probes, row_ptr)
@@ -232,6 +232,33 @@ def stage_updates(sde: VPSDE, model, method: str, times, cells, acc, n_probes: i
         return ode_heun_finish(sde, _Computed(done), b, kept=kept, times=times, cells_or_step=cells)
 
     return [lambda b: first_stage(b, kept), second_stage]
+
+
+def likelihood_plan(sde: VPSDE, method: str, model, batch, *, n_steps: int, eps: float = 1e-3, probe: str = "rademacher",
+                    n_probes: int = 1, seed: int, preprocess: Sequence[Callable] = (), static_edges: bool = False):
+    """The set-up of one likelihood run, with ``get_likelihood_fn``'s settings (which has checked them): the working copy of ``batch``
+    with the probes attached, the ascending grid of ``n_steps + 1`` times and its cells, ``stage_updates`` as the updates, and the
+    accumulator of the integral as loop state (``StepPlan.zero``).
+    -> (``StepPlan``, ``acc`` float64 [G_real], ``row_ptr``: the graphs' row pointers on the device, else None)"""
+    batch = batch.clone()
+    dev = batch["_n_nodes"].device
+    on_device = dev.type == "cuda"
+    batch.attrs["t"] = ("graph", "1x0e")
+    attach_probes(sde, batch, seed, probe, n_probes)
+    times = torch.linspace(eps, sde.T, n_steps + 1, device=dev, dtype=torch.float32 if on_device else None)
+    batch["t"] = torch.empty(len(batch), 1, device=dev, dtype=times.dtype)
+    if static_edges:
+        static_topology(batch, edge_plumbing(preprocess, static_edges)[0])
+    cells = torch.zeros(2, dtype=torch.int64, device=dev)
+    acc = torch.zeros(_real_graphs(batch), dtype=torch.float64, device=dev)
+    row_ptr = None
+    if on_device:
+        from ..backend import ops
+
+        # the real graphs come first in a padded batch too: one table serves every loop
+        row_ptr = ops.graph_row_pointers(batch["_n_nodes"].reshape(-1).contiguous())
+    updates = stage_updates(sde, model, method, times, cells, acc, n_probes, row_ptr)
+    return StepPlan(batch, updates, list(sde.irreps), times[:n_steps], cells, zero=(acc,)), acc, row_ptr
 
 
 def get_likelihood_fn(sde: VPSDE, method: str = "heun", *, n_steps: int, eps: float = 1e-3, probe: str = "rademacher", n_probes: int = 1,
@@ -268,7 +295,7 @@ def get_likelihood_fn(sde: VPSDE, method: str = "heun", *, n_steps: int, eps: fl
     if not 0 <= int(seed) < 1 << 64:
         raise ValueError("seed: at most 64 bits")
     n_steps, n_probes, seed = int(n_steps), int(n_probes), int(seed)
-    _check_loop_args(graph, static_edges, edge_capacity, r_max, criteria)
+    check_loop_args(graph, static_edges, edge_capacity, r_max, criteria)
     keys = list(sde.irreps)
     if scale is None:
         ln_scale = 0.0
@@ -277,35 +304,19 @@ def get_likelihood_fn(sde: VPSDE, method: str = "heun", *, n_steps: int, eps: fl
         if set(per_key) != set(keys) or not all(float(v) > 0.0 for v in per_key.values()):
             raise ValueError(f"scale: one positive number per diffusion key {keys} (got {scale!r})")
         ln_scale = sum(dim * math.log(float(per_key[key])) for key, dim in sde.irreps.items())
-    rebuild_edges, moved = _edge_plumbing(preprocess, static_edges)
+    _, moved = edge_plumbing(preprocess, static_edges)
     d_total = sum(int(d) for d in sde.irreps.values())
 
     def likelihood_fn(model, batch):
         names = set(batch.data)
-        batch = batch.clone()
-        dev = batch["_n_nodes"].device
-        on_device = dev.type == "cuda"
-        batch.attrs["t"] = ("graph", "1x0e")
-        n_all, n_graphs = len(batch), _real_graphs(batch)      # (a batch the caller padded: its ghost graph has no entry)
-        attach_probes(sde, batch, seed, probe, n_probes)
-        times = torch.linspace(eps, sde.T, n_steps + 1, device=dev, dtype=torch.float32 if on_device else None)
-        batch["t"] = torch.empty(n_all, 1, device=dev, dtype=times.dtype)
-        if static_edges:
-            _static_topology(batch, rebuild_edges)
-        _reset_criteria(model, criteria)
-        cells = torch.zeros(2, dtype=torch.int64, device=dev)
-        acc = torch.zeros(n_graphs, dtype=torch.float64, device=dev)
-        row_ptr = None
-        if on_device:
-            from ..backend import ops
-
-            # the real graphs come first in a padded batch too: one table serves every loop
-            row_ptr = ops.graph_row_pointers(batch["_n_nodes"].reshape(-1).contiguous())
-
-        updates = stage_updates(sde, model, method, times, cells, acc, n_probes, row_ptr)
+        n_graphs = _real_graphs(batch)      # (a batch the caller padded: its ghost graph has no entry)
+        plan, acc, row_ptr = likelihood_plan(sde, method, model, batch, n_steps=n_steps, eps=eps, probe=probe, n_probes=n_probes,
+                                             seed=seed, preprocess=preprocess, static_edges=static_edges)
         with torch.no_grad(), frozen_parameters(model):
-            latent = _run_loop(batch, model, updates, keys, times, n_steps, moved, batch["t"], graph=graph, edge_capacity=edge_capacity,
-                               r_max=r_max, criteria=criteria, header=(times[:n_steps], cells), zero=(acc,))
+            loop = make_loop(plan, model, moved, graph=graph, edge_capacity=edge_capacity, r_max=r_max, criteria=criteria)
+            loop.rewind()
+            loop.run(n_steps)
+            latent = loop.result()
         for name in [name for name in latent.data if name.startswith("probe") and name not in names]:
             latent.pop(name)
         prior = prior_logp(sde, latent, row_ptr)
@@ -313,7 +324,7 @@ def get_likelihood_fn(sde: VPSDE, method: str = "heun", *, n_steps: int, eps: fl
         counts = latent["_n_nodes"].reshape(-1)[:n_graphs].to(torch.int64)
         dims = counts * d_total
         logp = prior + delta - counts.double() * ln_scale
-        info = {"nfe": n_steps * len(updates), "prior_logp": prior, "delta_logp": delta, "dims": dims}
+        info = {"nfe": n_steps * len(plan.updates), "prior_logp": prior, "delta_logp": delta, "dims": dims}
         return logp, latent, info
 
     return likelihood_fn

@@ -34,7 +34,13 @@ themselves when the run ends.  Seeded, the replacement is a branch of the update
 
 ``get_ode_sampler(method="heun" | "euler", n_steps=K)`` integrates the probability-flow ODE of the same SDE on a fixed grid of K steps
 instead (the ``"ode"`` method the reference's ``get_sampling_fn`` dispatches to and never defines, :247-286): no noise after the prior,
-one launch per key and stage around each model call, the same three loops -- ``_run_loop`` drives them for both samplers.
+one launch per key and stage around each model call, the same three loops.
+
+A sampler is four stages.  ``pc_plan`` / ``ode_plan`` set a run up as a ``run/loops.StepPlan`` (the working copy of the batch with the
+prior drawn, the updates of one step, the table of times and the cells every step's first launch walks); ``run/loops.make_loop`` picks the driver
+(``EagerLoop``, ``StaticLoop``, ``CappedLoop``: ``rewind()``, ``run(steps)``, ``result()``); the loop runs; the sampler releases the
+fixed rows and applies ``inverse_scaler``.  The plans are callable on their own: ``tools/sample_bench.py`` times the loops of the
+plans the samplers build.
 """
 from __future__ import annotations
 
@@ -43,12 +49,9 @@ from typing import Callable, Dict, Optional, Sequence
 
 import torch
 
-from ..backend.graph import TOPO_KEYS, EdgeCapacityExceeded
-from ..data.compute_edge import PairCriterion, computeEdgeIndex, computeEdgeIndexCapped
-from .capped import EDGE_KEYS, CappedBucket, builder_cells, edge_layer_of, replayable_criterion
-from .graph_step import CapturedStep
+from .loops import StepPlan, check_loop_args, edge_plumbing, make_loop, static_topology
 from .sde_utils import (VPSDE, _node_t, _randn, fixed_rows, get_score_fn, langevin_step_counter, ode_euler_step, ode_heun_finish,
-                        prior_sampling, prior_sampling_counter, replace_fixed, reverse_step, reverse_step_counter, sampler_begin_step)
+                        prior_sampling, prior_sampling_counter, replace_fixed, reverse_step, reverse_step_counter)
 
 class _Registry(dict):
     """name -> class table with a decorator: ``@table.register(name="langevin")`` (bare ``@table.register`` uses the
@@ -132,7 +135,60 @@ class NoneCorrector(Corrector):
         return batch
 
 
-SAMPLER_EDGE_KEYS = EDGE_KEYS + TOPO_KEYS      # what the loop drops after every update: the list and the CSR topology built on it
+def pc_plan(sde: VPSDE, predictor, corrector, model, batch, generator=None, noise_fn=None, *, snr: float = 0.16, n_steps: int = 1,
+            eps: float = 1e-3, preprocess: Sequence[Callable] = (), static_edges: bool = False, seed: Optional[int] = None,
+            fixed: Optional[str] = None):
+    """The set-up of one predictor-corrector run, with ``get_pc_sampler``'s settings (which has checked them; ``predictor`` and
+    ``corrector`` are classes): the working copy of ``batch`` with conditional sampling's fields and the prior in it, the table of
+    ``sde.N`` times and its cells, and [corrector, predictor] as ``batch -> batch`` updates.
+    -> (``StepPlan``, what the caller held under conditional sampling's names -- for ``_release``; None without ``fixed``)"""
+    seeded = seed is not None
+    if seeded and (generator is not None or noise_fn is not None):
+        raise ValueError("seed: the noise is counter-based; generator and noise_fn have nothing to feed")
+    batch = batch.clone()
+    dev = batch["_n_nodes"].device
+    batch.attrs["t"] = ("graph", "1x0e")
+    given = None if fixed is None else _condition(sde, batch, fixed)
+    if seeded:
+        batch = prior_sampling_counter(sde, batch, seed, fixed=fixed)
+    else:
+        batch = prior_sampling(sde, batch, generator, noise_fn)
+        if fixed is not None:      # m(T) x0 + s(T) z with the prior's own z
+            lm = sde.log_mean_coeff(torch.tensor(float(sde.T)))
+            m, s = torch.exp(lm), torch.sqrt(1.0 - torch.exp(2.0 * lm))
+            rows = fixed_rows(batch, fixed)
+            for key in sde.irreps:
+                z = batch[key]
+                batch[key] = torch.where(rows, m * batch[f"known_{key}"].to(z.dtype) + s * z, z)
+    sde.alphas = sde.alphas.to(dev)      # resident before any capture (no pageable host copy inside a graph)
+    # fp32 on the device (what the step's first launch reads); torch's default dtype on the host, where float64 is the tests' reference
+    times = torch.linspace(sde.T, eps, sde.N, device=dev, dtype=torch.float32 if dev.type == "cuda" else None)
+    score_fn = get_score_fn(sde, model, train=False)
+    pred, corr = predictor(sde, score_fn), corrector(sde, score_fn, snr, n_steps)
+    batch["t"] = torch.empty(len(batch), 1, device=dev, dtype=times.dtype)
+    if static_edges:
+        static_topology(batch, edge_plumbing(preprocess, static_edges)[0])
+    keys = list(sde.irreps)
+    # the step's time and number: device cells (next step, step in use) that the step's first launch advances
+    cells = torch.zeros(2, dtype=torch.int64, device=dev)
+    if seeded:
+        same = lambda b: b      # noqa: E731  (the None classes)
+        corr_fn = (partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=snr, fixed=fixed)
+                   if corrector is LangevinCorrector else same)
+        pred_fn = partial(reverse_step_counter, sde, model, seed=seed, draw=cells, fixed=fixed) if predictor is EulerMaruyamaPredictor else same
+    else:
+        corr_fn = lambda b: corr.update_fn(b, generator, noise_fn)      # noqa: E731
+        pred_fn = lambda b: pred.update_fn(b, generator, noise_fn)      # noqa: E731
+        if fixed is not None:      # the replacement follows every update that is one (a None class draws nothing)
+            def replaced(update):
+                def fn(b):
+                    b = update(b)
+                    return replace_fixed(sde, b, fixed, {k: b[f"known_{k}"] for k in keys}, generator, noise_fn)
+                return fn
+
+            corr_fn = corr_fn if corrector is NoneCorrector else replaced(corr_fn)
+            pred_fn = pred_fn if predictor is NonePredictor else replaced(pred_fn)
+    return StepPlan(batch, [corr_fn, pred_fn], keys, times, cells, fixed=fixed), given
 
 
 def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = None, snr: float = 0.16,
@@ -182,10 +238,9 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
     inverse_scaler = inverse_scaler or (lambda b: b)
     predictor = predictor or NonePredictor
     corrector = corrector or NoneCorrector
-    _check_loop_args(graph, static_edges, edge_capacity, r_max, criteria,
-                     norms_served=corrector is NoneCorrector or (seed is not None and corrector is LangevinCorrector))
-    seeded = seed is not None
-    if seeded:
+    check_loop_args(graph, static_edges, edge_capacity, r_max, criteria,
+                    norms_served=corrector is NoneCorrector or (seed is not None and corrector is LangevinCorrector))
+    if seed is not None:
         if not 0 <= int(seed) < 1 << 64:
             raise ValueError("seed: at most 64 bits")
         if predictor not in (EulerMaruyamaPredictor, NonePredictor) or corrector not in (LangevinCorrector, NoneCorrector):
@@ -195,68 +250,51 @@ def get_pc_sampler(sde: VPSDE, predictor, corrector, inverse_scaler: Callable = 
             raise ValueError("seed: the draw layout holds one corrector draw per reverse step, and the capped loop would rebuild the "
                              "list between inner corrector steps where the eager loop does not: n_steps must be 1")
 
-    rebuild_edges, moved = _edge_plumbing(preprocess, static_edges)
+    _, moved = edge_plumbing(preprocess, static_edges)
     steps = sde.N if n_iter is None else min(int(n_iter), sde.N)
 
     def pc_sampler(model, batch, generator=None, noise_fn=None):
-        if seeded and (generator is not None or noise_fn is not None):
-            raise ValueError("seed: the noise is counter-based; generator and noise_fn have nothing to feed")
-        batch = batch.clone()
-        dev = batch["_n_nodes"].device
-        batch.attrs["t"] = ("graph", "1x0e")
-        given = None if fixed is None else _condition(sde, batch, fixed)
-        if seeded:
-            batch = prior_sampling_counter(sde, batch, seed, fixed=fixed)
-        else:
-            batch = prior_sampling(sde, batch, generator, noise_fn)
-            if fixed is not None:      # m(T) x0 + s(T) z with the prior's own z
-                lm = sde.log_mean_coeff(torch.tensor(float(sde.T)))
-                m, s = torch.exp(lm), torch.sqrt(1.0 - torch.exp(2.0 * lm))
-                rows = fixed_rows(batch, fixed)
-                for key in sde.irreps:
-                    z = batch[key]
-                    batch[key] = torch.where(rows, m * batch[f"known_{key}"].to(z.dtype) + s * z, z)
-        sde.alphas = sde.alphas.to(dev)      # resident before any capture (no pageable host copy inside a graph)
-        timesteps = torch.linspace(sde.T, eps, sde.N, device=dev)
-        score_fn = get_score_fn(sde, model, train=False)
-        pred, corr = predictor(sde, score_fn), corrector(sde, score_fn, snr, n_steps)
-        batch["t"] = torch.empty(len(batch), 1, device=dev)
-        if static_edges:
-            _static_topology(batch, rebuild_edges)
-        t_dev = batch["t"]
-        keys = list(sde.irreps)
-        _reset_criteria(model, criteria)
-
-        if seeded:
-            # the step's time and number: device cells (next step, step in use) that the step's first launch advances
-            cells = torch.zeros(2, dtype=torch.int64, device=dev)
-            times = timesteps.contiguous()
-            same = lambda b: b      # noqa: E731  (the None classes)
-            corr_fn = (partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=snr, fixed=fixed)
-                       if corrector is LangevinCorrector else same)
-            pred_fn = partial(reverse_step_counter, sde, model, seed=seed, draw=cells, fixed=fixed) if predictor is EulerMaruyamaPredictor else same
-        else:
-            corr_fn = lambda b: corr.update_fn(b, generator, noise_fn)      # noqa: E731
-            pred_fn = lambda b: pred.update_fn(b, generator, noise_fn)      # noqa: E731
-            if fixed is not None:      # the replacement follows every update that is one (a None class draws nothing)
-                def replaced(update):
-                    def fn(b):
-                        b = update(b)
-                        return replace_fixed(sde, b, fixed, {k: b[f"known_{k}"] for k in keys}, generator, noise_fn)
-                    return fn
-
-                corr_fn = corr_fn if corrector is NoneCorrector else replaced(corr_fn)
-                pred_fn = pred_fn if predictor is NonePredictor else replaced(pred_fn)
-
+        plan, given = pc_plan(sde, predictor, corrector, model, batch, generator, noise_fn, snr=snr, n_steps=n_steps, eps=eps,
+                              preprocess=preprocess, static_edges=static_edges, seed=seed, fixed=fixed)
         with torch.no_grad():
-            batch = _run_loop(batch, model, [corr_fn, pred_fn], keys, timesteps, steps, moved, t_dev, graph=graph,
-                              edge_capacity=edge_capacity, r_max=r_max, criteria=criteria, header=(times, cells) if seeded else None,
-                              fixed=fixed)
+            loop = make_loop(plan, model, moved, graph=graph, edge_capacity=edge_capacity, r_max=r_max, criteria=criteria)
+            loop.rewind()
+            loop.run(steps)
+            batch = loop.result()
         if fixed is not None:
             batch = _release(sde, batch, fixed, given)
         return inverse_scaler(batch), steps * (n_steps + 1)
 
     return pc_sampler
+
+
+def ode_plan(sde: VPSDE, method: str, model, batch, generator=None, noise_fn=None, *, n_steps: int, eps: float = 1e-3,
+             preprocess: Sequence[Callable] = (), static_edges: bool = False, seed: Optional[int] = None) -> StepPlan:
+    """The set-up of one run of the probability-flow ODE, with ``get_ode_sampler``'s settings (which has checked them): the working
+    copy of ``batch`` with the prior in it, the grid of ``n_steps + 1`` times and its cells, and the method's stages as updates."""
+    if seed is not None and (generator is not None or noise_fn is not None):
+        raise ValueError("seed: the prior is counter-based; generator and noise_fn have nothing to feed")
+    batch = batch.clone()
+    dev = batch["_n_nodes"].device
+    batch.attrs["t"] = ("graph", "1x0e")
+    if seed is not None:
+        batch = prior_sampling_counter(sde, batch, seed)
+    else:
+        batch = prior_sampling(sde, batch, generator, noise_fn)
+    # fp32 on the device (what the kernels read); torch's default dtype on the host, where float64 is the tests' reference
+    times = torch.linspace(sde.T, eps, n_steps + 1, device=dev, dtype=torch.float32 if dev.type == "cuda" else None)
+    batch["t"] = torch.empty(len(batch), 1, device=dev, dtype=times.dtype)
+    if static_edges:
+        static_topology(batch, edge_plumbing(preprocess, static_edges)[0])
+    cells = torch.zeros(2, dtype=torch.int64, device=dev)
+    if method == "euler":
+        updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells)]
+    else:
+        kept = {}      # stage A's (x, d1) per key: made and used inside one step (one captured step on the replays)
+        updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells, keep=kept),
+                   partial(ode_heun_finish, sde, model, kept=kept, times=times, cells_or_step=cells)]
+    # the loop walks the first n_steps entries: step k reads t_k and t_{k+1} from the whole grid
+    return StepPlan(batch, updates, list(sde.irreps), times[:n_steps], cells)
 
 
 def get_ode_sampler(sde: VPSDE, inverse_scaler: Callable = None, method: str = "heun", *, n_steps: int, eps: float = 1e-3,
@@ -293,170 +331,23 @@ def get_ode_sampler(sde: VPSDE, inverse_scaler: Callable = None, method: str = "
     if int(n_steps) < 1:
         raise ValueError(f"n_steps: at least one step (got {n_steps})")
     n_steps = int(n_steps)
-    _check_loop_args(graph, static_edges, edge_capacity, r_max, criteria)
+    check_loop_args(graph, static_edges, edge_capacity, r_max, criteria)
     if seed is not None and not 0 <= int(seed) < 1 << 64:
         raise ValueError("seed: at most 64 bits")
-    rebuild_edges, moved = _edge_plumbing(preprocess, static_edges)
+    _, moved = edge_plumbing(preprocess, static_edges)
     steps = n_steps if n_iter is None else min(int(n_iter), n_steps)
 
     def ode_sampler(model, batch, generator=None, noise_fn=None):
-        if seed is not None and (generator is not None or noise_fn is not None):
-            raise ValueError("seed: the prior is counter-based; generator and noise_fn have nothing to feed")
-        batch = batch.clone()
-        dev = batch["_n_nodes"].device
-        batch.attrs["t"] = ("graph", "1x0e")
-        if seed is not None:
-            batch = prior_sampling_counter(sde, batch, seed)
-        else:
-            batch = prior_sampling(sde, batch, generator, noise_fn)
-        # fp32 on the device (what the kernels read); torch's default dtype on the host, where float64 is the tests' reference
-        times = torch.linspace(sde.T, eps, n_steps + 1, device=dev, dtype=torch.float32 if dev.type == "cuda" else None)
-        batch["t"] = torch.empty(len(batch), 1, device=dev, dtype=times.dtype)
-        if static_edges:
-            _static_topology(batch, rebuild_edges)
-        _reset_criteria(model, criteria)
-        cells = torch.zeros(2, dtype=torch.int64, device=dev)
-        if method == "euler":
-            updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells)]
-        else:
-            kept = {}      # stage A's (x, d1) per key: made and used inside one step (one captured step on the replays)
-            updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells, keep=kept),
-                       partial(ode_heun_finish, sde, model, kept=kept, times=times, cells_or_step=cells)]
+        plan = ode_plan(sde, method, model, batch, generator, noise_fn, n_steps=n_steps, eps=eps, preprocess=preprocess,
+                        static_edges=static_edges, seed=seed)
         with torch.no_grad():
-            # the step header walks the first n_steps entries: a run replayed past its schedule stands still
-            batch = _run_loop(batch, model, updates, list(sde.irreps), times, steps, moved, batch["t"], graph=graph,
-                              edge_capacity=edge_capacity, r_max=r_max, criteria=criteria, header=(times[:n_steps], cells))
-        return inverse_scaler(batch), steps * len(updates)
+            loop = make_loop(plan, model, moved, graph=graph, edge_capacity=edge_capacity, r_max=r_max, criteria=criteria)
+            loop.rewind()
+            loop.run(steps)
+            batch = loop.result()
+        return inverse_scaler(batch), steps * len(plan.updates)
 
     return ode_sampler
-
-
-def _check_loop_args(graph, static_edges, edge_capacity, r_max, criteria, norms_served: bool = True) -> None:
-    """The refusals every sampler shares for the arguments that choose the loop.  ``norms_served``: whether the updates' batch-wide
-    reductions (the corrector's norms), if any, skip the ghost graph's rows."""
-    if graph and not static_edges and edge_capacity is None:
-        raise ValueError("graph capture needs static_edges=True (a changing edge count changes every launch)")
-    if edge_capacity is not None:
-        if not graph or static_edges:
-            raise ValueError("edge_capacity belongs to graph=True on cutoff graphs (static_edges=False)")
-        if not norms_served:
-            raise ValueError("edge_capacity: the ghost graph's nodes would enter the corrector's batch-wide norms; only NoneCorrector is served")
-        if r_max is None:
-            raise ValueError("edge_capacity needs the cutoff of the neighbour list: pass r_max")
-        if criteria is not None and not isinstance(criteria, PairCriterion):
-            raise ValueError("edge_capacity: criteria must be a data.PairCriterion (the capped builder evaluates it in its kernels)")
-
-
-def _edge_plumbing(preprocess, static_edges: bool):
-    """-> (rebuild_edges, moved): what the loops do to a batch's neighbour list, with the dataset's ``preprocess`` functions"""
-    def rebuild_edges(batch):
-        for k in SAMPLER_EDGE_KEYS:
-            batch.pop(k)
-        for fn in preprocess:
-            new, attrs = fn(batch.data, batch.attrs)
-            batch.attrs.update(attrs)
-            batch.update(new)
-        return batch
-
-    def moved(b):
-        # positions changed: the geometry cached in the batch by the model's first layer is stale
-        # (the reference pops edge_index / edge_vector here, :236-241)
-        if static_edges:
-            b.pop("edge_vector")
-            b.pop("edge_length")
-            return b
-        return rebuild_edges(b)
-
-    return rebuild_edges, moved
-
-
-def _static_topology(batch, rebuild_edges) -> None:
-    """(``static_edges``: the list and the CSR topology on it are built once, before the loop)"""
-    from ..backend.graph import build_topology
-
-    if "edge_index" not in batch:
-        rebuild_edges(batch)
-    if "_e3k_dst_ptr" not in batch and batch["edge_index"].is_cuda:
-        batch.update(build_topology(batch["edge_index"], batch.n_nodes).as_dict())
-
-
-def _reset_criteria(model, criteria) -> None:
-    own = edge_layer_of(model)
-    for crit in (criteria, own and own.criterion):
-        if isinstance(crit, PairCriterion):
-            crit.reset()      # build k of this run draws with index k
-
-
-def _run_loop(batch, model, updates, keys, timesteps, steps: int, moved, t_dev, *, graph: bool, edge_capacity, r_max, criteria,
-              header=None, fixed=None, zero=()):
-    """The three loop drivers of the samplers: ``steps`` steps, each the ``updates`` (``batch -> batch``: corrector and predictor, or the
-    ODE's stages) in order with ``moved`` after every one -- eager; one captured step replayed (``graph``: the edge set is static);
-    ``CappedLoop`` (``graph`` with ``edge_capacity``: cutoff graphs, the list rebuilt inside the captured step, which does ``moved``'s
-    work itself).  ``keys``: the tensors the updates move; ``t_dev``: the batch's time tensor.
-
-    ``header``: ``(times, cells)`` -- every step begins with ``sampler_begin_step(times, cells, t_dev)`` on the device, and replays
-    are bare.  None: the host copies ``timesteps[i]`` into ``t_dev`` before step i.  ``zero``: tensors the updates accumulate into
-    (the likelihood's integral): a replayed loop's warm-up step added to them, so they go back to zero with the cells.
-    -> the batch after the last step."""
-    def one_step(b):
-        for update in updates:
-            b = moved(update(b))
-        return b
-
-    if graph and edge_capacity is not None:
-        loop = CappedLoop(batch, model, updates, keys, float(timesteps[0]), int(edge_capacity), float(r_max), criteria, seeded=header,
-                          fixed=fixed, zero=zero)
-        loop.rewind()
-        loop.run(timesteps, steps)
-        return loop.result()
-    if graph:
-        # static buffers: the diffused tensors and t; the step writes its result back into them
-        state = {k: batch[k].clone() for k in keys}
-
-        def captured():
-            work = batch.clone()           # model layers add keys: work on a copy, keep `batch` pristine
-            for k in keys:
-                work[k] = state[k]
-            work["t"] = t_dev
-            if header is not None:
-                sampler_begin_step(header[0], header[1], t_dev)
-            work = one_step(work)
-            for k in keys:
-                state[k].copy_(work[k])
-
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            saved = {k: v.clone() for k, v in state.items()}
-            t_dev.fill_(float(timesteps[0]))
-            captured()                     # warm-up (allocations, plan creation) outside the capture
-            for k in keys:
-                state[k].copy_(saved[k])
-            if header is not None:
-                header[1].zero_()          # (the warm-up was step 0: the run starts there again)
-            for acc in zero:
-                acc.zero_()
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            captured()
-        for k in keys:                     # the capture pass itself does not execute; restore anyway
-            state[k].copy_(saved[k])
-        for i in range(steps):
-            if header is None:
-                t_dev.copy_(timesteps[i].expand_as(t_dev))
-            g.replay()
-        for k in keys:
-            batch[k] = state[k]
-        return batch
-    for i in range(steps):
-        if header is not None:
-            sampler_begin_step(header[0], header[1], t_dev)
-        else:
-            t_dev.copy_(timesteps[i].expand_as(t_dev))
-        batch["t"] = t_dev
-        batch = one_step(batch)
-    return batch
 
 
 def _condition(sde: VPSDE, batch, fixed: str):
@@ -495,103 +386,6 @@ def _release(sde: VPSDE, batch, fixed: str, given):
             batch.attrs[name] = attrs
         batch[name] = value
     return batch
-
-
-class CappedLoop:
-    """The reverse steps as replays of ONE graph on cutoff graphs: the batch padded to ``e_cap`` edges, the neighbour list rebuilt
-    inside the graph -- by the loop after every update in ``updates`` (corrector, predictor), or by the model's own ``edge_index``
-    layer in every model call (it finds ``_nlist_state`` in the batch and builds the capped list).  The ghost graph's rows of the
-    diffused tensors are never written back: its nodes stay where they are.
-
-    Construction sizes, pads and captures (``t0``: the time of the warm-up step); ``rewind()`` puts the state and the draw index
-    back on the start, ``run()`` replays, ``result()`` checks the capacity and unpads (``tools/sample_bench.py`` times ``run`` alone)."""
-
-    def __init__(self, batch, model, updates, keys, t0: float, e_cap: int, r_max: float, criteria=None, seeded=None, fixed=None,
-                 zero=()):
-        """``seeded``: ``(times, cells)`` of the seeded sampler -- the captured step then begins with ``e3k_sampler_begin_step``, which
-        sets the time from the table and advances the cells, and ``run`` is replays only.  ``fixed``: the name of conditional
-        sampling's mask field; padding collates integers as int64, so the padded mask is made uint8 again here, once -- the form the
-        kernels read, and no conversion joins the replayed step.  ``zero``: the tensors the updates accumulate into; ``rewind()`` zeroes
-        them."""
-        dev = batch["_n_nodes"].device
-        own = edge_layer_of(model)
-        if own is not None:
-            criteria, pos_key, build = replayable_criterion(own), own.key or keys[0], own.layer
-        else:
-            pos_key = keys[0]
-            build = partial(computeEdgeIndex, r_max=r_max, key=pos_key, criteria=criteria)
-        for k in SAMPLER_EDGE_KEYS:
-            batch.pop(k)
-        # eager, once: the sizes of the padded batch.  The same function, the same criterion, the draw of build 0 -- read from the
-        # cells, which the eager path never advances, so no draw is consumed
-        rng = builder_cells(dev)
-        batch.data["_nlist_rng"] = rng
-        new, attrs = build(batch.data, batch.attrs)
-        batch.data.pop("_nlist_rng")
-        batch.attrs.update(attrs)
-        batch.update(new)
-        n, e = batch.n_nodes, int(new["edge_index"].shape[1])
-        if e > e_cap:
-            raise EdgeCapacityExceeded(f"the first neighbour list has {e} edges: edge_capacity={e_cap} is too small")
-        batch["t"] = torch.full((len(batch), 1), float(t0), device=dev)
-        bucket = self.bucket = CappedBucket.around_list(batch, e_cap, pos_key, rng=rng)      # (the cells the sizing build read)
-        padded = bucket.padded
-        if fixed is not None:
-            padded.data[fixed] = (padded[fixed] != 0).to(torch.uint8)
-        state = {k: padded[k] for k in keys}
-
-        def relisted(b):
-            # a fresh view of the padded batch with the moved tensors: what the model left in ``b`` (edge vectors, harmonics, radial
-            # embeddings of the OLD list) stays behind, as the reference's loop drops it (:236-241)
-            fresh = padded.view()
-            for k in keys:
-                fresh[k] = b[k]
-            if own is None:      # in place, on the device, inside the capture (a model that owns its edge layer does this itself)
-                computeEdgeIndexCapped(fresh.data, fresh.attrs, r_max=r_max, key=pos_key, criteria=criteria)
-            return fresh
-
-        def captured():
-            if seeded is not None:
-                sampler_begin_step(seeded[0], seeded[1], padded["t"])
-            work = padded.view()
-            for update in updates:
-                work = relisted(update(work))
-            for k in keys:
-                state[k][:n].copy_(work[k][:n])
-
-        self.seeded, self.zero = seeded, tuple(zero)
-        self.padded, self.state, self.rng, self.keys, self.n, self.first_edges = padded, state, rng, keys, n, e
-        self.t_dev = padded["t"]
-        self.saved = {k: v.clone() for k, v in state.items()}
-        self.t_dev.fill_(float(t0))
-        self.step = CapturedStep(captured, warmup=1, device=dev)
-
-    def rewind(self) -> None:
-        """(the warm-up run moved the state and drew: both go back to the start)"""
-        for k in self.keys:
-            self.state[k].copy_(self.saved[k])
-        self.rng.zero_()
-        if self.seeded is not None:
-            self.seeded[1].zero_()
-        for acc in self.zero:
-            acc.zero_()
-
-    def run(self, timesteps, steps: int) -> None:
-        if self.seeded is not None:      # the time comes from the table inside the graph: bare replays
-            for _ in range(steps):
-                self.step()
-            return
-        t_dev = self.t_dev
-        for i in range(steps):
-            t_dev.copy_(timesteps[i].expand_as(t_dev))
-            self.step()
-
-    def result(self):
-        self.bucket.check()
-        out = self.bucket.real_graphs()
-        for k in self.keys:
-            out[k] = self.state[k][:self.n].clone()
-        return out
 
 
 def get_sampling_fn(config, sde: VPSDE, inverse_scaler, eps: float, **kwargs):

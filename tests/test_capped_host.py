@@ -28,7 +28,7 @@ def test_ghost_node_capacity_is_each_of_the_four_rules_it_replaced(n, ghost_edge
     n_cap = n + max(2, -(-(e_cap - e) // GHOST_DEGREE))
     n_cap = -(-n_cap // 32) * 32
     assert got == n_cap
-    # sde_sampling._CappedLoop.__init__
+    # loops.CappedLoop.__init__
     assert got == -(-(n + max(2, -(-(e_cap - e) // GHOST_DEGREE))) // 32) * 32
     # score_step.ReplayedScoreStep._sized_node_capacity
     assert got == -(-(n + max(2, -(-max(e_cap - e_min, 0) // GHOST_DEGREE))) // 32) * 32

@@ -298,15 +298,27 @@ def test_refusals():
 
 
 def test_the_accumulator_returns_to_zero_with_the_cells():
-    """what the replayed loops do after their warm-up step, on the host: ``_run_loop`` hands ``zero`` to ``CappedLoop``, whose
-    ``rewind()`` clears it with the cells"""
-    from e3_layers_amd.run.sde_sampling import CappedLoop
+    """what every loop's ``rewind()`` does to the plan's own state (the replayed loops after their warm-up step), on a real loop: the
+    accumulators of ``StepPlan.zero`` go back to zero with the cells and the neighbour-list builder's draw index -- here the host
+    counter of the ``PairCriterion`` in the model's own ``edge_index`` layer, which the eager loop resets"""
+    from functools import partial
+    from types import SimpleNamespace
 
-    loop = CappedLoop.__new__(CappedLoop)
-    acc, cells, rng = torch.ones(3), torch.tensor([2, 1]), torch.ones(2, dtype=torch.int64)
-    loop.keys, loop.state, loop.saved, loop.rng, loop.seeded, loop.zero = [], {}, {}, rng, (None, cells), (acc,)
+    from e3_layers_amd.data.compute_edge import PairCriterion
+    from e3_layers_amd.run.loops import EagerLoop, StepPlan
+
+    batch = _batch((3,), {"pos": 3})
+    batch.attrs["t"] = ("graph", "1x0e")
+    batch["t"] = torch.zeros(1, 1)
+    crit = PairCriterion()
+    crit.reset(7)      # (a counter that builds have advanced)
+    model = SimpleNamespace(layers=[("edge_index", partial(lambda data, attrs, criteria=None: ({}, attrs), criteria=crit))])
+    acc, cells = torch.ones(3), torch.tensor([2, 1])
+    plan = StepPlan(batch, [lambda b: b], ["pos"], torch.linspace(1.0, 1e-3, 4), cells, zero=(acc,))
+    loop = EagerLoop(plan, model, lambda b: b)
     loop.rewind()
-    assert (acc == 0).all() and (cells == 0).all() and (rng == 0).all()
+    assert (acc == 0).all() and (cells == 0).all() and crit._draw == 0
+    assert torch.equal(loop.result()["pos"], batch["pos"])
 
 
 def test_parameters_are_frozen_for_the_run_and_restored():

@@ -14,6 +14,14 @@ eager sampler loop on the same tree and start -- the only way to sample these ne
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/sample_bench.py --protein --trace-steps 40
     python tools/sample_bench.py --launches DIR_A/..._kernel_stats.csv 10 DIR_B/..._kernel_stats.csv 40    (launches per replayed step)
 
+What is timed is the sampler, not a copy of it: every loop is built from the plan function of the sampler it stands for
+(``run/sde_sampling.pc_plan`` / ``ode_plan``, ``run/likelihood.likelihood_plan``) and ``run/loops.make_loop``, as the sampler builds it,
+and driven through the loops' one interface -- ``rewind()`` outside the timed region, ``run(n)`` inside, ``result()`` after it -- the
+eager loops included.  Where a run starts: the seeded loops from the sampler's own counter-based prior at ``--seed`` (earlier
+versions of this tool started every loop from one generator-drawn x_T, so a seeded loop's first list may differ by a few edges from
+the figures recorded then); the unseeded loops from ``prior_sampling`` with the device's default generator seeded 1 -- the x_T bits
+they always had -- which the plan also hands to the predictor (a captured step can draw from no other generator).
+
 Protocol (tools/md_bench.py's): device events around ``--steps`` reverse steps after a warm-up, the two variants alternating in one
 process, ``--reps`` repetitions each (min / median / max); host-busy time is the wall time of the enqueue loop before the closing
 synchronisation.  No threshold is asserted: the numbers are quoted in README.md and DESIGN.md.
@@ -49,7 +57,7 @@ state so that both walk lists of one size.  The weights are untrained: the value
     python tools/sample_bench.py --protein --seed 7 --likelihood heun --ode-steps 100 --steps 100
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/sample_bench.py --protein --seed 7 \
         --likelihood heun --ode-steps 100 --trace-steps 40"""
-import argparse, csv, json, os, statistics, sys, time
+import argparse, contextlib, csv, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "equivariant-nn-zoo_amd")):
     sys.path.insert(0, p)
@@ -88,140 +96,57 @@ def molecules(argv):
 def protein_setup(n_prot, n_res, dev):
     from e3_layers_amd.configs import config_diffusion_CA
     from e3_layers_amd.data.synthetic import synth_protein
-    from e3_layers_amd.run.sde_utils import VPSDE, prior_sampling
+    from e3_layers_amd.run.sde_utils import VPSDE
     from e3_layers_amd.utils import build
 
-    crit = config_diffusion_CA.pair_criterion()
     torch.manual_seed(0)
-    model = build(config_diffusion_CA.get_config(edge_criteria=crit).model_config).to(dev).eval()
-    sde = VPSDE({"CA": 3}, N=1000)
-    sde.alphas = sde.alphas.to(dev)
-    clean = synth_protein(1, n_prot, n_res=n_res).to(dev)
-    batch = prior_sampling(sde, clean.clone(), torch.Generator(device=dev).manual_seed(1))      # x_T: where the sampler starts
-    timesteps = torch.linspace(sde.T, 1e-3, sde.N, device=dev)
-    return model, sde, batch, timesteps, crit, clean
+    model = build(config_diffusion_CA.get_config(edge_criteria=config_diffusion_CA.pair_criterion()).model_config).to(dev).eval()
+    return model, VPSDE({"CA": 3}, N=1000), synth_protein(1, n_prot, n_res=n_res).to(dev)
 
 
-def predictor(model, sde):
-    from e3_layers_amd.run.sde_sampling import EulerMaruyamaPredictor
-    from e3_layers_amd.run.sde_utils import get_score_fn
+def pc(model, sde, batch, seed=None, corrector="none", fixed=None):
+    """The plan of ``get_pc_sampler(sde, EulerMaruyamaPredictor, <corrector>, seed=seed, fixed=fixed)`` on ``batch``."""
+    from e3_layers_amd.run.sde_sampling import EulerMaruyamaPredictor, LangevinCorrector, NoneCorrector, pc_plan
 
-    return EulerMaruyamaPredictor(sde, get_score_fn(sde, model, train=False))
-
-
-def eager_loop(model, sde, batch, timesteps, crit, n_steps):
-    """pc_sampler's eager path with NoneCorrector: set the time, predictor update (one model call: its edge layer builds the list,
-    all pairs -> criterion -> edge count read back), drop the per-edge keys."""
-    from e3_layers_amd.run.sde_sampling import SAMPLER_EDGE_KEYS
-
-    pred = predictor(model, sde)
-    state = {"b": batch.clone()}
-    state["b"]["t"] = torch.empty(len(batch), 1, device=timesteps.device)
-    crit.reset()
-
-    def loop():
-        b = state["b"]
-        t_dev = b["t"]
-        t0 = time.perf_counter()
-        with torch.no_grad():
-            for i in range(n_steps):
-                t_dev.copy_(timesteps[i].expand_as(t_dev))
-                b = pred.update_fn(b)
-                for k in SAMPLER_EDGE_KEYS:
-                    b.pop(k)
-        state["b"] = b
-        return time.perf_counter() - t0
-
-    return loop
+    gen = None
+    if seed is None:      # x_T first, from seed 1; the default generator: the one a captured step may draw from
+        gen = torch.cuda.default_generators[batch["CA"].device.index]
+        gen.manual_seed(1)
+    return pc_plan(sde, EulerMaruyamaPredictor, LangevinCorrector if corrector == "langevin" else NoneCorrector, model, batch,
+                   generator=gen, seed=seed, fixed=fixed)[0]
 
 
-def replay_loop(model, sde, batch, timesteps, slack):
-    """The capped loop of get_pc_sampler(graph=True, edge_capacity=...): sized, padded and captured here, outside the timed region."""
+def first_edges(model, plan):
+    """The edges of the list the model's own layer builds on the plan's start state (the draw of build 0; none is consumed)."""
     from e3_layers_amd.run.capped import builder_cells, edge_layer_of
-    from e3_layers_amd.run.sde_sampling import CappedLoop
 
-    b = batch.clone()
-    b.attrs["t"] = ("graph", "1x0e")
-    pred = predictor(model, sde)
-    probe = b.clone()
-    probe.data["_nlist_rng"] = builder_cells(timesteps.device)
+    probe = plan.batch.view()
+    probe.data["_nlist_rng"] = builder_cells(plan.cells.device)
     new, _ = edge_layer_of(model).layer(probe.data, probe.attrs)
-    e_cap = -(-int(slack * new["edge_index"].shape[1]) // 1024) * 1024
-    with torch.no_grad():
-        return CappedLoop(b, model, [lambda w: w, lambda w: pred.update_fn(w)], ["CA"], float(timesteps[0]), e_cap, None), e_cap
+    return int(new["edge_index"].shape[1])
 
 
-def seeded_updates(model, sde, seed, cells, corrector, fixed=None):
-    """[corrector, predictor] of the seeded form, as get_pc_sampler builds them (``fixed``: the mask field's name, or None)"""
-    from functools import partial
-
-    from e3_layers_amd.run.sde_utils import langevin_step_counter, reverse_step_counter
-
-    corr = (partial(langevin_step_counter, sde, model, seed=seed, draw=cells, snr=0.16, fixed=fixed) if corrector == "langevin"
-            else (lambda w: w))
-    return [corr, partial(reverse_step_counter, sde, model, seed=seed, draw=cells, fixed=fixed)]
+def capacity(edges, slack):
+    return -(-int(slack * edges) // 1024) * 1024
 
 
-def seeded_replay_loop(model, sde, batch, timesteps, e_cap, seed, corrector, fixed=None):
-    from e3_layers_amd.run.sde_sampling import CappedLoop
+def loop_of(plan, model, e_cap=None, frozen=False):
+    """``make_loop`` as the samplers call it on these nets: the capped replay at ``e_cap`` (sized, padded and captured here, outside any
+    timed region), the eager loop without.  ``frozen``: inside ``frozen_parameters(model)``, as the likelihood builds and runs."""
+    from e3_layers_amd.run.capped import edge_layer_of
+    from e3_layers_amd.run.likelihood import frozen_parameters
+    from e3_layers_amd.run.loops import edge_plumbing, make_loop
 
-    b = batch.clone()
-    b.attrs["t"] = ("graph", "1x0e")
-    cells = torch.zeros(2, dtype=torch.int64, device=timesteps.device)
-    extra = {} if fixed is None else {"fixed": fixed}      # (the unconditioned call: as before)
-    with torch.no_grad():
-        return CappedLoop(b, model, seeded_updates(model, sde, seed, cells, corrector, fixed), ["CA"], float(timesteps[0]), e_cap, None,
-                          seeded=(timesteps, cells), **extra)
-
-
-def ode_replay_loop(model, sde, batch, method, n_steps, e_cap):
-    """The capped loop of get_ode_sampler(graph=True, edge_capacity=...), built as it builds it: the updates are the ODE's stages, the
-    step header walks the first n_steps entries of the table."""
-    from functools import partial
-
-    from e3_layers_amd.run.sde_sampling import CappedLoop
-    from e3_layers_amd.run.sde_utils import ode_euler_step, ode_heun_finish
-
-    dev = batch["CA"].device
-    b = batch.clone()
-    b.attrs["t"] = ("graph", "1x0e")
-    times = torch.linspace(sde.T, 1e-3, n_steps + 1, device=dev, dtype=torch.float32)
-    cells = torch.zeros(2, dtype=torch.int64, device=dev)
-    if method == "euler":
-        updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells)]
-    else:
-        kept = {}
-        updates = [partial(ode_euler_step, sde, model, times=times, cells_or_step=cells, keep=kept),
-                   partial(ode_heun_finish, sde, model, kept=kept, times=times, cells_or_step=cells)]
-    with torch.no_grad():
-        return CappedLoop(b, model, updates, ["CA"], float(times[0]), e_cap, None, seeded=(times[:n_steps], cells))
+    with torch.no_grad(), (frozen_parameters(model) if frozen else contextlib.nullcontext()):
+        return make_loop(plan, model, edge_plumbing((), False)[1], graph=e_cap is not None, edge_capacity=e_cap,
+                         r_max=edge_layer_of(model).r_max, criteria=None)
 
 
-def likelihood_replay_loop(model, sde, batch, method, n_steps, e_cap, seed):
-    """The capped loop of get_likelihood_fn(graph=True, edge_capacity=...), built as it builds it: the probes ride in the batch, the
-    table ascends, the accumulators go back to zero with the cells.  -> (loop, acc)"""
-    from e3_layers_amd.backend import ops
-    from e3_layers_amd.run.likelihood import attach_probes, frozen_parameters, stage_updates
-    from e3_layers_amd.run.sde_sampling import CappedLoop
-
-    dev = batch["CA"].device
-    b = batch.clone()
-    b.attrs["t"] = ("graph", "1x0e")
-    attach_probes(sde, b, seed, "rademacher", 1)
-    times = torch.linspace(1e-3, sde.T, n_steps + 1, device=dev, dtype=torch.float32)
-    cells = torch.zeros(2, dtype=torch.int64, device=dev)
-    acc = torch.zeros(len(b), dtype=torch.float64, device=dev)
-    row_ptr = ops.graph_row_pointers(b["_n_nodes"].reshape(-1).contiguous())
-    updates = stage_updates(sde, model, method, times, cells, acc, 1, row_ptr)
-    with torch.no_grad(), frozen_parameters(model):      # (the capture records the backward: what it walks is decided here)
-        return CappedLoop(b, model, updates, ["CA"], float(times[0]), e_cap, None, seeded=(times[:n_steps], cells), zero=(acc,)), acc
-
-
-def conditioned(sde, batch, clean, fraction):
-    """``batch`` (at x_T = z) with conditional sampling's fields, as get_pc_sampler(fixed="fixed") sets them up: the middle ``fraction``
-    of every chain of every protein is fixed (a contiguous stretch, chosen by the chain's length alone), ``known_CA`` = the clean
-    coordinates, and the fixed rows of x_T are m(T) x0 + s(T) z.  -> (batch, fixed rows)"""
-    b = batch.clone()
+def with_mask(clean, fraction):
+    """``clean`` with the mask field ``fixed`` that ``get_pc_sampler(fixed="fixed")`` reads: the middle ``fraction`` of every chain of
+    every protein (a contiguous stretch, chosen by the chain's length alone); the known values are the batch's own coordinates.
+    -> (batch, fixed rows)"""
+    b = clean.clone()
     chain = clean["chain_id"].reshape(-1) + (int(clean["chain_id"].max()) + 1) * clean.nodeSegment()
     mask = torch.zeros_like(chain, dtype=torch.bool)
     for c in torch.unique(chain).tolist():
@@ -229,41 +154,21 @@ def conditioned(sde, batch, clean, fraction):
         k = int(round(fraction * rows.numel()))
         start = (rows.numel() - k) // 2
         mask[rows[start:start + k]] = True
-    b.attrs["fixed"], b.attrs["known_CA"] = ("node", "1x0e"), b.attrs["CA"]
+    b.attrs["fixed"] = ("node", "1x0e")
     b["fixed"] = mask.reshape(-1, 1).to(torch.uint8)
-    b["known_CA"] = clean["CA"].float()
-    lm = sde.log_mean_coeff(torch.tensor(float(sde.T)))
-    b["CA"] = torch.where(mask.reshape(-1, 1), torch.exp(lm) * b["known_CA"] + torch.sqrt(-torch.expm1(2.0 * lm)) * b["CA"], b["CA"])
     return b, int(mask.sum())
 
 
-def seeded_eager_loop(model, sde, batch, timesteps, crit, n_steps, seed, corrector):
-    """pc_sampler's eager path with a seed: the step header, corrector, predictor; the per-edge keys dropped after each"""
-    from e3_layers_amd.run.sde_sampling import SAMPLER_EDGE_KEYS
-    from e3_layers_amd.run.sde_utils import sampler_begin_step
+def run_of(loop, n):
+    """``loop`` rewound; -> a callable that does ``n`` steps and returns the host's busy time"""
+    loop.rewind()      # (outside the timed region)
 
-    cells = torch.zeros(2, dtype=torch.int64, device=timesteps.device)
-    updates = seeded_updates(model, sde, seed, cells, corrector)
-    state = {"b": batch.clone()}
-    state["b"].attrs["t"] = ("graph", "1x0e")
-    state["b"]["t"] = torch.empty(len(batch), 1, device=timesteps.device)
-    crit.reset()
-
-    def loop():
-        b = state["b"]
-        t_dev = b["t"]
+    def run():
         t0 = time.perf_counter()
         with torch.no_grad():
-            for i in range(n_steps):
-                sampler_begin_step(timesteps, cells, t_dev)
-                for update in updates:
-                    b = update(b)
-                    for k in SAMPLER_EDGE_KEYS:
-                        b.pop(k)
-        state["b"] = b
+            loop.run(n)
         return time.perf_counter() - t0
-
-    return loop
+    return run
 
 
 def timed(fn):
@@ -279,6 +184,10 @@ def timed(fn):
 def total_calls(path):
     with open(path) as f:
         return sum(int(r["Calls"]) for r in csv.DictReader(f))
+
+
+def mmm(v):
+    return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
 
 
 def protein(argv):
@@ -307,55 +216,42 @@ def protein(argv):
         raise SystemExit("--ode METHOD: with --seed and --ode-steps K, without --fixed")
     if not 0.0 <= args.fixed < 1.0 or (args.fixed and args.seed is None):
         raise SystemExit("--fixed FRACTION: in [0, 1), with --seed (the conditioned replay is the seeded form's)")
-    dev = torch.device("cuda:0")
-    model, sde, batch, timesteps, crit, clean = protein_setup(args.proteins, args.residues, dev)
+    model, sde, clean = protein_setup(args.proteins, args.residues, torch.device("cuda:0"))
     if args.likelihood is not None:
-        return protein_likelihood(args, model, sde, batch, timesteps)
+        return protein_likelihood(args, model, sde, clean)
     if args.ode is not None:
-        return protein_ode(args, model, sde, batch, timesteps)
+        return protein_ode(args, model, sde, clean)
     if args.seed is not None:
-        return protein_seeded(args, model, sde, batch, timesteps, crit, clean)
+        return protein_seeded(args, model, sde, clean)
     if args.corrector != "none":
         raise SystemExit("--corrector langevin needs --seed: the unseeded replay serves NoneCorrector only")
-    loop, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
-
-    def replay(n):
-        def run():
-            t0 = time.perf_counter()
-            with torch.no_grad():
-                loop.run(timesteps, n)
-            return time.perf_counter() - t0
-        return run
-
+    plan = pc(model, sde, clean)
+    e_cap = capacity(first_edges(model, plan), args.slack)
+    loop = loop_of(plan, model, e_cap)
     if args.trace_steps:
-        loop.rewind()
-        replay(args.trace_steps)()
+        run_of(loop, args.trace_steps)()
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues}))
         return
-    loop.rewind()
-    replay(args.warmup)()
-    eager_loop(model, sde, batch, timesteps, crit, args.warmup)()
+    eager = loop_of(pc(model, sde, clean), model)
+    run_of(loop, args.warmup)()
+    run_of(eager, args.warmup)()
     rows = {"replay": [], "eager": [], "replay_host": [], "eager_host": []}
     edges = []
     for _ in range(args.reps):
-        loop.rewind()
-        ms, host = timed(replay(args.steps))
+        ms, host = timed(run_of(loop, args.steps))
         edges.append(int(loop.bucket.state[0]))
         loop.result()                               # (after the closing event: an overflowed repetition would raise here)
         rows["replay"].append(ms / args.steps)
         rows["replay_host"].append(1e3 * host / args.steps)
-        ms, host = timed(eager_loop(model, sde, batch, timesteps, crit, args.steps))
+        ms, host = timed(run_of(eager, args.steps))
         rows["eager"].append(ms / args.steps)
         rows["eager_host"].append(1e3 * host / args.steps)
-
-    def mmm(v):
-        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
 
     doc = {"workload": "reverse diffusion (Euler-Maruyama, NoneCorrector, first steps of N=1000) on config_diffusion_CA as shipped, "
                        "built with pair_criterion(); synth_protein",
            "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues,
-           "nodes": int(batch["CA"].shape[0]), "edges_first_list": loop.first_edges, "edges_last_list": edges, "e_cap": e_cap,
+           "nodes": int(clean["CA"].shape[0]), "edges_first_list": loop.first_edges, "edges_last_list": edges, "e_cap": e_cap,
            "n_cap": loop.bucket.n_cap, "steps": args.steps, "reps": args.reps, "recaptures": loop.step.recaptures,
            "replay_ms_per_step": mmm(rows["replay"]), "eager_ms_per_step": mmm(rows["eager"]),
            "replay_host_busy_ms_per_step": mmm(rows["replay_host"]), "eager_host_busy_ms_per_step": mmm(rows["eager_host"]),
@@ -367,68 +263,50 @@ def protein(argv):
             f.write(text + "\n")
 
 
-def protein_seeded(args, model, sde, batch, timesteps, crit, clean):
+def protein_seeded(args, model, sde, clean):
     """The seeded replay, the seeded eager loop and (NoneCorrector only) the unseeded replay, alternating; with ``--fixed`` the
     conditioned seeded replay as well."""
-    plain, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
+    plan = pc(model, sde, clean, args.seed, args.corrector)
+    e_cap = capacity(first_edges(model, plan), args.slack)
     if args.corrector == "langevin":      # (two model calls per step, and the corrector moves the nodes before the second list)
-        e_cap = -(-int(1.1 * e_cap) // 1024) * 1024
-    loop = seeded_replay_loop(model, sde, batch, timesteps, e_cap, args.seed, args.corrector)
+        e_cap = capacity(e_cap, 1.1)
+    loop = loop_of(plan, model, e_cap)
     cond = n_fixed = None
     if args.fixed:      # (the same capacity: the fixed rows start near their clean places, the rest as before)
-        cond_batch, n_fixed = conditioned(sde, batch, clean, args.fixed)
-        cond = seeded_replay_loop(model, sde, cond_batch, timesteps, e_cap, args.seed, args.corrector, fixed="fixed")
-
-    def replay(which, n):
-        def run():
-            t0 = time.perf_counter()
-            with torch.no_grad():
-                which.run(timesteps, n)
-            return time.perf_counter() - t0
-        return run
-
+        masked, n_fixed = with_mask(clean, args.fixed)
+        cond = loop_of(pc(model, sde, masked, args.seed, args.corrector, fixed="fixed"), model, e_cap)
     if args.trace_steps:
-        traced = loop if cond is None else cond
-        traced.rewind()
-        replay(traced, args.trace_steps)()
+        run_of(loop if cond is None else cond, args.trace_steps)()
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
                           "corrector": args.corrector, "fixed": args.fixed}))
         return
-    variants = {"seeded_replay": lambda n: (loop.rewind(), replay(loop, n))[1],
-                "seeded_eager": lambda n: seeded_eager_loop(model, sde, batch, timesteps, crit, n, args.seed, args.corrector)}
+    loops = {"seeded_replay": loop, "seeded_eager": loop_of(pc(model, sde, clean, args.seed, args.corrector), model)}
     if cond is not None:
-        variants["fixed_replay"] = lambda n: (cond.rewind(), replay(cond, n))[1]
+        loops["fixed_replay"] = cond
     if args.corrector == "none":
-        variants["replay"] = lambda n: (plain.rewind(), replay(plain, n))[1]
-    for make in variants.values():
-        make(args.warmup)()
-    rows = {name: [] for name in variants}
-    host = {name: [] for name in variants}
+        loops["replay"] = loop_of(pc(model, sde, clean), model, e_cap)
+    for which in loops.values():
+        run_of(which, args.warmup)()
+    rows = {name: [] for name in loops}
+    host = {name: [] for name in loops}
     for _ in range(args.reps):
-        for name, make in variants.items():
-            ms, busy = timed(make(args.steps))
-            if name == "seeded_replay":
-                loop.result()                       # (after the closing event: an overflowed repetition would raise here)
-            elif name == "fixed_replay":
-                cond.result()
-            elif name == "replay":
-                plain.result()
+        for name, which in loops.items():
+            ms, busy = timed(run_of(which, args.steps))
+            if name != "seeded_eager":
+                which.result()                      # (after the closing event: an overflowed repetition would raise here)
             rows[name].append(ms / args.steps)
             host[name].append(1e3 * busy / args.steps)
-
-    def mmm(v):
-        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
 
     doc = {"workload": f"reverse diffusion (Euler-Maruyama, corrector {args.corrector}, first steps of N=1000) on config_diffusion_CA as "
                        "shipped, built with pair_criterion(); synth_protein; seeded form",
            "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
-           "corrector": args.corrector, "nodes": int(batch["CA"].shape[0]), "edges_first_list": loop.first_edges, "e_cap": e_cap,
+           "corrector": args.corrector, "nodes": int(clean["CA"].shape[0]), "edges_first_list": loop.first_edges, "e_cap": e_cap,
            "n_cap": loop.bucket.n_cap, "steps": args.steps, "reps": args.reps, "recaptures": loop.step.recaptures}
-    for name in variants:
+    for name in loops:
         doc[f"{name}_ms_per_step"] = mmm(rows[name])
         doc[f"{name}_host_busy_ms_per_step"] = mmm(host[name])
-    if "replay" not in variants:
+    if "replay" not in loops:
         doc["replay_ms_per_step"] = "not measured: the unseeded replay refuses the Langevin corrector"
     doc["speedup_median_seeded_replay_over_seeded_eager"] = round(statistics.median(rows["seeded_eager"]) / statistics.median(rows["seeded_replay"]), 3)
     if cond is not None:
@@ -444,54 +322,58 @@ def protein_seeded(args, model, sde, batch, timesteps, crit, clean):
         f.write(text + "\n")
 
 
-def protein_ode(args, model, sde, batch, timesteps):
-    """The Heun replay, the Euler replay and the seeded Euler-Maruyama + Langevin replay, alternating, each repetition from x_T."""
+def ode(model, sde, batch, method, args):
+    """The plan of ``get_ode_sampler(sde, method=method, n_steps=args.ode_steps, seed=args.seed)`` on ``batch``."""
+    from e3_layers_amd.run.sde_sampling import ode_plan
+
+    return ode_plan(sde, method, model, batch, n_steps=args.ode_steps, seed=args.seed)
+
+
+def grid_checked(args):
     n_timed = args.trace_steps or args.steps
     if not 1 <= n_timed <= args.ode_steps or args.warmup > args.ode_steps:
-        raise SystemExit(f"--steps / --trace-steps / --warmup: at most --ode-steps = {args.ode_steps} (a replay past the grid stands still)")
-    _, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
-    e_cap = -(-int(1.1 * e_cap) // 1024) * 1024      # (the seeded Langevin replay's capacity; the same for every loop here)
-    loops = {"ode_heun_replay": ode_replay_loop(model, sde, batch, "heun", args.ode_steps, e_cap),
-             "ode_euler_replay": ode_replay_loop(model, sde, batch, "euler", args.ode_steps, e_cap)}
+        raise SystemExit(f"--steps / --trace-steps / --warmup: at most --ode-steps = {args.ode_steps} (a run stops at the end of its grid)")
 
-    def replay(which, n):
-        which.rewind()      # (outside the timed region)
 
-        def run():
-            t0 = time.perf_counter()
-            with torch.no_grad():
-                which.run(timesteps, n)
-            return time.perf_counter() - t0
-        return run
-
-    if args.trace_steps:
-        replay(loops[f"ode_{args.ode}_replay"], args.trace_steps)()
-        torch.cuda.synchronize()
-        print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
-                          "ode": args.ode, "ode_steps": args.ode_steps}))
-        return
-    loops["pc_langevin_replay"] = seeded_replay_loop(model, sde, batch, timesteps, e_cap, args.seed, "langevin")
-    for loop in loops.values():
-        replay(loop, args.warmup)()
-    rows = {name: [] for name in loops}
-    host = {name: [] for name in loops}
-    edges = {name: [] for name in loops}
+def alternate(args, loops):
+    """Warm-up, then ``--reps`` rounds over ``loops`` (name -> capped replay), each repetition from the loop's start state.
+    -> (ms per step, host-busy ms per step, edges of the last list), each name -> list"""
+    rows, host, edges = ({name: [] for name in loops} for _ in range(3))
+    for name, loop in loops.items():
+        run_of(loop, args.warmup)()
     for _ in range(args.reps):
         for name, loop in loops.items():
-            ms, busy = timed(replay(loop, args.steps))
+            ms, busy = timed(run_of(loop, args.steps))
             edges[name].append(int(loop.bucket.state[0]))
             loop.result()                                   # (after the closing event: an overflowed repetition would raise here)
             rows[name].append(ms / args.steps)
             host[name].append(1e3 * busy / args.steps)
+    return rows, host, edges
 
-    def mmm(v):
-        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
+
+def protein_ode(args, model, sde, clean):
+    """The Heun replay, the Euler replay and the seeded Euler-Maruyama + Langevin replay, alternating, each repetition from x_T."""
+    grid_checked(args)
+    heun = ode(model, sde, clean, "heun", args)
+    # (the seeded Langevin replay's capacity; the same for every loop here: all start from the x_T of one seed)
+    e_cap = capacity(capacity(first_edges(model, heun), args.slack), 1.1)
+    if args.trace_steps:
+        run_of(loop_of(heun if args.ode == "heun" else ode(model, sde, clean, "euler", args), model, e_cap), args.trace_steps)()
+        torch.cuda.synchronize()
+        print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
+                          "ode": args.ode, "ode_steps": args.ode_steps}))
+        return
+    loops = {"ode_heun_replay": loop_of(heun, model, e_cap),
+             "ode_euler_replay": loop_of(ode(model, sde, clean, "euler", args), model, e_cap),
+             "pc_langevin_replay": loop_of(pc(model, sde, clean, args.seed, "langevin"), model, e_cap)}
+    rows, host, edges = alternate(args, loops)
 
     doc = {"workload": f"probability-flow ODE (Heun, Euler; grid of {args.ode_steps} steps) beside reverse diffusion (Euler-Maruyama + "
                        "Langevin, first steps of N=1000, seeded) on config_diffusion_CA as shipped, built with pair_criterion(); "
                        "synth_protein; capped replays, every repetition from x_T",
            "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
-           "ode_steps": args.ode_steps, "nodes": int(batch["CA"].shape[0]), "e_cap": e_cap, "steps": args.steps, "reps": args.reps,
+           "ode_steps": args.ode_steps, "nodes": int(clean["CA"].shape[0]), "edges_first_list": loops["ode_heun_replay"].first_edges,
+           "e_cap": e_cap, "steps": args.steps, "reps": args.reps,
            "model_calls_per_step": {"ode_heun_replay": 2, "ode_euler_replay": 1, "pc_langevin_replay": 2},
            "sample_quality": "not assessed: untrained weights; only the time of a step is measured"}
     for name, loop in loops.items():
@@ -499,58 +381,35 @@ def protein_ode(args, model, sde, batch, timesteps):
         doc[f"{name}_host_busy_ms_per_step"] = mmm(host[name])
         doc[f"{name}_edges_last_list"] = edges[name]
         doc[f"{name}_recaptures"] = loop.step.recaptures
-    pc = statistics.median(rows["pc_langevin_replay"])
-    doc["ode_heun_step_over_pc_step_median"] = round(statistics.median(rows["ode_heun_replay"]) / pc, 4)
-    doc["ode_euler_step_over_pc_step_median"] = round(statistics.median(rows["ode_euler_replay"]) / pc, 4)
+    pc_ms = statistics.median(rows["pc_langevin_replay"])
+    doc["ode_heun_step_over_pc_step_median"] = round(statistics.median(rows["ode_heun_replay"]) / pc_ms, 4)
+    doc["ode_euler_step_over_pc_step_median"] = round(statistics.median(rows["ode_euler_replay"]) / pc_ms, 4)
     text = json.dumps(doc, indent=1)
     print(text)
     with open(args.out or os.path.join(ROOT, "profiles", "protein_sampler_ode.json"), "w") as f:
         f.write(text + "\n")
 
 
-def protein_likelihood(args, model, sde, batch, timesteps):
+def protein_likelihood(args, model, sde, clean):
     """The likelihood's replayed step and the ODE sampler's replayed Heun step, alternating, each repetition from the same state."""
-    n_timed = args.trace_steps or args.steps
-    if not 1 <= n_timed <= args.ode_steps or args.warmup > args.ode_steps:
-        raise SystemExit(f"--steps / --trace-steps / --warmup: at most --ode-steps = {args.ode_steps} (a replay past the grid stands still)")
-    _, e_cap = replay_loop(model, sde, batch, timesteps, args.slack)
-    e_cap = -(-int(1.1 * e_cap) // 1024) * 1024
+    from e3_layers_amd.run.likelihood import likelihood_plan
+
+    grid_checked(args)
     name = f"likelihood_{args.likelihood}_replay"
-    lik, acc = likelihood_replay_loop(model, sde, batch, args.likelihood, args.ode_steps, e_cap, args.seed)
-
-    def replay(which, n):
-        which.rewind()      # (outside the timed region)
-
-        def run():
-            t0 = time.perf_counter()
-            with torch.no_grad():
-                which.run(timesteps, n)
-            return time.perf_counter() - t0
-        return run
-
+    ode_heun = ode(model, sde, clean, "heun", args)
+    e_cap = capacity(capacity(first_edges(model, ode_heun), args.slack), 1.1)
+    # (the batch whose likelihood is taken: the ODE loop's x_T, so that both loops walk lists of one size)
+    plan, acc, _ = likelihood_plan(sde, args.likelihood, model, ode_heun.batch, n_steps=args.ode_steps, seed=args.seed)
+    lik = loop_of(plan, model, e_cap, frozen=True)      # (the capture records the backward: what it walks is decided here)
     if args.trace_steps:
-        replay(lik, args.trace_steps)()
+        run_of(lik, args.trace_steps)()
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
                           "likelihood": args.likelihood, "ode_steps": args.ode_steps}))
         return
-    loops = {name: lik, "ode_heun_replay": ode_replay_loop(model, sde, batch, "heun", args.ode_steps, e_cap)}
-    for loop in loops.values():
-        replay(loop, args.warmup)()
-    rows = {k: [] for k in loops}
-    host = {k: [] for k in loops}
-    edges = {k: [] for k in loops}
-    for _ in range(args.reps):
-        for k, loop in loops.items():
-            ms, busy = timed(replay(loop, args.steps))
-            edges[k].append(int(loop.bucket.state[0]))
-            loop.result()
-            rows[k].append(ms / args.steps)
-            host[k].append(1e3 * busy / args.steps)
+    loops = {name: lik, "ode_heun_replay": loop_of(ode_heun, model, e_cap)}
+    rows, host, edges = alternate(args, loops)
     finite = bool(torch.isfinite(acc).all()) and bool((acc != 0).all())
-
-    def mmm(v):
-        return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
 
     calls = 2 if args.likelihood == "heun" else 1
     doc = {"workload": f"log-likelihood through the probability-flow ODE ({args.likelihood}; grid of {args.ode_steps} steps, one Rademacher "
@@ -558,7 +417,8 @@ def protein_likelihood(args, model, sde, batch, timesteps):
                        "synth_protein; capped replays, every repetition from the same state (the ODE loop's x_T, so that both loops "
                        "walk lists of one size)",
            "device": torch.cuda.get_device_name(0), "proteins": args.proteins, "residues": args.residues, "seed": args.seed,
-           "ode_steps": args.ode_steps, "nodes": int(batch["CA"].shape[0]), "e_cap": e_cap, "steps": args.steps, "reps": args.reps,
+           "ode_steps": args.ode_steps, "nodes": int(clean["CA"].shape[0]), "edges_first_list": lik.first_edges, "e_cap": e_cap,
+           "steps": args.steps, "reps": args.reps,
            "model_calls_per_step": {name: f"{calls} (each a forward and one backward with respect to the positions)", "ode_heun_replay": 2},
            "logp": "not reported: untrained weights, the value says nothing about a model; the closed forms of "
                    "tests/test_likelihood_host.py pin that the number is a log-density",
@@ -568,9 +428,9 @@ def protein_likelihood(args, model, sde, batch, timesteps):
         doc[f"{k}_host_busy_ms_per_step"] = mmm(host[k])
         doc[f"{k}_edges_last_list"] = edges[k]
         doc[f"{k}_recaptures"] = loop.step.recaptures
-    ode = statistics.median(rows["ode_heun_replay"])
-    doc["likelihood_step_over_ode_heun_step_median"] = round(statistics.median(rows[name]) / ode, 4)
-    doc["likelihood_model_call_over_ode_model_call_median"] = round((statistics.median(rows[name]) / calls) / (ode / 2), 4)
+    ode_ms = statistics.median(rows["ode_heun_replay"])
+    doc["likelihood_step_over_ode_heun_step_median"] = round(statistics.median(rows[name]) / ode_ms, 4)
+    doc["likelihood_model_call_over_ode_model_call_median"] = round((statistics.median(rows[name]) / calls) / (ode_ms / 2), 4)
     text = json.dumps(doc, indent=1)
     print(text)
     with open(args.out or os.path.join(ROOT, "profiles", "protein_likelihood.json"), "w") as f:
