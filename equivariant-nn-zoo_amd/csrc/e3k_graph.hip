@@ -19,12 +19,10 @@ __global__ __launch_bounds__(256) void csr_count_kernel(const int64_t* __restric
                                                         int32_t* __restrict__ bad) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= E) return;
-  const int64_t s = edge_index[e], d = edge_index[E + e];
+  int64_t s = edge_index[e], d = edge_index[E + e];
   if (s < 0 || s >= N || d < 0 || d >= N) {   // reported by the host wrapper after the build (no sync here)
     *bad = 1;
-    src[e] = 0;
-    dst[e] = 0;
-    return;
+    s = d = 0;      // attached to node 0 AND counted there: fill claims a slot for every edge, so every slot of both lists is written
   }
   src[e] = (int32_t)s;
   dst[e] = (int32_t)d;
@@ -121,6 +119,7 @@ extern "C" int e3k_csr_build(const int64_t* edge_index, int64_t N, int64_t E, in
                              void* stream) {
   if (N < 0 || E < 0) return E3K_ERR_INVALID;
   if (N >= 0x7fffffffLL || E >= 0x7fffffffLL) return E3K_ERR_UNSUPPORTED;
+  if (N == 0 && E > 0) return E3K_ERR_INVALID;      // (no node 0 to attach an edge to: every endpoint is out of range)
   if (!dst_ptr || !src_ptr || !bad_flag) return E3K_ERR_INVALID;
   if (E > 0 && (!edge_index || !src || !dst || !dst_perm || !src_perm || !workspace)) return E3K_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;

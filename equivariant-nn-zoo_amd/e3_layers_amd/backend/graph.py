@@ -215,6 +215,8 @@ def build_topology(edge_index: torch.Tensor, num_nodes: int) -> GraphTopo:
         raise ValueError(f"edge_index must be [2, E], got {tuple(edge_index.shape)}")
     if int(num_nodes) >= 2 ** 31 - 1 or edge_index.shape[1] >= 2 ** 31 - 1:
         raise ValueError("node and edge ids must fit in int32")
+    if int(num_nodes) == 0 and edge_index.shape[1] > 0:      # (e3k_csr_build refuses it: no node 0 to attach a bad edge to)
+        raise ValueError(f"edge_index holds {edge_index.shape[1]} edges of a graph without nodes")
     if edge_index.is_cuda:
         return _build_topology_device(edge_index, int(num_nodes))
     src64, dst64 = edge_index[0].contiguous(), edge_index[1].contiguous()

@@ -368,7 +368,9 @@ int e3k_tp_bwd_x(const e3k_tp_plan* plan, const float* sh, const float* w, const
  *   src, dst [E] int32; dst_ptr/src_ptr [N+1] row pointers; dst_perm/src_perm [E] edge ids grouped by endpoint,
  *   ASCENDING inside a row (= a stable sort by endpoint, the reference's CPU summation order);
  * workspace: e3k_csr_workspace_ints(N, E) int32.  bad_flag [1]: set to 1 when an endpoint is outside [0, N)
- * (such edges are attached to node 0; the caller reads the flag when it chooses to).
+ * (such edges are attached to node 0 and counted there, so the lists stay complete: every edge id appears exactly once in
+ * each perm and every element of every output is written -- the result is that of the edge list with each such edge replaced
+ * by (0, 0); the caller reads the flag when it chooses to).  N = 0 with E > 0 (no node 0 to attach to): E3K_ERR_INVALID.
  * ------------------------------------------------------------------------------------------ */
 int64_t e3k_csr_workspace_ints(int64_t N, int64_t E);
 int e3k_csr_build(const int64_t* edge_index, int64_t N, int64_t E, int32_t* src, int32_t* dst, int32_t* dst_ptr,
@@ -387,7 +389,8 @@ int e3k_edge_records(const int32_t* perm, const int32_t* nbr, const int32_t* bin
 /* Rows grouped by a small categorical key (the keyed self-connection groups nodes by species: node_attrs =
  * Linear(one_hot(species)), layer_configs.py:104-118 feeding nn/message_passing.py:81-87,100): perm [R] int32 = row ids
  * sorted by key, stable; bounds [K,2] int32 = {start, count} per key; reps [K] int64 = first row of each key (0 for an
- * absent key).  K <= 256.  bad_flag [1]: set when a key is outside [0, K). */
+ * absent key).  K <= 256.  bad_flag [1]: set when a key is outside [0, K); such rows are left out of bounds and reps, perm holds
+ * the remaining rows in its first sum(count) elements and the rest of perm is not written (read perm through bounds only). */
 int e3k_group_rows(const int64_t* key, int64_t R, int32_t K, int32_t* perm, int32_t* bounds, int64_t* reps,
                    int32_t* bad_flag, void* stream);
 
