@@ -214,9 +214,11 @@ int radial_fwd(const e3k_layer* L, const e3k_layer_radial& r, void* st) {
 extern "C" int e3k_layer_create(const e3k_layer_desc* desc, e3k_layer** out) {
   if (!desc || !out || !desc->tp) return E3K_ERR_INVALID;
   if (desc->n_hidden < 1 || desc->n_hidden > 4) return E3K_ERR_UNSUPPORTED;
-  if (desc->w_live < 0 || desc->n_live < 0 || desc->n_live > 8 || (desc->w_live > 0) != (desc->n_live > 0)) return E3K_ERR_INVALID;
-  if (desc->w_live > 0) {      // a narrow layer: a scalar-output plan on the dense layer's weight row
-    if (!e3k_tp_scalar_supported(desc->tp) || (desc->w_live % 4) || desc->w_live > desc->W) return E3K_ERR_UNSUPPORTED;
+  if (desc->w_live < 0 || desc->n_live < 0 || desc->n_live > E3K_NARROW_MAX_SLOTS || (desc->w_live > 0) != (desc->n_live > 0))
+    return E3K_ERR_INVALID;
+  if (desc->w_live > 0) {      // a narrow layer: a scalar-output or a masked plan on the dense layer's weight row
+    if (!(e3k_tp_scalar_supported(desc->tp) || e3k_tp_masked_supported(desc->tp)) || (desc->w_live % 4) || desc->w_live > desc->W)
+      return E3K_ERR_UNSUPPORTED;
     int sum = 0;
     for (int i = 0; i < desc->n_live; ++i) {
       if (desc->live_col[i] < 0 || desc->live_len[i] <= 0 || desc->live_col[i] + desc->live_len[i] > desc->W) return E3K_ERR_INVALID;
@@ -418,7 +420,7 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   // already holds (layer 3 of config_energy at 256 molecules: 213 + 104 us -> 258 us isolated; 217 + 169 -> 261 in the replayed step)
   const bool fused_xw = a->fuse_xw && need_x1 && in_kernel_table(d, r) && r.P && need_radial_side && a->E > 0 && a->g_w && a->x1;
   // A narrow layer (d.w_live > 0: gy zero outside the columns its sets were pruned for) exists on that route only: its walk is the
-  // scalar-output one, its g_w and the transposed table gradient are w_live wide, and g_T -- what the radial stack's backward reads --
+  // scalar-output or the masked one (by its plan), its g_w and the transposed table gradient are w_live wide, and g_T -- what the radial stack's backward reads --
   // is the compact gradient spread over the dense columns.  Dead columns of g_mid and g_w are neither written nor read.
   const bool narrow = d.w_live > 0;
   const int32_t w_rows = narrow ? d.w_live : d.W;      // columns of g_w and of the table gradient the transpose forms
@@ -492,12 +494,18 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
   float* const g_T_rows = narrow ? a->g_T_live : a->g_T;
   auto spread_table_gradient = [&](void* st) -> int {
     if (!narrow) return E3K_OK;
-    int32_t src_col[8];
-    for (int i = 0, pos = 0; i < d.n_live; ++i) {
-      src_col[i] = pos;
-      pos += d.live_len[i];
+    // (compact columns follow each other; live slots that are neighbours in the dense row too make one range)
+    int32_t src_col[E3K_NARROW_MAX_SLOTS], dst_col[E3K_NARROW_MAX_SLOTS], len[E3K_NARROW_MAX_SLOTS];
+    int n = 0;
+    for (int i = 0, pos = 0; i < d.n_live; pos += d.live_len[i], ++i) {
+      if (n && dst_col[n - 1] + len[n - 1] == d.live_col[i]) {
+        len[n - 1] += d.live_len[i];
+      } else {
+        src_col[n] = pos; dst_col[n] = d.live_col[i]; len[n] = d.live_len[i];
+        ++n;
+      }
     }
-    return e3k_expand_columns(a->g_T_live, r.R, d.w_live, d.W, src_col, d.live_col, d.live_len, d.n_live, a->g_T, st);
+    return e3k_expand_columns(a->g_T_live, r.R, d.w_live, d.W, src_col, dst_col, len, n, a->g_T, st);
   };
   const bool ride = fused_xw && r.use_table && side == main && side3 == main && !rtable_timed && a->g_T && a->table_ws &&
                     (r.have_rows || !(need_last || need_hidden || a->need_radial));
@@ -506,8 +514,11 @@ extern "C" int e3k_layer_bwd(const e3k_layer* L, const e3k_layer_bwd_args* a) {
     if (!d.tp_bwd_x_overwrites && e3k::zero_fill(a->g_x1, sizeof(float) * a->N * d.d_x1, (hipStream_t)main))
       return E3K_ERR_LAUNCH;
     Timed t(L, E3K_PROF_TP_BWD_X, main, a->N, a->E);
-    if (narrow) {
+    if (narrow && e3k_tp_scalar_supported(d.tp)) {      // (the plan names the narrow form: include/e3k.h, e3k_layer_desc)
       E3K_TRY(e3k_tp_bwd_xw_scalar_ptable(d.tp, a->x1, r.P, d.W, d.live_col, r.erec_src, a->g_mid, a->src_ptr, a->N, a->E, a->g_x1, a->g_w,
+                                          main));
+    } else if (narrow) {
+      E3K_TRY(e3k_tp_bwd_xw_masked_ptable(d.tp, a->x1, r.P, d.W, d.live_col, r.erec_src, a->g_mid, a->src_ptr, a->N, a->E, a->g_x1, a->g_w,
                                           main));
     } else if (fused_xw) {      // ... and the per-edge weight gradient in the same walk: no tp_bwd_w pass below
       E3K_TRY(e3k_tp_bwd_xw_ptable(d.tp, a->x1, r.P, r.erec_src, a->g_mid, a->src_ptr, a->N, a->E, a->g_x1, a->g_w, main));

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void tp_bwd_xw_scalar_kernel(TpArgs a, ScalarC
   else tp_bwd_xw_scalar_body<2>(a, g, cols.w_live, toff, node, u);
 }
 
-constexpr int kExpandMaxRanges = 8;
+constexpr int kExpandMaxRanges = E3K_NARROW_MAX_SLOTS;      // (a range per live slot of a narrow layer; callers merge neighbours)
 struct ExpandRanges {
   int32_t n;
   int32_t src[kExpandMaxRanges], dst[kExpandMaxRanges], len[kExpandMaxRanges];      // columns; all multiples of 4

@@ -37,7 +37,18 @@ MAX_ROUNDS = 4
 # end in those columns only -- NativeLayer.narrow; everything else about the mark's absence or the layer's shape falls back to the
 # dense backward.  0: always dense (reference runs, tests)
 LIVE_GRAD = _knob("E3K_LIVE_GRAD")
-NARROW_MAX_GROUPS = 8      # (e3k_layer_desc.live_col)
+NARROW_MAX_GROUPS = 8      # groups of a narrow plan (kScalarMaxGroups, kMaskedMaxGroups: csrc/e3k_tp_scalar.hip, e3k_tp_masked.hip)
+NARROW_MAX_SLOTS = L.NARROW_MAX_SLOTS      # live path slots (e3k_layer_desc.live_col)
+# the masked narrow form is built when at most this share of the rows the dense walk gathers per (edge, channel) is live: a layer
+# that keeps nearly all of them (the layer two below a scalar head: 0.98) gains nothing from a second plan
+NARROW_MAX_SHARE = 0.75
+
+
+def live_input_cols(ls: "LiveSets") -> tuple:
+    """The column ranges of the layer INPUT outside which a narrow backward leaves g_x exactly zero: the input blocks of its live
+    linear_1 and self-connection instructions (the same ranges in the e3nn and the channel-fastest layout of the row)."""
+    ins_all = list(ls.lin1) + [ins for _, ins in ls.sc]
+    return tuple(sorted({(ins.in_off, ins.in_off + ins.mul_in * ins.dim) for ins in ins_all}))
 
 
 def _hits(lo: int, hi: int, ranges) -> bool:
@@ -209,8 +220,14 @@ class NativeLayer:
         return LiveSets(tuple(cols), conv, post, sc, mid, slots, w, sorted(set(x1)), lin1)
 
     def narrow(self, cols) -> Optional["NativeLayer"]:
-        """The layer object whose backward computes only what ``live_sets(cols)`` names, or None when the executor has no such form:
-        every live path must be a slot (l2 = l1, l3 = 0) with l1 <= 2 (``csrc/e3k_tp_scalar.hip``).  Built once per column set."""
+        """The layer object whose backward computes only what ``live_sets(cols)`` names, or None when the executor has no such form.
+        Two forms (``nl.form``), both for layers without an addend whose live groups have a multiple of 64 channels:
+
+        * "scalar": every live path is a slot (l2 = l1, l3 = 0) with l1 <= 2 -- one group per live slot (``csrc/e3k_tp_scalar.hip``);
+        * "masked": the live groups with the mask of their live slots (``csrc/e3k_tp_masked.hip``: l1 <= 2, l3 <= 2), when at most
+          ``NARROW_MAX_SHARE`` of the rows the dense walk gathers per (edge, channel), sum of 2 l3 + 1 over the slots, are live.
+
+        Built once per column set."""
         cols = tuple(cols)
         if cols in self.narrows:
             return self.narrows[cols]
@@ -219,20 +236,41 @@ class NativeLayer:
         plan, nl = self.plan, None
         ls = self.live_sets(cols)
         groups = plan.tp_plan.groups
-        fits = (0 < len(ls.slots) <= NARROW_MAX_GROUPS and len({gi for gi, _ in ls.slots}) == len(ls.slots) and not plan.addend
-                and all(tp_slots(groups[gi].l1)[q] == (groups[gi].l1, 0) and groups[gi].l1 <= 2 and groups[gi].mul % 64 == 0
-                        for gi, q in ls.slots))
+        tp = plan.tp_plan
+        usable = bool(ls.slots) and not plan.addend and all(groups[gi].l1 <= 2 and groups[gi].mul % 64 == 0 for gi, _ in ls.slots)
+        scalar = (usable and len(ls.slots) <= NARROW_MAX_GROUPS and len({gi for gi, _ in ls.slots}) == len(ls.slots)
+                  and all(tp_slots(groups[gi].l1)[q] == (groups[gi].l1, 0) for gi, q in ls.slots))
+        rows_live = sum(2 * tp_slots(groups[gi].l1)[q][1] + 1 for gi, q in ls.slots)
+        rows_all = sum(2 * l3 + 1 for g in groups for q, (_, l3) in enumerate(tp_slots(g.l1)) if (g.mask >> q) & 1)
+        masked = (usable and not scalar and len({gi for gi, _ in ls.slots}) <= NARROW_MAX_GROUPS and len(ls.slots) <= NARROW_MAX_SLOTS
+                  and tp.d_sh == 9 and all(tp_slots(groups[gi].l1)[q][1] <= 2 and tuple(groups[gi].y_off[:3]) == (0, 1, 4)
+                                           for gi, q in ls.slots)
+                  and rows_live <= NARROW_MAX_SHARE * rows_all)
+        fits = scalar or masked
         if fits:
             live_groups, pos = [], 0
-            for gi, q in ls.slots:
-                g, n = groups[gi], L.TpGroup()
-                n.l1, n.x_off, n.mul, n.mask = g.l1, g.x_off, g.mul, 1 << q
-                for t in range(4):
-                    n.y_off[t] = g.y_off[t]
-                n.w_off[q], n.out_off[q], n.out_stride[q], n.coeff[q] = pos, g.out_off[q], g.out_stride[q], g.coeff[q]
-                pos += g.mul
-                live_groups.append(n)
-            tp = plan.tp_plan
+            if scalar:
+                for gi, q in ls.slots:
+                    g, n = groups[gi], L.TpGroup()
+                    n.l1, n.x_off, n.mul, n.mask = g.l1, g.x_off, g.mul, 1 << q
+                    for t in range(4):
+                        n.y_off[t] = g.y_off[t]
+                    n.w_off[q], n.out_off[q], n.out_stride[q], n.coeff[q] = pos, g.out_off[q], g.out_stride[q], g.coeff[q]
+                    pos += g.mul
+                    live_groups.append(n)
+            else:
+                # the live groups in the dense order, each with its live slots' mask; compact weight columns in (group, slot) order,
+                # the order of ls.slots / ls.w (and of live_col below)
+                for gi in sorted({gi for gi, _ in ls.slots}):
+                    g, n = groups[gi], L.TpGroup()
+                    n.l1, n.x_off, n.mul, n.mask = g.l1, g.x_off, g.mul, 0
+                    for t in range(4):
+                        n.y_off[t] = g.y_off[t]
+                    for q in [q for gj, q in ls.slots if gj == gi]:
+                        n.mask |= 1 << q
+                        n.w_off[q], n.out_off[q], n.out_stride[q], n.coeff[q] = pos, g.out_off[q], g.out_stride[q], g.coeff[q]
+                        pos += g.mul
+                    live_groups.append(n)
             # the same layer with the dead instructions and paths taken out
             pruned = dict(tp_plan=ops.TpPlan(live_groups, tp.d_in, tp.d_sh, pos, tp.d_mid),
                           post_spec=dataclasses.replace(plan.post_spec, instr=ls.post, in_covered=_covers(ls.post, plan.post_spec.d_in)),
@@ -257,6 +295,7 @@ class NativeLayer:
             for i, (off, mul) in enumerate(ls.w):
                 d.live_col[i], d.live_len[i] = off, mul
             nl.live = ls
+            nl.form = "scalar" if scalar else "masked"      # (the executor reads it off the plan: e3k_tp_scalar_supported)
         self.narrows[cols] = nl
         return nl
 
@@ -878,6 +917,7 @@ class NativeConvBlockFn(torch.autograd.Function):
 
         plan, topo, groups, in_cf, out_cf, fork, n_hidden, table, carve, rcarve, need_relayout = ctx.cfg
         live_cols = memo.recall(gy, "live_cols") if (LIVE_GRAD and gy is not None) else None      # (before anything touches gy)
+        hint_cols = memo.recall(gy, "live_cols_hint") if (LIVE_GRAD and gy is not None and live_cols is None) else None
         saved = ctx.saved_tensors
         x_in, edge_radial, sh, buf, rbuf, w, w_lin1, w_post, w_sc, w_last, t_keep, m_pre = saved[:12]
         conv_ext = None
@@ -908,18 +948,20 @@ class NativeConvBlockFn(torch.autograd.Function):
         n, e, r = gy.shape[0], sh.shape[0], edge_radial.shape[0]
         # gy marked zero outside some columns, on the route the narrow form exists for (the executor's fused packed-table walk with
         # the rows from the radial stack): the backward of the live paths only.  Anything else: the dense layer.
-        narrow = None
-        if live_cols is not None:
+        narrow = cand = None
+        if live_cols is not None or hint_cols is not None:
             # (built, and its device objects made, at the first marked gradient whichever route that call takes: the eager warm-up of
-            #  a step that is captured afterwards may fork where the capture does not, and nothing may be created while capturing)
-            cand = native_layer(plan).narrow(live_cols)
+            #  a step that is captured afterwards may fork where the capture does not, and nothing may be created while capturing.
+            #  A layer that declines the narrow route hands the columns it WOULD have marked down as a "live_cols_hint": the layer
+            #  below makes its narrow form on that hint and runs dense -- a hint says nothing about the gradient's values.)
+            cand = native_layer(plan).narrow(live_cols if live_cols is not None else hint_cols)
             if cand is not None:
                 cand.handle(dev)
                 # (the executor states the same condition from its side -- csrc/e3k_layer.hip, e3k_layer_bwd: "if (narrow && !(fused_xw
                 #  && ...": it refuses a narrow layer off this route with E3K_ERR_UNSUPPORTED before its first launch.  Keep the two
                 #  in step: a route this gate lets through and the executor refuses raises instead of running the dense layer.)
-                if (stack and need_pre and table is not None and p_tab is not None and w is None and (need_x or need_lin1) and e > 0
-                        and gy.dtype == torch.float32 and gy.is_contiguous()):
+                if (live_cols is not None and stack and need_pre and table is not None and p_tab is not None and w is None
+                        and (need_x or need_lin1) and e > 0 and gy.dtype == torch.float32 and gy.is_contiguous()):
                     narrow = cand
         layer = (narrow or native_layer(plan)).handle(dev)
         main = ops.current_stream(dev)
@@ -1074,6 +1116,14 @@ class NativeConvBlockFn(torch.autograd.Function):
             HOST_TIMING[3] += time.perf_counter() - t_c
         else:
             L.check(L.load().e3k_layer_bwd(layer, C.byref(a)), "e3k_layer_bwd")
+        if narrow is not None and g_x is not None:
+            # The narrow layer wrote g_x through its live linear_1 and self-connection instructions only, on a row the executor
+            # zero-filled where they do not reach (csrc/e3k_layer.hip, e3k_layer_bwd: "if (!covered && e3k::zero_fill(a->g_xcf";
+            # the relayout to e3nn blocks copies whole blocks): everything else IS zero, and the layer below may run narrow in turn.
+            # Same rules as the mark of ops.StridedLinearFn.backward: it lives on this tensor object and is void once it is written to.
+            memo.remember(g_x, "live_cols", live_input_cols(narrow.live))
+        elif cand is not None and g_x is not None:
+            memo.remember(g_x, "live_cols_hint", live_input_cols(cand.live))      # (this call ran dense: see "narrow = cand = None")
         if fork:      # (see the forward: only the stream / tensor pairs that need it)
             for st in (side, side2, side3):
                 if st is not main:

@@ -20,6 +20,7 @@ CSRC_DIR = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc"))
 LIB_PATH = _knob("E3K_LIB") or os.path.join(CSRC_DIR, "libe3k.so")  # E3K_LIB: another build, for A/B runs
 
 TP_MAXQ = 8
+NARROW_MAX_SLOTS = 48      # E3K_NARROW_MAX_SLOTS (include/e3k.h): entries of e3k_layer_desc.live_col / live_len
 
 
 class GemmProblem(C.Structure):
@@ -85,7 +86,7 @@ class LayerDesc(C.Structure):
                 + [(k, C.c_int32) for k in ("d_in", "d_x1", "d_mid", "d_conv", "d_out", "W", "post_in_covered", "sc_in_covered",
                                             "lin1_in_covered", "sc_out_covered", "post_out_covered", "tp_bwd_x_overwrites",
                                             "w_live", "n_live")]
-                + [("live_col", C.c_int32 * 8), ("live_len", C.c_int32 * 8)])
+                + [("live_col", C.c_int32 * NARROW_MAX_SLOTS), ("live_len", C.c_int32 * NARROW_MAX_SLOTS)])
 
 
 class LayerRadial(C.Structure):
@@ -238,6 +239,8 @@ SIGNATURES = {
     "e3k_tp_bwd_xw_ptable": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "e3k_tp_scalar_supported": (C.c_int, [_P]),
     "e3k_tp_bwd_xw_scalar_ptable": (C.c_int, [_P, _P, _P, _I32, C.POINTER(_I32), _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "e3k_tp_masked_supported": (C.c_int, [_P]),
+    "e3k_tp_bwd_xw_masked_ptable": (C.c_int, [_P, _P, _P, _I32, C.POINTER(_I32), _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "e3k_expand_columns": (C.c_int, [_P, _I64, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _I32, _P, _P]),
     "e3k_tp_bwd_xw": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "e3k_tp_bwd_xe": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),

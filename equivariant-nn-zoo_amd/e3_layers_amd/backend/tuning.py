@@ -31,7 +31,7 @@ KNOBS: Dict[str, Tuple[object, str, str]] = {
     "E3K_RADIAL_STACK": (1, "path", "the radial MLPs of all layers on one edge embedding evaluated as one batch"),
     "E3K_KW_STACK": (1, "path", "the per-key self-connection weights of all layers formed as one batch"),
     "E3K_TP_TABLE": (1, "path", "table layers interpolate their path weights inside the tensor-product kernels, from the table packed into 12-byte Taylor records (no w[E, W]); 0: interpolation pass"),
-    "E3K_LIVE_GRAD": (1, "path", "a layer whose incoming gradient is marked zero outside some columns (the Linear in front of a scalar head marks it) runs the backward of the live paths only (conv_native.NativeLayer.narrow); 0: always the dense backward"),
+    "E3K_LIVE_GRAD": (1, "path", "a layer whose incoming gradient is marked zero outside some columns (the Linear in front of a scalar head marks it, and a layer that ran narrow marks its own input gradient) runs the backward of the live paths only (conv_native.NativeLayer.narrow); 0: always the dense backward"),
     # ---- streams ----
     "E3K_FWD_FORK": (1, "path", "0: one stream; 1: radial / self-connection / weight-gradient branches on side streams above the edge thresholds (never inside a graph capture)"),
     "E3K_WGRAD_SIDE": (1, "path", "sunk weight gradients of forked layers run on a side stream"),

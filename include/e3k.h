@@ -32,6 +32,7 @@ extern "C" {
 #define E3K_ERR_UNSUPPORTED (-3) /* degree beyond the generated CG tables */
 
 #define E3K_TP_MAXQ 8 /* max (l2,l3) slots per input degree — must equal E3K_MAXQ of e3k_cg_gen.h */
+#define E3K_NARROW_MAX_SLOTS 48 /* live path slots a narrow layer can name (e3k_layer_desc.live_col; e3k_expand_columns' ranges) */
 
 const char* e3k_strerror(int code);
 int e3k_version(void);
@@ -300,7 +301,20 @@ int e3k_tp_scalar_supported(const e3k_tp_plan* plan);
 int e3k_tp_bwd_xw_scalar_ptable(const e3k_tp_plan* plan, const float* x, const void* P, int32_t table_w, const int32_t* table_off,
                                 const int32_t* erec_src, const float* g_out, const int32_t* src_ptr, int64_t N, int64_t E, float* g_x,
                                 float* g_w, void* stream);
-/* dst [rows, w_dst] = 0, except dst[r, dst_col[k] + c] = src[r, src_col[k] + c] for c < len[k], k < n_ranges <= 8 (HOST arrays;
+/* ... and for plans that keep SOME slots of their groups (e3k_tp_masked_supported: at most 8 groups of a multiple of 64 channels,
+ * l1 <= 2, enabled slots with l3 <= 2, not split, d_sh = 9; else E3K_ERR_UNSUPPORTED, nothing written) -- what is left of a layer's
+ * product when the gradient of its output is zero outside some blocks -- csrc/e3k_tp_masked.hip.  The sums of e3k_tp_bwd_xw_ptable
+ * over the enabled slots only, in its order: g_x (the groups' blocks only: the caller zero-fills what no group owns, and all of it
+ * when two groups share an input block) and the enabled slots' columns of g_w [E, plan w_numel] carry the bits it gives on the
+ * dense plan when the other slots' rows of g_out are zero.  The plan numbers its weight columns compactly; the packed table may be
+ * a wider layer's: P [K + 1, 3 table_w] with the column of the k-th enabled slot, counted in (group, slot) order, at live_col[k]
+ * (HOST array).  live_col = NULL, table_w = 0: the table has the plan's own columns.  Of g_out only the enabled slots' rows are
+ * read. */
+int e3k_tp_masked_supported(const e3k_tp_plan* plan);
+int e3k_tp_bwd_xw_masked_ptable(const e3k_tp_plan* plan, const float* x, const void* P, int32_t table_w, const int32_t* live_col,
+                                const int32_t* erec_src, const float* g_out, const int32_t* src_ptr, int64_t N, int64_t E, float* g_x,
+                                float* g_w, void* stream);
+/* dst [rows, w_dst] = 0, except dst[r, dst_col[k] + c] = src[r, src_col[k] + c] for c < len[k], k < n_ranges <= 48 (HOST arrays;
  * columns, widths and lengths multiples of 4, src and dst 16-byte aligned, the ranges of dst disjoint): a compact knot-table
  * gradient spread over the dense table's columns.  One launch, every element of dst written. */
 int e3k_expand_columns(const float* src, int64_t rows, int32_t w_src, int32_t w_dst, const int32_t* src_col, const int32_t* dst_col,
@@ -1038,14 +1052,17 @@ typedef struct {
   int32_t d_in, d_x1, d_mid, d_conv, d_out, W;
   int32_t post_in_covered, sc_in_covered, lin1_in_covered, sc_out_covered, post_out_covered, tp_bwd_x_overwrites;
   /* A NARROW layer (w_live > 0; backward only): the same layer for a gy that is zero outside some columns, so that only n_live path
-   * slots, all of the form (l2 = l1, l3 = 0), carry a gradient.  `tp` is then a plan of e3k_tp_scalar_supported with one group per
-   * live slot and the weight columns numbered compactly (w_numel = w_live: group i's live_len[i] = mul columns behind those of the
-   * groups before it); group i's column in the DENSE weight row (W wide: the packed table, g_T) is live_col[i].  The backward template sets hold only the problems that end in a live block.  g_w is then
-   * [E, w_live], g_mid is written (and read) on the live slots' columns only, the table gradient is formed compactly in g_T_live
-   * [knots + 1, w_live] and spread into the dense, zero-filled g_T.  e3k_layer_bwd takes such a layer on the fused packed-table
-   * route with the rows from the radial stack only (E3K_ERR_UNSUPPORTED otherwise); e3k_layer_fwd refuses it. */
+   * slots carry a gradient.  `tp` is then a pruned plan with the weight columns numbered compactly (w_numel = w_live: live slot i's
+   * live_len[i] = mul columns behind those of the live slots before it, in (group, slot) order); slot i's column in the DENSE weight
+   * row (W wide: the packed table, g_T) is live_col[i].  The plan names which of the two forms the layer is:
+   *   SCALAR  e3k_tp_scalar_supported(tp): every live slot is (l2 = l1, l3 = 0), one group per live slot (csrc/e3k_tp_scalar.hip);
+   *   MASKED  otherwise, e3k_tp_masked_supported(tp): the live groups with their live slots' mask (csrc/e3k_tp_masked.hip).
+   * The backward template sets hold only the problems that end in a live block.  g_w is then [E, w_live], g_mid is written (and
+   * read) on the live slots' columns only, the table gradient is formed compactly in g_T_live [knots + 1, w_live] and spread into
+   * the dense, zero-filled g_T.  e3k_layer_bwd takes such a layer on the fused packed-table route with the rows from the radial
+   * stack only (E3K_ERR_UNSUPPORTED otherwise); e3k_layer_fwd refuses it. */
   int32_t w_live, n_live;
-  int32_t live_col[8], live_len[8];
+  int32_t live_col[E3K_NARROW_MAX_SLOTS], live_len[E3K_NARROW_MAX_SLOTS];
 } e3k_layer_desc;
 
 typedef struct e3k_layer e3k_layer;
