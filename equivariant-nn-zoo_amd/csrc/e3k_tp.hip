@@ -663,7 +663,13 @@ __device__ __forceinline__ void tp_bwd_x_body_full(const TpArgs& a, const e3k_tp
 #pragma unroll
     for (int i = 0; i < D1; ++i) xs2[i] = (xr2 + i * mul)[u];
   }
-  const int beg = uniform(a.ptr[node]), end = uniform(a.ptr[node + 1]);
+  int beg, end;
+  if constexpr (PACKED) {      // (the record walks: the row range by a scalar load as well, see row_range)
+    const int2 rr = row_range(a.ptr, node);
+    beg = rr.x; end = rr.y;
+  } else {
+    beg = uniform(a.ptr[node]); end = uniform(a.ptr[node + 1]);
+  }
   EdgeRec cur{};
   if constexpr (PACKED) {
     if (beg < end) cur = load_rec(a.erec, beg);

@@ -150,8 +150,21 @@ struct EdgeRec {
   float y[9];
   int e;
 };
+// The record is read through a constant-address-space pointer: a kernel that stores through other members of its TpArgs (g_x, g_w:
+// every backward walk) otherwise gets the record by vector loads of one lane-uniform address, a v_readfirstlane per dword and a wait
+// for the "prefetched" record in front of the edge's row loads, because nothing tells the compiler that its stores leave the records
+// alone.  This rests on ONE condition: the record buffer is written by EARLIER launches only (e3k_edge_records, in the preparation
+// that precedes the walks on the same stream or graph), never by the kernel that reads it -- the scalar cache is not coherent with
+// a kernel's own vector stores.  The forward walk's record loads, scalar by themselves, have always rested on the same condition.
+typedef const __attribute__((address_space(4))) int32_t* const_words;
+__device__ __forceinline__ const_words as_constant(const int32_t* p) { return (const_words)p; }
+// the row range [ptr[node], ptr[node + 1]) of a backward walk, the same way and on the same condition (e3k_csr_build precedes the walks)
+__device__ __forceinline__ int2 row_range(const int32_t* ptr, int node) {
+  const const_words p = as_constant(ptr + node);
+  return make_int2(p[0], p[1]);
+}
 __device__ __forceinline__ EdgeRec load_rec(const int32_t* __restrict__ erec, int t) {
-  const int32_t* __restrict__ p = static_cast<const int32_t*>(__builtin_assume_aligned(erec + 16 * (int64_t)t, 64));
+  const const_words p = as_constant(static_cast<const int32_t*>(__builtin_assume_aligned(erec + 16 * (int64_t)t, 64)));
   EdgeRec r;
   r.nbr = uniform(p[0]);
   r.bin = uniform(p[1]);

@@ -51,7 +51,8 @@ __device__ __forceinline__ void tp_bwd_xw_masked_body(const TpArgs& a, const e3k
     gx[i] = 0.0f;
     xs[i] = (xr + i * mul)[u];
   }
-  const int beg = uniform(a.ptr[node]), end = uniform(a.ptr[node + 1]);
+  const int2 rr = row_range(a.ptr, node);
+  const int beg = rr.x, end = rr.y;
   EdgeRec cur{};
   if (beg < end) cur = load_rec(a.erec, beg);
   for (int t = beg; t < end; ++t) {
