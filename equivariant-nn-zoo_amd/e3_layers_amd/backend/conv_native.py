@@ -27,7 +27,8 @@ from . import memo, ops, radial_table
 # bench.py reads these three to describe the path it measured; the executor, the packed table and the fused
 # tensor-product backward are the only forms there are
 ENABLED = TP_TABLE_PACKED = TP_BWD_FUSED = 1
-PROF_KINDS = {"tp_fwd": 0, "tp_bwd_x": 1, "tp_bwd_w": 2, "rtable_fwd": 3, "rtable_bwd": 4, "radial_last_fwd": 5}
+PROF_KINDS = {k: L.DEFINES["E3K_PROF_" + k.upper()]
+              for k in ("tp_fwd", "tp_bwd_x", "tp_bwd_w", "rtable_fwd", "rtable_bwd", "radial_last_fwd")}
 _LAYERS: List["NativeLayer"] = []      # every layer object created (bench.py arms / reads their per-kernel timers)
 
 

@@ -182,26 +182,27 @@ class Collation:
     def _describe(self) -> None:
         from ..backend import lib as L
 
-        ds, out, kinds = self.ds, self.batch.data, {"node": 0, "edge": 1, "graph": 2}
+        ds, out = self.ds, self.batch.data
+        K = {k[len("E3K_COLLATE_"):]: v for k, v in L.DEFINES.items() if k.startswith("E3K_COLLATE_")}      # include/e3k.h
         fields = []
         for key in ds.keys:
             if out[key].numel() == 0:
                 continue                # (no edges in the bucket: nothing to write)
             if key == "edge_index":
-                fields.append(L.CollateField(kind=3, src=L.ptr(ds.edge_index), dst=L.ptr(out[key]), src_ld=ds.edge_index.shape[1],
-                                             dst_ld=self.e_cap))
+                fields.append(L.CollateField(kind=K["EDGE_INDEX"], src=L.ptr(ds.edge_index), dst=L.ptr(out[key]),
+                                             src_ld=ds.edge_index.shape[1], dst_ld=self.e_cap))
                 continue
             kind, t = ds.fields[key]
             row_bytes = t.element_size() * int(np.prod(t.shape[1:], dtype=np.int64))
             table = key == "pos"
-            fields.append(L.CollateField(kind=kinds[kind], ghost=1 if table else 0, row_bytes=row_bytes, src=L.ptr(t),
-                                         dst=L.ptr(out[key]), table=L.ptr(self.table) if table else None))
-        fields.append(L.CollateField(kind=4, dst=L.ptr(out["_node_segment"])))
+            fields.append(L.CollateField(kind=K[kind.upper()], ghost=K["GHOST_TABLE"] if table else K["GHOST_FIRST"], row_bytes=row_bytes,
+                                         src=L.ptr(t), dst=L.ptr(out[key]), table=L.ptr(self.table) if table else None))
+        fields.append(L.CollateField(kind=K["NODE_SEGMENT"], dst=L.ptr(out["_node_segment"])))
         if self.e_cap:
-            fields.append(L.CollateField(kind=5, dst=L.ptr(out["_edge_segment"])))
-        fields.append(L.CollateField(kind=6, dst=L.ptr(out["_node_weight"])))
-        if len(fields) > 16:
-            raise ValueError(f"{len(fields)} collated fields: the kernel takes 16 (E3K_COLLATE_MAX_FIELDS)")
+            fields.append(L.CollateField(kind=K["EDGE_SEGMENT"], dst=L.ptr(out["_edge_segment"])))
+        fields.append(L.CollateField(kind=K["NODE_WEIGHT"], dst=L.ptr(out["_node_weight"])))
+        if len(fields) > K["MAX_FIELDS"]:
+            raise ValueError(f"{len(fields)} collated fields: the kernel takes {K['MAX_FIELDS']} (E3K_COLLATE_MAX_FIELDS)")
         self._fields = (L.CollateField * len(fields))(*fields)
 
     def __call__(self) -> None:

@@ -16,6 +16,18 @@
  *  - feature layouts: "e3nn" = each `mul x l` block stored [mul][2l+1] (reference layout,
  *    README.md:108-110); "cf" = channel-fastest, block stored [2l+1][mul] (internal layout of
  *    the fused convolution: 64 channels = 64 lanes read 256 contiguous bytes).
+ *
+ * THIS HEADER IS PARSED: the Python binding (e3_layers_amd/backend/abi.py -> lib.py) derives every ctypes struct, signature
+ * and constant from it at import, so it is the only place the interface is written down -- and it must stay inside the C
+ * subset that parser knows (anything else makes the import raise, naming the text):
+ *  - `#define E3K_NAME <integer literal>`, optionally parenthesised (expression bodies are allowed and ignored); no other
+ *    preprocessor line between the include guard and its #endif but the two `extern "C"` blocks;
+ *  - `typedef struct { ... } e3k_x;` and opaque `typedef struct e3k_x e3k_x;` -- no unions, enums, bit-fields, nested
+ *    struct bodies or function pointers;
+ *  - fields and parameters of the types int, int32_t, uint32_t, int64_t, uint8_t, float, double, structs defined above
+ *    (by value or by pointer), pointers (to pointers) to any of these, to void and to opaque types, `const` anywhere;
+ *    several declarators per line (`void *a, *b;`); field arrays sized by a literal or an integer #define;
+ *  - prototypes returning int, int64_t, void or const char*.
  */
 #ifndef E3K_H
 #define E3K_H
