@@ -173,6 +173,15 @@ __global__ __launch_bounds__(1024) void nlist_scan_kernel(const int32_t* __restr
   }
 }
 
+// The scan for the periodic builder of e3k_pbc.hip (declared there): the same kernel, no criterion cells.
+int nlist_scan_launch(const int32_t* counts, const int64_t* node_ptr, int64_t N, int32_t G, int64_t e_cap, int64_t* offsets,
+                      int64_t* n_edges, int64_t* state, int32_t* flag, hipStream_t stream) {
+  hipLaunchKernelGGL(nlist_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, node_ptr, N, G, e_cap, offsets, n_edges, state, flag,
+                     (int64_t*)nullptr);
+  E3K_CHECK_LAUNCH();
+  return E3K_OK;
+}
+
 }  // namespace e3k
 
 static bool nlist_args_ok(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G) {

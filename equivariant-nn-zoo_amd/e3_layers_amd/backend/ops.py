@@ -2306,6 +2306,37 @@ def edge_vector(pos, topo: GraphTopo):
     return EdgeVectorFn.apply(_c(pos), topo)
 
 
+class PeriodicEdgeVectorFn(torch.autograd.Function):
+    """``vec = pos[dst] - pos[src] + shift @ cell`` and its length (``e3k_pbc_edge_vector_fwd``).  The shift is a constant: the
+    backward is ``EdgeVectorFn``'s, and the second backward (``EdgeScatterFn.backward``) stays the UNSHIFTED gather
+    ``h[dst] - h[src]`` -- the adjoint of a linear map does not see its offset."""
+
+    @staticmethod
+    def forward(ctx, pos, topo: GraphTopo, shift, node_seg, cell):
+        L.require_cuda(pos, shift, node_seg, cell)
+        pos = L.f32c(pos)
+        e = topo.num_edges
+        vec = torch.empty(e, 3, device=pos.device, dtype=torch.float32)
+        length = torch.empty(e, device=pos.device, dtype=torch.float32)
+        L.check(L.load().e3k_pbc_edge_vector_fwd(L.ptr(pos), L.ptr(topo.src), L.ptr(topo.dst), L.ptr(shift), L.ptr(node_seg), L.ptr(cell),
+                                                 cell.shape[0], pos.shape[0], e, L.ptr(vec), L.ptr(length), L.stream_ptr()),
+                "e3k_pbc_edge_vector_fwd")
+        ctx.save_for_backward(vec, length)
+        ctx.topo, ctx.n = topo, pos.shape[0]
+        return vec, length
+
+    @staticmethod
+    def backward(ctx, g_vec, g_len):
+        return (EdgeVectorFn.backward(ctx, g_vec, g_len)[0], None, None, None, None)
+
+
+def edge_vector_periodic(pos, topo: GraphTopo, shift, node_seg, cell):
+    """``shift`` [E, 3] int32, ``node_seg`` [N] int64, ``cell`` [G, 3, 3] fp32: contiguous device tensors."""
+    if shift.dtype != torch.int32 or node_seg.dtype != torch.int64 or cell.dtype != torch.float32:
+        raise TypeError("edge_vector_periodic needs an int32 shift, an int64 node segment and an fp32 cell")
+    return PeriodicEdgeVectorFn.apply(_c(pos), topo, shift.contiguous(), node_seg.contiguous(), cell.contiguous())
+
+
 class SphHarmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vec, ls: Tuple[int, ...], normalize: bool, normalization: int):

@@ -25,6 +25,19 @@ the reverse-diffusion loop on cutoff graphs): it rewrites the FIXED ``[2, e_cap]
 ``run/graph_step.pad_batch`` in place (``csrc/e3k_nlist.hip``), reads nothing back, and is therefore part of a captured HIP graph.
 ``computeEdgeIndex`` hands a batch that carries ``_nlist_state`` (the marker the capped loops put into their padded batch) over to it:
 a model that owns its ``edge_index`` layer gets the capped build inside a capture without knowing of it.
+
+Periodic cells (ASE's data contract): a batch with ``cell`` (per graph ``[G, 3, 3]`` fp32, rows = lattice vectors a, b, c; attrs
+``("graph", "3x1o")``, stored flat as ``[G, 9]``) and optionally ``pbc`` (``[G, 3]`` integer or bool, ``("graph", "3x0e")``; absent:
+periodic on every axis) gets the minimum-image list: ``computeEdgeIndex`` / ``computeEdgeIndexCapped`` return ``edge_index`` and
+``edge_cell_shift`` (``[E, 3]`` int32, the image numbers of the destination, ``("edge", "3x0e")``), and ``computeEdgeVector`` forms
+``pos[dst] - pos[src] + shift @ cell`` (``csrc/e3k_pbc.hip``; one statement of the arithmetic: ``csrc/e3k_pbc.h``, restated in torch
+by ``_periodic_rule``).  The restriction that keeps one slot per ordered pair: every cell's perpendicular width along each periodic
+axis exceeds ``2 r_max (1 + 1e-3)`` -- ``check_cell`` raises otherwise, once on the host where a cell enters.  Positions stay unwrapped
+(the image is taken from differences; in fp32 that is sound up to about a thousand cell widths from the origin: the error of a
+fractional component, about ``|d| / w 2^-22``, must stay below the 5e-4 the margin leaves to the rounding tie); ``wrap_positions``
+is for output.  NOT served: narrower cells (crystal unit cells, several images per pair: replicate to a supercell); stress, virial
+and variable cells; cell lists (the search stays O(n^2) per graph); ``criteria`` and pre-existing edges together with a cell; the
+sampler and score-step loops and ``DeviceDataset`` with a cell.  A batch without ``cell`` takes exactly the paths it took before.
 """
 from __future__ import annotations
 
@@ -51,7 +64,12 @@ def computeEdgeVector(data: Dict[str, Tensor], attrs: Dict[str, Tuple[str, str]]
         return data, attrs
     topo = get_topology(data, pos.shape[0])
     data.update(topo.as_dict())
-    vec, length = ops.edge_vector(pos, topo)
+    if "edge_cell_shift" in data:      # a periodic list: the builder's vectors, recomputed from the stored image numbers
+        cell, _, _ = _cell_operands(data)
+        vec, length = ops.edge_vector_periodic(pos, topo, _shift_operand(data["edge_cell_shift"], topo.num_edges), _node_segment(data, pos),
+                                               cell)
+    else:
+        vec, length = ops.edge_vector(pos, topo)
     # functions of the input positions alone: no gradient under ops.params_only_backward()
     from_input = pos.grad_fn is None and not isinstance(pos, torch.nn.Parameter)
     ops.mark_data_only(vec, from_input)
@@ -63,6 +81,7 @@ def computeEdgeVector(data: Dict[str, Tensor], attrs: Dict[str, Tuple[str, str]]
 
 
 computeEdgeVector.data_only_inputs = ("pos", "edge_index")      # (SequentialGraphNetwork.prepare_data: parameter-free, reads these keys)
+computeEdgeVector.data_only_optional_inputs = ("edge_cell_shift", "cell")      # ... and these where the batch has them (a periodic batch)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -271,10 +290,192 @@ def _radius_graph_device(data, attrs, pos: Tensor, r_max: float):
     return {"edge_index": edge_index}, attrs
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Periodic cells: the minimum-image rule of csrc/e3k_pbc.h
+# ---------------------------------------------------------------------------------------------------------------------
+PBC_MARGIN = 1e-3      # every periodic perpendicular width must exceed 2 r_max (1 + PBC_MARGIN)
+
+
+def _cell_pbc_host(cell, pbc):
+    """float64 [G, 3, 3] and bool [G, 3] on the host (``pbc`` None: periodic on every axis)."""
+    c = torch.as_tensor(cell).detach().to("cpu", torch.float64).reshape(-1, 3, 3)
+    if pbc is None:
+        p = torch.ones(c.shape[0], 3, dtype=torch.bool)
+    else:
+        p = torch.as_tensor(pbc).detach().to("cpu").reshape(-1, 3) != 0
+        if p.shape[0] != c.shape[0]:
+            raise ValueError(f"pbc names {p.shape[0]} graphs, cell {c.shape[0]}")
+    return c, p
+
+
+def _inverse_cells(c: Tensor) -> Tensor:
+    """float64 inverses [G, 3, 3]; an all-zero cell (the ghost graph's, a graph without a periodic axis) has the zero inverse."""
+    inv = torch.zeros_like(c)
+    live = torch.linalg.det(c) != 0
+    if bool(live.any()):
+        inv[live] = torch.linalg.inv(c[live])
+    return inv
+
+
+def check_cell(cell, pbc, r_max: float) -> None:
+    """Raises ``ValueError`` (naming graph, axis, width and the required minimum) unless the perpendicular width of every cell along
+    each PERIODIC axis exceeds ``2 r_max (1 + 1e-3)``: the premise of the one-image-per-pair list.  Widths are computed in float64 on
+    the host: along axis k it is ``1 / |column k of cell^-1|``.  Non-periodic axes are ignored (their lattice vector still has to
+    make the cell invertible when another axis is periodic)."""
+    c, p = _cell_pbc_host(cell, pbc)
+    need = 2.0 * float(r_max) * (1.0 + PBC_MARGIN)
+    for g in range(c.shape[0]):
+        if not bool(p[g].any()):
+            continue
+        if float(torch.linalg.det(c[g])) == 0.0 or not bool(torch.isfinite(c[g]).all()):
+            raise ValueError(f"graph {g}: the cell is singular (or not finite) but has a periodic axis")
+        width = 1.0 / torch.linalg.inv(c[g]).norm(dim=0)
+        for k in range(3):
+            if bool(p[g, k]) and not float(width[k]) > need:
+                raise ValueError(f"graph {g}, axis {'abc'[k]}: the cell's perpendicular width {float(width[k]):.6g} does not exceed "
+                                 f"2 r_max (1 + {PBC_MARGIN:g}) = {need:.6g}; narrower cells are not served (replicate to a supercell)")
+
+
+def _cell_operands(data):
+    """``(cell, inv_cell, pbc)`` of a batch with ``cell`` as the kernels read them: fp32 [G, 3, 3] (contiguous), its inverse formed on
+    the host in float64 and rounded to fp32, int32 [G, 3]; the last two are kept in the batch (``_inv_cell``, ``_pbc_mask``: cells
+    do not vary), so that only the first call -- outside a capture -- goes to the host."""
+    cell = data["cell"]
+    dev = cell.device
+    if cell.dtype != torch.float32 or not cell.is_contiguous():
+        raise ValueError("cell must be a contiguous fp32 tensor of [G, 3, 3] (stored flat: [G, 9])")
+    n = cell.numel() // 9
+    inv, mask = data.get("_inv_cell"), data.get("_pbc_mask")
+    if inv is None or mask is None or inv.device != dev or inv.numel() != 9 * n or mask.numel() != 3 * n:
+        c, p = _cell_pbc_host(cell, data.get("pbc"))
+        inv = data["_inv_cell"] = _inverse_cells(c).to(torch.float32).reshape(n, 9).contiguous().to(dev)
+        mask = data["_pbc_mask"] = p.to(torch.int32).contiguous().to(dev)
+    return cell.reshape(n, 3, 3), inv.reshape(n, 3, 3), mask
+
+
+def _shift_operand(shift: Tensor, n_edges: int) -> Tensor:
+    if shift.dtype != torch.int32 or shift.numel() != 3 * n_edges:
+        raise ValueError(f"edge_cell_shift must be an int32 tensor of [E, 3] (got {str(shift.dtype).replace('torch.', '')} "
+                         f"{tuple(shift.shape)} for {n_edges} edges)")
+    return shift.contiguous()
+
+
+def _node_segment(data, pos: Tensor) -> Tensor:
+    seg = data.get("_node_segment")
+    if seg is None or seg.device != pos.device or seg.numel() != pos.shape[0]:
+        seg = segment_ids(data["_n_nodes"].reshape(-1).to(pos.device), pos.shape[0])
+    return seg.contiguous()
+
+
+def _fma32(a: Tensor, b: Tensor, c: Tensor) -> Tensor:
+    """fmaf on fp32 tensors: the product of two fp32 numbers is exact in float64."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _periodic_rule(d: Tensor, cell: Tensor, inv: Tensor, pbc: Tensor):
+    """The rule of ``csrc/e3k_pbc.h`` on fp32 displacements ``d`` [P, 3] with each pair's own ``cell``, ``inv`` [P, 3, 3] (fp32) and
+    ``pbc`` [P, 3]: the image numbers (int32 [P, 3]), the vectors (fp32 [P, 3]) and their lengths (fp32 [P]), operation by operation."""
+    s = _fma32(d[:, 2:3], inv[:, 2, :], _fma32(d[:, 1:2], inv[:, 1, :], d[:, 0:1] * inv[:, 0, :]))
+    n = torch.where(pbc != 0, -torch.round(s), torch.zeros_like(s))
+    v = _fma32(n[:, 2:3], cell[:, 2, :], _fma32(n[:, 1:2], cell[:, 1, :], _fma32(n[:, 0:1], cell[:, 0, :], d)))
+    sq = v * v
+    return n.to(torch.int32), v, torch.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])
+
+
+def _refuse_with_cell(data, criteria) -> None:
+    if criteria is not None:
+        raise ValueError("computeEdgeIndex: a pair criterion together with a periodic cell is not served")
+    if "edge_index" in data:
+        raise ValueError("computeEdgeIndex: pre-existing edges together with a periodic cell are not served (drop edge_index first)")
+
+
+def _periodic_graph_host(data, attrs, pos: Tensor, r_max: float):
+    """The torch restatement on whichever device holds the data: all ordered pairs of a graph, the rule, strict ``<``."""
+    cell, pbc = data["cell"], data.get("pbc")
+    check_cell(cell, pbc, r_max)
+    pos = pos.detach().to(torch.float32)
+    n_nodes = data["_n_nodes"]
+    c64, p = _cell_pbc_host(cell, pbc)
+    cell32 = torch.as_tensor(cell).detach().to(pos.device, torch.float32).reshape(-1, 3, 3)
+    inv32 = _inverse_cells(c64).to(torch.float32).to(pos.device)
+    p = p.to(pos.device)
+    cand = _all_pairs(n_nodes, pos.device)
+    cand = cand[:, cand[0] != cand[1]]
+    g = segment_ids(n_nodes.reshape(-1).to(pos.device), pos.shape[0])[cand[0]]
+    shift, _, length = _periodic_rule(pos[cand[1]] - pos[cand[0]], cell32[g], inv32[g], p[g])
+    keep = length < torch.tensor(float(r_max), dtype=torch.float32)
+    edge_index = cand[:, keep]
+    attrs["_n_edges"] = ("graph", "1x0e")
+    attrs["edge_cell_shift"] = ("edge", "3x0e")
+    data["_n_edges"] = torch.bincount(g[keep], minlength=n_nodes.numel()).view(-1, 1)
+    for k in _STALE:
+        data.pop(k, None)
+    return {"edge_index": edge_index, "edge_cell_shift": shift[keep].contiguous()}, attrs
+
+
+def _periodic_graph_device(data, attrs, pos: Tensor, r_max: float):
+    """HIP path: the capped pair of ``csrc/e3k_pbc.hip`` at exactly the list's size, after one host read of the count."""
+    check_cell(data["cell"], data.get("pbc"), r_max)
+    dev = pos.device
+    pos = L.f32c(pos.detach())
+    n = data["_n_nodes"].reshape(-1).to(dev)
+    total, n_graphs = pos.shape[0], n.numel()
+    cell, inv, mask = _cell_operands(data)
+    if cell.shape[0] != n_graphs:
+        raise ValueError(f"cell names {cell.shape[0]} graphs, the batch has {n_graphs}")
+    attrs["_n_edges"] = ("graph", "1x0e")
+    attrs["edge_cell_shift"] = ("edge", "3x0e")
+    for k in _STALE:
+        data.pop(k, None)
+    counts = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
+    if total:
+        # an empty ghost graph behind the real ones (the capped builder's layout): its cell, inverse and pbc are zero
+        node_ptr = torch.full((n_graphs + 2,), total, dtype=torch.int64, device=dev)
+        node_ptr[0] = 0
+        node_ptr[1:n_graphs + 1] = torch.cumsum(n, 0)
+        padded = [torch.cat([t, torch.zeros_like(t[:1])]).contiguous() for t in (cell, inv, mask)]      # (alive until the fill below)
+        geom = tuple(L.ptr(t) for t in padded)
+        node_seg = _node_segment(data, pos)
+        head = (L.ptr(pos), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max))
+        lib = L.load()
+        L.check(lib.e3k_pbc_nlist_count(*head, *geom, L.ptr(counts), L.stream_ptr()), "e3k_pbc_nlist_count")
+    n_edge = int(counts.sum().item())          # the one host sync: the size of the output
+    edge_index = torch.empty(2, n_edge, dtype=torch.int64, device=dev)
+    shift = torch.empty(n_edge, 3, dtype=torch.int32, device=dev)
+    n_edges = torch.zeros(n_graphs + 1, dtype=torch.int64, device=dev)
+    if n_edge:
+        offsets = torch.empty(total + 1, dtype=torch.int64, device=dev)
+        state = torch.zeros(2, dtype=torch.int64, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)      # (a list of exactly its own size cannot overflow)
+        L.check(lib.e3k_pbc_nlist_fill(*head, *geom, L.ptr(counts), n_edge, L.ptr(offsets), L.ptr(edge_index), L.ptr(shift),
+                                       L.ptr(n_edges), None, L.ptr(state), L.ptr(flag), L.stream_ptr()), "e3k_pbc_nlist_fill")
+    data["_n_edges"] = n_edges[:n_graphs].view(-1, 1)
+    return {"edge_index": edge_index, "edge_cell_shift": shift}, attrs
+
+
+def wrap_positions(pos: Tensor, cell: Tensor, pbc, node_ptr: Tensor) -> Tensor:
+    """``pos`` [N, 3] folded into each graph's cell along its periodic axes (fractional coordinates in [0, 1)), for output: the
+    force field and the integrators work on unwrapped positions and never need this.  ``cell`` [G, 3, 3] (or [G, 9]), ``pbc`` [G, 3]
+    or None (periodic everywhere), ``node_ptr`` [G + 1].  Computed in float64, returned in ``pos``'s dtype."""
+    c = cell.detach().reshape(-1, 3, 3).double()
+    counts = (node_ptr[1:] - node_ptr[:-1]).to(pos.device)
+    g = segment_ids(counts, pos.shape[0])
+    p = torch.ones(c.shape[0], 3, dtype=torch.bool, device=pos.device) if pbc is None else torch.as_tensor(pbc).to(pos.device).reshape(-1, 3) != 0
+    inv = _inverse_cells(c.cpu()).to(pos.device)
+    frac = torch.einsum("nc,nck->nk", pos.double(), inv[g])
+    frac = torch.where(p[g], frac - torch.floor(frac), frac)
+    return torch.einsum("nk,nkc->nc", frac, c.to(pos.device)[g]).to(pos.dtype)
+
+
 def computeEdgeIndex(data, attrs, r_max: float = None, key: str = "pos", criteria=None):
     if "_nlist_state" in data:      # a padded batch of a capped loop: the fixed-size list, rewritten in place inside the capture
         return computeEdgeIndexCapped(data, attrs, r_max=r_max, key=key, criteria=criteria)
     pos = torch.as_tensor(data[key], dtype=torch.get_default_dtype())
+    if "cell" in data:      # a periodic batch: the minimum-image list and its image numbers
+        _refuse_with_cell(data, criteria)
+        if r_max is None:
+            raise ValueError("computeEdgeIndex: a periodic cell needs r_max")
+        return (_periodic_graph_device if pos.is_cuda else _periodic_graph_host)(data, attrs, pos, r_max)
     if pos.is_cuda and criteria is None and r_max is not None:
         return _radius_graph_device(data, attrs, pos, r_max)
     n_nodes = data["_n_nodes"]
@@ -411,6 +612,11 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
     is read from the batch; the draw index from ``data['_nlist_rng']``, int64 [2], else ``nlist_rng(device)``: every build draws with
     the first cell and adds one to it).  The list then equals ``computeEdgeIndex(criteria=...)``'s at the same draw index.
 
+    A batch with ``cell`` (the ghost graph's cell zero; ``_inv_cell`` / ``_pbc_mask`` already in it, as ``run/capped.CappedBucket``
+    leaves them) takes the periodic builder (``csrc/e3k_pbc.hip``) and has its ``edge_cell_shift`` [e_cap, 3] int32 rewritten in place
+    beside ``edge_index`` (zero on the ghost edges).  The width restriction is NOT checked here (``check_cell``: on the host, where the
+    cell enters); a criterion together with a cell is refused.
+
     Not served (``computeEdgeIndex`` does both, eagerly): ``criteria`` callbacks that are arbitrary Python, edges kept from before with
     carried attributes."""
     if criteria is not None and not isinstance(criteria, PairCriterion):
@@ -422,7 +628,7 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
     if "_graph_weight" not in data or "edge_index" not in data or "_n_edges" not in data:
         raise ValueError("computeEdgeIndexCapped needs a batch padded by run.graph_step.pad_batch (it carries _graph_weight, and the "
                          "edge_index / _n_edges buffers that are rewritten in place)")
-    carried = [k for k, v in attrs.items() if v[0] == "edge" and k in data and k not in ("edge_vector", "edge_length")]
+    carried = [k for k, v in attrs.items() if v[0] == "edge" and k in data and k not in ("edge_vector", "edge_length", "edge_cell_shift")]
     if carried:
         raise ValueError(f"computeEdgeIndexCapped rebuilds the whole list: the edge attributes {carried} cannot be carried over "
                          "(computeEdgeIndex keeps pre-existing edges and their attributes)")
@@ -458,11 +664,28 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
         L.require_cuda(rng)
         if rng.dtype != torch.int64 or not rng.is_contiguous() or rng.numel() != 2:
             raise ValueError("_nlist_rng must be a contiguous int64 tensor of 2 elements (next draw index, draw index in use)")
+    periodic = "cell" in data
+    if periodic:
+        if criteria is not None:
+            raise ValueError("computeEdgeIndexCapped: a pair criterion together with a periodic cell is not served")
+        cell, inv, mask = _cell_operands(data)      # (the inverse is in the batch from the bucket's construction on: no host work here)
+        shift = data.get("edge_cell_shift")
+        L.require_cuda(cell, inv, mask, shift)
+        if cell.shape[0] != n_graphs + 1:
+            raise ValueError(f"cell names {cell.shape[0]} graphs, the padded batch has {n_graphs + 1} (the ghost graph's cell is zero)")
+        if shift is None or shift.dtype != torch.int32 or not shift.is_contiguous() or shift.numel() != 3 * e_cap:
+            raise ValueError(f"edge_cell_shift must be a contiguous int32 tensor of {3 * e_cap} elements to be rewritten in place")
     lib = L.load()
     counts = torch.empty(total, dtype=torch.int32, device=dev)
     offsets = torch.empty(total + 1, dtype=torch.int64, device=dev)
     pos_d = pos.detach()
-    if criteria is None:
+    if periodic:
+        head = (L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(cell), L.ptr(inv), L.ptr(mask))
+        L.check(lib.e3k_pbc_nlist_count(*head, L.ptr(counts), L.stream_ptr()), "e3k_pbc_nlist_count")
+        L.check(lib.e3k_pbc_nlist_fill(*head, L.ptr(counts), e_cap, L.ptr(offsets), L.ptr(ei), L.ptr(shift), L.ptr(n_edges), L.ptr(seg),
+                                       L.ptr(state), L.ptr(flag), L.stream_ptr()), "e3k_pbc_nlist_fill")
+        attrs["edge_cell_shift"] = ("edge", "3x0e")
+    elif criteria is None:
         L.check(lib.e3k_nlist_count(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts),
                                     L.stream_ptr()), "e3k_nlist_count")
         L.check(lib.e3k_nlist_fill(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts), e_cap,
@@ -482,4 +705,6 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
     memo.remember(n_nodes, "nlist_ptr", node_ptr)
     # (the flag bit stays on the device until somebody fetches the persistent flag: CapturedStep after a replay, the next eager
     #  caller of report_persistent, or check_edge_capacity)
+    if periodic:
+        return {"edge_index": ei, "edge_cell_shift": shift}, attrs
     return {"edge_index": ei}, attrs

@@ -141,6 +141,8 @@ class SequentialGraphNetwork(torch.nn.Sequential):
                 done["_topology"] = ((("edge_index", data["edge_index"], data["edge_index"]._version),), wrote)
             for name, layer in self.layers:
                 ins = self._data_only_inputs(layer)
+                if ins is not None:      # keys the layer reads only where the batch has them (a periodic batch's image numbers)
+                    ins = tuple(ins) + tuple(k for k in getattr(layer, "data_only_optional_inputs", ()) if k in data)
                 if ins is None or not all(k in avail for k in ins):
                     continue
                 before = dict(data)

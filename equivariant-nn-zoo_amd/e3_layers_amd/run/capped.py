@@ -1,17 +1,24 @@
 """What the clients of the capped neighbour list share (``run/md.ReplayedForceField``, ``run/loops.CappedLoop``,
 ``run/score_step.ReplayedScoreStep``; DESIGN.md section 4, "Capped neighbour list"): the names of the keys a rebuilt list touches,
-the model's own ``edge_index`` layer read once, and the padded batch that carries the capped builder's device cells."""
+the model's own ``edge_index`` layer read once, and the padded batch that carries the capped builder's device cells.
+
+A periodic batch (one with ``cell``; ``data/compute_edge.py``) is served through ``run/md.ReplayedForceField`` only: the bucket then
+also carries the cell's host-made inverse and the pbc mask, and ``edge_cell_shift`` is rebuilt beside ``edge_index``.  The sampler
+and score-step loops with a cell are not served."""
 from __future__ import annotations
 
 from collections import namedtuple
 
 import torch
 
-from ..data.compute_edge import PairCriterion, check_edge_capacity
+from ..data.compute_edge import PairCriterion, _cell_operands, check_edge_capacity
 from .graph_step import ghost_node_capacity, pad_batch
 
 REBUILT_KEYS = ("edge_index", "_n_edges", "_edge_segment")      # the in-graph build rewrites all of them: never copied in
 EDGE_KEYS = REBUILT_KEYS + ("edge_vector", "edge_length")       # what a rebuilt list invalidates
+# a periodic batch (one with ``cell``) adds the image numbers to the rebuilt keys: never carried, absent on open batches (every pop
+# of these tolerates that).  (``REBUILT_KEYS`` itself stays what the open clients copy around.)
+PERIODIC_REBUILT_KEYS = ("edge_cell_shift",)
 
 # the layer (data, attrs) -> (new, attrs) and what its keywords say: position key, cutoff, pair rule (None: not given to it)
 EdgeLayer = namedtuple("EdgeLayer", "layer key r_max criterion")
@@ -58,6 +65,13 @@ class CappedBucket:
         self.rng = None if rng is False else builder_cells(dev) if rng is True else rng
         if self.rng is not None:
             padded.data["_nlist_rng"] = self.rng
+        if "cell" in padded:      # periodic: the ghost graph's cell, inverse and pbc are zero (pad_batch; a zero cell has the zero inverse)
+            padded.data["cell"] = padded.data["cell"].contiguous()
+            _cell_operands(padded.data)      # ``_inv_cell`` / ``_pbc_mask``: on the host, once, before anything is captured
+            if "edge_cell_shift" not in padded:
+                raise ValueError("a periodic batch (one with 'cell') needs the 'edge_cell_shift' of its present list beside 'edge_index'")
+            # (collation stores integers as int64; the builder rewrites int32 [e_cap, 3] in place)
+            padded.data["edge_cell_shift"] = padded.data["edge_cell_shift"].to(torch.int32).reshape(-1, 3).contiguous()
         self.n_graphs, self.n_cap, self.e_cap = len(padded) - 1, int(padded[key].shape[0]), int(padded["edge_index"].shape[1])
 
     @property

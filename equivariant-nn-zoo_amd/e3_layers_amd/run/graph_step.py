@@ -160,6 +160,8 @@ def ghost_sample(like, n_nodes: int, n_edges: int, key: str = "pos"):
         elif torch.is_tensor(v) and (like.attrs.get(name, ("",))[0] == "node"
                                      or (name not in like.attrs and v.dim() >= 1 and v.shape[0] == like[key].shape[0])):
             tensors[name] = v[:1].expand(n_nodes, *v.shape[1:]).clone()      # node-wise (species): the first node's value
+        elif name == "edge_cell_shift":      # (a periodic batch's image numbers: the ghost graph has no cell)
+            tensors[name] = v.new_zeros((n_edges,) + tuple(v.shape[1:]))
         elif torch.is_tensor(v) and like.attrs.get(name, ("",))[0] == "edge":
             tensors[name] = (v[:1].expand(n_edges, *v.shape[1:]).clone() if v.shape[0] else v.new_zeros((n_edges,) + tuple(v.shape[1:])))
         elif torch.is_tensor(v):

@@ -21,6 +21,19 @@ fixed capacity (``csrc/e3k_nlist.hip``); the integrators' kernels are ``csrc/e3k
 
     bonds = BondConstraints(hydrogen_bonds(pos, species == 1, ff.node_ptr, 1.3), pos=pos, node_ptr=ff.node_ptr, masses=masses)
     md = Langevin(ff, masses, dt=2.0, kT=0.025, gamma=0.1, constraints=bonds)      # SHAKE / RATTLE inside the same two launches
+
+Periodic cells: a batch with ``cell`` ([G, 3, 3], rows = lattice vectors; ``pbc`` [G, 3] optional, ASE's contract) is captured with the
+periodic builder (``csrc/e3k_pbc.hip``: minimum image, one image number triple per edge) -- no new argument:
+
+    batch["cell"], batch.attrs["cell"] = cell.reshape(G, 9), ("graph", "3x1o")      # before ReplayedForceField(model, batch, r_max)
+    ff.cell, ff.pbc                           # what it uses
+    xyz = wrap_positions(ff.pos, ff.cell, ff.pbc, ff.node_ptr)      # for output only
+
+Every cell's perpendicular width along each periodic axis must exceed ``2 r_max (1 + 1e-3)`` (``ValueError`` at construction and at
+``grow()``, before anything is captured): a pair then has one image at most.  Positions stay UNWRAPPED -- the minimum image is taken
+from differences -- so the integrators, the thermostat, FIRE and the constraints run as they are (fp32: keep atoms within about a
+thousand cell widths of the origin).  Not served: narrower cells (replicate to a supercell), stress / virial / variable cells, cell
+lists (the search stays O(n^2) per graph).
 """
 from __future__ import annotations
 
@@ -31,12 +44,12 @@ import torch
 
 from ..backend import lib as L
 from ..backend.graph import EdgeCapacityExceeded
-from ..data.compute_edge import computeEdgeIndex, computeEdgeIndexCapped, normal_draw
-from .capped import EDGE_KEYS, CappedBucket
+from ..data.compute_edge import check_cell, computeEdgeIndex, computeEdgeIndexCapped, normal_draw, wrap_positions
+from .capped import EDGE_KEYS, PERIODIC_REBUILT_KEYS, CappedBucket
 from .graph_step import CapturedStep, bucket_capacity
 
 __all__ = ["EdgeCapacityExceeded", "ReplayedForceField", "VelocityVerlet", "Langevin", "Fire", "BondConstraints", "ConstraintFailure",
-           "hydrogen_bonds"]
+           "hydrogen_bonds", "wrap_positions"]
 
 
 class ReplayedForceField:
@@ -51,7 +64,7 @@ class ReplayedForceField:
             raise RuntimeError("ReplayedForceField needs a device batch: there is no CPU fallback for graph replay")
         if edge_slack < 1.0:
             raise ValueError("edge_slack must be >= 1")
-        carried = [k for k, v in batch.attrs.items() if v[0] == "edge" and k in batch and k not in EDGE_KEYS]
+        carried = [k for k, v in batch.attrs.items() if v[0] == "edge" and k in batch and k not in EDGE_KEYS + PERIODIC_REBUILT_KEYS]
         if carried:
             raise ValueError(f"the edge attributes {carried} cannot follow a rebuilt neighbour list")
         self.model, self.r_max, self.key = model, float(r_max), key
@@ -59,8 +72,12 @@ class ReplayedForceField:
         self.edge_slack, self.warmup, self.edge_multiple = float(edge_slack), warmup, int(edge_multiple)
         self.dev = batch[key].device
         self._base = batch.clone()
-        for k in EDGE_KEYS:
+        for k in EDGE_KEYS + PERIODIC_REBUILT_KEYS:
             self._base.pop(k)
+        # a periodic batch: what the builder uses (None: open boundaries) -- [G, 3, 3] fp32 and bool [G, 3]
+        self.cell = self._base["cell"].detach().reshape(-1, 3, 3) if "cell" in self._base else None
+        self.pbc = None if self.cell is None else (self._base["pbc"].reshape(-1, 3) != 0 if "pbc" in self._base else
+                                                   torch.ones(self.cell.shape[0], 3, dtype=torch.bool, device=self.dev))
         self.n_real = int(batch[key].shape[0])
         self.n_graphs = len(batch)
         n = self._base["_n_nodes"].reshape(-1)
@@ -73,6 +90,8 @@ class ReplayedForceField:
 
     # ---- capture ----------------------------------------------------------------------------------------------------
     def _build(self, pos, e_min: int):
+        if self.cell is not None:      # on the host, before anything is captured (construction and every grow())
+            check_cell(self.cell, self.pbc, self.r_max)
         base = self._base.clone()
         base[self.key] = pos.detach().to(torch.float32).clone()
         new, attrs = computeEdgeIndex(base.data, base.attrs, r_max=self.r_max, key=self.key)      # eager: the sizes go to the host once

@@ -1248,6 +1248,45 @@ int e3k_layer_profile(e3k_layer* layer, int32_t capacity);
 int e3k_layer_profile_mask(e3k_layer* layer, int32_t capacity, uint32_t kinds);
 int e3k_layer_profile_read(e3k_layer* layer, int32_t kind, float* ms, int64_t* n, int64_t* e, int32_t cap);
 
+/* ------------------------------------------------------------------------------------------
+ * Periodic cells, minimum image (csrc/e3k_pbc.hip; the rule itself: csrc/e3k_pbc.h).  Replaces the pbc branch of ASE's
+ * neighbour list as the reference's data sets use it (ase.neighborlist: cell, pbc, one image shift per edge) for the capped
+ * list above and the edge vectors, under ONE restriction the host checks (data/compute_edge.check_cell): the perpendicular
+ * width of every cell along each periodic axis exceeds 2 r_max (1 + 1e-3).  An ordered pair then has at most one image inside
+ * the cutoff, an atom never sees its own image, and that image is the one found by rounding the fractional displacement, so
+ * the list keeps one slot per ordered pair.  Narrower cells are NOT served (nothing here detects them: pairs are missed).
+ * For source i, destination j of graph g, in fp32:
+ *   d   = pos[j] - pos[i]
+ *   s_k = fmaf(d_z, inv[2][k], fmaf(d_y, inv[1][k], d_x * inv[0][k]))         inv = inv_cell[g]
+ *   n_k = pbc[g][k] ? -rintf(s_k) : 0
+ *   v_c = fmaf(n_2, c_c, fmaf(n_1, b_c, fmaf(n_0, a_c, d_c)))                  a, b, c = the rows of cell[g]
+ *   kept iff sqrtf((v_x v_x + v_y v_y) + v_z v_z) < r_max                      every product rounded on its own, strict
+ * With pbc = 0 on every axis v = d exactly and the kept set is e3k_nlist_fill's.  Positions are never wrapped: the image is
+ * taken from differences (fp32: sound up to about a thousand cell widths from the origin).
+ *   cell, inv_cell [G + 1, 3, 3] fp32 (rows = lattice vectors; inv_cell = the inverse, formed on the host in float64),
+ *   pbc [G + 1, 3] int32 (non-zero: periodic); the last entry of each is the ghost graph's (zeros), which is not searched.
+ *   e3k_pbc_nlist_count / e3k_pbc_nlist_fill: the contract of e3k_nlist_count / e3k_nlist_fill -- node_seg, node_ptr, counts,
+ *     offsets, edge_index [2, e_cap], n_edges, edge_segment (NULL: not wanted), state, flag, the ghost tail, the cut at e_cap
+ *     with the value 32 ORed into *flag and state[1] incremented, every node id clamped to [0, N], every store guarded by its
+ *     slot < e_cap -- and additionally edge_cell_shift [e_cap, 3] int32 = (n_0, n_1, n_2) of every real edge written, zeros on
+ *     the ghost edges.  Refused (E3K_ERR_INVALID, nothing launched): a NULL pointer other than edge_segment, N < 1 or
+ *     N >= 2^31, G < 0, e_cap < 0 or e_cap >= 2^31.
+ *   e3k_pbc_edge_vector_fwd: edge_vec [E, 3] = v above from the STORED shifts (the builder's vectors bit for bit), edge_len [E]
+ *     (NULL: not wanted) = the length the builder compared with r_max.  src, dst [E] int32 are clamped to [0, N - 1]; the graph
+ *     is node_seg[src] ([N] int64), clamped to [0, n_cells - 1]; cell [n_cells, 3, 3].  E = 0 launches nothing.  Refused: E, N
+ *     or n_cells < 0; with E > 0 a NULL pointer other than edge_len, N < 1 or n_cells < 1.  The backward is
+ *     e3k_edge_vector_bwd unchanged (the shift is a constant).
+ * ------------------------------------------------------------------------------------------ */
+int e3k_pbc_nlist_count(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                        const float* cell, const float* inv_cell, const int32_t* pbc, int32_t* counts, void* stream);
+int e3k_pbc_nlist_fill(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                       const float* cell, const float* inv_cell, const int32_t* pbc, const int32_t* counts, int64_t e_cap,
+                       int64_t* offsets, int64_t* edge_index, int32_t* edge_cell_shift, int64_t* n_edges, int64_t* edge_segment,
+                       int64_t* state, int32_t* flag, void* stream);
+int e3k_pbc_edge_vector_fwd(const float* pos, const int32_t* src, const int32_t* dst, const int32_t* edge_cell_shift,
+                            const int64_t* node_seg, const float* cell, int32_t n_cells, int64_t N, int64_t E, float* edge_vec,
+                            float* edge_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ evaluation, the neighbour list rebuilt inside it, two integrator launches beside
     python tools/md_bench.py --integrator langevin --out profiles/md_langevin.json      (the thermostatted step against the NVE step)
     python tools/md_bench.py --fire --out profiles/md_fire.json                         (the FIRE iteration against its eager loop)
     python tools/md_bench.py --constraints --out profiles/md_constraints.json           (the SHAKE / RATTLE step against the plain step)
+    python tools/md_bench.py --pbc --molecules 32 64 --out profiles/md_pbc.json         (the step in a vacuum cell against the open step)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/md_bench.py --trace-steps 60 --molecules 32
     python tools/md_bench.py --launches DIR_A/…_kernel_stats.csv 10 DIR_B/…_kernel_stats.csv 60      (launches per replayed step)
 
@@ -207,6 +208,49 @@ def bench_constraints(n_mol, steps, warmup, reps, dt, dev):
             "constrained_over_plain_median": round(statistics.median(rows["constrained"]) / statistics.median(rows["plain"]), 4)}
 
 
+def bench_pbc(n_mol, steps, warmup, reps, dt, dev):
+    """The periodic step against the open-boundary step of the same build: the same batch once without a cell and once in a cubic
+    vacuum cell (width: the batch's extent + 2 r_max + 8, so no image is ever inside the cutoff and the two edge sets are
+    identical -- asserted at the start).  What differs is the builder's two kernels (the rule of csrc/e3k_pbc.h in the pair loop,
+    the image numbers written) and the edge-vector kernel; each variant has its own force field, the two alternate."""
+    from e3_layers_amd.run.md import ReplayedForceField, VelocityVerlet
+
+    model, batch, r_max, x0, v0 = setup(n_mol, dev)
+    width = float((x0.max(0).values - x0.min(0).values).max()) + 2.0 * r_max + 8.0
+    vac = batch.clone()
+    vac.attrs["cell"] = ("graph", "3x1o")
+    vac["cell"] = (width * torch.eye(3, device=dev)).reshape(1, 9).repeat(len(batch), 1)
+    ffs = {"open": ReplayedForceField(model, batch, r_max), "periodic": ReplayedForceField(model, vac, r_max)}
+    mds = {k: VelocityVerlet(ff, torch.ones(x0.shape[0]), dt) for k, ff in ffs.items()}
+    rows = {k: [] for k in ("open", "periodic", "open_host", "periodic_host")}
+    for name, md in mds.items():
+        replay_start(md, ffs[name], x0, v0)
+        md.run(warmup, check_every=warmup)
+    edges = {}
+    for name, md in mds.items():      # the same list at the start
+        replay_start(md, ffs[name], x0, v0)
+        n = int(ffs[name].n_edges)
+        edges[name] = ffs[name].static["edge_index"][:, :n].clone()
+    if not torch.equal(edges["open"], edges["periodic"]):
+        raise RuntimeError("the vacuum cell's edge set differs from the open one")
+    for _ in range(reps):
+        for name, md in mds.items():
+            replay_start(md, ffs[name], x0, v0)
+            ms, host = timed(replay_steps(md, ffs[name], steps))
+            ffs[name].check()
+            rows[name].append(ms / steps)
+            rows[name + "_host"].append(1e3 * host / steps)
+    end = {k: int(ff.n_edges) for k, ff in ffs.items()}
+    diff = statistics.median(rows["periodic"]) - statistics.median(rows["open"])
+    return {"molecules": n_mol, "atoms": int(x0.shape[0]), "edges_at_start": int(edges["open"].shape[1]), "edges_at_end": end,
+            "cell_width": round(width, 3), "e_cap": {k: ff.e_cap for k, ff in ffs.items()}, "steps": steps, "reps": reps, "dt": dt,
+            "regrowths": sum(md.regrowths for md in mds.values()), "recaptures": sum(ff.recaptures for ff in ffs.values()),
+            "open_ms_per_step": mmm(rows["open"]), "periodic_ms_per_step": mmm(rows["periodic"]),
+            "open_host_busy_ms_per_step": mmm(rows["open_host"]), "periodic_host_busy_ms_per_step": mmm(rows["periodic_host"]),
+            "periodic_minus_open_us_median": round(1e3 * diff, 2),
+            "periodic_over_open_median": round(statistics.median(rows["periodic"]) / statistics.median(rows["open"]), 4)}
+
+
 def timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -324,6 +368,7 @@ def main():
     ap.add_argument("--integrator", choices=("nve", "langevin"), default="nve", help="langevin: the thermostatted step against the NVE step")
     ap.add_argument("--fire", action="store_true", help="the FIRE iteration against its eager loop")
     ap.add_argument("--constraints", action="store_true", help="the step with bonds to hydrogen constrained against the plain step")
+    ap.add_argument("--pbc", action="store_true", help="the step in a vacuum cell (periodic builder, same edge set) against the open step")
     ap.add_argument("--kT", type=float, default=0.25, help="thermostat temperature in the model's energy units (v0 has variance 0.25)")
     ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
@@ -339,6 +384,10 @@ def main():
         from e3_layers_amd.run.md import Langevin, ReplayedForceField, VelocityVerlet
 
         model, batch, r_max, x0, v0 = setup(args.molecules[0], dev)
+        if args.pbc:      # the vacuum cell of bench_pbc
+            width = float((x0.max(0).values - x0.min(0).values).max()) + 2.0 * r_max + 8.0
+            batch.attrs["cell"] = ("graph", "3x1o")
+            batch["cell"] = (width * torch.eye(3, device=dev)).reshape(1, 9).repeat(len(batch), 1)
         ff = ReplayedForceField(model, batch, r_max)
         if args.fire:
             make_fire(ff).run(args.trace_steps, check_every=args.trace_steps)
@@ -355,7 +404,7 @@ def main():
             md.run(args.trace_steps, check_every=args.trace_steps)
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0], "integrator": args.integrator, "fire": args.fire,
-                          "constraints": args.constraints}))
+                          "constraints": args.constraints, "pbc": args.pbc}))
         return
     if args.fire:
         workload = "FIRE relaxation with per-graph state on config_energy_force (as shipped), synth_qm9: replayed iteration vs the eager loop"
@@ -364,6 +413,10 @@ def main():
         workload = ("velocity-Verlet step with the bonds to hydrogen constrained (SHAKE / RATTLE) vs the plain step, both replayed, on "
                     "config_energy_force (as shipped), synth_qm9, masses 1 (H) and 12")
         results = [bench_constraints(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
+    elif args.pbc:
+        workload = ("velocity-Verlet step in a cubic vacuum cell (periodic builder and edge vectors, identical edge set) vs the "
+                    "open-boundary step, both replayed, on config_energy_force (as shipped), synth_qm9, unit masses")
+        results = [bench_pbc(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
     elif args.integrator == "langevin":
         workload = "Langevin step vs velocity-Verlet step, both replayed, on config_energy_force (as shipped), synth_qm9, unit masses"
         results = [bench_langevin(n, args.steps, args.warmup, args.reps, args.dt, args.kT, args.gamma, dev) for n in args.molecules]
