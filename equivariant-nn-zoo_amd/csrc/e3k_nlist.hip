@@ -9,7 +9,9 @@
 //
 // Three launches: count (one wave per source node), scan (one workgroup: offsets, per-graph counts, E_real, the overflow
 // report), fill (node waves + tail blocks).  Every store is guarded by its slot index < e_cap; every node id read from the
-// batch's own bookkeeping is clamped to [0, N] before it is used as an address.
+// batch's own bookkeeping is clamped to [0, N] before it is used as an address.  The kernel of the count and fill passes and their
+// launchers are e3k_nlist_body.h's (shared with the periodic builder of e3k_pbc.hip); this file holds the scan, the plain cutoff's
+// and the criterion form's pair rules, and their entry points.
 //
 // The criterion form (e3k_nlist_count_crit / _fill_crit) keeps a pair that is inside the cutoff OR that the declarative pair rule of
 // data/compute_edge.SequenceOrRandom keeps: same segment key and |i - j| < window, or a counter-based Bernoulli draw -- the 32-bit
@@ -18,6 +20,7 @@
 // index goes up once per build, three launches, and stream order is the only synchronisation needed.
 #include "e3k_common.h"
 #include "e3k_draw.h"
+#include "e3k_nlist_body.h"
 
 namespace e3k {
 
@@ -33,91 +36,50 @@ struct NlistCrit {
   int32_t keep_all;
 };
 
-// One wave per source node i walks its own graph's nodes 64 at a time; a ballot compacts the kept pairs in ascending j.
-// node_seg [N]: graph of every node; node_ptr [G + 2]: first node of every graph (the ghost graph is graph G: its nodes count 0).
-template <bool FILL, bool CRIT>
-__global__ __launch_bounds__(256) void nlist_kernel(const float* __restrict__ pos, const int64_t* __restrict__ node_seg,
-                                                    const int64_t* __restrict__ node_ptr, int64_t N, int32_t G, float r_max,
-                                                    int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
-                                                    int64_t e_cap, int32_t node_blocks, int64_t* __restrict__ edge_index,
-                                                    int64_t* __restrict__ edge_seg, const NlistCrit crit) {
-  if constexpr (FILL) {
-    if ((int)blockIdx.x >= node_blocks) {
-      // the ghost tail: slot k >= E_real holds ghost edge k - E_real -- (a, a + 1) with a = kk % (n_ghost - 1), flipped on odd rounds
-      const int64_t e_real = offsets[N] < e_cap ? offsets[N] : e_cap;
-      const int64_t gs = clampi(node_ptr[G], 0, N);
-      const int64_t m = N - gs - 1;      // n_ghost - 1
-      const int64_t stride = (int64_t)(gridDim.x - node_blocks) * 256;
-      for (int64_t k = e_real + (int64_t)(blockIdx.x - node_blocks) * 256 + threadIdx.x; k < e_cap; k += stride) {
-        int64_t s, d;
-        if (m >= 1) {
-          const int64_t kk = k - e_real, a = kk % m;
-          const bool flip = ((kk / m) & 1) != 0;
-          s = gs + (flip ? a + 1 : a);
-          d = gs + (flip ? a : a + 1);
-        } else {      // fewer than two ghost nodes (reported as overflow by the scan): a self loop on the last node, in range
-          s = d = N - 1;
-        }
-        edge_index[k] = s;
-        edge_index[e_cap + k] = d;
-        if (edge_seg) edge_seg[k] = G;
-      }
-      return;
-    }
+// The plain cutoff: within_cutoff of e3k_common.h and nothing else.
+struct CutoffRule {
+  static constexpr bool SHIFT = false;
+  struct Source {};
+  __device__ __forceinline__ int64_t graph_id(int64_t g) const { return g; }
+  template <bool FILL>
+  __device__ __forceinline__ Source source(int64_t, int64_t) const {
+    return {};
   }
-  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= N) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t g = node_seg[i];
-  if (g < 0 || g >= G) {      // the ghost graph (or a bad segment id): not searched
-    if constexpr (!FILL) {
-      if (lane == 0) counts[i] = 0;
-    }
-    return;
+  __device__ __forceinline__ bool keep(const Source&, float px, float py, float pz, const float* __restrict__ pos, int64_t, int64_t j,
+                                       float r_max, float*) const {
+    return within_cutoff(px, py, pz, pos, j, r_max);
   }
-  const int64_t beg = clampi(node_ptr[g], 0, N), end = clampi(node_ptr[g + 1], 0, N);
-  const float px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
-  const int64_t off = FILL ? offsets[i] : 0;
-  // criterion form: what does not depend on j -- the source's segment key and the hash of (seed, draw, i)
-  int64_t key_i = 0;
-  uint32_t h_i = 0;
-  bool seq_on = false;
-  if constexpr (CRIT) {
-    seq_on = crit.segment_key != nullptr && crit.window > 0;
-    if (seq_on) key_i = crit.segment_key[i];
+  int64_t* scan_rng() const { return nullptr; }
+};
+
+// The criterion form: inside the cutoff OR kept by the pair rule.  The count pass draws with rng[0], the fill pass with rng[1].
+struct CriterionRule {
+  static constexpr bool SHIFT = false;
+  NlistCrit crit;
+  struct Source {      // the source's segment key and the hash of (seed, draw, i)
+    int64_t key_i;
+    uint32_t h_i;
+    bool seq_on;
+  };
+  __device__ __forceinline__ int64_t graph_id(int64_t g) const { return g; }
+  template <bool FILL>
+  __device__ __forceinline__ Source source(int64_t i, int64_t) const {
+    Source s{0, 0, crit.segment_key != nullptr && crit.window > 0};
+    if (s.seq_on) s.key_i = crit.segment_key[i];
     const uint32_t draw = (uint32_t)crit.rng[FILL ? 1 : 0];
-    h_i = mix32(draw_prefix(crit.seed_lo, crit.seed_hi, draw) ^ (uint32_t)i);
+    s.h_i = mix32(draw_prefix(crit.seed_lo, crit.seed_hi, draw) ^ (uint32_t)i);
+    return s;
   }
-  int cnt = 0;
-  for (int64_t j0 = beg; j0 < end; j0 += 64) {
-    const int64_t j = j0 + lane;
-    bool keep = false;
-    if (j < end && j != i) {
-      keep = within_cutoff(px, py, pz, pos, j, r_max);
-      if constexpr (CRIT) {
-        if (!keep) {
-          const int64_t gap = i > j ? i - j : j - i;
-          const bool seq = seq_on && gap < crit.window && crit.segment_key[j] == key_i;
-          const bool rnd = crit.keep_all != 0 || mix32(h_i ^ (uint32_t)j) < crit.threshold;
-          keep = seq || rnd;
-        }
-      }
-    }
-    const unsigned long long mask = __ballot(keep);
-    if constexpr (FILL) {
-      const int64_t at = off + cnt + __popcll(mask & ((1ull << lane) - 1ull));
-      if (keep && at < e_cap) {      // (overflow: the list is cut at e_cap)
-        edge_index[at] = i;
-        edge_index[e_cap + at] = j;
-        if (edge_seg) edge_seg[at] = g;
-      }
-    }
-    cnt += __popcll(mask);
+  __device__ __forceinline__ bool keep(const Source& s, float px, float py, float pz, const float* __restrict__ pos, int64_t i,
+                                       int64_t j, float r_max, float*) const {
+    if (within_cutoff(px, py, pz, pos, j, r_max)) return true;
+    const int64_t gap = i > j ? i - j : j - i;
+    const bool seq = s.seq_on && gap < crit.window && crit.segment_key[j] == s.key_i;
+    const bool rnd = crit.keep_all != 0 || mix32(s.h_i ^ (uint32_t)j) < crit.threshold;
+    return seq || rnd;
   }
-  if constexpr (!FILL) {
-    if (lane == 0) counts[i] = cnt;
-  }
-}
+  int64_t* scan_rng() const { return crit.rng; }
+};
 
 // One workgroup: offsets [N + 1] = exclusive scan of counts (offsets[N] = E_real), n_edges [G + 1] = the graphs' shares of the
 // list as written (cut at e_cap; the ghost graph takes the rest), state[0] = E_real; overflow: the flag bit and state[1] += 1.
@@ -173,62 +135,26 @@ __global__ __launch_bounds__(1024) void nlist_scan_kernel(const int32_t* __restr
   }
 }
 
-// The scan for the periodic builder of e3k_pbc.hip (declared there): the same kernel, no criterion cells.
+// The one launch site of the scan (declared in e3k_nlist_body.h); rng: the criterion form's draw-index cells, else nullptr.
 int nlist_scan_launch(const int32_t* counts, const int64_t* node_ptr, int64_t N, int32_t G, int64_t e_cap, int64_t* offsets,
-                      int64_t* n_edges, int64_t* state, int32_t* flag, hipStream_t stream) {
-  hipLaunchKernelGGL(nlist_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, node_ptr, N, G, e_cap, offsets, n_edges, state, flag,
-                     (int64_t*)nullptr);
+                      int64_t* n_edges, int64_t* state, int32_t* flag, int64_t* rng, hipStream_t stream) {
+  hipLaunchKernelGGL(nlist_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, node_ptr, N, G, e_cap, offsets, n_edges, state, flag, rng);
   E3K_CHECK_LAUNCH();
   return E3K_OK;
 }
 
 }  // namespace e3k
 
-static bool nlist_args_ok(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G) {
-  return pos && node_seg && node_ptr && N >= 1 && N < (int64_t)1 << 31 && G >= 0;
-}
-
-template <bool CRIT>
-static int nlist_count(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
-                       const e3k::NlistCrit& crit, int32_t* counts, void* stream) {
-  if (!nlist_args_ok(pos, node_seg, node_ptr, N, G) || !counts) return E3K_ERR_INVALID;
-  hipLaunchKernelGGL((e3k::nlist_kernel<false, CRIT>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pos, node_seg,
-                     node_ptr, N, G, r_max, counts, (const int64_t*)nullptr, (int64_t)0, 0, (int64_t*)nullptr, (int64_t*)nullptr, crit);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
-}
-
-template <bool CRIT>
-static int nlist_fill(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
-                      const e3k::NlistCrit& crit, const int32_t* counts, int64_t e_cap, int64_t* offsets, int64_t* edge_index,
-                      int64_t* n_edges, int64_t* edge_segment, int64_t* state, int32_t* flag, void* stream) {
-  if (!nlist_args_ok(pos, node_seg, node_ptr, N, G) || !counts || !offsets || !edge_index || !n_edges || !state || !flag ||
-      e_cap < 0 || e_cap >= (int64_t)1 << 31)
-    return E3K_ERR_INVALID;
-  hipLaunchKernelGGL(e3k::nlist_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, node_ptr, N, G, e_cap, offsets,
-                     n_edges, state, flag, CRIT ? crit.rng : (int64_t*)nullptr);
-  E3K_CHECK_LAUNCH();
-  const int node_blocks = (int)((N + 3) / 4);
-  int64_t tail_blocks = (e_cap + 255) / 256;      // the tail is at most the whole buffer (an empty list)
-  if (tail_blocks > 256) tail_blocks = 256;
-  if (tail_blocks < 1) tail_blocks = 1;
-  hipLaunchKernelGGL((e3k::nlist_kernel<true, CRIT>), dim3((unsigned)(node_blocks + tail_blocks)), dim3(256), 0, (hipStream_t)stream,
-                     pos, node_seg, node_ptr, N, G, r_max, (int32_t*)nullptr, (const int64_t*)offsets, e_cap, node_blocks, edge_index,
-                     edge_segment, crit);
-  E3K_CHECK_LAUNCH();
-  return E3K_OK;
-}
-
 extern "C" int e3k_nlist_count(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
                                int32_t* counts, void* stream) {
-  return nlist_count<false>(pos, node_seg, node_ptr, N, G, r_max, e3k::NlistCrit{}, counts, stream);
+  return e3k::nlist_count(pos, node_seg, node_ptr, N, G, r_max, e3k::CutoffRule{}, counts, stream);
 }
 
 extern "C" int e3k_nlist_fill(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
                               const int32_t* counts, int64_t e_cap, int64_t* offsets, int64_t* edge_index, int64_t* n_edges,
                               int64_t* edge_segment, int64_t* state, int32_t* flag, void* stream) {
-  return nlist_fill<false>(pos, node_seg, node_ptr, N, G, r_max, e3k::NlistCrit{}, counts, e_cap, offsets, edge_index, n_edges,
-                           edge_segment, state, flag, stream);
+  return e3k::nlist_fill(pos, node_seg, node_ptr, N, G, r_max, e3k::CutoffRule{}, counts, e_cap, offsets, edge_index, nullptr, n_edges,
+                         edge_segment, state, flag, stream);
 }
 
 static bool nlist_crit_ok(const int64_t* rng, int64_t window) { return rng != nullptr && window >= 0; }
@@ -237,8 +163,8 @@ extern "C" int e3k_nlist_count_crit(const float* pos, const int64_t* node_seg, c
                                     const int64_t* segment_key, int64_t window, uint32_t threshold, int32_t keep_all, uint32_t seed_lo,
                                     uint32_t seed_hi, int64_t* rng, int32_t* counts, void* stream) {
   if (!nlist_crit_ok(rng, window)) return E3K_ERR_INVALID;
-  const e3k::NlistCrit crit{segment_key, rng, window, threshold, seed_lo, seed_hi, keep_all};
-  return nlist_count<true>(pos, node_seg, node_ptr, N, G, r_max, crit, counts, stream);
+  const e3k::CriterionRule rule{{segment_key, rng, window, threshold, seed_lo, seed_hi, keep_all}};
+  return e3k::nlist_count(pos, node_seg, node_ptr, N, G, r_max, rule, counts, stream);
 }
 
 extern "C" int e3k_nlist_fill_crit(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
@@ -247,7 +173,7 @@ extern "C" int e3k_nlist_fill_crit(const float* pos, const int64_t* node_seg, co
                                    int64_t* edge_index, int64_t* n_edges, int64_t* edge_segment, int64_t* state, int32_t* flag,
                                    void* stream) {
   if (!nlist_crit_ok(rng, window)) return E3K_ERR_INVALID;
-  const e3k::NlistCrit crit{segment_key, rng, window, threshold, seed_lo, seed_hi, keep_all};
-  return nlist_fill<true>(pos, node_seg, node_ptr, N, G, r_max, crit, counts, e_cap, offsets, edge_index, n_edges, edge_segment,
-                          state, flag, stream);
+  const e3k::CriterionRule rule{{segment_key, rng, window, threshold, seed_lo, seed_hi, keep_all}};
+  return e3k::nlist_fill(pos, node_seg, node_ptr, N, G, r_max, rule, counts, e_cap, offsets, edge_index, nullptr, n_edges, edge_segment,
+                         state, flag, stream);
 }

@@ -382,11 +382,27 @@ def _periodic_rule(d: Tensor, cell: Tensor, inv: Tensor, pbc: Tensor):
     return n.to(torch.int32), v, torch.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])
 
 
-def _refuse_with_cell(data, criteria) -> None:
+def _refuse_with_cell(who: str, criteria, data=None) -> None:
+    """What no builder serves together with a cell: a pair criterion, and (``data`` given: the eager builders) edges kept from before."""
     if criteria is not None:
-        raise ValueError("computeEdgeIndex: a pair criterion together with a periodic cell is not served")
-    if "edge_index" in data:
+        raise ValueError(f"{who}: a pair criterion together with a periodic cell is not served")
+    if data is not None and "edge_index" in data:
         raise ValueError("computeEdgeIndex: pre-existing edges together with a periodic cell are not served (drop edge_index first)")
+
+
+def _nlist_pair(stem: str, head, rule, counts: Tensor, fill=None, shift: Tensor = None, passes=("count", "fill")) -> None:
+    """The count pass and the scan-and-fill pass of a capped builder through the C ABI.  ``stem``: the entry points' name with ``{}``
+    for the pass; ``head``: what the three builders share (pos, node_seg, node_ptr, N, G, r_max); ``rule``: the operands of the pair
+    rule, behind the head; ``fill``: (e_cap, offsets, edge_index, n_edges, edge_segment, state, flag) as tensors; ``shift``: the
+    periodic builder's image numbers, behind ``edge_index``."""
+    lib, stream = L.load(), L.stream_ptr()
+    if "count" in passes:
+        L.check(getattr(lib, stem.format("count"))(*head, *rule, L.ptr(counts), stream), stem.format("count"))
+    if "fill" in passes:
+        e_cap, offsets, edge_index, *rest = fill
+        out = (L.ptr(edge_index),) + ((L.ptr(shift),) if shift is not None else ())
+        L.check(getattr(lib, stem.format("fill"))(*head, *rule, L.ptr(counts), e_cap, L.ptr(offsets), *out, *(L.ptr(t) for t in rest),
+                                                  stream), stem.format("fill"))
 
 
 def _periodic_graph_host(data, attrs, pos: Tensor, r_max: float):
@@ -437,8 +453,7 @@ def _periodic_graph_device(data, attrs, pos: Tensor, r_max: float):
         geom = tuple(L.ptr(t) for t in padded)
         node_seg = _node_segment(data, pos)
         head = (L.ptr(pos), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max))
-        lib = L.load()
-        L.check(lib.e3k_pbc_nlist_count(*head, *geom, L.ptr(counts), L.stream_ptr()), "e3k_pbc_nlist_count")
+        _nlist_pair("e3k_pbc_nlist_{}", head, geom, counts, passes=("count",))
     n_edge = int(counts.sum().item())          # the one host sync: the size of the output
     edge_index = torch.empty(2, n_edge, dtype=torch.int64, device=dev)
     shift = torch.empty(n_edge, 3, dtype=torch.int32, device=dev)
@@ -447,8 +462,7 @@ def _periodic_graph_device(data, attrs, pos: Tensor, r_max: float):
         offsets = torch.empty(total + 1, dtype=torch.int64, device=dev)
         state = torch.zeros(2, dtype=torch.int64, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)      # (a list of exactly its own size cannot overflow)
-        L.check(lib.e3k_pbc_nlist_fill(*head, *geom, L.ptr(counts), n_edge, L.ptr(offsets), L.ptr(edge_index), L.ptr(shift),
-                                       L.ptr(n_edges), None, L.ptr(state), L.ptr(flag), L.stream_ptr()), "e3k_pbc_nlist_fill")
+        _nlist_pair("e3k_pbc_nlist_{}", head, geom, counts, (n_edge, offsets, edge_index, n_edges, None, state, flag), shift, passes=("fill",))
     data["_n_edges"] = n_edges[:n_graphs].view(-1, 1)
     return {"edge_index": edge_index, "edge_cell_shift": shift}, attrs
 
@@ -472,7 +486,7 @@ def computeEdgeIndex(data, attrs, r_max: float = None, key: str = "pos", criteri
         return computeEdgeIndexCapped(data, attrs, r_max=r_max, key=key, criteria=criteria)
     pos = torch.as_tensor(data[key], dtype=torch.get_default_dtype())
     if "cell" in data:      # a periodic batch: the minimum-image list and its image numbers
-        _refuse_with_cell(data, criteria)
+        _refuse_with_cell("computeEdgeIndex", criteria, data)
         if r_max is None:
             raise ValueError("computeEdgeIndex: a periodic cell needs r_max")
         return (_periodic_graph_device if pos.is_cuda else _periodic_graph_host)(data, attrs, pos, r_max)
@@ -646,10 +660,7 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
     if n_graphs < 0 or data["_graph_weight"].numel() != n_graphs + 1:
         raise ValueError("_graph_weight and _n_nodes disagree on the number of graphs")
     dev = pos.device
-    node_seg = data.get("_node_segment")
-    if node_seg is None or node_seg.device != dev or node_seg.numel() != total:
-        node_seg = segment_ids(n_nodes.to(dev), total)
-    node_seg = node_seg.contiguous()
+    node_seg = _node_segment(data, pos)
     node_ptr = _node_pointers(n_nodes)
     state = data["_nlist_state"] if "_nlist_state" in data else nlist_state(dev)
     flag = persistent_flag(dev)
@@ -666,8 +677,7 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
             raise ValueError("_nlist_rng must be a contiguous int64 tensor of 2 elements (next draw index, draw index in use)")
     periodic = "cell" in data
     if periodic:
-        if criteria is not None:
-            raise ValueError("computeEdgeIndexCapped: a pair criterion together with a periodic cell is not served")
+        _refuse_with_cell("computeEdgeIndexCapped", criteria)
         cell, inv, mask = _cell_operands(data)      # (the inverse is in the batch from the bucket's construction on: no host work here)
         shift = data.get("edge_cell_shift")
         L.require_cuda(cell, inv, mask, shift)
@@ -675,29 +685,18 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
             raise ValueError(f"cell names {cell.shape[0]} graphs, the padded batch has {n_graphs + 1} (the ghost graph's cell is zero)")
         if shift is None or shift.dtype != torch.int32 or not shift.is_contiguous() or shift.numel() != 3 * e_cap:
             raise ValueError(f"edge_cell_shift must be a contiguous int32 tensor of {3 * e_cap} elements to be rewritten in place")
-    lib = L.load()
     counts = torch.empty(total, dtype=torch.int32, device=dev)
     offsets = torch.empty(total + 1, dtype=torch.int64, device=dev)
-    pos_d = pos.detach()
     if periodic:
-        head = (L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(cell), L.ptr(inv), L.ptr(mask))
-        L.check(lib.e3k_pbc_nlist_count(*head, L.ptr(counts), L.stream_ptr()), "e3k_pbc_nlist_count")
-        L.check(lib.e3k_pbc_nlist_fill(*head, L.ptr(counts), e_cap, L.ptr(offsets), L.ptr(ei), L.ptr(shift), L.ptr(n_edges), L.ptr(seg),
-                                       L.ptr(state), L.ptr(flag), L.stream_ptr()), "e3k_pbc_nlist_fill")
+        stem, rule = "e3k_pbc_nlist_{}", (L.ptr(cell), L.ptr(inv), L.ptr(mask))
         attrs["edge_cell_shift"] = ("edge", "3x0e")
     elif criteria is None:
-        L.check(lib.e3k_nlist_count(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts),
-                                    L.stream_ptr()), "e3k_nlist_count")
-        L.check(lib.e3k_nlist_fill(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), L.ptr(counts), e_cap,
-                                   L.ptr(offsets), L.ptr(ei), L.ptr(n_edges), L.ptr(seg), L.ptr(state), L.ptr(flag), L.stream_ptr()),
-                "e3k_nlist_fill")
+        stem, rule = "e3k_nlist_{}", ()
     else:
+        stem = "e3k_nlist_{}_crit"
         rule = (L.ptr(seg_key), criteria.window, criteria.threshold, int(criteria.keep_all), *L.seed_words(criteria.seed), L.ptr(rng))
-        L.check(lib.e3k_nlist_count_crit(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), *rule,
-                                         L.ptr(counts), L.stream_ptr()), "e3k_nlist_count_crit")
-        L.check(lib.e3k_nlist_fill_crit(L.ptr(pos_d), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max), *rule,
-                                        L.ptr(counts), e_cap, L.ptr(offsets), L.ptr(ei), L.ptr(n_edges), L.ptr(seg), L.ptr(state),
-                                        L.ptr(flag), L.stream_ptr()), "e3k_nlist_fill_crit")
+    head = (L.ptr(pos.detach()), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max))
+    _nlist_pair(stem, head, rule, counts, (e_cap, offsets, ei, n_edges, seg, state, flag), shift if periodic else None)
     attrs["_n_edges"] = ("graph", "1x0e")
     for k in TOPO_KEYS + ("edge_vector", "edge_length"):
         data.pop(k, None)

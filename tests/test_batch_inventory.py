@@ -86,7 +86,7 @@ def test_every_batch_kernel_has_an_exactly_checked_case(tmp_path):
     shipped -= {"edge_records_kernel"}
     table = M.table_kernels()
     assert len(shipped) == 13, sorted(shipped)
-    assert {f"nlist_kernel<{a}, {b}>" for a in ("false", "true") for b in ("false", "true")} <= shipped
+    assert {f"nlist_kernel<{a}, e3k::{b}>" for a in ("false", "true") for b in ("CutoffRule", "CriterionRule")} <= shipped
     assert shipped - table == set(), f"kernels without a case in test_gpu_batch_matrix.CASES: {sorted(shipped - table)}"
     assert table - shipped == set(), f"the case table names kernels the library does not ship: {sorted(table - shipped)}"
     for k in shipped:      # every kernel is named by a case that calls the library (a refusal launches nothing and names none)

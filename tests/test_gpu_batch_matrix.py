@@ -1,5 +1,5 @@
 """Every kernel that builds the batch itself -- csrc/e3k_graph.hip (csr_count / scan / fill / sort, group_rows), csrc/e3k_collate.hip
-(collate_plan, collate_gather), csrc/e3k_nlist.hip (the four nlist_kernel<FILL, CRIT>, nlist_scan) and e3k_common.h's zero_words_kernel
+(collate_plan, collate_gather), csrc/e3k_nlist.hip (the four nlist_kernel<FILL, CutoffRule | CriterionRule>, nlist_scan) and e3k_common.h's zero_words_kernel
 as e3k_csr_build launches it -- against an exact host model, element by element.
 
 These are the integer kernels every other kernel indexes memory through.  One case per C-ABI call or short chain (plan -> gather,
@@ -47,8 +47,8 @@ I64_MIN = -2 ** 63
 M32 = 0xFFFFFFFF
 
 CSR_K = {"csr_count_kernel", "csr_scan_kernel", "csr_fill_kernel", "csr_sort_kernel", "zero_words_kernel"}
-NL_K = {False: {"nlist_kernel<false, false>", "nlist_kernel<true, false>", "nlist_scan_kernel"},
-        True: {"nlist_kernel<false, true>", "nlist_kernel<true, true>", "nlist_scan_kernel"}}
+NL_K = {False: {"nlist_kernel<false, e3k::CutoffRule>", "nlist_kernel<true, e3k::CutoffRule>", "nlist_scan_kernel"},
+        True: {"nlist_kernel<false, e3k::CriterionRule>", "nlist_kernel<true, e3k::CriterionRule>", "nlist_scan_kernel"}}
 ROWS = (0, 1, 63, 64, 65, 128, 129, 200)      # row lengths: empty, one lane, around one 64-wide tile, two tiles, a partial third / fourth
 
 

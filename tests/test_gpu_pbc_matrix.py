@@ -1,4 +1,4 @@
-"""The periodic kernels of csrc/e3k_pbc.hip -- pbc_nlist_kernel<FILL> (with e3k_nlist.hip's nlist_scan_kernel between its two passes) and
+"""The periodic kernels of csrc/e3k_pbc.hip -- nlist_kernel<FILL, PeriodicRule> (with e3k_nlist.hip's nlist_scan_kernel between its two passes) and
 pbc_edge_vector_fwd_kernel -- through the C ABI, word for word against a numpy fp32 model of the rule in csrc/e3k_pbc.h.
 
 A case lays its operands out in ONE arena of 4-byte words (the Arena of tests/test_gpu_rtable_matrix.py: slack on both sides of every
@@ -32,7 +32,7 @@ E3K_OK, E3K_ERR_INVALID = 0, -1
 R_MAX = 1.875
 MIN_WIDTH = 2.0 * R_MAX * (1.0 + 1e-3)
 U24 = 2.0 ** -24
-NL_K = {"pbc_nlist_kernel<false>", "pbc_nlist_kernel<true>"}      # (+ nlist_scan_kernel of e3k_nlist.o, between the two)
+NL_K = {"nlist_kernel<false, e3k::PeriodicRule>", "nlist_kernel<true, e3k::PeriodicRule>"}     # (+ nlist_scan_kernel of e3k_nlist.o, between the two)
 EV_K = {"pbc_edge_vector_fwd_kernel"}
 PLANT_CELL = np.diag([4.0, 4.5, 5.0])
 # (image, |v| components): the destination sits one lattice vector along each named axis minus these components from the source

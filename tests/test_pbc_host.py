@@ -43,6 +43,8 @@ def test_every_pbc_kernel_has_an_exactly_checked_case(tmp_path):
     shipped = _shipped_kernels(tmp_path, "e3k_pbc")
     table = M.table_kernels()
     assert len(shipped) == 3, sorted(shipped)
+    builders = {k for k in shipped if "nlist" in k}      # the one builder kernel of e3k_nlist_body.h, no copy of its own
+    assert len(builders) == 2 and all(k.startswith("nlist_kernel<") for k in builders) and "pbc_nlist_kernel" not in str(shipped), builders
     assert shipped - table == set(), f"kernels without a case in test_gpu_pbc_matrix.CASES: {sorted(shipped - table)}"
     assert table - shipped == set(), f"the case table names kernels the library does not ship: {sorted(table - shipped)}"
     for k in shipped:
