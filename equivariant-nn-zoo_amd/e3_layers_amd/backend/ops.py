@@ -212,6 +212,44 @@ def params_only_backward() -> _Mode:
     return PARAMS_ONLY
 
 
+class _VirialSink:
+    """``with ops.virial_sink(buffer, graph_ptr) as sink: torch.autograd.grad(energy, pos)``: while it is active the force
+    backward of the edge vectors (the no-grad branch of ``EdgeVectorFn.backward``, which ``PeriodicEdgeVectorFn`` shares) also files the
+    virial ``-sum_e v_e (x) dE/dv_e`` of every graph into ``buffer`` [G, 9] fp32 (``e3k_virial_edges``, beside ``e3k_edge_vector_bwd``
+    and from the same per-edge gradients; written, not accumulated).  ``graph_ptr``: int32 [G + 1] row pointers of the graphs over
+    the nodes.  ``sink.written`` counts the backward passes that filed one: 0 after the scope means no edge-vector function ran (the
+    caller supplied the edge vectors).  Under ``create_graph=True`` the backward raises ``NotImplementedError``: the virial's own
+    derivative is not formed.  Process-wide and not nestable, as the backward modes are."""
+
+    def __init__(self, buffer, graph_ptr):
+        L.require_cuda(buffer, graph_ptr)
+        if graph_ptr.dtype != torch.int32 or not graph_ptr.is_contiguous() or graph_ptr.dim() != 1 or graph_ptr.numel() < 1:
+            raise ValueError("virial_sink: graph_ptr must be a contiguous int32 device tensor [n_graphs + 1]")
+        self.n_graphs = graph_ptr.numel() - 1
+        if buffer.dtype != torch.float32 or not buffer.is_contiguous() or buffer.numel() != 9 * self.n_graphs:
+            raise ValueError(f"virial_sink: the buffer must be a contiguous fp32 device tensor [{self.n_graphs}, 9]")
+        self.buffer, self.graph_ptr, self.written = buffer, graph_ptr, 0
+
+    def __enter__(self):
+        global _VIRIAL_SINK
+        if _VIRIAL_SINK is not None:
+            raise RuntimeError("ops.virial_sink is already active: one force backward at a time per process")
+        _VIRIAL_SINK = self
+        return self
+
+    def __exit__(self, *exc):
+        global _VIRIAL_SINK
+        _VIRIAL_SINK = None
+        return False
+
+
+_VIRIAL_SINK = None
+
+
+def virial_sink(buffer, graph_ptr) -> _VirialSink:
+    return _VirialSink(buffer, graph_ptr)
+
+
 def is_data_only(t) -> bool:
     """Set by computeEdgeVector / SphericalEncoding on tensors computed from the input positions alone."""
     return bool(getattr(t, "_e3k_data_only", False))
@@ -2267,7 +2305,10 @@ class EdgeVectorFn(torch.autograd.Function):
     def backward(ctx, g_vec, g_len):
         vec, length = ctx.saved_tensors
         topo = ctx.topo
+        sink = _VIRIAL_SINK
         if torch.is_grad_enabled():
+            if sink is not None:
+                raise NotImplementedError("virial under create_graph is not served")
             # d len = vec/len . d vec (elementwise torch ops), then the linear scatter dst(+) / src(-)
             gv = g_vec
             if g_len is not None:
@@ -2281,7 +2322,44 @@ class EdgeVectorFn(torch.autograd.Function):
         L.check(L.load().e3k_edge_vector_bwd(L.ptr(g_vec), L.ptr(g_len), L.ptr(vec), L.ptr(length), L.ptr(topo.dst_ptr),
                                              L.ptr(topo.dst_perm), L.ptr(topo.src_ptr), L.ptr(topo.src_perm), ctx.n,
                                              L.ptr(g_pos), L.stream_ptr()), "e3k_edge_vector_bwd")
+        if sink is not None:      # the virial of the same per-edge gradients, one launch more
+            _virial_edges_raw(g_vec, g_len, vec, length, topo, sink.graph_ptr, sink.n_graphs, ctx.n, sink.buffer)
+            sink.written += 1
         return g_pos, None
+
+
+def _virial_edges_raw(g_vec, g_len, vec, length, topo, graph_ptr, n_graphs: int, n_nodes: int, out) -> None:
+    L.check(L.load().e3k_virial_edges(L.ptr(g_vec), L.ptr(g_len), L.ptr(vec), L.ptr(length), L.ptr(topo.src_ptr), L.ptr(topo.src_perm),
+                                      L.ptr(graph_ptr), int(n_nodes), int(vec.shape[0]), int(n_graphs), L.ptr(out), L.stream_ptr()),
+            "e3k_virial_edges")
+
+
+def edge_virial(g_vec, g_len, vec, length, topo: GraphTopo, graph_ptr, n_graphs: int):
+    """The virial ``[G, 9]`` fp32 of the per-edge gradients (``e3k_virial_edges``): ``out[g, 3 a + b] = -sum_e vec_e[a] g_e[b]`` over
+    the edges of graph ``g``, ``g_e = g_vec_e + (g_len_e / len_e) vec_e`` (the gradient of the energy with respect to the edge vector,
+    as ``e3k_edge_vector_bwd`` forms it).  ``g_vec`` [E, 3] or None, ``g_len`` [E] or None (one at least); ``vec`` [E, 3], ``length``
+    [E]; ``topo``: the batch's ``GraphTopo`` (its by-source CSR is walked); ``graph_ptr``: int32 [G + 1] row pointers of the graphs over
+    the nodes, which are sorted by graph.  One launch, no atomics: the same bits every run."""
+    if g_vec is None and g_len is None:
+        raise ValueError("edge_virial needs g_vec or g_len")
+    L.require_cuda(g_vec, g_len, vec, length, graph_ptr)
+    n_graphs = int(n_graphs)
+    if graph_ptr.dtype != torch.int32 or not graph_ptr.is_contiguous() or n_graphs < 0 or graph_ptr.numel() < n_graphs + 1:
+        raise ValueError("edge_virial: graph_ptr must be a contiguous int32 device tensor [n_graphs + 1]")
+    vec = L.f32c(vec.detach())
+    e = topo.num_edges
+    if vec.dim() != 2 or tuple(vec.shape) != (e, 3):
+        raise ValueError(f"edge_virial: vec is {tuple(vec.shape)} for a topology of {e} edges")
+    g_vec = L.f32c(g_vec.detach()) if g_vec is not None else None
+    g_len = L.f32c(g_len.detach()) if g_len is not None else None
+    length = L.f32c(length.detach()) if length is not None else None
+    if g_vec is not None and g_vec.shape != vec.shape:
+        raise ValueError(f"edge_virial: g_vec {tuple(g_vec.shape)} and vec {tuple(vec.shape)} differ in shape")
+    if g_len is not None and (length is None or g_len.numel() != e or length.numel() != e):
+        raise ValueError("edge_virial: g_len needs a length, both of [E]")
+    out = torch.empty(n_graphs, 9, device=vec.device, dtype=torch.float32)
+    _virial_edges_raw(g_vec, g_len, vec, length, topo, graph_ptr, n_graphs, topo.src_ptr.numel() - 1, out)
+    return out
 
 
 class EdgeScatterFn(torch.autograd.Function):

@@ -79,7 +79,8 @@ def addEnergyOutput(config, shifts=None, output_key="total_energy"):
     return config
 
 
-def addForceOutput(config, gradients="forces", y="energy", sign=-1.0):
+def addForceOutput(config, gradients="forces", y="energy", sign=-1.0, virial=None, stress=None):
+    """``virial`` / ``stress``: output keys of ``GradientOutput`` (None, the default: not emitted, and the tree is what it was)."""
     plain = config.to_dict()
     layers = plain.pop("layers")
     module = plain.pop("module")
@@ -87,4 +88,7 @@ def addForceOutput(config, gradients="forces", y="energy", sign=-1.0):
     out.func = {"module": module, "layers": layers}
     out.update({"module": GradientOutput, "x": ("1x1o", "pos"), "y": ("1x0e", y),
                 "gradients": ("1x1o", gradients), "sign": sign})
+    for name, key in (("virial", virial), ("stress", stress)):
+        if key is not None:
+            out[name] = key
     return out

@@ -35,9 +35,11 @@ by ``_periodic_rule``).  The restriction that keeps one slot per ordered pair: e
 axis exceeds ``2 r_max (1 + 1e-3)`` -- ``check_cell`` raises otherwise, once on the host where a cell enters.  Positions stay unwrapped
 (the image is taken from differences; in fp32 that is sound up to about a thousand cell widths from the origin: the error of a
 fractional component, about ``|d| / w 2^-22``, must stay below the 5e-4 the margin leaves to the rounding tie); ``wrap_positions``
-is for output.  NOT served: narrower cells (crystal unit cells, several images per pair: replicate to a supercell); stress, virial
-and variable cells; cell lists (the search stays O(n^2) per graph); ``criteria`` and pre-existing edges together with a cell; the
-sampler and score-step loops and ``DeviceDataset`` with a cell.  A batch without ``cell`` takes exactly the paths it took before.
+is for output.  Virial and stress come from the force backward of these vectors (``nn.output.GradientOutput(virial=, stress=)``,
+``csrc/e3k_virial.hip``), and a captured force field's cell changes through ``run/md.ReplayedForceField.set_cell``, driven by the host.
+NOT served: narrower cells (crystal unit cells, several images per pair: replicate to a supercell); barostats and cell dynamics on
+the device; training on stress; cell lists (the search stays O(n^2) per graph); ``criteria`` and pre-existing edges together with
+a cell; the sampler and score-step loops and ``DeviceDataset`` with a cell.  A batch without ``cell`` takes exactly the paths it took before.
 """
 from __future__ import annotations
 

@@ -7,12 +7,12 @@ from .embedding import (
 )
 from .message_passing import FactorizedConvolution, MessagePassing
 from .scaling import PerTypeScaleShift
-from .output import GradientOutput, Pooling
+from .output import GradientOutput, Pooling, enable_virial
 
 __all__ = [
     "Module", "SequentialGraphNetwork", "Linear", "FullyConnectedNet", "FullyConnectedTensorProduct", "Gate", "NormActivation",
     "UVUTensorProduct", "PointwiseLinear", "LayerNormalization", "TensorProductExpansion", "Concat",
     "symmetricCutoff", "_poly_cutoff", "PolynomialCutoff", "BesselBasis", "SphericalEncoding", "RadialBasisEncoding",
     "Broadcast", "OneHotEncoding", "RelativePositionEncoding", "FactorizedConvolution", "MessagePassing",
-    "PerTypeScaleShift", "GradientOutput", "Pooling",
+    "PerTypeScaleShift", "GradientOutput", "Pooling", "enable_virial",
 ]

@@ -32,8 +32,20 @@ periodic builder (``csrc/e3k_pbc.hip``: minimum image, one image number triple p
 Every cell's perpendicular width along each periodic axis must exceed ``2 r_max (1 + 1e-3)`` (``ValueError`` at construction and at
 ``grow()``, before anything is captured): a pair then has one image at most.  Positions stay UNWRAPPED -- the minimum image is taken
 from differences -- so the integrators, the thermostat, FIRE and the constraints run as they are (fp32: keep atoms within about a
-thousand cell widths of the origin).  Not served: narrower cells (replicate to a supercell), stress / virial / variable cells, cell
-lists (the search stays O(n^2) per graph).
+thousand cell widths of the origin).
+
+Virial and stress (``nn.output.GradientOutput``'s definitions: ``virial = -dE/d eps`` in the row-vector convention of ``cell``,
+``stress = -virial / V``; one launch more inside the graph, ``csrc/e3k_virial.hip``):
+
+    enable_virial(model)                      # nn.output: sets the keys "virial" / "stress" on the tree's GradientOutput
+    ff = ReplayedForceField(model, batch, r_max, virial_key="virial", stress_key="stress")
+    ff(pos); ff.check()
+    ff.virial, ff.stress, ff.volume           # [G, 3, 3] fp32 static views (stress None on an open batch), float64 [G]
+    p = pressure(ff.virial, out["kinetic"][-1], ff.volume)      # (2 K + tr virial) / (3 V)
+    ff.set_cell(cell * 1.01); ff(pos * 1.01)  # a host-driven cell scan: nothing is captured again; positions are the caller's to scale
+
+Not served: narrower cells (replicate to a supercell), barostats and cell dynamics on the device (variable cells are served through
+``set_cell``, driven by the host), training on stress, the kinetic part of the stress, cell lists (the search stays O(n^2) per graph).
 """
 from __future__ import annotations
 
@@ -44,12 +56,21 @@ import torch
 
 from ..backend import lib as L
 from ..backend.graph import EdgeCapacityExceeded
-from ..data.compute_edge import check_cell, computeEdgeIndex, computeEdgeIndexCapped, normal_draw, wrap_positions
+from ..data.compute_edge import _inverse_cells, check_cell, computeEdgeIndex, computeEdgeIndexCapped, normal_draw, wrap_positions
 from .capped import EDGE_KEYS, PERIODIC_REBUILT_KEYS, CappedBucket
 from .graph_step import CapturedStep, bucket_capacity
 
 __all__ = ["EdgeCapacityExceeded", "ReplayedForceField", "VelocityVerlet", "Langevin", "Fire", "BondConstraints", "ConstraintFailure",
-           "hydrogen_bonds", "wrap_positions"]
+           "hydrogen_bonds", "wrap_positions", "pressure"]
+
+
+def pressure(virial, kinetic, volume):
+    """``(2 K + tr virial) / (3 V)`` per graph, float64, on whichever device the operands are: ``virial`` [G, 3, 3] or [G, 9] (``ff.virial``),
+    ``kinetic`` [G] (a row of the integrators' kinetic record), ``volume`` [G] (``ff.volume``)."""
+    w = torch.as_tensor(virial).to(torch.float64).reshape(-1, 9)
+    k = torch.as_tensor(kinetic, device=w.device).to(torch.float64).reshape(-1)
+    v = torch.as_tensor(volume, device=w.device).to(torch.float64).reshape(-1)
+    return (2.0 * k + w[:, 0] + w[:, 4] + w[:, 8]) / (3.0 * v)
 
 
 class ReplayedForceField:
@@ -59,7 +80,8 @@ class ReplayedForceField:
     bucket grid of ``bucket_capacity``)."""
 
     def __init__(self, model, batch, r_max: float, energy_key: str = "energy", forces_key: str = "forces", edge_slack: float = 1.5,
-                 key: str = "pos", warmup: int = 3, edge_multiple: int = 1024):
+                 key: str = "pos", warmup: int = 3, edge_multiple: int = 1024, virial_key: Optional[str] = None,
+                 stress_key: Optional[str] = None):
         if not batch[key].is_cuda:
             raise RuntimeError("ReplayedForceField needs a device batch: there is no CPU fallback for graph replay")
         if edge_slack < 1.0:
@@ -69,6 +91,10 @@ class ReplayedForceField:
             raise ValueError(f"the edge attributes {carried} cannot follow a rebuilt neighbour list")
         self.model, self.r_max, self.key = model, float(r_max), key
         self.energy_key, self.forces_key = energy_key, forces_key
+        self.virial_key, self.stress_key = virial_key, stress_key
+        if "cell" not in batch:
+            self.stress_key = None      # an open batch has no volume: ``stress`` stays None
+        self._require_emitted(model, self.virial_key, self.stress_key)      # before anything is captured
         self.edge_slack, self.warmup, self.edge_multiple = float(edge_slack), warmup, int(edge_multiple)
         self.dev = batch[key].device
         self._base = batch.clone()
@@ -78,6 +104,7 @@ class ReplayedForceField:
         self.cell = self._base["cell"].detach().reshape(-1, 3, 3) if "cell" in self._base else None
         self.pbc = None if self.cell is None else (self._base["pbc"].reshape(-1, 3) != 0 if "pbc" in self._base else
                                                    torch.ones(self.cell.shape[0], 3, dtype=torch.bool, device=self.dev))
+        self.volume = None if self.cell is None else self._volume(self.cell)
         self.n_real = int(batch[key].shape[0])
         self.n_graphs = len(batch)
         n = self._base["_n_nodes"].reshape(-1)
@@ -109,17 +136,72 @@ class ReplayedForceField:
             work = bucket.view()
             computeEdgeIndexCapped(work.data, work.attrs, r_max=self.r_max, key=self.key)
             out = model(work)
-            return out[self.energy_key].reshape(-1)[:self.n_graphs], out[self.forces_key][:self.n_real]
+            res = (out[self.energy_key].reshape(-1)[:self.n_graphs], out[self.forces_key][:self.n_real])
+            # (the model files them for the padded batch's graphs, the ghost graph last: the real graphs' rows)
+            return res + tuple(out[k].reshape(-1, 9)[:self.n_graphs] for k in self._extra_keys)
 
         self.captured = CapturedStep(evaluate, warmup=self.warmup, device=self.dev)
         self.valid = False
-        self._check_outputs(self.captured.out)
+        self._out = self.captured.out
+        self._check_outputs(self._out)
+
+    @property
+    def _extra_keys(self):
+        return tuple(k for k in (self.virial_key, self.stress_key) if k is not None)
+
+    @staticmethod
+    def _require_emitted(model, virial_key, stress_key) -> None:
+        from ..nn.output import GradientOutput
+
+        heads = [m for m in getattr(model, "modules", lambda: [])() if isinstance(m, GradientOutput)]
+        for what, key in (("virial", virial_key), ("stress", stress_key)):
+            if key is not None and not any(getattr(m, what) == key for m in heads):
+                raise KeyError(f"the model does not emit the {what} '{key}': nn.output.enable_virial(model, ...) sets the keys of its "
+                               "GradientOutput")
+
+    @staticmethod
+    def _volume(cell) -> torch.Tensor:
+        """float64 [G] on the cell's device: |det| of the fp32 cell the builder uses, formed on the host."""
+        return torch.linalg.det(cell.detach().to("cpu", torch.float64).reshape(-1, 3, 3)).abs().to(cell.device)
+
+    @property
+    def virial(self):
+        """[G, 3, 3] fp32, ``-dE_g / d eps`` (``GradientOutput``'s definition): a static view, overwritten by the next evaluation and
+        covered by ``valid`` / ``check()`` like energy and forces; None without a ``virial_key``."""
+        return None if self.virial_key is None else self._out[2].view(-1, 3, 3)
+
+    @property
+    def stress(self):
+        """[G, 3, 3] fp32, ``-virial / volume``: as ``virial``; None without a ``stress_key`` or without a cell."""
+        return None if self.stress_key is None else self._out[len(self._extra_keys) + 1].view(-1, 3, 3)
+
+    def set_cell(self, cell) -> None:
+        """New cells for the captured graph, ``[G, 3, 3]`` or ``[G, 9]`` (host or device), WITHOUT capturing again: ``check_cell`` runs
+        on the host first and raises before anything changes; then the static ``cell`` and its host-made float64 inverse (rounded to
+        fp32, as at construction) are overwritten in place -- the pointers stay, the next replay rebuilds the list -- ``cell`` and
+        ``volume`` follow and ``valid`` is False.  The ghost graph's rows stay zero.  The positions are the CALLER's to scale (a
+        homogeneous strain moves them with the cell: ``pos @ (I + eps)``); an open force field raises ``ValueError``.  For cell scans
+        and relaxations driven from the host (one synchronising copy per call); ``pbc`` does not change."""
+        if self.cell is None:
+            raise ValueError("set_cell: this force field was captured on an open batch (no 'cell'): there is no cell to change")
+        new = torch.as_tensor(cell).detach().to("cpu", torch.float64)
+        if new.numel() != 9 * self.n_graphs:
+            raise ValueError(f"set_cell needs [{self.n_graphs}, 3, 3] (or [{self.n_graphs}, 9]), got {tuple(new.shape)}")
+        new = new.reshape(-1, 3, 3).to(torch.float32)      # what the builder uses
+        check_cell(new, self.pbc, self.r_max)
+        inv = _inverse_cells(new.to(torch.float64)).to(torch.float32)
+        static = self.static.data
+        static["cell"].view(-1, 9)[:self.n_graphs].copy_(new.reshape(-1, 9))
+        static["_inv_cell"].view(-1, 9)[:self.n_graphs].copy_(inv.reshape(-1, 9))
+        self.cell.copy_(new)      # (a view of the base batch: a grow() captures on it)
+        self.volume = self._volume(self.cell)
+        self.valid = False
 
     @staticmethod
     def _check_outputs(out) -> None:
         # the integrator's kernels read these through raw pointers: dense fp32 rows or nothing (a slice of the leading rows of a
         # contiguous model output is contiguous; anything else is refused here, once per capture, not read wrongly)
-        for name, t in zip(("energy", "forces"), out):
+        for name, t in zip(("energy", "forces", "virial or stress", "stress"), out):
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise TypeError(f"the captured {name} output is {t.dtype}, contiguous={t.is_contiguous()}: the MD kernels need "
                                 "contiguous float32")
@@ -145,12 +227,14 @@ class ReplayedForceField:
             out = self.captured()
             if out is not self.captured.out:      # a re-capture replaced the static outputs
                 self._check_outputs(out)
+            self._out = out
             self.valid = True
-            return out
+            return out[:2]
         except EdgeCapacityExceeded:
             self._overflow = True
             self.valid = False
-            return self.captured.out
+            self._out = self.captured.out
+            return self._out[:2]
 
     def __call__(self, pos):
         self.pos.copy_(pos)

@@ -1287,6 +1287,25 @@ int e3k_pbc_edge_vector_fwd(const float* pos, const int32_t* src, const int32_t*
                             const int64_t* node_seg, const float* cell, int32_t n_cells, int64_t N, int64_t E, float* edge_vec,
                             float* edge_len, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Virial (csrc/e3k_virial.hip): the strain derivative of the energy from the operands of the force backward.
+ * Row-vector convention (cell's): under x -> x (I + eps), cell -> cell (I + eps),
+ *   dE_g / d eps_ab = sum over the edges e of graph g of  v_e[a] g_e[b],
+ *   g_e = fmaf(len > 0 ? g_len / len : 0, vec, g_vec)      (fp32: e3k_edge_vector_bwd's per-edge gradient, bit for bit)
+ * with v_e = edge_vec[e], the vector the model saw (the periodic shift included).  e3k_virial_edges writes
+ *   out[g, 3 a + b] = -(that sum)      the virial, fp32 [G, 9]; written, never accumulated: a graph without edges gets zeros.
+ * The nine products and sums are formed in double and rounded once.  One workgroup per graph walks the graph's slots of the
+ * by-source CSR -- nodes are sorted by graph, so they are [src_ptr[graph_ptr[g]], src_ptr[graph_ptr[g + 1]]) of src_perm -- and
+ * adds in a fixed order: no atomics, the same bits every run, one launch and no zero fill (safe inside a capture).
+ *   g_vec [E, 3] or NULL, g_len [E] or NULL (one of them at least), edge_vec [E, 3], edge_len [E] (needed with g_len),
+ *   src_ptr [N + 1], src_perm [E] int32 (GraphTopo's), graph_ptr [G + 1] int32 row pointers of the graphs over the nodes.
+ *   Every index read is clamped to its table.  G == 0 launches nothing; E == 0 writes the zeros.  Refused (E3K_ERR_INVALID,
+ *   nothing launched): N, E or G < 0, N or E >= 2^31; with G > 0 a NULL out, graph_ptr or src_ptr; with E > 0 a NULL edge_vec or
+ *   src_perm, both gradients NULL, g_len without edge_len.
+ * ------------------------------------------------------------------------------------------ */
+int e3k_virial_edges(const float* g_vec, const float* g_len, const float* edge_vec, const float* edge_len, const int32_t* src_ptr,
+                     const int32_t* src_perm, const int32_t* graph_ptr, int64_t N, int64_t E, int32_t G, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ evaluation, the neighbour list rebuilt inside it, two integrator launches beside
     python tools/md_bench.py --fire --out profiles/md_fire.json                         (the FIRE iteration against its eager loop)
     python tools/md_bench.py --constraints --out profiles/md_constraints.json           (the SHAKE / RATTLE step against the plain step)
     python tools/md_bench.py --pbc --molecules 32 64 --out profiles/md_pbc.json         (the step in a vacuum cell against the open step)
+    python tools/md_bench.py --stress --out profiles/md_stress.json                     (virial and stress delivered against the same step without)
+    python tools/md_bench.py --stress --one-graph --molecules 128                       (... with the molecules as ONE graph of 2 000+ atoms)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/md_bench.py --trace-steps 60 --molecules 32
     python tools/md_bench.py --launches DIR_A/…_kernel_stats.csv 10 DIR_B/…_kernel_stats.csv 60      (launches per replayed step)
 
@@ -251,6 +253,77 @@ def bench_pbc(n_mol, steps, warmup, reps, dt, dev):
             "periodic_over_open_median": round(statistics.median(rows["periodic"]) / statistics.median(rows["open"]), 4)}
 
 
+def vacuum_cell(batch, x0, r_max, dev):
+    """``batch`` in the cubic vacuum cell of ``bench_pbc`` (in place), and the cell's width"""
+    width = float((x0.max(0).values - x0.min(0).values).max()) + 2.0 * r_max + 8.0
+    batch.attrs["cell"] = ("graph", "3x1o")
+    batch["cell"] = (width * torch.eye(3, device=dev)).reshape(1, 9).repeat(len(batch), 1)
+    return width
+
+
+def single_graph(n_mol: int, dev):
+    """``setup`` with the molecules of the batch laid out on a line, 40 A apart, as ONE graph (the generator's molecules have 29 atoms
+    at most: this is how it supplies a graph of thousands of atoms).  The virial kernel then walks every edge in one workgroup."""
+    from e3_layers_amd.configs import config_energy_force
+    from e3_layers_amd.data import computeEdgeIndex
+    from e3_layers_amd.data.data import Batch
+    from e3_layers_amd.data.synthetic import synth_qm9_list
+    from e3_layers_amd.utils import build
+
+    tree = config_energy_force.get_config().model_config
+    torch.manual_seed(0)
+    model = build(tree).to(dev).eval()
+    lst, attrs = synth_qm9_list(4000 + n_mol, n_mol, config_energy_force.SHIFTS, r_max=None)
+    pos = torch.cat([s["pos"] + torch.tensor([40.0 * k, 0.0, 0.0]) for k, s in enumerate(lst)])
+    one = {"pos": pos, "species": torch.cat([s["species"] for s in lst]), "total_energy": sum(s["total_energy"] for s in lst),
+           "_n_nodes": torch.tensor([[pos.shape[0]]])}
+    new, _ = computeEdgeIndex(one, dict(attrs), r_max=float(tree.r_max))
+    one["edge_index"] = new["edge_index"]
+    one.pop("_n_edges", None)
+    batch = Batch.from_data_list([one], dict(attrs)).to(dev)
+    x0 = batch["pos"].clone()
+    v0 = 0.5 * torch.randn(x0.shape, generator=torch.Generator().manual_seed(1)).to(dev)
+    return model, batch, float(tree.r_max), x0, v0
+
+
+def bench_stress(n_mol, steps, warmup, reps, dt, dev, one_graph=False):
+    """The replayed step with virial and stress delivered against the same step without, both in the vacuum cell of ``bench_pbc``:
+    two models of the same weights (the keys are attributes of the tree), a force field each, the two alternating.  What differs is
+    one launch inside the graph (``e3k_virial_edges``) and the elementwise ops of the stress.  ``one_graph``: the molecules as a
+    single graph (``single_graph``): the kernel's one-workgroup walk at its longest."""
+    from e3_layers_amd.nn import enable_virial
+    from e3_layers_amd.run.md import ReplayedForceField, VelocityVerlet, pressure
+
+    make = single_graph if one_graph else setup
+    model, batch, r_max, x0, v0 = make(n_mol, dev)
+    keyed = enable_virial(make(n_mol, dev)[0])
+    width = vacuum_cell(batch, x0, r_max, dev)
+    ffs = {"plain": ReplayedForceField(model, batch, r_max),
+           "stress": ReplayedForceField(keyed, batch, r_max, virial_key="virial", stress_key="stress")}
+    mds = {k: VelocityVerlet(ff, torch.ones(x0.shape[0]), dt) for k, ff in ffs.items()}
+    rows = {k: [] for k in ("plain", "stress", "plain_host", "stress_host")}
+    for name, md in mds.items():
+        replay_start(md, ffs[name], x0, v0)
+        md.run(warmup, check_every=warmup)
+    for _ in range(reps):
+        for name, md in mds.items():
+            replay_start(md, ffs[name], x0, v0)
+            ms, host = timed(replay_steps(md, ffs[name], steps))
+            ffs[name].check()
+            rows[name].append(ms / steps)
+            rows[name + "_host"].append(1e3 * host / steps)
+    diff = statistics.median(rows["stress"]) - statistics.median(rows["plain"])
+    ff = ffs["stress"]
+    return {"molecules": n_mol, "graphs": len(batch), "atoms": int(x0.shape[0]), "edges_at_end": int(ff.n_edges), "cell_width": round(width, 3),
+            "e_cap": ff.e_cap, "steps": steps, "reps": reps, "dt": dt, "regrowths": sum(md.regrowths for md in mds.values()),
+            "recaptures": sum(f.recaptures for f in ffs.values()),
+            "plain_ms_per_step": mmm(rows["plain"]), "stress_ms_per_step": mmm(rows["stress"]),
+            "plain_host_busy_ms_per_step": mmm(rows["plain_host"]), "stress_host_busy_ms_per_step": mmm(rows["stress_host"]),
+            "stress_minus_plain_us_median": round(1e3 * diff, 2),
+            "stress_over_plain_median": round(statistics.median(rows["stress"]) / statistics.median(rows["plain"]), 4),
+            "virial_pressure_at_end": [round(float(p), 6) for p in pressure(ff.virial, torch.zeros(len(batch)), ff.volume)[:4]]}
+
+
 def timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -369,6 +442,8 @@ def main():
     ap.add_argument("--fire", action="store_true", help="the FIRE iteration against its eager loop")
     ap.add_argument("--constraints", action="store_true", help="the step with bonds to hydrogen constrained against the plain step")
     ap.add_argument("--pbc", action="store_true", help="the step in a vacuum cell (periodic builder, same edge set) against the open step")
+    ap.add_argument("--stress", action="store_true", help="the step with virial and stress delivered against the step without (vacuum cell)")
+    ap.add_argument("--one-graph", action="store_true", help="with --stress: the molecules as ONE graph (the virial kernel's longest walk)")
     ap.add_argument("--kT", type=float, default=0.25, help="thermostat temperature in the model's energy units (v0 has variance 0.25)")
     ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
@@ -384,11 +459,14 @@ def main():
         from e3_layers_amd.run.md import Langevin, ReplayedForceField, VelocityVerlet
 
         model, batch, r_max, x0, v0 = setup(args.molecules[0], dev)
-        if args.pbc:      # the vacuum cell of bench_pbc
-            width = float((x0.max(0).values - x0.min(0).values).max()) + 2.0 * r_max + 8.0
-            batch.attrs["cell"] = ("graph", "3x1o")
-            batch["cell"] = (width * torch.eye(3, device=dev)).reshape(1, 9).repeat(len(batch), 1)
-        ff = ReplayedForceField(model, batch, r_max)
+        if args.pbc or args.stress:      # the vacuum cell of bench_pbc
+            vacuum_cell(batch, x0, r_max, dev)
+        if args.stress:
+            from e3_layers_amd.nn import enable_virial
+
+            ff = ReplayedForceField(enable_virial(model), batch, r_max, virial_key="virial", stress_key="stress")
+        else:
+            ff = ReplayedForceField(model, batch, r_max)
         if args.fire:
             make_fire(ff).run(args.trace_steps, check_every=args.trace_steps)
         else:
@@ -404,7 +482,7 @@ def main():
             md.run(args.trace_steps, check_every=args.trace_steps)
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0], "integrator": args.integrator, "fire": args.fire,
-                          "constraints": args.constraints, "pbc": args.pbc}))
+                          "constraints": args.constraints, "pbc": args.pbc, "stress": args.stress}))
         return
     if args.fire:
         workload = "FIRE relaxation with per-graph state on config_energy_force (as shipped), synth_qm9: replayed iteration vs the eager loop"
@@ -413,6 +491,10 @@ def main():
         workload = ("velocity-Verlet step with the bonds to hydrogen constrained (SHAKE / RATTLE) vs the plain step, both replayed, on "
                     "config_energy_force (as shipped), synth_qm9, masses 1 (H) and 12")
         results = [bench_constraints(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
+    elif args.stress:
+        workload = ("velocity-Verlet step with virial and stress delivered vs the same step without, both replayed in a cubic vacuum cell, on "
+                    "config_energy_force (as shipped), synth_qm9" + (" laid out as one graph" if args.one_graph else "") + ", unit masses")
+        results = [bench_stress(n, args.steps, args.warmup, args.reps, args.dt, dev, args.one_graph) for n in args.molecules]
     elif args.pbc:
         workload = ("velocity-Verlet step in a cubic vacuum cell (periodic builder and edge vectors, identical edge set) vs the "
                     "open-boundary step, both replayed, on config_energy_force (as shipped), synth_qm9, unit masses")
