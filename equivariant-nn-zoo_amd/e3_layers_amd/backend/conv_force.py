@@ -110,7 +110,7 @@ def _edge_grad_buffers(tp, e: int, dev):
         part = None
     else:
         buf = torch.empty(e * (tp.d_sh + 1), device=dev, dtype=torch.float32)
-        part = torch.empty(max(int(L.load().e3k_tp_edge_partials_floats(tp.handle(dev), e)), 1), device=dev, dtype=torch.float32)
+        part = torch.empty(tp.edge_partials_floats(dev, e), device=dev, dtype=torch.float32)
     return buf[:e * tp.d_sh].view(e, tp.d_sh), buf[e * tp.d_sh:], part
 
 
@@ -182,8 +182,7 @@ def _gate_bwd2(conv, gy, h, spec, out_cf: bool, want_gy: bool = True, want_x: bo
     """(cot g_y, cot conv) of g_conv = gate'(conv) g_y for the cotangent h of g_conv"""
     g_gy = torch.empty_like(gy) if want_gy else None
     g_x = torch.empty_like(conv) if want_x else None
-    L.check(L.load().e3k_gate_bwd2(L.ptr(conv), L.ptr(gy), L.ptr(h), conv.shape[0], spec.in_dim, spec.out_dim, spec.c_array(),
-                                   len(spec.segs), int(out_cf), L.ptr(g_gy), L.ptr(g_x), L.stream_ptr()), "e3k_gate_bwd2")
+    ops._gate_bwd2_raw(conv, gy, h, g_gy, g_x, spec, out_cf)
     return g_gy, g_x
 
 

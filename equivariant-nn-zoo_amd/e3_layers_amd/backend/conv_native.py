@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import time
 from typing import List, Optional
 
 import torch
@@ -185,8 +186,11 @@ class NativeLayer:
                 L.check(L.load().e3k_layer_create(C.byref(self.desc), C.byref(out)), "e3k_layer_create")
             h = self.handles[idx] = out.value
             if self.prof[0]:
-                L.check(L.load().e3k_layer_profile_mask(h, *self.prof), "e3k_layer_profile_mask")
+                self._arm(h)
         return h
+
+    def _arm(self, h) -> None:
+        L.check(L.load().e3k_layer_profile_mask(h, *self.prof), "e3k_layer_profile_mask")
 
     # ---- the backward for a gradient that is zero outside some columns ----
     def live_sets(self, cols) -> LiveSets:
@@ -310,7 +314,7 @@ class NativeLayer:
         for lay in self._all():
             lay.prof = (capacity, mask)
             for h in lay.handles.values():
-                L.check(L.load().e3k_layer_profile_mask(h, capacity, mask), "e3k_layer_profile_mask")
+                lay._arm(h)
 
     def profile_read(self, kind: str):
         out = []
@@ -856,14 +860,10 @@ class NativeConvBlockFn(torch.autograd.Function):
             a.conv = _ptr(buf, off["conv"])
             if addend is not None:
                 buf[off["conv"]:off["conv"] + n * plan.post_spec.d_out].view(n, plan.post_spec.d_out).copy_(addend)
+        t_c = time.perf_counter() if HOST_TIMING is not None else 0.0
+        L.check(L.load().e3k_layer_fwd(layer, C.byref(a)), "e3k_layer_fwd")
         if HOST_TIMING is not None:
-            import time
-
-            t_c = time.perf_counter()
-            L.check(L.load().e3k_layer_fwd(layer, C.byref(a)), "e3k_layer_fwd")
             HOST_TIMING[1] += time.perf_counter() - t_c
-        else:
-            L.check(L.load().e3k_layer_fwd(layer, C.byref(a)), "e3k_layer_fwd")
         if own_table is not None:      # the a-posteriori error guard of the table just built (radial stream)
             with conv_block._on(side, main):
                 radial_table.guard(plan.guard_key if plan.guard_key is not None else w_last, own_table, blocks=table.blocks)
@@ -1070,15 +1070,14 @@ class NativeConvBlockFn(torch.autograd.Function):
                     sc_.add("g_T", r * last.d_out)
                 if narrow is not None:
                     sc_.add("g_T_live", r * w_cols)
-                sc_.add("table_ws", int(L.load().e3k_rtable_bwd_workspace_floats(e, table.knots, w_cols)))
+                sc_.add("table_ws", radial_table.interp_bwd_workspace_floats(e, table.knots, w_cols))
             if need_radial or any(need_hidden):
                 sc_.add("g_h", r * last.d_in)
         if want_sc:
             sc_.add("gm", groups.n_keys * plan.sc_ld_m)
             if need_attrs:
                 sc_.add("ga", groups.n_keys * sc.v)
-                sc_.add("kw_ws", int(L.load().e3k_keyed_weights_bwd_workspace(ops._kw_array(sc, plan.sc_m_off), len(sc.instr),
-                                                                               groups.n_keys, sc.v)))
+                sc_.add("kw_ws", ops._kw_bwd_workspace(sc, plan.sc_m_off, groups.n_keys))
         work = sc_.alloc(dev)
         so = sc_.off
         a.g_conv, a.g_mid = _ptr(work, so["g_conv"]), _ptr(work, so["g_mid"])
@@ -1109,14 +1108,10 @@ class NativeConvBlockFn(torch.autograd.Function):
             with conv_block._on(side, main):
                 g_radial = torch.empty_like(edge_radial)
             a.g_radial = g_radial.data_ptr()
+        t_c = time.perf_counter() if HOST_TIMING is not None else 0.0
+        L.check(L.load().e3k_layer_bwd(layer, C.byref(a)), "e3k_layer_bwd")
         if HOST_TIMING is not None:
-            import time
-
-            t_c = time.perf_counter()
-            L.check(L.load().e3k_layer_bwd(layer, C.byref(a)), "e3k_layer_bwd")
             HOST_TIMING[3] += time.perf_counter() - t_c
-        else:
-            L.check(L.load().e3k_layer_bwd(layer, C.byref(a)), "e3k_layer_bwd")
         if narrow is not None and g_x is not None:
             # The narrow layer wrote g_x through its live linear_1 and self-connection instructions only, on a row the executor
             # zero-filled where they do not reach (csrc/e3k_layer.hip, e3k_layer_bwd: "if (!covered && e3k::zero_fill(a->g_xcf";

@@ -444,6 +444,29 @@ def _templates(spec, key, build) -> _GemmTemplates:
     return t
 
 
+def _gemm_problem(ins, spec, role: str, b_off: int, alpha: float) -> "L.GemmProblem":
+    """One instruction of a ``LinearSpec`` / ``FctpSpec`` as a plain ``e3k_gemm_problem`` in one of its three roles -- the one place
+    that says which block is A, which is C and how B is walked:
+
+      ``"fwd"``    C = output block (+)= A = input block . B        (B [mul_in, mul_out] as stored)
+      ``"dgrad"``  C = input block (+)= A = output block . B^T
+      ``"wgrad"``  B += A = input block ^T . C = output block       (the fields of ``"fwd"``: the entry exchanges the roles)
+
+    A and C hold BYTE OFFSETS from their tensors' bases (the ``*_rebased`` entries add those), B the offset of ``b_off`` elements;
+    no bias, no activation, ``accumulate`` 0: the callers set what is theirs."""
+    src = (ins.in_off, ins.mul_in, spec.in_layout, spec.d_in)
+    dst = (ins.out_off, ins.mul_out, spec.out_layout, spec.d_out)
+    (a_off, k, a_layout, a_r1), (c_off, n, c_layout, c_r1) = (dst, src) if role == "dgrad" else (src, dst)
+    p = L.GemmProblem()
+    p.A, p.A2, p.B, p.C, p.bias = 4 * a_off, None, 4 * b_off, 4 * c_off, None
+    p.M1, p.M2, p.N, p.K, p.V = 0, ins.dim, n, k, 0
+    p.a_r1, (p.a_r2, p.a_k) = a_r1, _layout_strides(a_layout, k, ins.dim)
+    p.b_k, p.b_n = (1, ins.mul_out) if role == "dgrad" else (ins.mul_out, 1)
+    p.c_r1, (p.c_r2, p.c_n) = c_r1, _layout_strides(c_layout, n, ins.dim)
+    p.alpha = alpha
+    return p
+
+
 def _lin_fwd_templates(spec: "LinearSpec", scale: float, accumulate: bool, act: int, act_cst: float, has_bias: bool):
     bias_at = {off: 4 * boff + 1 for off, mul, boff in spec.bias_blocks} if has_bias else {}
     done_bias = set()
@@ -454,20 +477,11 @@ def _lin_fwd_templates(spec: "LinearSpec", scale: float, accumulate: bool, act: 
     for r, group in enumerate(rounds):
         probs = []
         for ins in group:
-            a_r2, a_k = _layout_strides(spec.in_layout, ins.mul_in, ins.dim)
-            c_r2, c_n = _layout_strides(spec.out_layout, ins.mul_out, ins.dim)
-            p = L.GemmProblem()
-            p.A, p.A2, p.B, p.C = 4 * ins.in_off, None, 4 * ins.w_off, 4 * ins.out_off
-            p.bias = None
+            p = _gemm_problem(ins, spec, "fwd", ins.w_off, ins.alpha * scale)
             if r == 0 and ins.out_off in bias_at:
                 p.bias = bias_at[ins.out_off]
                 done_bias.add(ins.out_off)
-            p.M1, p.M2, p.N, p.K, p.V = 0, ins.dim, ins.mul_out, ins.mul_in, 0
             p.accumulate = 1 if (r > 0 or accumulate) else 0
-            p.a_r1, p.a_r2, p.a_k = spec.d_in, a_r2, a_k
-            p.b_k, p.b_n = ins.mul_out, 1
-            p.c_r1, p.c_r2, p.c_n = spec.d_out, c_r2, c_n
-            p.alpha = ins.alpha * scale
             if act:
                 p.act, p.act_cst = act, act_cst
             probs.append(p)
@@ -492,16 +506,8 @@ def _lin_dgrad_templates(spec: "LinearSpec", scale: float, accumulate: bool = Fa
     for r, group in enumerate(spec.rounds("i_in")):
         probs = []
         for ins in group:
-            a_r2, a_k = _layout_strides(spec.out_layout, ins.mul_out, ins.dim)
-            c_r2, c_n = _layout_strides(spec.in_layout, ins.mul_in, ins.dim)
-            p = L.GemmProblem()
-            p.A, p.A2, p.B, p.C, p.bias = 4 * ins.out_off, None, 4 * ins.w_off, 4 * ins.in_off, None
-            p.M1, p.M2, p.N, p.K, p.V = 0, ins.dim, ins.mul_in, ins.mul_out, 0
+            p = _gemm_problem(ins, spec, "dgrad", ins.w_off, ins.alpha * scale)
             p.accumulate = 1 if (r > 0 or accumulate) else 0
-            p.a_r1, p.a_r2, p.a_k = spec.d_out, a_r2, a_k
-            p.b_k, p.b_n = 1, ins.mul_out  # W^T
-            p.c_r1, p.c_r2, p.c_n = spec.d_in, c_r2, c_n
-            p.alpha = ins.alpha * scale
             probs.append(p)
         out.append(probs)
     return _GemmTemplates(out)
@@ -520,16 +526,8 @@ def _lin_dgrad_raw(gy, weight, spec: LinearSpec, scale: float, out=None, accumul
 def _lin_wgrad_templates(spec: "LinearSpec", scale: float):
     probs = []
     for ins in spec.instr:
-        a_r2, a_k = _layout_strides(spec.in_layout, ins.mul_in, ins.dim)
-        c_r2, c_n = _layout_strides(spec.out_layout, ins.mul_out, ins.dim)
-        p = L.GemmProblem()
-        p.A, p.A2, p.B, p.C, p.bias = 4 * ins.in_off, None, 4 * ins.w_off, 4 * ins.out_off, None
-        p.M1, p.M2, p.N, p.K, p.V = 0, ins.dim, ins.mul_out, ins.mul_in, 0
+        p = _gemm_problem(ins, spec, "wgrad", ins.w_off, ins.alpha * scale)
         p.accumulate = 1
-        p.a_r1, p.a_r2, p.a_k = spec.d_in, a_r2, a_k
-        p.b_k, p.b_n = ins.mul_out, 1
-        p.c_r1, p.c_r2, p.c_n = spec.d_out, c_r2, c_n
-        p.alpha = ins.alpha * scale
         probs.append(p)
     return _GemmTemplates([probs], wgrad=True)
 
@@ -768,16 +766,9 @@ class MlpHiddenFn(torch.autograd.Function):
         L.require_cuda(x, *weights)
         x = L.f32c(x)
         weights = tuple(L.f32c(w) for w in weights)
-        e, k0 = x.shape
-        h, n = weights[0].shape[1], len(weights)
-        need_grad = any(ctx.needs_input_grad)
-        out = torch.empty(e, h, device=x.device, dtype=torch.float32)
-        zs = [torch.empty(e, h, device=x.device, dtype=torch.float32) for _ in range(n)] if need_grad else []
-        L.check(L.load().e3k_mlp_hidden_fwd(L.ptr(x), e, k0, h, n, _ptr_array(weights), (C.c_float * n)(*alphas), ACT_IDS[act],
-                                            cst, _ptr_array(zs) if zs else None, L.ptr(out), L.stream_ptr()),
-                "e3k_mlp_hidden_fwd")
+        out, zs = _mlp_fwd_raw(x, weights, alphas, act, cst, keep=any(ctx.needs_input_grad))      # (no gradient wanted: no zs)
         ctx.save_for_backward(x, *weights, *zs)
-        ctx.cfg = (alphas, act, cst, n)
+        ctx.cfg = (alphas, act, cst, len(weights))
         return out
 
     @staticmethod
@@ -795,8 +786,6 @@ class MlpHiddenFn(torch.autograd.Function):
             gws = [grads.pop(0) if nd else None for nd in need[4:]]
             return (gx, None, None, None, *gws)
         g = L.f32c(g)
-        e, k0 = x.shape
-        h = weights[0].shape[1]
         gx = torch.empty_like(x) if need[0] else None
         gws, ret = [], []
         for w, nd in zip(weights, need[4:]):
@@ -812,9 +801,7 @@ class MlpHiddenFn(torch.autograd.Function):
                 buf = torch.zeros_like(w)
                 gws.append(buf)
                 ret.append(buf)
-        L.check(L.load().e3k_mlp_hidden_bwd(L.ptr(x), e, k0, h, n, _ptr_array(weights), (C.c_float * n)(*alphas), ACT_IDS[act],
-                                            cst, _ptr_array(zs), L.ptr(g), _ptr_array(gws), L.ptr(gx), L.stream_ptr()),
-                "e3k_mlp_hidden_bwd")
+        _mlp_bwd_raw(x, weights, zs, alphas, act, cst, g, gws, gx)
         return (gx, None, None, None, *ret)
 
 
@@ -861,16 +848,11 @@ def _fctp_problems(x, attrs, b, c, spec: FctpSpec, rows: int, wgrad: bool):
     for r, group in enumerate(rounds):
         probs = []
         for ins in group:
-            a_r2, a_k = _layout_strides(spec.in_layout, ins.mul_in, ins.dim)
-            c_r2, c_n = _layout_strides(spec.out_layout, ins.mul_out, ins.dim)
-            p = L.GemmProblem()
-            p.A, p.A2, p.B, p.C, p.bias = _addr(x, ins.in_off), _addr(attrs), _addr(b, ins.w_off), _addr(c, ins.out_off), None
-            p.M1, p.M2, p.N, p.K, p.V = rows, ins.dim, ins.mul_out, ins.mul_in * spec.v, spec.v
+            p = _gemm_problem(ins, spec, "wgrad" if wgrad else "fwd", ins.w_off, ins.alpha)
+            # the outer mode: absolute addresses, the second operand, K over (u, v)
+            p.A, p.A2, p.B, p.C = _addr(x, ins.in_off), _addr(attrs), _addr(b, ins.w_off), _addr(c, ins.out_off)
+            p.M1, p.K, p.V, p.a2_r1 = rows, ins.mul_in * spec.v, spec.v, spec.v
             p.accumulate = 1 if (wgrad or r > 0) else 0
-            p.a_r1, p.a_r2, p.a_k, p.a2_r1 = spec.d_in, a_r2, a_k, spec.v
-            p.b_k, p.b_n = ins.mul_out, 1
-            p.c_r1, p.c_r2, p.c_n = spec.d_out, c_r2, c_n
-            p.alpha = ins.alpha
             probs.append(p)
         out.append(probs)
     return out
@@ -908,16 +890,11 @@ def _fctp_bwd_inputs_raw(gy, x, attrs, weight, spec: FctpSpec, want_x: bool, wan
     H = torch.empty(rows * hmax, device=dev, dtype=torch.float32)
     seen_in = set()
     for ins in spec.instr:
-        a_r2, a_k = _layout_strides(spec.out_layout, ins.mul_out, ins.dim)
         uv = ins.mul_in * spec.v
-        p = L.GemmProblem()
-        p.A, p.A2, p.B, p.C, p.bias = _addr(gy, ins.out_off), None, _addr(weight, ins.w_off), _addr(H), None
-        p.M1, p.M2, p.N, p.K, p.V = rows, ins.dim, uv, ins.mul_out, 0
-        p.accumulate = 0
-        p.a_r1, p.a_r2, p.a_k = spec.d_out, a_r2, a_k
-        p.b_k, p.b_n = 1, ins.mul_out  # W viewed [(u,v), w] transposed
-        p.c_r1, p.c_r2, p.c_n = ins.dim * uv, uv, 1
-        p.alpha = ins.alpha
+        p = _gemm_problem(ins, spec, "dgrad", ins.w_off, ins.alpha)      # gy . W^T, W viewed [(u, v), w] ...
+        p.A, p.B, p.C = _addr(gy, ins.out_off), _addr(weight, ins.w_off), _addr(H)
+        p.M1, p.N = rows, uv
+        p.c_r1, p.c_r2, p.c_n = ins.dim * uv, uv, 1                      # ... into the scratch rows [rows, dim, (u, v)]
         _run_gemm([p])
         L.check(
             lib.e3k_fctp_reduce_bwd(_addr(H), _addr(x, ins.in_off), _addr(attrs), rows, ins.dim, ins.mul_in, spec.v,
@@ -1084,6 +1061,11 @@ def _kw_array(spec: "FctpSpec", m_off):
     return _templates(spec, ("kw", tuple(m_off)), build)
 
 
+def _kw_bwd_workspace(spec: "FctpSpec", m_off, n_keys: int) -> int:
+    """floats of scratch ``e3k_keyed_weights_bwd`` needs to form the attributes' gradient"""
+    return int(L.load().e3k_keyed_weights_bwd_workspace(_kw_array(spec, m_off), len(spec.instr), n_keys, spec.v))
+
+
 def _kw_fwd_raw(a_rep, weight, spec: "FctpSpec", m_off, ld_m: int):
     k = a_rep.shape[0]
     m = torch.empty(k, ld_m, device=a_rep.device, dtype=torch.float32)
@@ -1100,7 +1082,7 @@ def _kw_bwd_raw(a_rep, weight, gm, spec: "FctpSpec", m_off, ld_m: int, want_a: b
     ga = work = None
     if want_a:
         ga = torch.zeros(k, spec.v, device=gm.device, dtype=torch.float32)
-        work = torch.empty(lib.e3k_keyed_weights_bwd_workspace(arr, len(spec.instr), k, spec.v), device=gm.device, dtype=torch.float32)
+        work = torch.empty(_kw_bwd_workspace(spec, m_off, k), device=gm.device, dtype=torch.float32)
     L.check(lib.e3k_keyed_weights_bwd(L.ptr(a_rep), L.ptr(weight), L.ptr(gm), arr, len(spec.instr), k, spec.v, ld_m, L.ptr(ga),
                                       L.ptr(gw), acc, L.ptr(work), L.stream_ptr()), "e3k_keyed_weights_bwd")
     return ga
@@ -1206,44 +1188,14 @@ def _grouped_templates(spec, m_off, mode: str):
     expands them over the keys inside the kernel), split into rounds so that no two problems of one launch write the
     same block; cached on the spec."""
     def build():
-        tmpl = []
-        for j, ins in enumerate(spec.instr):
-            in_r2, in_k = _layout_strides(spec.in_layout, ins.mul_in, ins.dim)
-            out_r2, out_n = _layout_strides(spec.out_layout, ins.mul_out, ins.dim)
-            p = L.GemmProblem()
-            p.bias, p.A2, p.V = None, None, 0
-            p.M1, p.M2 = 0, ins.dim
-            p.alpha = ins.alpha
-            if mode == "fwd":      # y = x . M
-                p.A, p.B, p.C = 4 * ins.in_off, 4 * m_off[j], 4 * ins.out_off
-                p.N, p.K = ins.mul_out, ins.mul_in
-                p.a_r1, p.a_r2, p.a_k = spec.d_in, in_r2, in_k
-                p.b_k, p.b_n = ins.mul_out, 1
-                p.c_r1, p.c_r2, p.c_n = spec.d_out, out_r2, out_n
-            elif mode in ("dgrad", "dgrad_acc"):  # gx (+)= gy . M^T      (A := gy, C := gx)
-                p.A, p.B, p.C = 4 * ins.out_off, 4 * m_off[j], 4 * ins.in_off
-                p.N, p.K = ins.mul_in, ins.mul_out
-                p.a_r1, p.a_r2, p.a_k = spec.d_out, out_r2, out_n
-                p.b_k, p.b_n = 1, ins.mul_out
-                p.c_r1, p.c_r2, p.c_n = spec.d_in, in_r2, in_k
-            else:                  # wgrad: gm += x^T . gy   (C := gy)
-                p.A, p.B, p.C = 4 * ins.in_off, 4 * m_off[j], 4 * ins.out_off
-                p.N, p.K = ins.mul_out, ins.mul_in
-                p.a_r1, p.a_r2, p.a_k = spec.d_in, in_r2, in_k
-                p.b_k, p.b_n = ins.mul_out, 1
-                p.c_r1, p.c_r2, p.c_n = spec.d_out, out_r2, out_n
-            tmpl.append((ins, p))
-        key = {"fwd": "i_out", "dgrad": "i_in", "dgrad_acc": "i_in", "wgrad": ""}[mode]
-        seen: Dict[int, int] = {}
-        rounds: List[List] = []
-        for ins, p in tmpl:
-            k = getattr(ins, key) if key else id(p)
-            r = seen.get(k, 0)
-            seen[k] = r + 1
-            while len(rounds) <= r:
-                rounds.append([])
-            p.accumulate = 1 if (r > 0 or mode in ("wgrad", "dgrad_acc")) else 0
-            rounds[r].append(p)
+        role = "dgrad" if mode == "dgrad_acc" else mode      # y = x . M;  gx (+)= gy . M^T;  gm += x^T . gy
+        b_off = {id(ins): off for ins, off in zip(spec.instr, m_off)}
+        groups = [list(spec.instr)] if mode == "wgrad" else spec.rounds("i_out" if mode == "fwd" else "i_in")
+        rounds = []
+        for r, group in enumerate(groups):
+            rounds.append([_gemm_problem(ins, spec, role, b_off[id(ins)], ins.alpha) for ins in group])
+            for p in rounds[r]:
+                p.accumulate = 1 if (r > 0 or mode in ("wgrad", "dgrad_acc")) else 0
         if mode != "wgrad":
             rounds = _chain_rounds(rounds)
         return [((L.GemmProblem * len(g))(*g), len(g)) for g in rounds]
@@ -1281,14 +1233,10 @@ def _run_segments(segment_lists, wgrad: bool = False) -> None:
     library packs up to 16 problems per launch); a multi-round set runs its rounds in order, alone."""
     lib, st = L.load(), L.stream_ptr()
     merged = [sl[0] for sl in segment_lists if len(sl) == 1]
-    if merged:
-        arr = (L.GemmSegment * len(merged))(*merged)
-        L.check(lib.e3k_gemm_multi(arr, len(merged), int(wgrad), st), "e3k_gemm_multi")
-    for sl in segment_lists:
-        if len(sl) > 1:
-            for sg in sl:
-                arr = (L.GemmSegment * 1)(sg)
-                L.check(lib.e3k_gemm_multi(arr, 1, int(wgrad), st), "e3k_gemm_multi")
+    alone = [[sg] for sl in segment_lists if len(sl) > 1 for sg in sl]
+    for segs in ([merged] if merged else []) + alone:
+        arr = (L.GemmSegment * len(segs))(*segs)
+        L.check(lib.e3k_gemm_multi(arr, len(segs), int(wgrad), st), "e3k_gemm_multi")
 
 
 def _lin_fwd_segs(x, weight, y, spec: "LinearSpec", scale: float, accumulate: bool):
@@ -1434,6 +1382,10 @@ class TpPlan:
             self._bwd_x_overwrites = bool(L.load().e3k_tp_bwd_x_overwrites(self.handle(device)))
         return self._bwd_x_overwrites
 
+    def edge_partials_floats(self, device: torch.device, e: int) -> int:
+        """floats of the per-item slices from which the ordered kernels combine the edge gradients (at least 1: never an empty tensor)"""
+        return max(int(L.load().e3k_tp_edge_partials_floats(self.handle(device), e)), 1)
+
     def __del__(self):
         try:
             lib = L.load()
@@ -1486,7 +1438,7 @@ def _tp_bwd_w_raw(x, sh, w, g_out, topo: GraphTopo, plan: TpPlan, want_sh: bool,
         # the harmonics' gradient in a fixed order: per-item slices (zero-filled: a group writes only the degrees it reads) and
         # an ordered combine, where e3k_tp_bwd_w adds the shares of an edge that several work items visit with float atomics
         gsh = torch.empty(e, plan.d_sh, device=x.device, dtype=torch.float32)
-        part = torch.zeros(max(int(L.load().e3k_tp_edge_partials_floats(handle, e)), 1), device=x.device, dtype=torch.float32)
+        part = torch.zeros(plan.edge_partials_floats(x.device, e), device=x.device, dtype=torch.float32)
         with timed_launch("tp_bwd_w_sh", (n, e, plan)):
             L.check(L.load().e3k_tp_bwd_w_ordered(handle, L.ptr(x), L.ptr(sh), L.ptr(w), L.ptr(g_out), L.ptr(topo.src),
                                                   L.ptr(topo.dst_ptr), L.ptr(topo.dst_perm), n, e, L.ptr(gw), L.ptr(gsh), L.ptr(part),
@@ -1619,23 +1571,55 @@ def tp_uvu_scatter(x, sh, w, topo: GraphTopo, plan: TpPlan):
 # --------------------------------------------------------------------------------------
 # elementwise / node-side ops
 # --------------------------------------------------------------------------------------
-class ActFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, act_id: int, cst: float):
+def _pointwise_pair(name: str, fwd, bwd, bwd2, packed: bool = False, doc: str = "", bwd_doc: str = ""):
+    """``(Fn, BwdFn)``: the autograd functions of an op ``y = f(x; cfg)`` with one tensor input, differentiable twice, from its three
+    raw launches ``fwd(x, *cfg) -> y``, ``bwd(x, gy, *cfg) -> gx`` and ``bwd2(x, gy, h, g_gy, g_x, *cfg)`` (writes the buffers that
+    are not None).  ``Fn`` saves ``x``; its backward is the raw ``bwd`` launch, or ``BwdFn`` when grad mode is on (force training
+    differentiates the backward).  ``BwdFn`` saves ``(x, gy)`` and is differentiable once more: its backward allocates the cotangents
+    its inputs need and skips the ``bwd2`` launch when neither is wanted.  ``packed``: ``bwd`` / ``bwd2`` / ``BwdFn.apply`` take the
+    configuration as ONE tuple argument."""
+
+    def bwd_forward(ctx, x, gy, *cfg):
+        x, gy = L.f32c(x), L.f32c(gy)
+        ctx.save_for_backward(x, gy)
+        ctx.cfg = cfg
+        return bwd(x, gy, *cfg)
+
+    @once_differentiable
+    def bwd_backward(ctx, h):
+        x, gy = ctx.saved_tensors
+        h = L.f32c(h)
+        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        g_gy = torch.empty_like(gy) if ctx.needs_input_grad[1] else None
+        if g_x is not None or g_gy is not None:
+            bwd2(x, gy, h, g_gy, g_x, *ctx.cfg)
+        return (g_x, g_gy) + (None,) * len(ctx.cfg)
+
+    def forward(ctx, x, *cfg):
         L.require_cuda(x)
         x = L.f32c(x)
-        y = torch.empty_like(x)
-        L.check(L.load().e3k_act_fwd(L.ptr(x), x.numel(), act_id, cst, L.ptr(y), L.stream_ptr()), "e3k_act_fwd")
         ctx.save_for_backward(x)
-        ctx.act_id, ctx.cst = act_id, cst
-        return y
+        ctx.cfg = cfg
+        return fwd(x, *cfg)
 
-    @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
-        if torch.is_grad_enabled():
-            return ActBwdFn.apply(x, gy, ctx.act_id, ctx.cst), None, None
-        return _act_bwd_raw(x, L.f32c(gy), ctx.act_id, ctx.cst), None, None
+        cfg = (ctx.cfg,) if packed else ctx.cfg
+        gx = BwdFn.apply(x, gy, *cfg) if torch.is_grad_enabled() else bwd(x, L.f32c(gy), *cfg)
+        return (gx,) + (None,) * len(ctx.cfg)
+
+    # (``type`` and not two ``class`` statements: autograd names the graph's nodes after the class -- ActFnBackward, ...)
+    BwdFn = type(name + "BwdFn", (torch.autograd.Function,),
+                 {"__doc__": bwd_doc or None, "forward": staticmethod(bwd_forward), "backward": staticmethod(bwd_backward)})
+    Fn = type(name + "Fn", (torch.autograd.Function,),
+              {"__doc__": doc or None, "forward": staticmethod(forward), "backward": staticmethod(backward)})
+    return Fn, BwdFn
+
+
+def _act_fwd_raw(x, act_id: int, cst: float):
+    y = torch.empty_like(x)
+    L.check(L.load().e3k_act_fwd(L.ptr(x), x.numel(), act_id, cst, L.ptr(y), L.stream_ptr()), "e3k_act_fwd")
+    return y
 
 
 def _act_bwd_raw(x, gy, act_id, cst):
@@ -1644,27 +1628,13 @@ def _act_bwd_raw(x, gy, act_id, cst):
     return gx
 
 
-class ActBwdFn(torch.autograd.Function):
-    """gx = gy * cst * act'(x), differentiable once more (e3k_act_bwd2: act'')."""
+def _act_bwd2_raw(x, gy, h, g_gy, g_x, act_id, cst) -> None:
+    L.check(L.load().e3k_act_bwd2(L.ptr(x), L.ptr(gy), L.ptr(h), x.numel(), act_id, cst, L.ptr(g_gy), L.ptr(g_x), L.stream_ptr()),
+            "e3k_act_bwd2")
 
-    @staticmethod
-    def forward(ctx, x, gy, act_id: int, cst: float):
-        x, gy = L.f32c(x), L.f32c(gy)
-        ctx.save_for_backward(x, gy)
-        ctx.act_id, ctx.cst = act_id, cst
-        return _act_bwd_raw(x, gy, act_id, cst)
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, h):
-        x, gy = ctx.saved_tensors
-        h = L.f32c(h)
-        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        g_gy = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        if g_x is not None or g_gy is not None:
-            L.check(L.load().e3k_act_bwd2(L.ptr(x), L.ptr(gy), L.ptr(h), x.numel(), ctx.act_id, ctx.cst, L.ptr(g_gy),
-                                          L.ptr(g_x), L.stream_ptr()), "e3k_act_bwd2")
-        return g_x, g_gy, None, None
+ActFn, ActBwdFn = _pointwise_pair("Act", _act_fwd_raw, _act_bwd_raw, _act_bwd2_raw,
+                                  bwd_doc="gx = gy * cst * act'(x), differentiable once more (e3k_act_bwd2: act'').")
 
 
 def activation(x, name: str, cst: float):
@@ -1699,12 +1669,8 @@ class RelayoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blocks, to_cf: bool):
         L.require_cuda(x)
-        x = L.f32c(x)
-        y = torch.empty_like(x)
-        L.check(L.load().e3k_relayout(L.ptr(x), x.shape[0], x.shape[1], _blocks(blocks), len(blocks), int(to_cf), L.ptr(y),
-                                      L.stream_ptr()), "e3k_relayout")
         ctx.blocks, ctx.to_cf = blocks, to_cf
-        return y
+        return _relayout_raw(L.f32c(x), blocks, to_cf)      # (``relayout()`` hands in blocks that move: never ``x`` itself)
 
     @staticmethod
     def backward(ctx, gy):   # a permutation: its backward is the inverse permutation (any order of derivative)
@@ -1735,31 +1701,8 @@ class GateSpec:
         return arr
 
 
-class GateFn(torch.autograd.Function):
-    """x (channel-fastest) -> gated output in the e3nn layout, or (``out_cf``) in the channel-fastest layout: consecutive
-    MessagePassing layers hand their features over in cf, so neither direction pays a relayout between them."""
-
-    @staticmethod
-    def forward(ctx, x, spec: GateSpec, out_cf: bool = False):
-        L.require_cuda(x)
-        x = L.f32c(x)
-        assert x.shape[1] == spec.in_dim
-        y = torch.empty(x.shape[0], spec.out_dim, device=x.device, dtype=torch.float32)
-        L.check(L.load().e3k_gate_fwd(L.ptr(x), x.shape[0], spec.in_dim, spec.out_dim, spec.c_array(), len(spec.segs),
-                                      int(out_cf), L.ptr(y), L.stream_ptr()), "e3k_gate_fwd")
-        ctx.save_for_backward(x)
-        ctx.spec, ctx.out_cf = spec, bool(out_cf)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        if torch.is_grad_enabled():
-            return GateBwdFn.apply(x, gy, ctx.spec, ctx.out_cf), None, None
-        return _gate_bwd_raw(x, L.f32c(gy), ctx.spec, ctx.out_cf), None, None
-
-
 def _gate_fwd_raw(x, spec: GateSpec, out_cf: bool = False):
+    assert x.shape[1] == spec.in_dim
     y = torch.empty(x.shape[0], spec.out_dim, device=x.device, dtype=torch.float32)
     L.check(L.load().e3k_gate_fwd(L.ptr(x), x.shape[0], spec.in_dim, spec.out_dim, spec.c_array(), len(spec.segs),
                                   int(out_cf), L.ptr(y), L.stream_ptr()), "e3k_gate_fwd")
@@ -1773,87 +1716,46 @@ def _gate_bwd_raw(x, gy, spec: GateSpec, out_cf: bool = False, gy2=None):
     return gx
 
 
-class GateBwdFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gy, spec: GateSpec, out_cf: bool = False):
-        x, gy = L.f32c(x), L.f32c(gy)
-        ctx.save_for_backward(x, gy)
-        ctx.spec, ctx.out_cf = spec, bool(out_cf)
-        return _gate_bwd_raw(x, gy, spec, out_cf)
+def _gate_bwd2_raw(x, gy, h, g_gy, g_x, spec: GateSpec, out_cf: bool = False) -> None:
+    """(cot g_y, cot x) of g_x = gate'(x) g_y for the cotangent h of g_x, into the buffers that are not None"""
+    L.check(L.load().e3k_gate_bwd2(L.ptr(x), L.ptr(gy), L.ptr(h), x.shape[0], spec.in_dim, spec.out_dim, spec.c_array(),
+                                   len(spec.segs), int(out_cf), L.ptr(g_gy), L.ptr(g_x), L.stream_ptr()), "e3k_gate_bwd2")
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, h):
-        x, gy = ctx.saved_tensors
-        spec = ctx.spec
-        h = L.f32c(h)
-        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        g_gy = torch.empty_like(gy) if ctx.needs_input_grad[1] else None
-        if g_x is not None or g_gy is not None:
-            L.check(L.load().e3k_gate_bwd2(L.ptr(x), L.ptr(gy), L.ptr(h), x.shape[0], spec.in_dim, spec.out_dim,
-                                           spec.c_array(), len(spec.segs), int(ctx.out_cf), L.ptr(g_gy), L.ptr(g_x),
-                                           L.stream_ptr()), "e3k_gate_bwd2")
-        return g_x, g_gy, None, None
+
+GateFn, GateBwdFn = _pointwise_pair(
+    "Gate", _gate_fwd_raw, _gate_bwd_raw, _gate_bwd2_raw,
+    doc="x (channel-fastest) -> gated output in the e3nn layout, or (``out_cf``) in the channel-fastest layout: consecutive "
+        "MessagePassing layers hand their features over in cf, so neither direction pays a relayout between them.")
 
 
 def gate(x, spec: GateSpec, out_cf: bool = False):
     return GateFn.apply(_c(x), spec, bool(out_cf))
 
 
-class NormActFn(torch.autograd.Function):
-    """e3nn.nn.NormActivation: x (channel-fastest) -> x * act(|x|) / |x| per irrep channel, e3nn layout out."""
-
-    @staticmethod
-    def forward(ctx, x, blocks, act_id: int, eps: float, normalize: bool):
-        L.require_cuda(x)
-        x = L.f32c(x)
-        y = torch.empty_like(x)
-        L.check(L.load().e3k_norm_act_fwd(L.ptr(x), x.shape[0], x.shape[1], _blocks(blocks), len(blocks), act_id, eps,
-                                          int(normalize), L.ptr(y), L.stream_ptr()), "e3k_norm_act_fwd")
-        ctx.save_for_backward(x)
-        ctx.cfg = (blocks, act_id, eps, normalize)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        blocks, act_id, eps, normalize = ctx.cfg
-        if torch.is_grad_enabled():   # double backward (force training): e3k_norm_act_bwd2
-            return NormActBwdFn.apply(x, gy, blocks, act_id, eps, normalize), None, None, None, None
-        return _norm_act_bwd_raw(x, gy, blocks, act_id, eps, normalize), None, None, None, None
+def _norm_act_fwd_raw(x, blocks, act_id: int, eps: float, normalize: bool):
+    y = torch.empty_like(x)
+    L.check(L.load().e3k_norm_act_fwd(L.ptr(x), x.shape[0], x.shape[1], _blocks(blocks), len(blocks), act_id, eps,
+                                      int(normalize), L.ptr(y), L.stream_ptr()), "e3k_norm_act_fwd")
+    return y
 
 
 def _norm_act_bwd_raw(x, gy, blocks, act_id, eps, normalize):
-    gy = L.f32c(gy)
     gx = torch.empty_like(x)
     L.check(L.load().e3k_norm_act_bwd(L.ptr(x), L.ptr(gy), x.shape[0], x.shape[1], _blocks(blocks), len(blocks), act_id,
                                       eps, int(normalize), L.ptr(gx), L.stream_ptr()), "e3k_norm_act_bwd")
     return gx
 
 
-class NormActBwdFn(torch.autograd.Function):
-    """The first backward of NormActivation as a differentiable op (round 2 differentiated a torch restatement here)."""
+def _norm_act_bwd2_raw(x, gy, h, g_gy, g_x, blocks, act_id, eps, normalize) -> None:
+    L.check(L.load().e3k_norm_act_bwd2(L.ptr(x), L.ptr(gy), L.ptr(h), x.shape[0], x.shape[1], _blocks(blocks), len(blocks),
+                                       act_id, eps, int(normalize), L.ptr(g_gy), L.ptr(g_x), L.stream_ptr()),
+            "e3k_norm_act_bwd2")
 
-    @staticmethod
-    def forward(ctx, x, gy, blocks, act_id: int, eps: float, normalize: bool):
-        x, gy = L.f32c(x), L.f32c(gy)
-        ctx.save_for_backward(x, gy)
-        ctx.cfg = (blocks, act_id, eps, normalize)
-        return _norm_act_bwd_raw(x, gy, blocks, act_id, eps, normalize)
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, h):
-        x, gy = ctx.saved_tensors
-        blocks, act_id, eps, normalize = ctx.cfg
-        h = L.f32c(h)
-        g_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        g_gy = torch.empty_like(gy) if ctx.needs_input_grad[1] else None
-        if g_x is not None or g_gy is not None:
-            L.check(L.load().e3k_norm_act_bwd2(L.ptr(x), L.ptr(gy), L.ptr(h), x.shape[0], x.shape[1], _blocks(blocks), len(blocks),
-                                               act_id, eps, int(normalize), L.ptr(g_gy), L.ptr(g_x), L.stream_ptr()),
-                    "e3k_norm_act_bwd2")
-        return g_x, g_gy, None, None, None, None
+NormActFn, NormActBwdFn = _pointwise_pair(
+    "NormAct", _norm_act_fwd_raw, _norm_act_bwd_raw, _norm_act_bwd2_raw,
+    doc="e3nn.nn.NormActivation: x (channel-fastest) -> x * act(|x|) / |x| per irrep channel, e3nn layout out.",
+    bwd_doc="The first backward of NormActivation as a differentiable op; its backward is e3k_norm_act_bwd2.")
 
 
 def norm_activation(x, blocks, act: str, eps: float, normalize: bool):
@@ -1879,13 +1781,7 @@ class LayerNormFn(torch.autograd.Function):
         if torch.is_grad_enabled():      # double backward (force training): e3k_layernorm_bwd2
             gx, gstd = LayerNormBwdFn.apply(x, std, inv, gy, ctx.blocks)
             return (gx if ctx.needs_input_grad[0] else None), (gstd if ctx.needs_input_grad[1] else None), None
-        gy = L.f32c(gy)
-        gx = torch.empty_like(x) if _blocks_cover(ctx.blocks, x.shape[1]) else torch.zeros_like(x)
-        gstd = torch.zeros_like(std)
-        L.check(L.load().e3k_layernorm_bwd(L.ptr(x), L.ptr(gy), L.ptr(inv), x.shape[0], x.shape[1], _blocks(ctx.blocks),
-                                           len(ctx.blocks), L.ptr(std), L.ptr(gx), L.ptr(gstd), L.stream_ptr()),
-                "e3k_layernorm_bwd")
-        return gx, gstd, None
+        return (*_layer_norm_bwd_raw(x, std, inv, L.f32c(gy), ctx.blocks), None)
 
 
 def _layer_norm_bwd_raw(x, std, inv, gy, blocks):
@@ -2007,27 +1903,6 @@ def sq_error(pred, target, weight=None, scale: float = 1.0):
     return SqErrorFn.apply(pred, target, weight, float(scale))
 
 
-def vpsde_perturb(x0, node_seg, n_graphs: int, beta_0: float, beta_1: float, eps: float, T: float, seed: int, draw, word0: int = 0):
-    """The VP-SDE perturbation with counter-based draws (``csrc/e3k_score.hip``): ``(t [G + 1], x_t, z [N, D], std [N])`` for
-    ``x0`` [N, D] and ``node_seg`` [N] int64; rows whose segment is not one of the ``n_graphs`` real graphs (the ghost graph of a
-    padded batch) keep ``x0``, with ``z = 0``, ``std = 1`` and ``t = 0.5``.  ``draw``: a DEVICE int64 cell (its first element is the
-    draw index; read, not written: a captured step hands in its own step counter).  One launch, no host synchronisation."""
-    L.require_cuda(x0, node_seg, draw)
-    x0 = L.f32c(x0.detach())
-    if x0.dim() != 2 or node_seg.dtype != torch.int64 or node_seg.numel() != x0.shape[0] or not node_seg.is_contiguous():
-        raise ValueError("vpsde_perturb needs x0 [N, D] and a contiguous int64 node_seg [N]")
-    if draw.dtype != torch.int64 or draw.numel() < 1 or not draw.is_contiguous():
-        raise ValueError("vpsde_perturb: draw must be a contiguous int64 device tensor (its first element is the draw index)")
-    n, d = x0.shape
-    t = torch.empty(n_graphs + 1, device=x0.device, dtype=torch.float32)
-    x_t, z = torch.empty_like(x0), torch.empty_like(x0)
-    std = torch.empty(n, device=x0.device, dtype=torch.float32)
-    L.check(L.load().e3k_vpsde_perturb(L.ptr(x0), L.ptr(node_seg), n, d, int(n_graphs), float(beta_0), float(beta_1), float(eps), float(T),
-                                       *L.seed_words(seed), L.ptr(draw), int(word0), L.ptr(t),
-                                       L.ptr(x_t), L.ptr(z), L.ptr(std), L.stream_ptr()), "e3k_vpsde_perturb")
-    return t, x_t, z, std
-
-
 class DenoiseLossFn(torch.autograd.Function):
     """sum_i w_i mean_c (-raw - std_i x_t + z)^2 (w = 1 / N without weights) -- the denoising loss of a score head that emits
     ``raw`` with score = -raw / std - x_t, and its gradient with respect to ``raw``, in one launch."""
@@ -2060,224 +1935,6 @@ def denoise_loss(raw, x_t, z, std, w=None):
     """``(w * ((-raw - std * x_t + z) ** 2).mean(-1)).sum()`` (``w`` [N] per node; None: the mean over the nodes) -- first order only,
     differentiated with respect to ``raw``."""
     return DenoiseLossFn.apply(raw, x_t, z, std, w)
-
-
-def _sampler_operands(name, x, raw, node_seg, t, n_graphs, cells, out):
-    L.require_cuda(x, raw, node_seg, t, cells)
-    x, raw, t = L.f32c(x.detach()), L.f32c(raw.detach()), L.f32c(t.detach()).reshape(-1)
-    if x.dim() != 2 or raw.shape != x.shape or node_seg.dtype != torch.int64 or node_seg.numel() != x.shape[0] or not node_seg.is_contiguous():
-        raise ValueError(f"{name} needs x, raw [N, D] and a contiguous int64 node_seg [N]")
-    if t.numel() < int(n_graphs):
-        raise ValueError(f"{name}: t holds {t.numel()} times for {int(n_graphs)} graphs")
-    if cells.dtype != torch.int64 or cells.numel() < 2 or not cells.is_contiguous():
-        raise ValueError(f"{name}: cells must be a contiguous int64 device tensor [2] = (next step, step in use)")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or not out.is_cuda:
-        raise ValueError(f"{name}: out must be a contiguous fp32 device tensor of x's shape")
-    return x, raw, t, out
-
-
-def sampler_begin_step(times, cells, t) -> None:
-    """The seeded sampler's step header (``csrc/e3k_sampler.hip``): with ``k = cells[0]`` inside the table ``times`` [n] fp32, every
-    element of ``t`` (fp32, the ghost graph's included) becomes ``times[k]`` and ``cells`` (DEVICE int64 [2]) becomes ``(k + 1, k)``;
-    outside the table nothing is written.  One launch, in place, no host synchronisation."""
-    L.require_cuda(times, cells, t)
-    if times.dtype != torch.float32 or t.dtype != torch.float32 or not times.is_contiguous() or not t.is_contiguous():
-        raise ValueError("sampler_begin_step needs contiguous fp32 times [n] and t")
-    if cells.dtype != torch.int64 or cells.numel() < 2 or not cells.is_contiguous():
-        raise ValueError("sampler_begin_step: cells must be a contiguous int64 device tensor [2] = (next step, step in use)")
-    L.check(L.load().e3k_sampler_begin_step(L.ptr(times), times.numel(), L.ptr(cells), L.ptr(t), t.numel(), L.stream_ptr()),
-            "e3k_sampler_begin_step")
-
-
-def sampler_langevin(x, raw, node_seg, t, alphas, n_graphs: int, beta_0: float, beta_1: float, T: float, snr: float, seed: int, cells,
-                     word0: int = 0, out=None):
-    """One Langevin corrector update of a diffusion key with counter-based noise (``csrc/e3k_sampler.hip``): ``(x', norms [2])`` for
-    ``x``, ``raw`` [N, D] (the score head's output: score = -raw / std(t) - x), ``t`` per graph and the ``alphas`` table; ``norms`` =
-    (mean score row norm, mean noise row norm) over the rows of the ``n_graphs`` real graphs; the other rows (the ghost graph of a
-    padded batch) are copied through.  The noise is draw ``cells[1]``, words ``word0 + c``.  ``out`` may be ``x``.  One launch."""
-    x, raw, t, out = _sampler_operands("sampler_langevin", x, raw, node_seg, t, n_graphs, cells, out)
-    L.require_cuda(alphas)
-    alphas = L.f32c(alphas).reshape(-1)
-    n, d = x.shape
-    norms = torch.empty(2, device=x.device, dtype=torch.float32)
-    L.check(L.load().e3k_sampler_langevin(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(node_seg), L.ptr(t), L.ptr(alphas), n, d, int(n_graphs),
-                                          alphas.numel(), float(beta_0), float(beta_1), float(T), float(snr), *L.seed_words(seed),
-                                          L.ptr(cells), int(word0), L.ptr(norms), L.stream_ptr()), "e3k_sampler_langevin")
-    return out, norms
-
-
-def sampler_reverse_em(x, raw, node_seg, t, n_graphs: int, beta_0: float, beta_1: float, n_sde: int, seed: int, cells, word0: int,
-                       out=None):
-    """One Euler-Maruyama step of the reverse VP-SDE (``dt = -1 / n_sde``) of a diffusion key with counter-based noise
-    (``csrc/e3k_sampler.hip``); operands as ``sampler_langevin``'s.  ``word0``: D_total + the key's first word (the predictor's words
-    of the draw layout, ``csrc/e3k_draw.h``).  ``out`` may be ``x``.  One launch."""
-    x, raw, t, out = _sampler_operands("sampler_reverse_em", x, raw, node_seg, t, n_graphs, cells, out)
-    n, d = x.shape
-    L.check(L.load().e3k_sampler_reverse_em(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(node_seg), L.ptr(t), n, d, int(n_graphs), float(beta_0),
-                                            float(beta_1), int(n_sde), *L.seed_words(seed), L.ptr(cells), int(word0), L.stream_ptr()),
-            "e3k_sampler_reverse_em")
-    return out
-
-
-def _fixed_operands(name, x, known, fixed, out):
-    """known [N, D] fp32 and the mask [N] uint8 of the FIXED forms, refused as their siblings' operands are"""
-    L.require_cuda(known, fixed)
-    known = L.f32c(known.detach())
-    if known.shape != x.shape:
-        raise ValueError(f"{name}: known must have x's shape {tuple(x.shape)} (got {tuple(known.shape)})")
-    if fixed.dtype != torch.uint8 or fixed.numel() != x.shape[0] or not fixed.is_contiguous():
-        raise ValueError(f"{name}: fixed must be a contiguous uint8 device tensor [N] (not zero: the row is fixed)")
-    if known.data_ptr() == out.data_ptr():
-        raise ValueError(f"{name}: out must not be the known values")
-    return known
-
-
-def sampler_langevin_fixed(x, raw, known, fixed, node_seg, t, alphas, n_graphs: int, beta_0: float, beta_1: float, T: float, snr: float,
-                           seed: int, cells, word0: int, word_fixed: int, out=None):
-    """``sampler_langevin`` for conditional sampling (``e3k_sampler_langevin_fixed``): the real rows whose ``fixed`` byte (uint8 [N]) is
-    not zero become ``exp(lm(t)) known + std(t) z`` instead, z the draw ``cells[1]``'s words ``word_fixed + c`` (2 D_total + the key's
-    first word); the norms run over all real rows, as its sibling's.  Still one launch."""
-    x, raw, t, out = _sampler_operands("sampler_langevin_fixed", x, raw, node_seg, t, n_graphs, cells, out)
-    known = _fixed_operands("sampler_langevin_fixed", x, known, fixed, out)
-    L.require_cuda(alphas)
-    alphas = L.f32c(alphas).reshape(-1)
-    n, d = x.shape
-    norms = torch.empty(2, device=x.device, dtype=torch.float32)
-    L.check(L.load().e3k_sampler_langevin_fixed(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(known), L.ptr(fixed), L.ptr(node_seg), L.ptr(t),
-                                                L.ptr(alphas), n, d, int(n_graphs), alphas.numel(), float(beta_0), float(beta_1), float(T),
-                                                float(snr), *L.seed_words(seed), L.ptr(cells), int(word0), int(word_fixed), L.ptr(norms),
-                                                L.stream_ptr()), "e3k_sampler_langevin_fixed")
-    return out, norms
-
-
-def sampler_reverse_em_fixed(x, raw, known, fixed, node_seg, t, n_graphs: int, beta_0: float, beta_1: float, n_sde: int, seed: int, cells,
-                             word0: int, word_fixed: int, out=None):
-    """``sampler_reverse_em`` for conditional sampling (``e3k_sampler_reverse_em_fixed``): the fixed rows become ``exp(lm(t)) known +
-    std(t) z`` at the step's own t, z at words ``word_fixed + c`` (3 D_total + the key's first word).  Still one launch."""
-    x, raw, t, out = _sampler_operands("sampler_reverse_em_fixed", x, raw, node_seg, t, n_graphs, cells, out)
-    known = _fixed_operands("sampler_reverse_em_fixed", x, known, fixed, out)
-    n, d = x.shape
-    L.check(L.load().e3k_sampler_reverse_em_fixed(L.ptr(out), L.ptr(x), L.ptr(raw), L.ptr(known), L.ptr(fixed), L.ptr(node_seg), L.ptr(t), n, d,
-                                                  int(n_graphs), float(beta_0), float(beta_1), int(n_sde), *L.seed_words(seed), L.ptr(cells),
-                                                  int(word0), int(word_fixed), L.stream_ptr()), "e3k_sampler_reverse_em_fixed")
-    return out
-
-
-def _ode_operands(name, x, raw, node_seg, times, n_graphs, cells, out):
-    """``_sampler_operands`` with the time table where its siblings take t: contiguous fp32 ``times`` [n >= 2] on the device"""
-    L.require_cuda(times)
-    x, raw, _, out = _sampler_operands(name, x, raw, node_seg, times, 0, cells, out)
-    if times.dtype != torch.float32 or not times.is_contiguous() or times.dim() != 1 or times.numel() < 2:
-        raise ValueError(f"{name}: times must be a contiguous fp32 device tensor [n_steps + 1]")
-    if int(n_graphs) < 0:
-        raise ValueError(f"{name}: n_graphs = {int(n_graphs)}")
-    return x, raw, out
-
-
-def sampler_ode_euler(x, raw, node_seg, times, cells, n_graphs: int, beta_0: float, beta_1: float, t_out=None, want_d: bool = True,
-                      out=None):
-    """One Euler step of the probability-flow ODE of a diffusion key, which is Heun's stage A (``e3k_sampler_ode_euler``):
-    ``(x + h d1, d1)`` with ``d1 = (0.5 beta(t_k)) (raw / s(t_k))``, ``k = cells[1]``, ``t_k = times[k]``, ``h = times[k + 1] - t_k``
-    read from the table on the device; ``d1`` is None without ``want_d``.  ``t_out`` (contiguous fp32, the batch's t): every element
-    becomes ``times[k + 1]`` in the same launch.  Rows outside the ``n_graphs`` real graphs are copied through (``d1 = 0``), and so is
-    everything when ``k`` or ``k + 1`` is outside the table.  ``out`` may be ``x``.  One launch."""
-    x, raw, out = _ode_operands("sampler_ode_euler", x, raw, node_seg, times, n_graphs, cells, out)
-    g1 = 0
-    if t_out is not None:
-        L.require_cuda(t_out)
-        if t_out.dtype != torch.float32 or not t_out.is_contiguous() or t_out.numel() < 1:
-            raise ValueError("sampler_ode_euler: t_out must be a contiguous fp32 device tensor")
-        g1 = t_out.numel()
-    d = torch.empty_like(x) if want_d else None
-    n, dim = x.shape
-    L.check(L.load().e3k_sampler_ode_euler(L.ptr(out), L.ptr(d), L.ptr(x), L.ptr(raw), L.ptr(node_seg), L.ptr(times),
-                                           times.numel(), L.ptr(cells), L.ptr(t_out), g1, n, dim,
-                                           int(n_graphs), float(beta_0), float(beta_1), L.stream_ptr()), "e3k_sampler_ode_euler")
-    return out, d
-
-
-def sampler_ode_heun(x0, d1, raw2, node_seg, times, cells, n_graphs: int, beta_0: float, beta_1: float, out=None):
-    """Heun's stage B of the same step (``e3k_sampler_ode_heun``): ``x0 + (0.5 h) (d1 + d2)`` with ``d2 = (0.5 beta(t_{k+1}))
-    (raw2 / s(t_{k+1}))``; ``x0``, ``d1``: the state before stage A and its drift, ``raw2``: the model's output at the stage-A state.
-    Ghost rows and steps outside the table: ``x0``.  ``out`` may be ``x0``, never ``d1``.  One launch."""
-    x0, raw2, out = _ode_operands("sampler_ode_heun", x0, raw2, node_seg, times, n_graphs, cells, out)
-    L.require_cuda(d1)
-    d1 = L.f32c(d1.detach())
-    if d1.shape != x0.shape:
-        raise ValueError(f"sampler_ode_heun: d1 must have x0's shape {tuple(x0.shape)} (got {tuple(d1.shape)})")
-    if d1.data_ptr() == out.data_ptr():
-        raise ValueError("sampler_ode_heun: out must not be d1")
-    n, dim = x0.shape
-    L.check(L.load().e3k_sampler_ode_heun(L.ptr(out), L.ptr(x0), L.ptr(d1), L.ptr(raw2), L.ptr(node_seg), L.ptr(times), times.numel(),
-                                          L.ptr(cells), n, dim, int(n_graphs), float(beta_0), float(beta_1), L.stream_ptr()),
-            "e3k_sampler_ode_heun")
-    return out
-
-
-def graph_row_pointers(counts) -> torch.Tensor:
-    """int32 [G + 1] row pointers of per-graph node counts (contiguous int64 on the device): one ``e3k_counts_to_ptr`` launch"""
-    L.require_cuda(counts)
-    n = counts.reshape(-1)
-    if n.dtype != torch.int64 or not n.is_contiguous():
-        raise ValueError("graph_row_pointers needs contiguous int64 counts")
-    ptr = torch.empty(n.numel() + 1, dtype=torch.int32, device=n.device)
-    L.check(L.load().e3k_counts_to_ptr(L.ptr(n), n.numel(), L.ptr(ptr), L.stream_ptr()), "e3k_counts_to_ptr")
-    return ptr
-
-
-def sampler_probe(node_seg, dim: int, n_graphs: int, seed: int, draw: int, word0: int, kind: int) -> torch.Tensor:
-    """The Hutchinson probe of one diffusion key (``e3k_sampler_probe``): fp32 [N, dim], component c of node i from draw index
-    ``draw``, word ``word0 + c`` of the stream of ``csrc/e3k_draw.h`` -- ``kind`` 0: Rademacher (``data.compute_edge.rademacher_draw``),
-    1: ``normal_draw``; rows outside the ``n_graphs`` real graphs are 0.  One launch."""
-    L.require_cuda(node_seg)
-    if node_seg.dtype != torch.int64 or node_seg.dim() != 1 or not node_seg.is_contiguous():
-        raise ValueError("sampler_probe needs a contiguous int64 node_seg [N]")
-    out = torch.empty(node_seg.numel(), int(dim), device=node_seg.device, dtype=torch.float32)
-    L.check(L.load().e3k_sampler_probe(L.ptr(out), L.ptr(node_seg), node_seg.numel(), int(dim), int(n_graphs), *L.seed_words(seed),
-                                       int(draw) & 0xFFFFFFFF, int(word0), int(kind), L.stream_ptr()), "e3k_sampler_probe")
-    return out
-
-
-def _per_graph_operands(name, acc, x, row_ptr, n_graphs):
-    L.require_cuda(acc, x, row_ptr)
-    x = L.f32c(x.detach())
-    if x.dim() != 2:
-        raise ValueError(f"{name} needs [N, D] operands")
-    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.numel() < int(n_graphs):
-        raise ValueError(f"{name}: the accumulator must be a contiguous float64 device tensor of at least {int(n_graphs)} entries")
-    if row_ptr.dtype != torch.int32 or not row_ptr.is_contiguous() or row_ptr.numel() < int(n_graphs) + 1 or int(n_graphs) < 0:
-        raise ValueError(f"{name}: row_ptr must be a contiguous int32 device tensor [n_graphs + 1]")
-    return x
-
-
-def sampler_ode_div(acc, probe, vjp, row_ptr, times, cells, n_graphs: int, stage: int, scale: float, beta_0: float, beta_1: float) -> None:
-    """One quadrature term of the likelihood's integral, in place (``e3k_sampler_ode_div``): ``acc[g] += w c(t) scale sum(probe vjp)``
-    over the rows of each of the ``n_graphs`` real graphs; ``acc`` float64 on the device, ``row_ptr`` int32 ``[n_graphs + 1]``, the step
-    ``k = cells[1]`` and its times from the table.  ``stage`` 0: ``w = h``, ``t = t_k``; 1: ``h / 2``, ``t_k``; 2: ``h / 2``,
-    ``t_{k+1}``; ``c(t) = (0.5 beta(t)) / s(t)`` in double.  Outside the table nothing is written.  One launch."""
-    vjp = _per_graph_operands("sampler_ode_div", acc, vjp, row_ptr, n_graphs)
-    L.require_cuda(probe, times, cells)
-    probe = L.f32c(probe.detach())
-    if probe.shape != vjp.shape:
-        raise ValueError(f"sampler_ode_div: probe {tuple(probe.shape)} and vjp {tuple(vjp.shape)} differ in shape")
-    if times.dtype != torch.float32 or not times.is_contiguous() or times.dim() != 1 or times.numel() < 2:
-        raise ValueError("sampler_ode_div: times must be a contiguous fp32 device tensor [n_steps + 1]")
-    if cells.dtype != torch.int64 or cells.numel() < 2 or not cells.is_contiguous():
-        raise ValueError("sampler_ode_div: cells must be a contiguous int64 device tensor [2] = (next step, step in use)")
-    n, dim = vjp.shape
-    L.check(L.load().e3k_sampler_ode_div(L.ptr(acc), L.ptr(probe), L.ptr(vjp), L.ptr(row_ptr), L.ptr(times), times.numel(), L.ptr(cells), n,
-                                         dim, int(n_graphs), int(stage), float(scale), float(beta_0), float(beta_1), L.stream_ptr()),
-            "e3k_sampler_ode_div")
-
-
-def sampler_prior_logp(out, x, row_ptr, n_graphs: int) -> None:
-    """``out[g] += log N(x_g; 0, I)`` over the rows of each real graph, in place (``e3k_sampler_prior_logp``; ``out`` float64)."""
-    x = _per_graph_operands("sampler_prior_logp", out, x, row_ptr, n_graphs)
-    n, dim = x.shape
-    L.check(L.load().e3k_sampler_prior_logp(L.ptr(out), L.ptr(x), L.ptr(row_ptr), n, dim, int(n_graphs), L.stream_ptr()),
-            "e3k_sampler_prior_logp")
 
 
 def segment_sum(x, ptr, seg_index, mean=False):
@@ -2318,14 +1975,21 @@ class EdgeVectorFn(torch.autograd.Function):
             return EdgeScatterFn.apply(gv, topo, ctx.n), None
         g_vec = L.f32c(g_vec) if g_vec is not None else None
         g_len = L.f32c(g_len) if g_len is not None else None
-        g_pos = torch.empty(ctx.n, 3, device=vec.device, dtype=torch.float32)
-        L.check(L.load().e3k_edge_vector_bwd(L.ptr(g_vec), L.ptr(g_len), L.ptr(vec), L.ptr(length), L.ptr(topo.dst_ptr),
-                                             L.ptr(topo.dst_perm), L.ptr(topo.src_ptr), L.ptr(topo.src_perm), ctx.n,
-                                             L.ptr(g_pos), L.stream_ptr()), "e3k_edge_vector_bwd")
+        g_pos = _edge_vector_bwd_raw(g_vec, g_len, vec, length, topo, ctx.n)
         if sink is not None:      # the virial of the same per-edge gradients, one launch more
             _virial_edges_raw(g_vec, g_len, vec, length, topo, sink.graph_ptr, sink.n_graphs, ctx.n, sink.buffer)
             sink.written += 1
         return g_pos, None
+
+
+def _edge_vector_bwd_raw(g_vec, g_len, vec, length, topo: GraphTopo, n: int):
+    """g_pos[i] = sum_{dst(e)=i} g_e - sum_{src(e)=i} g_e with g_e = g_vec_e + (g_len_e / len_e) vec_e; ``g_vec`` or ``g_len`` may be
+    None, and without ``g_len`` so may ``vec`` and ``length`` (the plain scatter of ``g_vec``)."""
+    g_pos = torch.empty(n, 3, device=(g_vec if g_vec is not None else g_len).device, dtype=torch.float32)
+    L.check(L.load().e3k_edge_vector_bwd(L.ptr(g_vec), L.ptr(g_len), L.ptr(vec), L.ptr(length), L.ptr(topo.dst_ptr),
+                                         L.ptr(topo.dst_perm), L.ptr(topo.src_ptr), L.ptr(topo.src_perm), n, L.ptr(g_pos),
+                                         L.stream_ptr()), "e3k_edge_vector_bwd")
+    return g_pos
 
 
 def _virial_edges_raw(g_vec, g_len, vec, length, topo, graph_ptr, n_graphs: int, n_nodes: int, out) -> None:
@@ -2367,13 +2031,8 @@ class EdgeScatterFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gv, topo: GraphTopo, n: int):
-        gv = L.f32c(gv)
-        g_pos = torch.empty(n, 3, device=gv.device, dtype=torch.float32)
-        L.check(L.load().e3k_edge_vector_bwd(L.ptr(gv), None, None, None, L.ptr(topo.dst_ptr), L.ptr(topo.dst_perm),
-                                             L.ptr(topo.src_ptr), L.ptr(topo.src_perm), n, L.ptr(g_pos),
-                                             L.stream_ptr()), "e3k_edge_vector_bwd")
         ctx.topo = topo
-        return g_pos
+        return _edge_vector_bwd_raw(L.f32c(gv), None, None, None, topo, n)
 
     @staticmethod
     def backward(ctx, h):   # h ~ pos: gather h[dst] - h[src]
@@ -2415,27 +2074,13 @@ def edge_vector_periodic(pos, topo: GraphTopo, shift, node_seg, cell):
     return PeriodicEdgeVectorFn.apply(_c(pos), topo, shift.contiguous(), node_seg.contiguous(), cell.contiguous())
 
 
-class SphHarmFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, vec, ls: Tuple[int, ...], normalize: bool, normalization: int):
-        L.require_cuda(vec)
-        vec = L.f32c(vec)
-        rows = vec.numel() // 3
-        dim = sum(2 * l + 1 for l in ls)
-        sh = torch.empty(rows, dim, device=vec.device, dtype=torch.float32)
-        arr = (C.c_int32 * len(ls))(*ls)
-        L.check(L.load().e3k_sph_harm_fwd(L.ptr(vec), rows, arr, len(ls), int(normalize), normalization, L.ptr(sh),
-                                          L.stream_ptr()), "e3k_sph_harm_fwd")
-        ctx.save_for_backward(vec)
-        ctx.cfg = (ls, normalize, normalization)
-        return sh
-
-    @staticmethod
-    def backward(ctx, g_sh):
-        (vec,) = ctx.saved_tensors
-        if torch.is_grad_enabled():
-            return SphHarmBwdFn.apply(vec, g_sh, ctx.cfg), None, None, None
-        return _sph_bwd_raw(vec, L.f32c(g_sh), ctx.cfg), None, None, None
+def _sph_fwd_raw(vec, ls: Tuple[int, ...], normalize: bool, normalization: int):
+    rows = vec.numel() // 3
+    sh = torch.empty(rows, sum(2 * l + 1 for l in ls), device=vec.device, dtype=torch.float32)
+    arr = (C.c_int32 * len(ls))(*ls)
+    L.check(L.load().e3k_sph_harm_fwd(L.ptr(vec), rows, arr, len(ls), int(normalize), normalization, L.ptr(sh),
+                                      L.stream_ptr()), "e3k_sph_harm_fwd")
+    return sh
 
 
 def _sph_bwd_raw(vec, g_sh, cfg):
@@ -2448,31 +2093,17 @@ def _sph_bwd_raw(vec, g_sh, cfg):
     return g_vec
 
 
-class SphHarmBwdFn(torch.autograd.Function):
-    """g_vec = J(vec)^T g_sh; its backward (e3k_sph_harm_bwd2) evaluates the same polynomials on dual numbers."""
+def _sph_bwd2_raw(vec, g_sh, h, g_gsh, g_vec, cfg) -> None:
+    ls, normalize, normalization = cfg
+    arr = (C.c_int32 * len(ls))(*ls)
+    L.check(L.load().e3k_sph_harm_bwd2(L.ptr(vec), L.ptr(g_sh), L.ptr(h), vec.numel() // 3, arr, len(ls), int(normalize),
+                                       normalization, L.ptr(g_gsh), L.ptr(g_vec), L.stream_ptr()), "e3k_sph_harm_bwd2")
 
-    @staticmethod
-    def forward(ctx, vec, g_sh, cfg):
-        vec, g_sh = L.f32c(vec), L.f32c(g_sh)
-        ctx.save_for_backward(vec, g_sh)
-        ctx.cfg = cfg
-        return _sph_bwd_raw(vec, g_sh, cfg)
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, h):
-        vec, g_sh = ctx.saved_tensors
-        ls, normalize, normalization = ctx.cfg
-        h = L.f32c(h)
-        rows = vec.numel() // 3
-        g_vec = torch.empty_like(vec) if ctx.needs_input_grad[0] else None
-        g_gsh = torch.empty_like(g_sh) if ctx.needs_input_grad[1] else None
-        if g_vec is not None or g_gsh is not None:
-            arr = (C.c_int32 * len(ls))(*ls)
-            L.check(L.load().e3k_sph_harm_bwd2(L.ptr(vec), L.ptr(g_sh), L.ptr(h), rows, arr, len(ls), int(normalize),
-                                               normalization, L.ptr(g_gsh), L.ptr(g_vec), L.stream_ptr()),
-                    "e3k_sph_harm_bwd2")
-        return g_vec, g_gsh, None
+# (the backward pair takes (ls, normalize, normalization) as one tuple)
+SphHarmFn, SphHarmBwdFn = _pointwise_pair(
+    "SphHarm", _sph_fwd_raw, _sph_bwd_raw, _sph_bwd2_raw, packed=True,
+    bwd_doc="g_vec = J(vec)^T g_sh; its backward (e3k_sph_harm_bwd2) evaluates the same polynomials on dual numbers.")
 
 
 NORMALIZATIONS = {"component": 0, "integral": 1, "norm": 2}

@@ -607,13 +607,18 @@ def interp_packed_raw(packed: torch.Tensor, bins: KnotBins) -> torch.Tensor:
     return w
 
 
+def interp_bwd_workspace_floats(e: int, knots: int, width: int) -> int:
+    """floats of scratch ``e3k_rtable_interp_bwd`` needs for ``e`` edges onto a table of ``knots`` + 1 rows of ``width`` columns"""
+    return int(L.load().e3k_rtable_bwd_workspace_floats(e, knots, width))
+
+
 def interp_bwd_raw(g_w: torch.Tensor, bins: KnotBins, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """g_T = (interpolation)^T g_w; ``scale`` [E]: every edge's weights times scale[e] (the slope table's gradient in the double
     backward of force training)."""
     e, width = bins.bin.numel(), g_w.shape[1]
     lib = L.load()
     g_t = torch.empty(bins.knots + 1, width, device=g_w.device, dtype=torch.float32)
-    work = torch.empty(lib.e3k_rtable_bwd_workspace_floats(e, bins.knots, width), device=g_w.device, dtype=torch.float32)
+    work = torch.empty(interp_bwd_workspace_floats(e, bins.knots, width), device=g_w.device, dtype=torch.float32)
     with ops.timed_launch("rtable_bwd", (e, bins.knots, width)):
         L.check(lib.e3k_rtable_interp_bwd(L.ptr(g_w), L.ptr(bins.coef), L.ptr(scale), L.ptr(bins.ptr), L.ptr(bins.seg), L.ptr(bins.perm),
                                           e, bins.knots, width, L.ptr(work), L.ptr(g_t), 0, L.stream_ptr()), "e3k_rtable_interp_bwd")

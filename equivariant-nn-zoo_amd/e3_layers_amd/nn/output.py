@@ -151,12 +151,12 @@ class Pooling(Module):
         if hit is not None:
             return hit
         n = counts.view(-1).to(device)
-        ptr = torch.empty(n.numel() + 1, dtype=torch.int32, device=device)
         if n.is_cuda and n.dtype == torch.int64 and n.is_contiguous():
-            from ..backend import lib as L
+            from ..backend.diffusion_ops import graph_row_pointers
 
-            L.check(L.load().e3k_counts_to_ptr(L.ptr(n), n.numel(), L.ptr(ptr), L.stream_ptr()), "e3k_counts_to_ptr")
+            ptr = graph_row_pointers(n)
         else:
+            ptr = torch.empty(n.numel() + 1, dtype=torch.int32, device=device)
             ptr[0] = 0
             ptr[1:] = torch.cumsum(n, 0).to(torch.int32)
         return memo.remember(counts, "ptr", ptr, device)

@@ -81,9 +81,9 @@ def make_probes(sde: VPSDE, batch, seed: int, kind: str, n_probes: int, dtype=No
     for p in range(n_probes):
         for key, dim in sde.irreps.items():
             if seg.is_cuda:
-                from ..backend import ops
+                from ..backend import diffusion_ops
 
-                out[p, key] = ops.sampler_probe(seg, dim, n_real, seed, sde.N + 1 + p, words[key], _PROBES[kind])
+                out[p, key] = diffusion_ops.sampler_probe(seg, dim, n_real, seed, sde.N + 1 + p, words[key], _PROBES[kind])
                 continue
             dt = batch[key].dtype if dtype is None else dtype
             node = torch.arange(seg.shape[0], dtype=torch.int64).reshape(-1, 1)
@@ -116,12 +116,12 @@ def prior_logp(sde: VPSDE, batch, row_ptr=None):
     n_real = _real_graphs(batch)
     first = batch[next(iter(sde.irreps))]
     if first.is_cuda:
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         out = torch.zeros(n_real, dtype=torch.float64, device=first.device)
-        row_ptr = ops.graph_row_pointers(batch["_n_nodes"]) if row_ptr is None else row_ptr
+        row_ptr = diffusion_ops.graph_row_pointers(batch["_n_nodes"]) if row_ptr is None else row_ptr
         for key in sde.irreps:
-            ops.sampler_prior_logp(out, batch[key], row_ptr, n_real)
+            diffusion_ops.sampler_prior_logp(out, batch[key], row_ptr, n_real)
         return out
     counts = batch["_n_nodes"].reshape(-1)[:n_real].double()
     out = torch.zeros(n_real, dtype=torch.float64)
@@ -142,7 +142,7 @@ def div_stage(sde: VPSDE, model, batch, acc, times, cells_or_step, stage: int, n
     The keys are differentiated as detached leaves over the batch's own storage, inside ``torch.enable_grad()`` (the loops run under
     ``no_grad``): the step kernels may then update that storage in place, after and outside the graph.  A vector-Jacobian product that
     comes back ``None`` raises: a missing term is never integrated as zero."""
-    from ..backend import ops
+    from ..backend import diffusion_ops, ops
 
     keys = list(sde.irreps)
     with torch.enable_grad():
@@ -177,8 +177,8 @@ def div_stage(sde: VPSDE, model, batch, acc, times, cells_or_step, stage: int, n
     if leaves[0].is_cuda:
         n_real = _real_graphs(batch)
         for (p, key), g in vjps.items():
-            ops.sampler_ode_div(acc, batch[probe_name(p, key)], g, row_ptr, times, cells_or_step, n_real, stage, scale, sde.beta_0,
-                                sde.beta_1)
+            diffusion_ops.sampler_ode_div(acc, batch[probe_name(p, key)], g, row_ptr, times, cells_or_step, n_real, stage, scale,
+                                          sde.beta_0, sde.beta_1)
         return detached
     k = _step_in_use(cells_or_step)
     if 0 <= k < times.numel() - 1:
@@ -253,10 +253,10 @@ def likelihood_plan(sde: VPSDE, method: str, model, batch, *, n_steps: int, eps:
     acc = torch.zeros(_real_graphs(batch), dtype=torch.float64, device=dev)
     row_ptr = None
     if on_device:
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         # the real graphs come first in a padded batch too: one table serves every loop
-        row_ptr = ops.graph_row_pointers(batch["_n_nodes"].reshape(-1).contiguous())
+        row_ptr = diffusion_ops.graph_row_pointers(batch["_n_nodes"].reshape(-1).contiguous())
     updates = stage_updates(sde, model, method, times, cells, acc, n_probes, row_ptr)
     return StepPlan(batch, updates, list(sde.irreps), times[:n_steps], cells, zero=(acc,)), acc, row_ptr
 

@@ -175,11 +175,11 @@ def sde_perturb_counter(sde: VPSDE, batch, seed: int, draw, eps: float = 1e-5, d
     pert.attrs["t"] = ("graph", "1x0e")
     zs, word0, std = {}, 0, None
     if dev.type == "cuda":
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         cell = draw if torch.is_tensor(draw) else torch.tensor([int(draw)], dtype=torch.int64, device=dev)
         for key in keys:
-            t, x_t, z, s = ops.vpsde_perturb(batch[key], seg, n_real, sde.beta_0, sde.beta_1, eps, sde.T, seed, cell, word0)
+            t, x_t, z, s = diffusion_ops.vpsde_perturb(batch[key], seg, n_real, sde.beta_0, sde.beta_1, eps, sde.T, seed, cell, word0)
             pert[key], zs[key] = x_t, z
             word0 += int(batch[key].shape[1])
             if std is None:
@@ -303,9 +303,9 @@ def sampler_begin_step(times, cells, t) -> None:
     included) becomes ``times[k]`` and ``cells`` (int64 [2]) becomes ``(k + 1, k)``; outside the table nothing moves.  Device tensors:
     one ``e3k_sampler_begin_step`` launch, no host synchronisation.  CPU tensors: the same in torch."""
     if t.is_cuda:
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
-        return ops.sampler_begin_step(times, cells, t)
+        return diffusion_ops.sampler_begin_step(times, cells, t)
     k = int(cells[0])
     if 0 <= k < times.numel():
         t.fill_(float(times[k]))
@@ -330,7 +330,7 @@ def prior_sampling_counter(sde: VPSDE, batch, seed: int, draw=None, dtype=None, 
     draw = sde.N if draw is None else draw
     words, _ = draw_words(sde)
     if dev.type == "cuda":
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         cell = draw if torch.is_tensor(draw) else torch.tensor([int(draw)], dtype=torch.int64, device=dev)
         real = (seg < n_real).reshape(-1, 1) if padded else None
@@ -338,10 +338,10 @@ def prior_sampling_counter(sde: VPSDE, batch, seed: int, draw=None, dtype=None, 
         for key, dim in sde.irreps.items():
             if rows is None:
                 zero = torch.zeros(n, dim, device=dev)
-                z = ops.vpsde_perturb(zero, seg, n_real, sde.beta_0, sde.beta_1, 0.0, sde.T, seed, cell, words[key])[2]
+                z = diffusion_ops.vpsde_perturb(zero, seg, n_real, sde.beta_0, sde.beta_1, 0.0, sde.T, seed, cell, words[key])[2]
             else:      # eps = T: every graph's time is T, x_t = fma(m(T), x0, s(T) z)
-                _, x_t, z, _ = ops.vpsde_perturb(_known_of(batch, known, key), seg, n_real, sde.beta_0, sde.beta_1, sde.T, sde.T, seed, cell,
-                                                 words[key])
+                _, x_t, z, _ = diffusion_ops.vpsde_perturb(_known_of(batch, known, key), seg, n_real, sde.beta_0, sde.beta_1, sde.T, sde.T, seed, cell,
+                                                           words[key])
             free = torch.where(real, z, batch[key].float()) if padded and key in batch else z
             batch[key] = free if rows is None else torch.where(rows, x_t, free)
         return batch
@@ -378,18 +378,15 @@ def langevin_step_counter(sde: VPSDE, model, batch, seed: int, draw, snr: float,
     words, total = draw_words(sde)
     dev = batch[next(iter(sde.irreps))].device
     if dev.type == "cuda":
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         cells, seg, n_real = _sampler_cells(draw, dev), batch.nodeSegment(), _real_graphs(batch)
         mask = None if fixed is None else _device_mask(batch, fixed)
         for key in sde.irreps:
-            if mask is None:
-                batch[key], _ = ops.sampler_langevin(batch[key], raw[key], seg, batch["t"], sde.alphas, n_real, sde.beta_0, sde.beta_1,
-                                                     sde.T, snr, seed, cells, words[key])
-            else:
-                batch[key], _ = ops.sampler_langevin_fixed(batch[key], raw[key], _known_of(batch, known, key), mask, seg, batch["t"],
-                                                           sde.alphas, n_real, sde.beta_0, sde.beta_1, sde.T, snr, seed, cells, words[key],
-                                                           2 * total + words[key])
+            batch[key], _ = diffusion_ops.sampler_langevin(batch[key], raw[key], seg, batch["t"], sde.alphas, n_real, sde.beta_0, sde.beta_1,
+                                                           sde.T, snr, seed, cells, words[key],
+                                                           known=None if mask is None else _known_of(batch, known, key), fixed=mask,
+                                                           word_fixed=2 * total + words[key])
         return batch
     from ..data.compute_edge import normal_draw
 
@@ -424,18 +421,15 @@ def reverse_step_counter(sde: VPSDE, model, batch, seed: int, draw, dtype=None, 
     words, total = draw_words(sde)
     dev = batch[next(iter(sde.irreps))].device
     if dev.type == "cuda":
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         cells, seg, n_real = _sampler_cells(draw, dev), batch.nodeSegment(), _real_graphs(batch)
         mask = None if fixed is None else _device_mask(batch, fixed)
         for key in sde.irreps:
-            if mask is None:
-                batch[key] = ops.sampler_reverse_em(batch[key], raw[key], seg, batch["t"], n_real, sde.beta_0, sde.beta_1, sde.N, seed,
-                                                    cells, total + words[key])
-            else:
-                batch[key] = ops.sampler_reverse_em_fixed(batch[key], raw[key], _known_of(batch, known, key), mask, seg, batch["t"], n_real,
-                                                          sde.beta_0, sde.beta_1, sde.N, seed, cells, total + words[key],
-                                                          3 * total + words[key])
+            batch[key] = diffusion_ops.sampler_reverse_em(batch[key], raw[key], seg, batch["t"], n_real, sde.beta_0, sde.beta_1, sde.N, seed,
+                                                          cells, total + words[key],
+                                                          known=None if mask is None else _known_of(batch, known, key), fixed=mask,
+                                                          word_fixed=3 * total + words[key])
         return batch
     from ..data.compute_edge import normal_draw
 
@@ -489,15 +483,15 @@ def ode_euler_step(sde: VPSDE, model, batch, times, cells_or_step, dtype=None, k
     keys = list(sde.irreps)
     dev = batch[keys[0]].device
     if dev.type == "cuda":
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         cells, seg, n_real = _sampler_cells(cells_or_step, dev), batch.nodeSegment(), _real_graphs(batch)
         for key in keys:
             x = batch[key]
             in_place = keep is None and x.dtype == torch.float32 and x.is_contiguous()
-            batch[key], d1 = ops.sampler_ode_euler(x, raw[key], seg, times, cells, n_real, sde.beta_0, sde.beta_1,
-                                                   t_out=batch["t"] if key == keys[0] else None, want_d=keep is not None,
-                                                   out=x if in_place else None)
+            batch[key], d1 = diffusion_ops.sampler_ode_euler(x, raw[key], seg, times, cells, n_real, sde.beta_0, sde.beta_1,
+                                                             t_out=batch["t"] if key == keys[0] else None, want_d=keep is not None,
+                                                             out=x if in_place else None)
             if keep is not None:
                 keep[key] = (x, d1)
         return batch
@@ -526,12 +520,12 @@ def ode_heun_finish(sde: VPSDE, model, batch, kept, times, cells_or_step, dtype=
     keys = list(sde.irreps)
     dev = batch[keys[0]].device
     if dev.type == "cuda":
-        from ..backend import ops
+        from ..backend import diffusion_ops
 
         cells, seg, n_real = _sampler_cells(cells_or_step, dev), batch.nodeSegment(), _real_graphs(batch)
         for key in keys:
             x0, d1 = kept[key]
-            batch[key] = ops.sampler_ode_heun(x0, d1, raw2[key], seg, times, cells, n_real, sde.beta_0, sde.beta_1)
+            batch[key] = diffusion_ops.sampler_ode_heun(x0, d1, raw2[key], seg, times, cells, n_real, sde.beta_0, sde.beta_1)
         return batch
     k = _step_in_use(cells_or_step)
     for key in keys:

@@ -38,6 +38,21 @@ def test_library_exports_every_declared_symbol():
     assert handle.e3k_version() >= 100
 
 
+def test_every_c_entry_has_one_python_launch_site():
+    """Each ``e3k_*`` function is called from ONE place in the package; everything else goes through that function, so an argument
+    list is never written twice.  The sources are read as text: nothing of the package is compiled or imported."""
+    pkg = os.path.join(ROOT, "equivariant-nn-zoo_amd", "e3_layers_amd")
+    sites = {}
+    for base, _, files in os.walk(pkg):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                path = os.path.join(base, f)
+                for m in re.finditer(r"\.(e3k_[a-z0-9_]+)\(", open(path).read()):
+                    sites.setdefault(m.group(1), []).append(os.path.relpath(path, pkg))
+    assert len(sites) >= 100 and set(sites) <= set(_declared_functions()), sorted(set(sites) - set(_declared_functions()))
+    assert {name: where for name, where in sites.items() if len(where) != 1} == {}
+
+
 def test_struct_layouts_match_the_c_compiler(tmp_path):
     """sizeof of every struct of the header, offsetof and sizeof of every field: the C compiler against the derived mirror."""
     from e3_layers_amd.backend import abi

@@ -69,10 +69,10 @@ def _sde(n=1000):
 
 def _watched(monkeypatch, sde, run):
     """-> (run()'s result, M [G] float64): the majorant of delta_logp from the ``sampler_ode_div`` launches of an EAGER device run"""
-    from e3_layers_amd.backend import ops
+    from e3_layers_amd.backend import diffusion_ops
     from e3_layers_amd.run.likelihood import div_weight
 
-    launch, major = ops.sampler_ode_div, {}
+    launch, major = diffusion_ops.sampler_ode_div, {}
 
     def spy(acc, probe, vjp, row_ptr, times, cells, n_graphs, stage, scale, beta_0, beta_1):
         ptr, k = row_ptr.cpu().tolist(), int(cells[1])
@@ -82,11 +82,11 @@ def _watched(monkeypatch, sde, run):
             major[g] = major.get(g, 0.0) + coef * float(probe[rows].double().norm()) * float(vjp[rows].double().norm())
         return launch(acc, probe, vjp, row_ptr, times, cells, n_graphs, stage, scale, beta_0, beta_1)
 
-    monkeypatch.setattr(ops, "sampler_ode_div", spy)
+    monkeypatch.setattr(diffusion_ops, "sampler_ode_div", spy)
     try:
         out = run()
     finally:
-        monkeypatch.setattr(ops, "sampler_ode_div", launch)
+        monkeypatch.setattr(diffusion_ops, "sampler_ode_div", launch)
     return out, torch.tensor([major[g] for g in sorted(major)], dtype=torch.float64)
 
 

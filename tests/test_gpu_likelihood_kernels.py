@@ -277,12 +277,12 @@ def test_prior_logp(dev, case):
 
 def test_keys_accumulate_into_one_accumulator(dev):
     """several keys are consecutive launches into the same acc, through the wrappers"""
-    from e3_layers_amd.backend import ops
+    from e3_layers_amd.backend import diffusion_ops
 
     rng = np.random.default_rng(5)
     counts = _graphs(5, 1)
     n_all = int(counts.sum())
-    ptr = ops.graph_row_pointers(torch.from_numpy(counts).to(dev))
+    ptr = diffusion_ops.graph_row_pointers(torch.from_numpy(counts).to(dev))
     assert ptr.cpu().tolist() == np.concatenate([[0], np.cumsum(counts)]).tolist()
     times, cells = torch.from_numpy(ASC).to(dev), torch.tensor([2, 1], dtype=torch.int64, device=dev)
     acc = torch.zeros(5, dtype=torch.float64, device=dev)
@@ -290,7 +290,7 @@ def test_keys_accumulate_into_one_accumulator(dev):
     mags = np.zeros(5)
     for d in (3, 2):
         p, v = rng.standard_normal((n_all, d)).astype(f32), rng.standard_normal((n_all, d)).astype(f32)
-        ops.sampler_ode_div(acc, torch.from_numpy(p).to(dev), torch.from_numpy(v).to(dev), ptr, times, cells, 5, 2, 0.5, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_div(acc, torch.from_numpy(p).to(dev), torch.from_numpy(v).to(dev), ptr, times, cells, 5, 2, 0.5, BETA_0, BETA_1)
         coef = _coef_ld(1, 2, 0.5)
         for j, (s, mag, n) in enumerate(_per_graph(p.astype(f64) * v.astype(f64), counts, 5)):
             want[j] += coef * s
@@ -299,20 +299,20 @@ def test_keys_accumulate_into_one_accumulator(dev):
     assert (np.abs(got.astype(ld) - want).astype(f64) <= mags * (1.0 + 2.0 ** -40) + 1e-300).all()
     out = torch.zeros(5, dtype=torch.float64, device=dev)
     x = torch.from_numpy(rng.standard_normal((n_all, 3)).astype(f32)).to(dev)
-    ops.sampler_prior_logp(out, x, ptr, 5)
+    diffusion_ops.sampler_prior_logp(out, x, ptr, 5)
     first = out.clone()
-    ops.sampler_prior_logp(out, x, ptr, 5)
+    diffusion_ops.sampler_prior_logp(out, x, ptr, 5)
     assert torch.equal(out, first + first)      # (doubling is exact)
     with pytest.raises(RuntimeError):
-        ops.sampler_prior_logp(out.cpu(), x.cpu(), ptr.cpu(), 5)      # no CPU fallback
+        diffusion_ops.sampler_prior_logp(out.cpu(), x.cpu(), ptr.cpu(), 5)      # no CPU fallback
     with pytest.raises(ValueError, match="float64"):
-        ops.sampler_prior_logp(out.float(), x, ptr, 5)
+        diffusion_ops.sampler_prior_logp(out.float(), x, ptr, 5)
     with pytest.raises(ValueError, match="row_ptr"):
-        ops.sampler_ode_div(acc, x, x, ptr.long(), times, cells, 5, 0, 1.0, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_div(acc, x, x, ptr.long(), times, cells, 5, 0, 1.0, BETA_0, BETA_1)
     with pytest.raises(ValueError, match="cells"):
-        ops.sampler_ode_div(acc, x, x, ptr, times, cells[:1], 5, 0, 1.0, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_div(acc, x, x, ptr, times, cells[:1], 5, 0, 1.0, BETA_0, BETA_1)
     with pytest.raises(ValueError, match="shape"):
-        ops.sampler_ode_div(acc, x, x[:, :2], ptr, times, cells, 5, 0, 1.0, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_div(acc, x, x[:, :2], ptr, times, cells, 5, 0, 1.0, BETA_0, BETA_1)
 
 
 def test_the_entry_points_refuse_bad_arguments(dev):

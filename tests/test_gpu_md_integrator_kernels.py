@@ -157,7 +157,7 @@ def test_score_step_noise_is_the_thermostat_stream_bit_for_bit(dev, word0):
     """``e3k_vpsde_perturb``'s z (D = 3, every node in a real graph) and ``e3k_md_kick_langevin``'s velocities at c = 0, s = 1, unit
     masses, no forces -- 0 v + 1 xi is xi exactly -- for the same seed, draw index and first word: one stream (csrc/e3k_draw.h), so
     ``torch.equal``.  The draw index is a device cell there and an argument here; both take it modulo 2^32."""
-    from e3_layers_amd.backend import ops
+    from e3_layers_amd.backend import diffusion_ops
     from e3_layers_amd.run.md import _kick_langevin
 
     n = sum(SIZES)
@@ -167,7 +167,7 @@ def test_score_step_noise_is_the_thermostat_stream_bit_for_bit(dev, word0):
     mass = torch.ones(n, device=dev)
     for draw in (7, (1 << 32) + 7):
         cell = torch.tensor([draw], dtype=torch.int64, device=dev)
-        _, _, z, _ = ops.vpsde_perturb(x0, node_seg, len(SIZES), 0.1, 20.0, 1e-3, 1.0, SEED, cell, word0)
+        _, _, z, _ = diffusion_ops.vpsde_perturb(x0, node_seg, len(SIZES), 0.1, 20.0, 1e-3, 1.0, SEED, cell, word0)
         v = torch.full((n, 3), 3.0, device=dev)
         _kick_langevin(v, None, mass, ptr, 0.0, 0.0, 1.0, SEED, draw, word0, None)
         assert float(z.abs().max()) > 1.0                       # (something was drawn)

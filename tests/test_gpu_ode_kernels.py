@@ -226,7 +226,7 @@ def test_the_entry_points_refuse_bad_arguments(dev):
 
 
 def test_the_wrappers_refuse_host_tensors_and_bad_cells(dev):
-    from e3_layers_amd.backend import ops
+    from e3_layers_amd.backend import diffusion_ops
 
     rng = np.random.default_rng(23)
     x_np, raw_np, seg_np, _, _ = _case(65, 3, 19, 3, rng)
@@ -236,32 +236,32 @@ def test_the_wrappers_refuse_host_tensors_and_bad_cells(dev):
     t = torch.zeros(4, 1, device=dev)
     # the wrappers are the entry points: the same bits as the direct calls
     want, want_d, _ = _call_euler(dev, x_np, raw_np, seg_np, 3, 2)
-    new, d1 = ops.sampler_ode_euler(x, raw, seg, times, cells, 3, BETA_0, BETA_1, t_out=t)
+    new, d1 = diffusion_ops.sampler_ode_euler(x, raw, seg, times, cells, 3, BETA_0, BETA_1, t_out=t)
     assert _same(new.cpu().numpy(), want) and _same(d1.cpu().numpy(), want_d) and (t == float(TIMES[3])).all()
-    fin = ops.sampler_ode_heun(x, d1, raw, seg, times, cells, 3, BETA_0, BETA_1)
+    fin = diffusion_ops.sampler_ode_heun(x, d1, raw, seg, times, cells, 3, BETA_0, BETA_1)
     assert _same(fin.cpu().numpy(), _call_heun(dev, x_np, want_d, raw_np, seg_np, 3, 2))
-    same, none = ops.sampler_ode_euler(x.clone(), raw, seg, times, cells, 3, BETA_0, BETA_1, want_d=False)
+    same, none = diffusion_ops.sampler_ode_euler(x.clone(), raw, seg, times, cells, 3, BETA_0, BETA_1, want_d=False)
     assert none is None and torch.equal(same, new)
     y = x.clone()
-    assert ops.sampler_ode_euler(y, raw, seg, times, cells, 3, BETA_0, BETA_1, out=y)[0] is y and torch.equal(y, new)
+    assert diffusion_ops.sampler_ode_euler(y, raw, seg, times, cells, 3, BETA_0, BETA_1, out=y)[0] is y and torch.equal(y, new)
     with pytest.raises(RuntimeError):
-        ops.sampler_ode_euler(x.cpu(), raw.cpu(), seg.cpu(), times.cpu(), cells.cpu(), 3, BETA_0, BETA_1)      # no CPU fallback
+        diffusion_ops.sampler_ode_euler(x.cpu(), raw.cpu(), seg.cpu(), times.cpu(), cells.cpu(), 3, BETA_0, BETA_1)      # no CPU fallback
     with pytest.raises(RuntimeError):
-        ops.sampler_ode_heun(x.cpu(), d1.cpu(), raw.cpu(), seg.cpu(), times.cpu(), cells.cpu(), 3, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_heun(x.cpu(), d1.cpu(), raw.cpu(), seg.cpu(), times.cpu(), cells.cpu(), 3, BETA_0, BETA_1)
     with pytest.raises(RuntimeError):
-        ops.sampler_ode_euler(x, raw, seg, times, cells, 3, BETA_0, BETA_1, t_out=t.cpu())
+        diffusion_ops.sampler_ode_euler(x, raw, seg, times, cells, 3, BETA_0, BETA_1, t_out=t.cpu())
     for bad in (cells[:1], cells.int(), cells.repeat(2)[::2]):
         with pytest.raises(ValueError, match="cells"):
-            ops.sampler_ode_euler(x, raw, seg, times, bad, 3, BETA_0, BETA_1)
+            diffusion_ops.sampler_ode_euler(x, raw, seg, times, bad, 3, BETA_0, BETA_1)
         with pytest.raises(ValueError, match="cells"):
-            ops.sampler_ode_heun(x, d1, raw, seg, times, bad, 3, BETA_0, BETA_1)
+            diffusion_ops.sampler_ode_heun(x, d1, raw, seg, times, bad, 3, BETA_0, BETA_1)
     with pytest.raises(ValueError, match="times"):
-        ops.sampler_ode_euler(x, raw, seg, times[:1], cells, 3, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_euler(x, raw, seg, times[:1], cells, 3, BETA_0, BETA_1)
     with pytest.raises(ValueError, match="times"):
-        ops.sampler_ode_heun(x, d1, raw, seg, times.double(), cells, 3, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_heun(x, d1, raw, seg, times.double(), cells, 3, BETA_0, BETA_1)
     with pytest.raises(ValueError, match="t_out"):
-        ops.sampler_ode_euler(x, raw, seg, times, cells, 3, BETA_0, BETA_1, t_out=t.double())
+        diffusion_ops.sampler_ode_euler(x, raw, seg, times, cells, 3, BETA_0, BETA_1, t_out=t.double())
     with pytest.raises(ValueError, match="d1"):
-        ops.sampler_ode_heun(x, d1, raw, seg, times, cells, 3, BETA_0, BETA_1, out=d1)
+        diffusion_ops.sampler_ode_heun(x, d1, raw, seg, times, cells, 3, BETA_0, BETA_1, out=d1)
     with pytest.raises(ValueError, match="node_seg"):
-        ops.sampler_ode_heun(x, d1, raw[:, :2], seg, times, cells, 3, BETA_0, BETA_1)
+        diffusion_ops.sampler_ode_heun(x, d1, raw[:, :2], seg, times, cells, 3, BETA_0, BETA_1)

@@ -232,19 +232,21 @@ def test_the_fixed_entry_points_refuse_bad_arguments(dev):
 
 
 def test_the_fixed_wrappers_refuse_what_their_siblings_refuse(dev):
-    from e3_layers_amd.backend import ops
+    from e3_layers_amd.backend import diffusion_ops
 
     x, raw, known = torch.zeros(4, 3, device=dev), torch.ones(4, 3, device=dev), torch.full((4, 3), 2.0, device=dev)
     seg = torch.zeros(4, dtype=torch.int64, device=dev)
     mask = torch.tensor([1, 0, 0, 1], dtype=torch.uint8, device=dev)
     t, alphas = torch.full((1, 1), 0.5, device=dev), torch.full((5,), 0.9, device=dev)
     cells = torch.zeros(2, dtype=torch.int64, device=dev)
-    lang = lambda **o: ops.sampler_langevin_fixed(*[o.get(k, v) for k, v in dict(x=x, raw=raw, known=known, fixed=mask, seg=seg, t=t, alphas=alphas).items()],  # noqa: E731
-                                                  1, 0.1, 20.0, 1.0, 0.16, 7, o.get("cells", cells), 0, 6, out=o.get("out"))
-    rev = lambda **o: ops.sampler_reverse_em_fixed(*[o.get(k, v) for k, v in dict(x=x, raw=raw, known=known, fixed=mask, seg=seg, t=t).items()],  # noqa: E731
-                                                   1, 0.1, 20.0, 1000, 7, o.get("cells", cells), 3, 9, out=o.get("out"))
+    lang = lambda **o: diffusion_ops.sampler_langevin(*[o.get(k, v) for k, v in dict(x=x, raw=raw, seg=seg, t=t, alphas=alphas).items()],  # noqa: E731
+                                                      1, 0.1, 20.0, 1.0, 0.16, 7, o.get("cells", cells), 0, out=o.get("out"),
+                                                      known=o.get("known", known), fixed=o.get("fixed", mask), word_fixed=6)
+    rev = lambda **o: diffusion_ops.sampler_reverse_em(*[o.get(k, v) for k, v in dict(x=x, raw=raw, seg=seg, t=t).items()],  # noqa: E731
+                                                       1, 0.1, 20.0, 1000, 7, o.get("cells", cells), 3, out=o.get("out"),
+                                                       known=o.get("known", known), fixed=o.get("fixed", mask), word_fixed=9)
     out, norms = lang()
-    plain, plain_norms = ops.sampler_langevin(x, raw, seg, t, alphas, 1, 0.1, 20.0, 1.0, 0.16, 7, cells, 0)
+    plain, plain_norms = diffusion_ops.sampler_langevin(x, raw, seg, t, alphas, 1, 0.1, 20.0, 1.0, 0.16, 7, cells, 0)
     assert torch.equal(out[1:3], plain[1:3]) and torch.equal(norms, plain_norms) and (out[0] != plain[0]).all()
     assert rev(out=x) is x
     for call in (lang, rev):

@@ -306,20 +306,20 @@ def test_the_entry_points_refuse_bad_arguments(dev):
 
 
 def test_the_wrappers_refuse_host_tensors_and_bad_cells(dev):
-    from e3_layers_amd.backend import ops
+    from e3_layers_amd.backend import diffusion_ops
 
     x, raw = torch.zeros(4, 3, device=dev), torch.ones(4, 3, device=dev)
     seg = torch.zeros(4, dtype=torch.int64, device=dev)
     t, alphas = torch.full((1, 1), 0.5, device=dev), torch.full((5,), 0.9, device=dev)
     cells = torch.zeros(2, dtype=torch.int64, device=dev)
-    out, norms = ops.sampler_langevin(x, raw, seg, t, alphas, 1, 0.1, 20.0, 1.0, 0.16, 7, cells)
+    out, norms = diffusion_ops.sampler_langevin(x, raw, seg, t, alphas, 1, 0.1, 20.0, 1.0, 0.16, 7, cells)
     assert out.shape == x.shape and norms.shape == (2,) and torch.isfinite(out).all()
-    assert ops.sampler_reverse_em(x, raw, seg, t, 1, 0.1, 20.0, 1000, 7, cells, 3, out=x) is x
+    assert diffusion_ops.sampler_reverse_em(x, raw, seg, t, 1, 0.1, 20.0, 1000, 7, cells, 3, out=x) is x
     with pytest.raises(RuntimeError):
-        ops.sampler_langevin(x.cpu(), raw.cpu(), seg.cpu(), t.cpu(), alphas.cpu(), 1, 0.1, 20.0, 1.0, 0.16, 7, cells.cpu())      # no CPU fallback
+        diffusion_ops.sampler_langevin(x.cpu(), raw.cpu(), seg.cpu(), t.cpu(), alphas.cpu(), 1, 0.1, 20.0, 1.0, 0.16, 7, cells.cpu())      # no CPU fallback
     with pytest.raises(ValueError, match="cells"):
-        ops.sampler_reverse_em(x, raw, seg, t, 1, 0.1, 20.0, 1000, 7, cells[:1], 3)
+        diffusion_ops.sampler_reverse_em(x, raw, seg, t, 1, 0.1, 20.0, 1000, 7, cells[:1], 3)
     with pytest.raises(ValueError, match="times"):
-        ops.sampler_langevin(x, raw, seg, t, alphas, 2, 0.1, 20.0, 1.0, 0.16, 7, cells)
+        diffusion_ops.sampler_langevin(x, raw, seg, t, alphas, 2, 0.1, 20.0, 1.0, 0.16, 7, cells)
     with pytest.raises(ValueError, match="cells"):
-        ops.sampler_begin_step(alphas, cells.int(), t)
+        diffusion_ops.sampler_begin_step(alphas, cells.int(), t)

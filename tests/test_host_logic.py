@@ -1,6 +1,8 @@
 """CPU tests of the host side: irreps algebra, config trees, path tables, Data/Batch, edge
 construction (bit-exact integer contract), factory helpers.  No kernel is launched."""
+import ctypes as C
 import math
+import os
 from functools import partial
 
 import pytest
@@ -481,6 +483,111 @@ def test_linear_terms_that_add_onto_one_block_become_one_k_chain(monkeypatch):
     assert [cnt for _, cnt in plain.rounds] == [n - 1, 1]
     assert all(plain.rounds[r][0][i].chain == 0 for r in range(2) for i in range(plain.rounds[r][1]))
     assert plain.rounds[1][0][0].accumulate == 1 and plain.rounds[1][0][0].C == h.C
+
+
+_PIN_CONFIGS = ["config_energy", "config_energy_force", "config_diffusion", "config_diffusion_CA", "config_diffusion_backbone"]
+_PIN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_descriptor_pins.json")
+
+
+def _problem_fields(p, bases=None):
+    """Every field of one ``GemmProblem`` in declaration order; a pointer field as an integer (null = 0), relative to its tensor's
+    address where ``bases`` names one."""
+    from e3_layers_amd.backend import lib as L
+
+    out = []
+    for name, ctype in L.GemmProblem._fields_:
+        v = getattr(p, name)
+        if ctype is C.c_void_p:
+            v = int(v or 0) - (bases.get(name, 0) if bases and v else 0)
+        out.append(repr(v))
+    return out
+
+
+def _descriptor_dump(name):
+    """{(module path, pass): canonical dump} of every GEMM descriptor set the modules of one shipped configuration can ask for:
+    every field of every problem of every round, the round sizes and ``loose_bias``, with ``E3K_GEMM_CHAIN`` on and off."""
+    import importlib
+    import itertools
+
+    from e3_layers_amd.backend import ops
+    from e3_layers_amd.nn import core
+    from e3_layers_amd.utils import build
+
+    def rounds_of(rounds):      # [(ctypes array, n)] -> [[fields of a problem]]
+        return [[_problem_fields(arr[i]) for i in range(n)] for arr, n in rounds]
+
+    def templates(fn):
+        try:
+            t = fn()
+        except NotImplementedError:
+            return "NotImplementedError"
+        return [rounds_of(t.rounds), [list(b) for b in t.loose_bias]]
+
+    def linear_passes(spec):
+        fwd = [templates(lambda: ops._lin_fwd_templates(spec, 0.3, acc, act, cst, bias))
+               for bias in (False, True) for acc in (False, True) for act, cst in ((0, 1.0), (1, 1.7))]
+        dgrad = [templates(lambda: ops._lin_dgrad_templates(spec, 0.3, acc)) for acc in (False, True)]
+        return {"fwd": fwd, "dgrad": dgrad, "wgrad": templates(lambda: ops._lin_wgrad_templates(spec, 0.3))}
+
+    def fctp_passes(spec):
+        m_off, pos = [], 0
+        for ins in spec.instr:
+            m_off.append(pos)
+            pos += ins.mul_in * ins.mul_out
+        grouped = []
+        for mode in ("fwd", "dgrad", "dgrad_acc", "wgrad"):
+            spec.__dict__.pop("_gemm_templates", None)      # (cached per spec: the knob is read when a set is built)
+            grouped.append(rounds_of(ops._grouped_templates(spec, m_off, mode)))
+        spec.__dict__.pop("_gemm_templates", None)
+        x, attrs, b, c = (torch.empty(4) for _ in range(4))
+        bases = {"A": x.data_ptr(), "A2": attrs.data_ptr(), "B": b.data_ptr(), "C": c.data_ptr()}
+        fctp = [[[_problem_fields(p, bases) for p in g] for g in ops._fctp_problems(x, attrs, b, c, spec, 7, wgrad)]
+                for wgrad in (False, True)]
+        return {"grouped": grouped, "fctp": fctp}
+
+    tree = importlib.import_module(f"e3_layers_amd.configs.{name}").get_config().model_config
+    torch.manual_seed(0)
+    model = build(tree)
+    out = {}
+    for chain in ("1", "0"):
+        os.environ["E3K_GEMM_CHAIN"] = chain      # (the caller restores it)
+        for path, mod in model.named_modules():
+            passes = {}
+            if isinstance(mod, core.Linear):
+                for lay in itertools.product(("e3nn", "cf"), repeat=2):
+                    for k, v in linear_passes(mod.spec(*lay)).items():
+                        passes.setdefault(k, []).append(v)
+            elif isinstance(getattr(mod, "_spec", None), ops.LinearSpec):
+                passes = linear_passes(mod._spec)
+            elif isinstance(getattr(mod, "_spec", None), ops.FctpSpec):
+                passes = fctp_passes(mod._spec)
+            for k, v in passes.items():
+                out.setdefault((path, k), []).append(v)
+    return out
+
+
+def _descriptor_pins(name):
+    import hashlib
+    import json
+
+    return {f"{path}:{k}": hashlib.sha256(json.dumps(v).encode()).hexdigest() for (path, k), v in sorted(_descriptor_dump(name).items())}
+
+
+@pytest.mark.parametrize("name", _PIN_CONFIGS)
+def test_gemm_descriptors_of_the_shipped_configs_are_pinned(name, monkeypatch):
+    """The GEMM descriptors are cached host data that every Linear, self-connection and keyed GEMM launch reads: whatever builds them,
+    they stay what they were.  A SHA-256 per (module path, pass) of the dump above -- ``_lin_fwd_templates`` with and without bias,
+    accumulating or not, plain and with the fused activation; ``_lin_dgrad_templates`` with both ``accumulate`` values;
+    ``_lin_wgrad_templates``; ``_grouped_templates`` in its four modes; ``_fctp_problems`` with and without ``wgrad`` -- against
+    ``tests/golden/gemm_descriptor_pins.json``, which was written from the hand-filled builders (one copy of the field table per
+    pass) before they were folded into one."""
+    import json
+
+    monkeypatch.setenv("E3K_GEMM_CHAIN", "1")      # restored after the test, whatever the dump leaves
+    want = json.load(open(_PIN_FILE))[name]
+    got = _descriptor_pins(name)
+    assert len(got) > 10 and sorted(got) == sorted(want)
+    assert [k for k in got if got[k] != want[k]] == []
 
 
 # ---- per-batch memos (backend/memo.py) -----------------------------------------------------------------
