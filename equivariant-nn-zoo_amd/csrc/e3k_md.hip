@@ -140,7 +140,9 @@ __global__ __launch_bounds__(256) void fire_step_kernel(float* __restrict__ x, f
   ff = wave_sum(ff);
   vv = wave_sum(vv);
   const float fmax = sqrtf(wave_max_f(f2max));
-  const bool frozen = fmax < p.ftol;      // (wave-uniform, like every branch below: the reductions leave all lanes the same values)
+  // (wave-uniform, like every branch below: the reductions leave all lanes the same values.)  An empty graph is frozen whatever
+  // ftol is: with ftol = 0 its fmax = 0 is not below the tolerance, and its dt, alpha and n_pos would go on adapting to nothing.
+  const bool frozen = end <= beg || fmax < p.ftol;
   if (frozen) {
     for (int64_t i = beg + lane; i < end; i += 64) v[3 * i] = v[3 * i + 1] = v[3 * i + 2] = 0.f;
   } else {

@@ -288,7 +288,7 @@ def _fire_step_torch(x, v, f, node_ptr, state, fire, energy=None, energy_record=
         dt, alpha, n_pos = state[g, 0].clone(), state[g, 1].clone(), state[g, 2].clone()
         f2 = (fg * fg).sum(1)
         fmax = torch.sqrt(f2.max()) if b > a else f2.sum()
-        if bool(fmax < fire.ftol):
+        if b <= a or bool(fmax < fire.ftol):      # (an empty graph is frozen whatever ftol is: ftol = 0 is accepted)
             vg.zero_()
         else:
             if bool((fg * vg).sum() < 0):

@@ -207,3 +207,30 @@ def test_fire_step_host_path_is_the_rule_of_the_header():
     assert torch.allclose(xh[:n], x64[:n], rtol=1e-13, atol=1e-13) and torch.allclose(vh[:n], v64[:n], rtol=1e-13, atol=1e-13)
     assert torch.allclose(sh, state64, rtol=1e-13, atol=0)
     assert torch.equal(xh[n:], x.double()[n:]) and torch.equal(vh[n:], v.double()[n:])
+
+
+def test_fire_step_host_path_freezes_an_empty_graph_at_ftol_zero():
+    """include/e3k.h: "An empty graph is frozen with fmax = 0" -- also with ftol = 0 (accepted), where fmax = 0 is not below the
+    tolerance: (dt, alpha, n_pos) of the empty graphs stay although n_pos > n_min, the graph between them moves (the case
+    fire_ftol0_empty of tests/test_gpu_md_matrix.py, on the torch path)."""
+    from e3_layers_amd.run.md import _fire_step
+    from tests.test_gpu_md_integrator_kernels import FIRE
+
+    class _Params:
+        pass
+
+    fire = _Params()
+    fire.__dict__.update(FIRE, ftol=0.0)
+    gen = torch.Generator().manual_seed(3)
+    x, f = torch.randn(3, 3, generator=gen, dtype=torch.float64), torch.randn(3, 3, generator=gen, dtype=torch.float64)
+    v = 0.1 * f
+    node_ptr = torch.tensor([0, 0, 3, 3])
+    state = torch.tensor([[0.3, 0.08, 9.0, math.inf], [0.1, 0.1, 9.0, math.inf], [0.2, 0.05, 7.0, math.inf]], dtype=torch.float64)
+    assert FIRE["n_min"] < 7
+    x0, want = x.clone(), state.clone()
+    record = torch.full((3,), -7.0, dtype=torch.float64)
+    _fire_step(x, v, f, node_ptr, state, fire, None, None, record)
+    want[:, 3] = 0.0
+    assert torch.equal(state[0], want[0]) and torch.equal(state[2], want[2])
+    assert float(record[0]) == 0.0 and float(record[2]) == 0.0
+    assert float(state[1, 2]) == 10.0 and float(state[1, 0]) > 0.1 and float(state[1, 3]) > 0 and not torch.equal(x, x0)
