@@ -6,6 +6,8 @@
 //     seed low, seed high, draw index, src, dst
 //   * draw_prefix() is the chain over the first three: what does not depend on the node.
 //   * src is a node index (N < 2^31), or 0xFFFFFFFF for a graph's time (then dst is the graph).
+//   * src = 0xFFFFFFFE is a graph's barostat (e3k_barostat.hip): a standard normal for (that src, word = the graph), the draw index
+//     being the absolute MD step, with the integrator's seed.
 //   * a pair's Bernoulli draw: src = i, dst = j, the 32-bit hash against a threshold.
 //   * a standard normal for (node, word): src = the node, dst = 2 word and 2 word + 1 give the two uniforms of normal_draw().
 //   * the seeded sampler (e3k_sampler.hip; run/sde_utils.py restates it): D_total = the sum of the dimensions of the diffusion keys

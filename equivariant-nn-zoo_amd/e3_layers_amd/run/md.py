@@ -44,8 +44,22 @@ Virial and stress (``nn.output.GradientOutput``'s definitions: ``virial = -dE/d 
     p = pressure(ff.virial, out["kinetic"][-1], ff.volume)      # (2 K + tr virial) / (3 V)
     ff.set_cell(cell * 1.01); ff(pos * 1.01)  # a host-driven cell scan: nothing is captured again; positions are the caller's to scale
 
-Not served: narrower cells (replicate to a supercell), barostats and cell dynamics on the device (variable cells are served through
-``set_cell``, driven by the host), training on stress, the kinetic part of the stress, cell lists (the search stays O(n^2) per graph).
+Constant pressure (isotropic; ``csrc/e3k_barostat.hip``: ONE launch more per step, between the drift kernel and the graph, on the
+static buffers -- nothing is read back but the chunk's check):
+
+    md = Langevin(ff, masses, dt=0.5, kT=0.025, gamma=0.1, barostat=Barostat(p0=6e-7, compressibility=50.0, tau=500.0))      # mode="scr"
+    out = md.run(1000)                        # + "volume", "pressure": [steps, G] float64; ff.cell / ff.volume follow every verified chunk
+    VelocityVerlet(ff, masses, dt, barostat=Barostat(p0, compressibility, tau, mode="berendsen"))      # weak coupling, no ensemble
+
+The barostat of step k acts on the pressure of the START of the step -- the virial of the last evaluation (at x_k) and the kinetic
+energy the previous kick filed -- and rescales the positions the drift has just produced, so the graph is evaluated at the rescaled
+positions in the rescaled cell and both half kicks that use those forces see forces that belong to their positions.  The one-step
+lag is deliberate (GROMACS couples its weak-coupling barostats the same way).  A cell that would become narrower than the list allows,
+or a pressure that is not finite, freezes that graph's step on the device and is REPORTED at the chunk's check: ``BarostatFailure``.
+
+Not served: narrower cells (replicate to a supercell), semi-isotropic and anisotropic coupling, cell degrees of freedom with momenta
+(MTK, Parrinello-Rahman), a barostat together with constraints, variable-cell FIRE (variable cells driven by the host are served
+through ``set_cell``), training on stress, the kinetic part of the stress, cell lists (the search stays O(n^2) per graph).
 """
 from __future__ import annotations
 
@@ -56,12 +70,12 @@ import torch
 
 from ..backend import lib as L
 from ..backend.graph import EdgeCapacityExceeded
-from ..data.compute_edge import _inverse_cells, check_cell, computeEdgeIndex, computeEdgeIndexCapped, normal_draw, wrap_positions
+from ..data.compute_edge import PBC_MARGIN, _inverse_cells, check_cell, computeEdgeIndex, computeEdgeIndexCapped, normal_draw, wrap_positions
 from .capped import EDGE_KEYS, PERIODIC_REBUILT_KEYS, CappedBucket
 from .graph_step import CapturedStep, bucket_capacity
 
 __all__ = ["EdgeCapacityExceeded", "ReplayedForceField", "VelocityVerlet", "Langevin", "Fire", "BondConstraints", "ConstraintFailure",
-           "hydrogen_bonds", "wrap_positions", "pressure"]
+           "hydrogen_bonds", "wrap_positions", "pressure", "Barostat", "BarostatFailure"]
 
 
 def pressure(virial, kinetic, volume):
@@ -196,6 +210,36 @@ class ReplayedForceField:
         self.cell.copy_(new)      # (a view of the base batch: a grow() captures on it)
         self.volume = self._volume(self.cell)
         self.valid = False
+
+    # ---- what a barostat reads and writes on the device (``Barostat``): the REAL graphs' rows of the static buffers the periodic
+    # builder reads through fixed pointers; new tensors after every capture
+    @property
+    def static_cell(self):
+        """[G, 9] fp32: a view of the captured graph's cells"""
+        return self.static.data["cell"].view(-1, 9)[:self.n_graphs]
+
+    @property
+    def static_inv_cell(self):
+        """[G, 9] fp32: a view of the inverses the builder uses"""
+        return self.static.data["_inv_cell"].view(-1, 9)[:self.n_graphs]
+
+    @property
+    def static_pbc(self):
+        """[G, 3] int32"""
+        return self.static.data["_pbc_mask"].view(-1, 3)[:self.n_graphs]
+
+    @property
+    def min_width(self) -> float:
+        """What every periodic perpendicular width must exceed: ``check_cell``'s ``2 r_max (1 + 1e-3)``"""
+        return 2.0 * self.r_max * (1.0 + PBC_MARGIN)
+
+    def sync_cell(self) -> None:
+        """After a synchronising ``check()``: the cells the device holds (a barostat rescales them in place) become ``cell`` -- the
+        base batch's view, what a ``grow()`` captures on -- and ``volume`` follows.  One small copy to the host."""
+        if self.cell is None:
+            raise ValueError("sync_cell: this force field was captured on an open batch (no 'cell')")
+        self.cell.copy_(self.static_cell.view(-1, 3, 3))
+        self.volume = self._volume(self.cell)
 
     @staticmethod
     def _check_outputs(out) -> None:
@@ -594,6 +638,128 @@ def _kick_langevin(v, f, mass, node_ptr, dt: float, c: float, s: float, seed: in
             kinetic[g] = per_node[int(node_ptr[g]):int(node_ptr[g + 1])].sum()
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Pressure control (csrc/e3k_barostat.hip): one launch between the drift kernel and the force graph.
+# ---------------------------------------------------------------------------------------------------------------------
+BAROSTAT_SRC = 0xFFFFFFFE      # the draw stream's src word of "a graph's barostat" (csrc/e3k_draw.h); the word is the graph
+
+
+class BarostatFailure(RuntimeError):
+    """Graphs whose barostat step could not be taken since the last check (a singular cell, a pressure that is not finite, a new
+    cell narrower than the periodic list allows): ``count`` graph-steps were frozen.  The driver is back at the last verified step
+    and the counter is cleared."""
+
+    def __init__(self, count: int):
+        self.count = int(count)
+        super().__init__(f"the barostat froze {self.count} graph-steps since the last check (a cell that would become narrower than "
+                         "2 r_max (1 + 1e-3), a singular cell, or a pressure that is not finite); the state is that of the last "
+                         "verified step (a smaller compressibility / tau ratio, another p0, or a supercell)")
+
+
+class Barostat:
+    """Isotropic pressure coupling at ``p0`` (the model's energy per volume) for ``VelocityVerlet`` / ``Langevin(barostat=)``:
+    once per step and graph, ``d_eps = a (P - p0) + sqrt(b / V) xi`` in ``eps = ln V`` with ``a = compressibility dt / tau``,
+    then cell and positions scale by ``mu = exp(d_eps / 3)``.
+
+    ``mode="scr"``: stochastic cell rescaling (Bernetti & Bussi, J. Chem. Phys. 153, 114107 (2020)), Euler-Maruyama:
+    ``b = 2 kT compressibility dt / tau`` with the integrator's ``kT``, velocities scale by ``1 / mu``; it samples the NPT
+    volume distribution up to a bias of first order in ``a``.  ``mode="berendsen"``: ``b = 0`` and the velocities are left alone --
+    Berendsen's weak coupling to first order in ``a``; it relaxes the volume and samples no ensemble."""
+
+    MODES = ("scr", "berendsen")
+
+    def __init__(self, p0: float, compressibility: float, tau: float, mode: str = "scr"):
+        if mode not in self.MODES:
+            raise ValueError(f"Barostat: mode must be one of {self.MODES}, got {mode!r}")
+        if not tau > 0:
+            raise ValueError(f"Barostat: tau must be > 0 (the coupling time), got {tau}")
+        if not compressibility >= 0 or not math.isfinite(compressibility):
+            raise ValueError(f"Barostat: compressibility must be >= 0 and finite, got {compressibility}")
+        self.p0, self.compressibility, self.tau, self.mode = float(p0), float(compressibility), float(tau), mode
+
+    def coefficients(self, dt: float, kT: Optional[float]):
+        """``(a, b)`` of one step of length ``dt``"""
+        a = self.compressibility * abs(dt) / self.tau
+        return a, (2.0 * float(kT) * a if self.mode == "scr" else 0.0)
+
+
+def _det3(c):
+    """``a . (b x c)`` of the rows of ``c`` [G, 9], in the kernel's expression"""
+    return c[:, 0] * (c[:, 4] * c[:, 8] - c[:, 5] * c[:, 7]) - c[:, 1] * (c[:, 3] * c[:, 8] - c[:, 5] * c[:, 6]) + \
+        c[:, 2] * (c[:, 3] * c[:, 7] - c[:, 4] * c[:, 6])
+
+
+def _adjugate3(c):
+    """[G, 9]: the transposed cofactors of ``c`` [G, 9]; ``inverse = adjugate / det`` (the barostat's rule for ``inv_cell``)"""
+    return torch.stack([c[:, 4] * c[:, 8] - c[:, 5] * c[:, 7], c[:, 2] * c[:, 7] - c[:, 1] * c[:, 8], c[:, 1] * c[:, 5] - c[:, 2] * c[:, 4],
+                        c[:, 5] * c[:, 6] - c[:, 3] * c[:, 8], c[:, 0] * c[:, 8] - c[:, 2] * c[:, 6], c[:, 2] * c[:, 3] - c[:, 0] * c[:, 5],
+                        c[:, 3] * c[:, 7] - c[:, 4] * c[:, 6], c[:, 1] * c[:, 6] - c[:, 0] * c[:, 7], c[:, 0] * c[:, 4] - c[:, 1] * c[:, 3]], 1)
+
+
+def _barostat(x, v, cell, inv_cell, pbc, virial, kinetic, node_ptr, p0: float, a: float, b: float, min_width: float, seed: int,
+              draw: int, counter, volume=None, pressure=None) -> None:
+    """One barostat step on every graph, in place (``e3k_barostat_step``; include/e3k.h, "Barostat", states the arithmetic): ``x``
+    [N, 3], ``v`` [N, 3] or None (not rescaled), ``cell`` / ``inv_cell`` [G, 9] (rows of a buffer that may be longer),
+    ``pbc`` [G, 3] integers, ``virial`` [G, 9] or [G, 3, 3], ``kinetic`` [G], ``counter`` int32 [1] (frozen graphs are added),
+    ``volume`` / ``pressure`` float64 [G] or None.  The torch path (host tensors): all graphs at once in float64 -- ``mu`` as the
+    kernel forms it, with the same ``xi`` (``normal_draw(seed, draw, 0xFFFFFFFE, g)``) -- and the products in the tensors' own
+    dtype, rounded once each: on fp32 tensors it is the kernel's arithmetic but for ``exp`` and the draw's ``log`` / ``cos``."""
+    n_graphs = node_ptr.numel() - 1
+    if not (a >= 0 and b >= 0 and math.isfinite(a) and math.isfinite(b) and min_width >= 0):
+        raise ValueError(f"_barostat: a = {a}, b = {b} and min_width = {min_width} must be >= 0 and finite")
+    if x.is_cuda:
+        L.check(L.load().e3k_barostat_step(L.ptr(x), L.ptr(v), L.ptr(cell), L.ptr(inv_cell), L.ptr(pbc), L.ptr(virial), L.ptr(kinetic),
+                                           L.ptr(node_ptr), n_graphs, x.shape[0], float(p0), float(a), float(b), float(min_width),
+                                           *L.seed_words(seed), draw & 0xFFFFFFFF, L.ptr(counter), L.ptr(volume), L.ptr(pressure),
+                                           L.stream_ptr()), "e3k_barostat_step")
+        return
+    f64 = torch.float64
+    det = _det3
+    vol = det(cell.reshape(-1, 9)[:n_graphs].to(f64)).abs()
+    w = virial.reshape(-1, 9)[:n_graphs].to(f64)
+    p = (2.0 * kinetic.reshape(-1)[:n_graphs].to(f64) + ((w[:, 0] + w[:, 4]) + w[:, 8])) / (3.0 * vol)
+    d_eps = a * (p - p0)
+    if b > 0:
+        xi = normal_draw(seed, draw & 0xFFFFFFFF, BAROSTAT_SRC, torch.arange(n_graphs, dtype=torch.int64), f64)
+        d_eps = d_eps + torch.sqrt(b / vol) * xi
+    mu = torch.exp(d_eps / 3.0)
+    frozen = (vol == 0) | ~torch.isfinite(p) | ~torch.isfinite(d_eps) | ~torch.isfinite(mu)
+    mu_t, inv_mu_t = mu.to(cell.dtype), (1.0 / mu).to(cell.dtype)
+    new = cell.reshape(-1, 9)[:n_graphs] * mu_t[:, None]
+    c = new.to(f64)
+    new_det = det(c)
+    adj = _adjugate3(c)
+    frozen = frozen | (new_det == 0) | ~torch.isfinite(new_det)
+    inv = adj / torch.where(frozen, torch.ones_like(new_det), new_det)[:, None]
+    width = 1.0 / torch.sqrt((inv.reshape(-1, 3, 3) ** 2).sum(1))      # [G, 3]: 1 / |column k|
+    frozen = frozen | ((pbc.reshape(-1, 3)[:n_graphs] != 0) & ~(width > min_width)).any(1)
+    live = ~frozen
+    if volume is not None:
+        volume.copy_(torch.where(live, new_det.abs(), vol))
+    if pressure is not None:
+        pressure.copy_(p)
+    counter += int(frozen.sum())
+    rows = cell.reshape(-1, 9)[:n_graphs]
+    rows.copy_(torch.where(live[:, None], new, rows))
+    inv_rows = inv_cell.reshape(-1, 9)[:n_graphs]
+    inv_rows.copy_(torch.where(live[:, None], inv.to(inv_cell.dtype), inv_rows))
+    bounds = node_ptr.clamp(0, x.shape[0])
+    counts = (bounds[1:] - bounds[:-1]).clamp(min=0)
+    if int(bounds[0]) != 0 or int(bounds[-1]) != x.shape[0] or bool((bounds[1:] < bounds[:-1]).any()):
+        for g in range(n_graphs):      # (a table that does not tile the nodes: graph by graph, as the kernel's workgroups)
+            if bool(live[g]) and int(counts[g]):
+                lo, hi = int(bounds[g]), int(bounds[g + 1])
+                x[lo:hi] *= mu_t[g].to(x.dtype)
+                if v is not None:
+                    v[lo:hi] *= inv_mu_t[g].to(v.dtype)
+        return
+    one = torch.ones_like(mu)
+    seg = torch.repeat_interleave(torch.arange(n_graphs), counts)
+    x.mul_(torch.where(live, mu, one).to(x.dtype)[seg][:, None])
+    if v is not None:
+        v.mul_(torch.where(live, 1.0 / mu, one).to(v.dtype)[seg][:, None])
+
+
 class _ChunkedDriver:
     """What the integrators and the minimiser share: iterations are enqueued in chunks of ``check_every``; the list's capacity is
     checked once per chunk (the one synchronisation); a chunk that overflowed is thrown away -- positions and the driver's own
@@ -695,14 +861,33 @@ class VelocityVerlet(_ChunkedDriver):
     One step = drift kernel, the force field's graph, kick kernel (which also files the step's potential and kinetic energies:
     two launches outside the graph).  ``constraints``: a ``BondConstraints`` set -- the two launches become ``e3k_md_drift_shake`` and
     ``e3k_md_kick_rattle`` (still two), the kinetic record is that of the projected velocities, ``dof`` counts 3 n - c; a star that
-    did not converge is found at the chunk's check: the chunk is rolled back and ``ConstraintFailure`` raised.  Every ``check_every`` steps the list's capacity is checked
+    did not converge is found at the chunk's check: the chunk is rolled back and ``ConstraintFailure`` raised.  ``barostat``: a
+    ``Barostat`` -- one launch more (``e3k_barostat_step``) between the drift kernel and the graph, on the pressure of the START of
+    the step (a deliberate one-step lag: the module docstring); ``run()`` then also returns "volume" and "pressure" [steps, G]
+    float64, the cell and its inverse are chunk state beside ``v`` (rolled back with it; a regrowth captures on the last verified
+    cell), ``ff.sync_cell()`` follows every verified chunk, and a frozen graph raises ``BarostatFailure`` at the chunk's check.
+    Needs a force field with a cell, every axis periodic and a ``virial_key``; not together with ``constraints``.  Every ``check_every`` steps the list's capacity is checked
     (the one synchronisation); a chunk that overflowed is thrown away -- positions, velocities and records go back to the last
     verified step, the capacity grows, the chunk runs again -- so an overflowed step never reaches the caller."""
 
-    def __init__(self, ff, masses, dt: float, grow_factor: float = 1.5, seed: int = 0, *, constraints=None):
+    def __init__(self, ff, masses, dt: float, grow_factor: float = 1.5, seed: int = 0, *, constraints=None, barostat=None):
         super().__init__(ff, grow_factor)
         self.dt, self.seed = float(dt), int(seed)
         x = ff.pos
+        if barostat is not None:      # refused before anything is allocated, each with its reason
+            if constraints is not None:
+                raise ValueError("barostat= together with constraints= is not served: scaling every atom about the origin changes the "
+                                 "fixed bond lengths, and the constraint forces' virial is not formed")
+            if getattr(ff, "cell", None) is None:
+                raise ValueError("a barostat needs a periodic force field: this one has no cell")
+            if not bool(torch.as_tensor(ff.pbc).all()):
+                raise ValueError("a barostat needs every axis periodic: this force field has a non-periodic axis (isotropic scaling "
+                                 "of an open direction has no pressure to answer to)")
+            if getattr(ff, "virial_key", None) is None:
+                raise ValueError("a barostat reads the virial: capture the force field with a virial_key (nn.output.enable_virial)")
+            if barostat.mode == "scr" and getattr(self, "kT", None) is None:
+                raise ValueError("Barostat(mode='scr') takes kT from the integrator: use Langevin, or mode='berendsen'")
+        self.barostat = barostat
         self.mass = masses.to(device=x.device, dtype=x.dtype).reshape(-1).contiguous()
         if self.mass.numel() != x.shape[0]:
             raise ValueError(f"{self.mass.numel()} masses for {x.shape[0]} atoms")
@@ -717,6 +902,10 @@ class VelocityVerlet(_ChunkedDriver):
         self.v = torch.zeros_like(x).contiguous()
         self.thermalizations = 0      # the draw counter of thermalize()
         self._forces = None      # forces at the present positions (the graph's static tensor), None: not evaluated yet
+        if barostat is not None:
+            n_graphs = ff.node_ptr.numel() - 1
+            self._baro_counter = torch.zeros(1, dtype=torch.int32, device=x.device)      # graph-steps the barostat froze
+            self._kin0 = torch.zeros(n_graphs, dtype=x.dtype, device=x.device)           # the kinetic energies a run() starts from
 
     def thermalize(self, kT: Optional[float] = None) -> None:
         """Maxwell-Boltzmann velocities at ``kT`` (the model's energy units; default: the thermostat's, where there is one):
@@ -755,6 +944,15 @@ class VelocityVerlet(_ChunkedDriver):
         return 1.0, 0.0      # (c, s) of the second half step: no thermostat
 
     def _chunk_failure(self, start: int, stop: int):
+        if self.barostat is not None:      # (never together with constraints)
+            frozen = int(self._baro_counter.item())      # (the device is idle: the capacity check has synchronised)
+            if frozen == 0:
+                return None
+            self._baro_counter.zero_()
+            if stop > start:
+                for record in (self._pot, self._kin, self._vol, self._prs):
+                    record[start:stop].zero_()
+            return BarostatFailure(frozen)
         con = self.constraints
         if con is None:
             return None
@@ -768,6 +966,8 @@ class VelocityVerlet(_ChunkedDriver):
         return ConstraintFailure(shake, rattle)
 
     def _tensors(self):
+        if self.barostat is not None:      # the cell and its inverse are chunk state beside v: the PRESENT static buffers' rows
+            return (self.v, self.ff.static_cell, self.ff.static_inv_cell)
         return (self.v,)
 
     def _begin_chunk(self) -> None:
@@ -775,15 +975,28 @@ class VelocityVerlet(_ChunkedDriver):
 
     def _commit_chunk(self) -> None:
         self._forces = self._chunk_forces
+        if self.barostat is not None:
+            self.ff.sync_cell()      # ff.cell is the last VERIFIED cell: what a regrowth captures on
 
     def _after_restore(self) -> None:
         _, self._forces = self._verified_forces()      # the forces at the snapshot's positions, on the grown list
         if self.constraints is not None:
             self.constraints.counters.zero_()          # what the thrown-away steps counted
+        if self.barostat is not None:
+            self._baro_counter.zero_()
 
     def _step(self, i: int, k: int) -> None:
         con = self.constraints
         _drift(self.x, self.v, self._chunk_forces, self.mass, self.dt, con)
+        baro = self.barostat
+        if baro is not None:
+            # the pressure of the START of the step: the virial of the last evaluation (at x_k) and the kinetic energy the last
+            # kick filed; the drifted positions are rescaled, and the graph below sees them in the rescaled cell
+            ff = self.ff
+            a, b = baro.coefficients(self.dt, getattr(self, "kT", None))
+            _barostat(self.x, self.v if baro.mode == "scr" else None, ff.static_cell, ff.static_inv_cell, ff.static_pbc, ff.virial,
+                      self._kin[i - 1] if i > 0 else self._kin0, ff.node_ptr, baro.p0, a, b, ff.min_width, self.seed, k,
+                      self._baro_counter, self._vol[i], self._prs[i])
         energy, self._chunk_forces = self.ff.evaluate()
         c, s = self._ou()
         _kick_langevin(self.v, self._chunk_forces, self.mass, self.ff.node_ptr, self.dt, c, s, self.seed, k, THERMOSTAT_WORD,
@@ -799,8 +1012,15 @@ class VelocityVerlet(_ChunkedDriver):
         n_graphs = self.ff.node_ptr.numel() - 1
         self._pot = torch.zeros(n_steps, n_graphs, dtype=self.v.dtype, device=self.v.device)
         self._kin = torch.zeros_like(self._pot)
+        if self.barostat is None:
+            self._run_chunks(n_steps, check_every)
+            return {"potential": self._pot, "kinetic": self._kin}
+        self._vol = torch.zeros(n_steps, n_graphs, dtype=torch.float64, device=self.v.device)
+        self._prs = torch.zeros_like(self._vol)
+        # the kinetic energies of the state the run starts from: a kick with dt = 0 and no forces changes nothing and files them
+        _kick_langevin(self.v, None, self.mass, self.ff.node_ptr, 0.0, 1.0, 0.0, 0, 0, 0, self._kin0)
         self._run_chunks(n_steps, check_every)
-        return {"potential": self._pot, "kinetic": self._kin}
+        return {"potential": self._pot, "kinetic": self._kin, "volume": self._vol, "pressure": self._prs}
 
 
 class Langevin(VelocityVerlet):
@@ -816,11 +1036,12 @@ class Langevin(VelocityVerlet):
     ``xi`` is counter-based (``data/compute_edge.normal_draw``) with the ABSOLUTE step number as its draw index: a chunk that is
     rolled back and redone after an overflow sees the same noise, and a trajectory does not depend on ``check_every``."""
 
-    def __init__(self, ff, masses, dt: float, kT: float, gamma: float, seed: int = 0, grow_factor: float = 1.5, *, constraints=None):
+    def __init__(self, ff, masses, dt: float, kT: float, gamma: float, seed: int = 0, grow_factor: float = 1.5, *, constraints=None,
+                 barostat=None):
         if kT < 0 or gamma < 0:
             raise ValueError("kT >= 0 and gamma >= 0")
-        super().__init__(ff, masses, dt, grow_factor, seed, constraints=constraints)
-        self.kT, self.gamma = float(kT), float(gamma)
+        self.kT, self.gamma = float(kT), float(gamma)      # (before the base class: Barostat(mode="scr") asks for kT there)
+        super().__init__(ff, masses, dt, grow_factor, seed, constraints=constraints, barostat=barostat)
         self.c = math.exp(-self.gamma * self.dt)                    # (float64 on the host; the kernel takes them as floats)
         self.s = math.sqrt(-math.expm1(-2.0 * self.gamma * self.dt) * self.kT)
 

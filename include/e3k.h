@@ -1306,6 +1306,38 @@ int e3k_pbc_edge_vector_fwd(const float* pos, const int32_t* src, const int32_t*
 int e3k_virial_edges(const float* g_vec, const float* g_len, const float* edge_vec, const float* edge_len, const int32_t* src_ptr,
                      const int32_t* src_perm, const int32_t* graph_ptr, int64_t N, int64_t E, int32_t G, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Barostat (csrc/e3k_barostat.hip): one isotropic pressure-coupling step per graph, on the device, between the drift kernel
+ * and the force graph of an MD step.  Stochastic cell rescaling (Bernetti & Bussi 2020) in eps = ln V, Euler-Maruyama; b = 0 is
+ * its deterministic limit (Berendsen's weak coupling to first order in a).  Per real graph g, in double:
+ *   V     = |det cell[g]|                                  of the fp32 cell
+ *   P     = (2 kinetic[g] + virial[g][0] + virial[g][4] + virial[g][8]) / (3 V)
+ *   d_eps = a (P - p0) + sqrt(b / V) xi                    a = compressibility dt / tau, b = 2 kT compressibility dt / tau
+ *   mu    = exp(d_eps / 3)
+ * xi is the standard normal of the draw stream (csrc/e3k_draw.h) for (seed, draw, src = 0xFFFFFFFE, word = g), fp32; b = 0
+ * draws nothing.  In the eps form the drift has no kT / V term.  Then, with mu_f = (float)mu and inv_mu_f = (float)(1.0 / mu):
+ *   cell[g][k] <- mu_f cell[g][k];  x[c] <- mu_f x[c];  v[c] <- inv_mu_f v[c]  (v NULL: positions and cell only)
+ * over the components c of the graph's nodes [node_ptr[g], node_ptr[g + 1]) (each entry clamped to [0, n]); every product is
+ * rounded to fp32 once, on its own.  inv_cell[g] <- adjugate / determinant of the NEW fp32 cell, formed in double and rounded to
+ * fp32: the inverse of the cell as the periodic builder reads it (exact zeros stay zeros).  volume[g] (NULL: not wanted) = the
+ * new |det|, pressure[g] (NULL: not wanted) = the P used; both double.
+ * A graph is FROZEN for the call -- nothing of it is written, volume[g] = the old V, pressure[g] = the computed P -- and adds one
+ * to *counter (int32, never reset here) when V is 0; when P, d_eps or mu is not finite; when the new cell's determinant is 0 or
+ * not finite; or when the new cell's perpendicular width along an axis with pbc[g][k] != 0, 1 / |column k of the inverse| in
+ * double, does not exceed min_width (data/compute_edge.check_cell's rule: min_width = 2 r_max (1 + 1e-3)).  Valid numbers, wrong
+ * physics, reported: the builder never sees a cell that breaks its one-image premise.
+ * One launch, one workgroup of 256 per graph; no atomics in the arithmetic (the counter is an integer add), written not
+ * accumulated, no zero fill: the same bits every run, safe beside a capture.  G counts the REAL graphs: the ghost graph's rows
+ * of cell, inv_cell and pbc (index G) are never touched.
+ *   x [n, 3], v [n, 3] or NULL, cell, inv_cell [>= G, 3, 3] fp32; pbc [>= G, 3] int32; virial [G, 9], kinetic [G] fp32;
+ *   node_ptr [G + 1] int64.  G == 0: E3K_OK, nothing launched.  Refused (E3K_ERR_INVALID, nothing launched): G < 0, n < 0, a or b
+ *   negative or not finite, min_width < 0 (or NaN); with G > 0 a NULL x, cell, inv_cell, pbc, virial, kinetic, node_ptr or counter.
+ * ------------------------------------------------------------------------------------------ */
+int e3k_barostat_step(float* x, float* v, float* cell, float* inv_cell, const int32_t* pbc, const float* virial,
+                      const float* kinetic, const int64_t* node_ptr, int32_t G, int64_t n, double p0, double a, double b,
+                      double min_width, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, int32_t* counter, double* volume,
+                      double* pressure, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@ evaluation, the neighbour list rebuilt inside it, two integrator launches beside
     python tools/md_bench.py --pbc --molecules 32 64 --out profiles/md_pbc.json         (the step in a vacuum cell against the open step)
     python tools/md_bench.py --stress --out profiles/md_stress.json                     (virial and stress delivered against the same step without)
     python tools/md_bench.py --stress --one-graph --molecules 128                       (... with the molecules as ONE graph of 2 000+ atoms)
+    python tools/md_bench.py --npt --molecules 32 64 --out profiles/md_npt.json         (Langevin + scr barostat against the same step without, keys on)
+    python tools/md_bench.py --npt --one-graph --molecules 128                          (... one workgroup of the barostat walks every component)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o s -- python tools/md_bench.py --trace-steps 60 --molecules 32
     python tools/md_bench.py --launches DIR_A/…_kernel_stats.csv 10 DIR_B/…_kernel_stats.csv 60      (launches per replayed step)
 
@@ -134,6 +136,10 @@ def replay_start(md, ff, x0, v0):
     md.v.copy_(v0)
     md._forces = None
     _, md._forces = md._verified_forces()
+    if getattr(md, "barostat", None) is not None:      # the kinetic energies the first barostat step reads (run() files them)
+        from e3_layers_amd.run import md as M
+
+        M._kick_langevin(md.v, None, md.mass, ff.node_ptr, 0.0, 1.0, 0.0, 0, 0, 0, md._kin0)
 
 
 def replay_steps(md, ff, n_steps):
@@ -146,12 +152,21 @@ def replay_steps(md, ff, n_steps):
     pot = torch.zeros(n_steps, n_graphs, device=ff.dev)
     kin = torch.zeros_like(pot)
     forces, con, (c, s) = md._forces, md.constraints, md._ou()
+    baro = getattr(md, "barostat", None)
+    if baro is not None:
+        vol = torch.zeros(n_steps, n_graphs, dtype=torch.float64, device=ff.dev)
+        prs = torch.zeros_like(vol)
+        a, b = baro.coefficients(md.dt, getattr(md, "kT", None))
 
     def loop():
         nonlocal forces
         t0 = time.perf_counter()
         for i in range(n_steps):
             M._drift(ff.pos, md.v, forces, md.mass, md.dt, con)
+            if baro is not None:      # e3k_barostat_step: the launch VelocityVerlet._step puts between drift and graph
+                M._barostat(ff.pos, md.v if baro.mode == "scr" else None, ff.static_cell, ff.static_inv_cell, ff.static_pbc, ff.virial,
+                            kin[i - 1] if i else md._kin0, ff.node_ptr, baro.p0, a, b, ff.min_width, md.seed, i, md._baro_counter,
+                            vol[i], prs[i])
             energy, forces = ff.evaluate()
             M._kick_langevin(md.v, forces, md.mass, ff.node_ptr, md.dt, c, s, md.seed, i, M.THERMOSTAT_WORD, kin[i], energy, pot[i],
                              con=con, x=ff.pos)      # e3k_md_kick, e3k_md_kick_langevin or e3k_md_kick_rattle, with draw index i
@@ -324,6 +339,51 @@ def bench_stress(n_mol, steps, warmup, reps, dt, dev, one_graph=False):
             "virial_pressure_at_end": [round(float(p), 6) for p in pressure(ff.virial, torch.zeros(len(batch)), ff.volume)[:4]]}
 
 
+def bench_npt(n_mol, steps, warmup, reps, dt, kT, gamma, dev, one_graph=False):
+    """The replayed Langevin step with virial and stress delivered and ``barostat=Barostat(mode="scr")`` against the same step without
+    the barostat, in the protocol of ``bench_stress`` (the vacuum cell, two force fields of the same keyed model, alternating).  What
+    differs is ONE launch outside the graph (``e3k_barostat_step``).  p0 = 0 with a small compressibility: the cells breathe by
+    parts in 10^5 over the run, so both sides walk the same lists.  ``one_graph``: one workgroup scales every component."""
+    from e3_layers_amd.nn import enable_virial
+    from e3_layers_amd.run.md import Barostat, Langevin, ReplayedForceField
+
+    make = single_graph if one_graph else setup
+    model, batch, r_max, x0, v0 = make(n_mol, dev)
+    keyed = enable_virial(model)
+    width = vacuum_cell(batch, x0, r_max, dev)
+    ffs = {k: ReplayedForceField(keyed, batch, r_max, virial_key="virial", stress_key="stress") for k in ("keys", "npt")}
+    first_cell = ffs["npt"].cell.clone()
+    baro = Barostat(p0=0.0, compressibility=1e-2, tau=1.0, mode="scr")
+    mds = {"keys": Langevin(ffs["keys"], torch.ones(x0.shape[0]), dt, kT, gamma),
+           "npt": Langevin(ffs["npt"], torch.ones(x0.shape[0]), dt, kT, gamma, barostat=baro)}
+    rows = {k: [] for k in ("keys", "npt", "keys_host", "npt_host")}
+    for name, md in mds.items():
+        replay_start(md, ffs[name], x0, v0)
+        md.run(warmup, check_every=warmup)
+    for _ in range(reps):
+        for name, md in mds.items():
+            if name == "npt":
+                ffs[name].set_cell(first_cell)
+            replay_start(md, ffs[name], x0, v0)
+            ms, host = timed(replay_steps(md, ffs[name], steps))
+            ffs[name].check()
+            rows[name].append(ms / steps)
+            rows[name + "_host"].append(1e3 * host / steps)
+    frozen = int(mds["npt"]._baro_counter.item())
+    ff = ffs["npt"]
+    ff.sync_cell()
+    diff = statistics.median(rows["npt"]) - statistics.median(rows["keys"])
+    return {"molecules": n_mol, "graphs": len(batch), "atoms": int(x0.shape[0]), "edges_at_end": int(ff.n_edges), "cell_width": round(width, 3),
+            "e_cap": ff.e_cap, "steps": steps, "reps": reps, "dt": dt, "kT": kT, "gamma": gamma, "compressibility": baro.compressibility,
+            "tau": baro.tau, "p0": baro.p0, "frozen_graph_steps": frozen, "regrowths": sum(md.regrowths for md in mds.values()),
+            "recaptures": sum(f.recaptures for f in ffs.values()),
+            "relative_cell_change_max": float(((ff.cell - first_cell).flatten(1).norm(dim=1) / first_cell.flatten(1).norm(dim=1)).max()),
+            "keys_ms_per_step": mmm(rows["keys"]), "npt_ms_per_step": mmm(rows["npt"]),
+            "keys_host_busy_ms_per_step": mmm(rows["keys_host"]), "npt_host_busy_ms_per_step": mmm(rows["npt_host"]),
+            "npt_minus_keys_us_median": round(1e3 * diff, 2),
+            "npt_over_keys_median": round(statistics.median(rows["npt"]) / statistics.median(rows["keys"]), 4)}
+
+
 def timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -443,7 +503,8 @@ def main():
     ap.add_argument("--constraints", action="store_true", help="the step with bonds to hydrogen constrained against the plain step")
     ap.add_argument("--pbc", action="store_true", help="the step in a vacuum cell (periodic builder, same edge set) against the open step")
     ap.add_argument("--stress", action="store_true", help="the step with virial and stress delivered against the step without (vacuum cell)")
-    ap.add_argument("--one-graph", action="store_true", help="with --stress: the molecules as ONE graph (the virial kernel's longest walk)")
+    ap.add_argument("--one-graph", action="store_true", help="with --stress / --npt: the molecules as ONE graph (the kernels' longest walk)")
+    ap.add_argument("--npt", action="store_true", help="the Langevin step with keys on and an scr barostat against the same step without it")
     ap.add_argument("--kT", type=float, default=0.25, help="thermostat temperature in the model's energy units (v0 has variance 0.25)")
     ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--trace-steps", type=int, default=0, help="run this many replayed steps and nothing else (under rocprofv3)")
@@ -459,9 +520,9 @@ def main():
         from e3_layers_amd.run.md import Langevin, ReplayedForceField, VelocityVerlet
 
         model, batch, r_max, x0, v0 = setup(args.molecules[0], dev)
-        if args.pbc or args.stress:      # the vacuum cell of bench_pbc
+        if args.pbc or args.stress or args.npt:      # the vacuum cell of bench_pbc
             vacuum_cell(batch, x0, r_max, dev)
-        if args.stress:
+        if args.stress or args.npt:
             from e3_layers_amd.nn import enable_virial
 
             ff = ReplayedForceField(enable_virial(model), batch, r_max, virial_key="virial", stress_key="stress")
@@ -474,7 +535,11 @@ def main():
             if args.constraints:
                 con, mass = bonds_to_hydrogen(batch, x0, ff)
                 kw = {"constraints": con}
-            md = Langevin(ff, mass, args.dt, args.kT, args.gamma, **kw) if args.integrator == "langevin" else \
+            if args.npt:
+                from e3_layers_amd.run.md import Barostat
+
+                kw = {"barostat": Barostat(p0=0.0, compressibility=1e-2, tau=1.0, mode="scr")}
+            md = Langevin(ff, mass, args.dt, args.kT, args.gamma, **kw) if args.integrator == "langevin" or args.npt else \
                 VelocityVerlet(ff, mass, args.dt, **kw)
             md.v.copy_(v0)
             if args.constraints:
@@ -482,7 +547,7 @@ def main():
             md.run(args.trace_steps, check_every=args.trace_steps)
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0], "integrator": args.integrator, "fire": args.fire,
-                          "constraints": args.constraints, "pbc": args.pbc, "stress": args.stress}))
+                          "constraints": args.constraints, "pbc": args.pbc, "stress": args.stress, "npt": args.npt}))
         return
     if args.fire:
         workload = "FIRE relaxation with per-graph state on config_energy_force (as shipped), synth_qm9: replayed iteration vs the eager loop"
@@ -491,6 +556,11 @@ def main():
         workload = ("velocity-Verlet step with the bonds to hydrogen constrained (SHAKE / RATTLE) vs the plain step, both replayed, on "
                     "config_energy_force (as shipped), synth_qm9, masses 1 (H) and 12")
         results = [bench_constraints(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
+    elif args.npt:
+        workload = ("Langevin step with virial and stress delivered and an scr barostat (e3k_barostat_step) vs the same step without the "
+                    "barostat, both replayed in a cubic vacuum cell, on config_energy_force (as shipped), synth_qm9" +
+                    (" laid out as one graph" if args.one_graph else "") + ", unit masses")
+        results = [bench_npt(n, args.steps, args.warmup, args.reps, args.dt, args.kT, args.gamma, dev, args.one_graph) for n in args.molecules]
     elif args.stress:
         workload = ("velocity-Verlet step with virial and stress delivered vs the same step without, both replayed in a cubic vacuum cell, on "
                     "config_energy_force (as shipped), synth_qm9" + (" laid out as one graph" if args.one_graph else "") + ", unit masses")
