@@ -466,9 +466,57 @@ __device__ __forceinline__ const float* kw_locate(const KwArgs& ka, int64_t c, c
 // so the launcher picks it: 64 keys, or 512 when the columns alone fill the chip -- the protein net's 80 keys are then ONE
 // tile and MODE 1 stores its sums instead of adding two tiles' with 77 M atomics.
 constexpr int KW_KT = 64, KW_KT_WIDE = 512;
+// The key loops of both modes take the keys in blocks of KW_SB (then 2, 1 for the rest) and the attributes in chunks of
+// KW_VC: the chunk's attribute values of ALL the block's keys -- KW_SB * KW_VC scalar loads, 16 SGPRs -- are requested
+// together and waited for once; MODE 1 has the gM values of KW_KB keys in flight.  (Before: one scalar load per (key,
+// attribute), each behind its own `v < V` test and each waited for: K * V dependent trips to the scalar cache.)  Every sum
+// keeps its order: over v ascending (MODE 0), over the keys ascending (MODE 1).
+constexpr int KW_SB = 4, KW_KB = 8, KW_VC = 4;
 static inline unsigned kw_tiles(int n_keys, int64_t col_blocks) {
   const int kt = col_blocks >= 1024 ? KW_KT_WIDE : KW_KT;
   return (unsigned)((n_keys + kt - 1) / kt);
+}
+// f(i, v, a[key i, v]) for the NB keys whose attribute rows start at `ab`, v ascending; a chunk of KW_VC attributes that lies
+// inside V is loaded for all the keys before its first use, the last partial chunk one attribute at a time
+template <int NB, class F>
+__device__ __forceinline__ void kw_chunks(const float* __restrict__ ab, const int V, F&& f) {
+#pragma unroll
+  for (int v0 = 0; v0 < KW_MAXV; v0 += KW_VC) {
+    if (v0 + KW_VC <= V) {
+      float x[NB][KW_VC];
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int q = 0; q < KW_VC; ++q) x[i][q] = ab[i * V + v0 + q];
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int q = 0; q < KW_VC; ++q) f(i, v0 + q, x[i][q]);
+    } else if (v0 < V) {
+#pragma unroll
+      for (int q = 0; q < KW_VC - 1; ++q)
+        if (v0 + q < V) {
+#pragma unroll
+          for (int i = 0; i < NB; ++i) f(i, v0 + q, ab[i * V + v0 + q]);
+        }
+    }
+  }
+}
+// MODE 0 for NB consecutive keys: M[t, c] = sum_v a[t, v] wv[v], v ascending; `ab`: the keys' attribute rows, `Mp`: M[first key, c]
+template <int NB>
+__device__ __forceinline__ void kw_fwd_keys(const float* __restrict__ ab, const int V, const float (&wv)[KW_MAXV],
+                                            float* __restrict__ Mp, const int64_t ld_m) {
+  float acc[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) acc[i] = 0.f;
+  kw_chunks<NB>(ab, V, [&](int i, int v, float x) { acc[i] = fmaf(x, wv[v], acc[i]); });
+#pragma unroll
+  for (int i = 0; i < NB; ++i) Mp[(int64_t)i * ld_m] = acc[i];
+}
+// MODE 1 for NB consecutive keys: gv[v] = fma(a[t, v], g[t], gv[v]), the keys ascending
+template <int NB>
+__device__ __forceinline__ void kw_bwd_keys(const float* __restrict__ ab, const int V, const float* g, float (&gv)[KW_MAXV]) {
+  kw_chunks<NB>(ab, V, [&](int i, int v, float x) { gv[v] = fmaf(x, g[i], gv[v]); });
 }
 template <int MODE>   // 0: M = a . W    1: gW (+)= a^T . gM    (MODE 1: `M` is gM, `Wout_` is gW)
 __device__ __forceinline__ void kw_body(const float* __restrict__ a, const float* __restrict__ W, const KwArgs& ka, const int K,
@@ -489,30 +537,51 @@ __device__ __forceinline__ void kw_body(const float* __restrict__ a, const float
     float wv[KW_MAXV];
 #pragma unroll
     for (int v = 0; v < KW_MAXV; ++v) wv[v] = v < V ? base[(int64_t)v * wout] : 0.f;
-    for (int t = 0; t < kt; ++t) {
-      const float* __restrict__ ar = a + (int64_t)(t0 + t) * V;
-      float acc = 0.f;
-#pragma unroll
-      for (int v = 0; v < KW_MAXV; ++v)
-        if (v < V) acc = fmaf(ar[v], wv[v], acc);
-      M[(int64_t)(t0 + t) * ka.ld_m + c] = acc;
-    }
+    const float* __restrict__ ab = a + (int64_t)t0 * V;
+    float* __restrict__ Mp = M + (int64_t)t0 * ka.ld_m + c;
+    int tb = 0;
+    for (; tb + KW_SB <= kt; tb += KW_SB) kw_fwd_keys<KW_SB>(ab + (int64_t)tb * V, V, wv, Mp + (int64_t)tb * ka.ld_m, ka.ld_m);
+    static_assert(KW_SB == 4, "the rest below: 2, 1 keys");
+    if (kt - tb >= 2) kw_fwd_keys<2>(ab + (int64_t)tb * V, V, wv, Mp + (int64_t)tb * ka.ld_m, ka.ld_m), tb += 2;
+    if (kt - tb >= 1) kw_fwd_keys<1>(ab + (int64_t)tb * V, V, wv, Mp + (int64_t)tb * ka.ld_m, ka.ld_m);
   } else {
+    // A thread owns its V elements of gW: their old values (accumulate) are requested before the key loop and all of them
+    // before the first store -- the compiler cannot move a load over a store to `dst + v * wout` for an unknown `wout`, and a
+    // load-add-store per v was V dependent round trips to memory (as store_acc of e3k_gemm.hip explains).
+    float* dst = Wout_ + (base - W);
+    const bool stores = gridDim.y == 1;
+    float old[KW_MAXV];
+#pragma unroll
+    for (int v = 0; v < KW_MAXV; ++v) old[v] = (stores && accumulate && v < V) ? dst[(int64_t)v * wout] : 0.f;
     float gv[KW_MAXV];
 #pragma unroll
     for (int v = 0; v < KW_MAXV; ++v) gv[v] = 0.f;
-    for (int t = 0; t < kt; ++t) {
-      const float* __restrict__ ar = a + (int64_t)(t0 + t) * V;
-      const float g = M[(int64_t)(t0 + t) * ka.ld_m + c];
+    // the gM values of a block of keys are in flight together
+    const float* __restrict__ gp = M + (int64_t)t0 * ka.ld_m + c;
+    const float* __restrict__ ab = a + (int64_t)t0 * V;
+    for (int tb = 0; tb < kt; tb += KW_KB) {
+      float g[KW_KB];
 #pragma unroll
-      for (int v = 0; v < KW_MAXV; ++v)
-        if (v < V) gv[v] = fmaf(ar[v], g, gv[v]);
+      for (int i = 0; i < KW_KB; ++i) g[i] = tb + i < kt ? gp[(int64_t)(tb + i) * ka.ld_m] : 0.f;
+      const float* __restrict__ abk = ab + (int64_t)tb * V;
+      int nb = kt - tb < KW_KB ? kt - tb : KW_KB;
+      static_assert(KW_KB == 8 && KW_SB == 4, "blocks of 4 keys, then 2, 1; g moves down so that every index into it is a constant");
+      for (; nb >= 4; nb -= 4) {
+        kw_bwd_keys<4>(abk, V, g, gv);
+        abk += 4 * V;
+        g[0] = g[4], g[1] = g[5], g[2] = g[6], g[3] = g[7];
+      }
+      if (nb >= 2) {
+        kw_bwd_keys<2>(abk, V, g, gv);
+        abk += 2 * V, nb -= 2;
+        g[0] = g[2];
+      }
+      if (nb >= 1) kw_bwd_keys<1>(abk, V, g, gv);
     }
-    float* dst = Wout_ + (base - W);
-    if (gridDim.y == 1) {
+    if (stores) {
 #pragma unroll
       for (int v = 0; v < KW_MAXV; ++v)
-        if (v < V) dst[(int64_t)v * wout] = accumulate ? dst[(int64_t)v * wout] + gv[v] : gv[v];
+        if (v < V) dst[(int64_t)v * wout] = accumulate ? old[v] + gv[v] : gv[v];
     } else {   // several key tiles add into the same element (the launcher zero-fills when not accumulating)
 #pragma unroll
       for (int v = 0; v < KW_MAXV; ++v)
@@ -561,20 +630,37 @@ __device__ __forceinline__ void kw_bwd_a_body(const float* __restrict__ gM, cons
   const int t_id = threadIdx.x;
   const int64_t c = (int64_t)blockIdx.x * KWA_COLS + t_id;
   const bool ok = c < ka.total;
-  {
-    int wout = 1;
-    const float* base = ok ? kw_locate(ka_, c, W, wout) : W;
-    for (int v = 0; v < ka.V; ++v) wsm[v][t_id] = ok ? base[(int64_t)v * wout] : 0.f;
-  }
-  float* out = ws + (int64_t)blockIdx.x * ka.K * ka.V;
   // grid.y splits the keys into ranges of KWA_RANGE (outputs of different keys are distinct: no conflicts)
   const int t_begin = blockIdx.y * KWA_RANGE;
   const int t_end = (t_begin + KWA_RANGE < ka.K) ? t_begin + KWA_RANGE : ka.K;
+  // Staging goes through registers, fully unrolled: the thread's V values of W and the first chunk's KWA_KT values of gM are
+  // all requested before the first LDS write (a rolled `LDS[..] = global[..]` loop waited for every load in turn: V + kt
+  // round trips to memory), and the NEXT chunk's values are requested before the current chunk is summed.
+  float greg[KWA_KT];
+  auto fetch = [&](int t0) {
+#pragma unroll
+    for (int t = 0; t < KWA_KT; ++t) greg[t] = (ok && t0 + t < t_end) ? gM[(int64_t)(t0 + t) * ka.ld_m + c] : 0.f;
+  };
+  {
+    int wout = 1;
+    const float* base = ok ? kw_locate(ka_, c, W, wout) : W;
+    float wreg[KW_MAXV];
+#pragma unroll
+    for (int v = 0; v < KW_MAXV; ++v) wreg[v] = (ok && v < ka.V) ? base[(int64_t)v * wout] : 0.f;
+    fetch(t_begin);
+#pragma unroll
+    for (int v = 0; v < KW_MAXV; ++v)
+      if (v < ka.V) wsm[v][t_id] = wreg[v];
+  }
+  float* out = ws + (int64_t)blockIdx.x * ka.K * ka.V;
   for (int t0 = t_begin; t0 < t_end; t0 += KWA_KT) {
     const int kt = (t_end - t0 < KWA_KT) ? t_end - t0 : KWA_KT;
     __syncthreads();   // previous chunk's readers are done (and wsm is complete on the first trip)
-    for (int t = 0; t < kt; ++t) gs[t][t_id] = ok ? gM[(int64_t)(t0 + t) * ka.ld_m + c] : 0.f;
+#pragma unroll
+    for (int t = 0; t < KWA_KT; ++t)
+      if (t < kt) gs[t][t_id] = greg[t];
     __syncthreads();
+    if (t0 + KWA_KT < t_end) fetch(t0 + KWA_KT);
     for (int o = t_id; o < kt * ka.V; o += 256) {
       const int t = o / ka.V, v = o - t * ka.V;
       const float4* g4 = reinterpret_cast<const float4*>(gs[t]);

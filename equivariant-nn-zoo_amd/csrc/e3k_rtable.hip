@@ -85,19 +85,36 @@ __global__ __launch_bounds__(256) void rtable_bins_rank_kernel(const float* __re
       bin[e] = i;
       *reinterpret_cast<float4*>(coef + 4 * e) = c;
     }
-    // stable rank among the edges of the same knot seen so far by this wave: the lanes of one knot are served together
-    unsigned long long todo = __ballot(live);
-    int rank = 0;
-    while (todo) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const int b = __shfl(i, leader, 64);
-      const unsigned long long same = __ballot(live && i == b) & todo;
-      const int seen = hist[b];                                // (uniform address: one LDS read, broadcast)
-      if (live && i == b) rank = seen + __popcll(same & ((1ull << lane) - 1ull));
-      if (lane == leader) hist[b] = seen + __popcll(same);
-      todo &= ~same;
-    }
     my_bin[it] = live ? i : -1;
+  }
+  // Stable rank among the edges of the same knot seen so far by this wave.  The lanes that share a lane's knot are found
+  // without touching LDS: 64 broadcasts of one lane's knot, each compared by every lane (the comparison's lane mask IS the
+  // set of that knot's lanes; a lane keeps the mask of its own knot) -- a fixed 64 register-only steps per 64 edges, all four
+  // sets of them independent of each other and of the loads above.  (Before: one round per DISTINCT knot among the 64 edges,
+  // each behind an LDS read of hist[b] and before an LDS write: up to 64 dependent LDS round trips per 64 edges.)  The
+  // histogram is then read once per lane and written once by the first lane of every knot: distinct addresses, and every
+  // read of the instruction is served before any lane's write because the written value depends on it.
+  unsigned long long same[PER_WAVE];      // (dead lanes, knot -1, share a mask nobody uses)
+#pragma unroll
+  for (int it = 0; it < PER_WAVE; ++it) same[it] = 0ull;
+#pragma unroll 8
+  for (int j = 0; j < 64; ++j) {
+#pragma unroll
+    for (int it = 0; it < PER_WAVE; ++it) {
+      const bool eq = my_bin[it] == __builtin_amdgcn_readlane(my_bin[it], j);
+      const unsigned long long m = __ballot(eq);
+      if (eq) same[it] = m;
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < PER_WAVE; ++it) {
+    int rank = 0;
+    if (my_bin[it] >= 0) {
+      const int before = __popcll(same[it] & ((1ull << lane) - 1ull));
+      const int seen = hist[my_bin[it]];
+      rank = seen + before;
+      if (before == 0) hist[my_bin[it]] = seen + __popcll(same[it]);
+    }
     my_rank[it] = rank;
   }
   __syncthreads();
@@ -114,6 +131,7 @@ __global__ __launch_bounds__(256) void rtable_bins_rank_kernel(const float* __re
 
 // ---- pass 2: one workgroup.  chunk_hist[c][b] -> number of edges of knot b in the chunks before c (in place);
 // ptr[b] = first position of knot b in knot order (ptr[K + 1] = E); seg[b] = first segment of knot b (RT_SEG edges each)
+constexpr int RT_SCAN_B = 16;      // chunks of a knot's column in flight per thread
 __global__ __launch_bounds__(1024) void rtable_bins_scan_kernel(int32_t* __restrict__ chunk_hist, int32_t n_chunks, int32_t K,
                                                                 int32_t* __restrict__ ptr, int32_t* __restrict__ seg) {
   __shared__ int32_t wave_tot[2][16];
@@ -125,10 +143,20 @@ __global__ __launch_bounds__(1024) void rtable_bins_scan_kernel(int32_t* __restr
     const int b = base + t;
     int32_t cnt = 0;
     if (b <= K) {
-      for (int c = 0; c < n_chunks; ++c) {
-        const int32_t v = chunk_hist[(int64_t)c * (K + 1) + b];
-        chunk_hist[(int64_t)c * (K + 1) + b] = cnt;
-        cnt += v;
+      // the knot's column in blocks of RT_SCAN_B chunks: the block's counts are all requested before the first of them is
+      // replaced by its running sum (read, write and add of one chunk at a time were n_chunks dependent round trips)
+      int32_t* col = chunk_hist + b;
+      const int64_t ld = K + 1;
+      for (int c0 = 0; c0 < n_chunks; c0 += RT_SCAN_B) {
+        int32_t v[RT_SCAN_B];
+#pragma unroll
+        for (int i = 0; i < RT_SCAN_B; ++i) v[i] = c0 + i < n_chunks ? col[(int64_t)(c0 + i) * ld] : 0;
+#pragma unroll
+        for (int i = 0; i < RT_SCAN_B; ++i)
+          if (c0 + i < n_chunks) {
+            col[(int64_t)(c0 + i) * ld] = cnt;
+            cnt += v[i];
+          }
       }
     }
     const int32_t sg = (cnt + RT_SEG - 1) / RT_SEG;
@@ -221,6 +249,7 @@ __global__ __launch_bounds__(256) void rtable_bwd_partial_kernel(const float* __
 
 // pass 2: g_T[j] (+)= sum_k sum over the segments of knot j + 1 - k of P[segment][k]  (a fixed order: deterministic),
 // one thread per 16 bytes
+constexpr int RT_COMB_B = 4;      // partial rows of one knot in flight per thread
 __global__ __launch_bounds__(256) void rtable_bwd_combine_kernel(const float* __restrict__ P, const int32_t* __restrict__ seg,
                                                                  int32_t K, int32_t W, int32_t accumulate, float* __restrict__ gT) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -229,15 +258,37 @@ __global__ __launch_bounds__(256) void rtable_bwd_combine_kernel(const float* __
   const int j = (int)(q / w4), col = (int)(q - (int64_t)j * w4) * 4;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   float4* out = reinterpret_cast<float4*>(gT + (int64_t)j * W + col);
-  if (accumulate) acc = *out;
+  // The four knots' segment ranges are requested together, then the first RT_COMB_B partial rows of every knot (and the old
+  // value) before the first addition; the additions run in the order they always did: k ascending, segments ascending.
+  // (Before: range, then one partial row at a time, each waited for -- about 4 * (1 + segments) dependent round trips.)
+  int s0[4], s1[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int b = j + 1 - k;
-    if (b < 1 || b > K - 2) continue;       // (K = the stacked table's last row: inside it, knots that hold no edges have no segments)
-    const int s0 = seg[b], s1 = seg[b + 1];
-    for (int s = s0; s < s1; ++s) {
-      const float4 v = *reinterpret_cast<const float4*>(P + ((int64_t)s * 4 + k) * W + col);
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    const bool has = b >= 1 && b <= K - 2;  // (K = the stacked table's last row: inside it, knots that hold no edges have no segments)
+    s0[k] = has ? seg[b] : 0;
+    s1[k] = has ? seg[b + 1] : 0;
+  }
+  if (accumulate) acc = *out;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto row = [&](int s, int k) { return *reinterpret_cast<const float4*>(P + ((int64_t)s * 4 + k) * W + col); };
+  float4 v[4][RT_COMB_B];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int i = 0; i < RT_COMB_B; ++i) v[k][i] = s0[k] + i < s1[k] ? row(s0[k] + i, k) : zero;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int i = 0; i < RT_COMB_B; ++i)
+      if (s0[k] + i < s1[k]) acc.x += v[k][i].x, acc.y += v[k][i].y, acc.z += v[k][i].z, acc.w += v[k][i].w;
+    for (int s = s0[k] + RT_COMB_B; s < s1[k]; s += RT_COMB_B) {      // a knot of more than RT_COMB_B segments: blocks of as many
+      float4 u[RT_COMB_B];
+#pragma unroll
+      for (int i = 0; i < RT_COMB_B; ++i) u[i] = s + i < s1[k] ? row(s + i, k) : zero;
+#pragma unroll
+      for (int i = 0; i < RT_COMB_B; ++i)
+        if (s + i < s1[k]) acc.x += u[i].x, acc.y += u[i].y, acc.z += u[i].z, acc.w += u[i].w;
     }
   }
   *out = acc;
