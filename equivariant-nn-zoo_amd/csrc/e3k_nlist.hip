@@ -39,6 +39,7 @@ struct NlistCrit {
 // The plain cutoff: within_cutoff of e3k_common.h and nothing else.
 struct CutoffRule {
   static constexpr bool SHIFT = false;
+  static constexpr bool IMAGES = false;
   struct Source {};
   __device__ __forceinline__ int64_t graph_id(int64_t g) const { return g; }
   template <bool FILL>
@@ -55,6 +56,7 @@ struct CutoffRule {
 // The criterion form: inside the cutoff OR kept by the pair rule.  The count pass draws with rng[0], the fill pass with rng[1].
 struct CriterionRule {
   static constexpr bool SHIFT = false;
+  static constexpr bool IMAGES = false;
   NlistCrit crit;
   struct Source {      // the source's segment key and the hash of (seed, draw, i)
     int64_t key_i;

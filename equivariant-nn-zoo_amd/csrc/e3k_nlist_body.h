@@ -1,5 +1,5 @@
 // The capped neighbour-list builder, stated once: the kernel of the count and fill passes and their two host launchers.  The pair
-// rules that instantiate it: CutoffRule and CriterionRule (e3k_nlist.hip), PeriodicRule (e3k_pbc.hip).
+// rules that instantiate it: CutoffRule and CriterionRule (e3k_nlist.hip), PeriodicRule (e3k_pbc.hip), ImagesRule (e3k_images.hip).
 //
 // Everything a capture depends on lives here and nowhere else: the ghost tail, the ghost-graph exit, the clamp of every node id
 // read from the batch's own bookkeeping to [0, N] before it is used as an address, the 64-lane walk, the ballot compaction in
@@ -12,6 +12,9 @@
 //                                   per-graph operands are to be loaded there
 //   source<FILL>(i, g)              what does not depend on j (FILL: the pass, for a rule that reads per-pass cells)
 //   keep(src, px, py, pz, pos, i, j, r_max, n)      the test of one pair, j != i; a SHIFT rule leaves the image numbers in n
+//   static constexpr bool IMAGES    false: the walk above, one candidate per destination j != i.  true (ImagesRule, e3k_images.hip):
+//                                   a destination, j == i included, has candidates(src) candidates (wave-uniform) and the rule gives
+//   keep_image(src, px, py, pz, pos, i, j, mi, r_max, n)      the test of candidate mi of destination j, in place of keep()
 //   scan_rng()                      host: the draw-index cells the scan advances between the two passes (nullptr: none)
 #pragma once
 #include "e3k_common.h"
@@ -76,11 +79,8 @@ __global__ __launch_bounds__(256) void nlist_kernel(const float* __restrict__ po
   const float px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
   const int64_t off = FILL ? offsets[i] : 0;
   int cnt = 0;
-  for (int64_t j0 = beg; j0 < end; j0 += 64) {
-    const int64_t j = j0 + lane;
-    bool keep = false;
-    float n[3] = {0.0f, 0.0f, 0.0f};
-    if (j < end && j != i) keep = rule.keep(src, px, py, pz, pos, i, j, r_max, n);
+  // one round of 64 lanes: the ballot compacts the kept candidates in lane order behind the source's earlier rounds
+  const auto emit = [&](bool keep, int64_t j, const float (&n)[3]) {
     const unsigned long long mask = __ballot(keep);
     if constexpr (FILL) {
       const int64_t at = off + cnt + __popcll(mask & ((1ull << lane) - 1ull));
@@ -96,6 +96,35 @@ __global__ __launch_bounds__(256) void nlist_kernel(const float* __restrict__ po
       }
     }
     cnt += __popcll(mask);
+  };
+  if constexpr (Rule::IMAGES) {
+    // the candidates q = (j - beg) M + mi of the graph in ascending q, M per destination (wave-uniform, 1 <= M <= 15^3), j == i
+    // included: (j, mi) advance by (64 / M, 64 % M) with one carry per round, so nothing is divided by M inside the loop
+    const uint32_t M = (uint32_t)rule.candidates(src);
+    const uint32_t step_j = 64u / M, step_m = 64u - step_j * M;
+    const int64_t q_end = (end - beg) * (int64_t)M;
+    int64_t j = beg + (uint32_t)lane / M;
+    uint32_t mi = (uint32_t)lane % M;
+    for (int64_t q = lane; q - lane < q_end; q += 64) {
+      bool keep = false;
+      float n[3] = {0.0f, 0.0f, 0.0f};
+      if (q < q_end) keep = rule.keep_image(src, px, py, pz, pos, i, j, mi, r_max, n);
+      emit(keep, j, n);
+      j += step_j;
+      mi += step_m;
+      if (mi >= M) {
+        mi -= M;
+        ++j;
+      }
+    }
+  } else {
+    for (int64_t j0 = beg; j0 < end; j0 += 64) {
+      const int64_t j = j0 + lane;
+      bool keep = false;
+      float n[3] = {0.0f, 0.0f, 0.0f};
+      if (j < end && j != i) keep = rule.keep(src, px, py, pz, pos, i, j, r_max, n);
+      emit(keep, j, n);
+    }
   }
   if constexpr (!FILL) {
     if (lane == 0) counts[i] = cnt;

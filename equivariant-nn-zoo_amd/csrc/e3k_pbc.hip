@@ -6,8 +6,8 @@
 //
 // Every cell's perpendicular width along a periodic axis must exceed 2 r_max (1 + 1e-3) (the host checks it once, where the cell
 // enters): an ordered pair then has at most one image inside the cutoff, the rounded one, and the list keeps one slot per ordered pair.
-// Narrower cells (crystal unit cells, several images per pair) are not served: the caller replicates to a supercell.  The search
-// stays O(n^2) per graph: no cell list.
+// Narrower cells (crystal unit cells, several images per pair) are served by the all-images rule of e3k_images.h / e3k_images.hip,
+// on request; THIS rule misses pairs on them.  The search stays O(n^2) per graph: no cell list.
 //
 // The edge-vector kernel recomputes v from the stored integers with the same fmaf chain: its vectors are the builder's bit for bit,
 // and its length is the number the builder compared with r_max.
@@ -19,6 +19,7 @@ namespace e3k {
 // The minimum-image rule of e3k_pbc.h for the builder of e3k_nlist_body.h.  cell, inv_cell [G + 1, 3, 3]; pbc [G + 1, 3].
 struct PeriodicRule {
   static constexpr bool SHIFT = true;
+  static constexpr bool IMAGES = false;
   const float* cell;
   const float* inv_cell;
   const int32_t* pbc;

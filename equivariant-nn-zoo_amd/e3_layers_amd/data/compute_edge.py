@@ -37,9 +37,20 @@ axis exceeds ``2 r_max (1 + 1e-3)`` -- ``check_cell`` raises otherwise, once on 
 fractional component, about ``|d| / w 2^-22``, must stay below the 5e-4 the margin leaves to the rounding tie); ``wrap_positions``
 is for output.  Virial and stress come from the force backward of these vectors (``nn.output.GradientOutput(virial=, stress=)``,
 ``csrc/e3k_virial.hip``), and a captured force field's cell changes through ``run/md.ReplayedForceField.set_cell``, driven by the host.
-NOT served: narrower cells (crystal unit cells, several images per pair: replicate to a supercell); barostats and cell dynamics on
-the device; training on stress; cell lists (the search stays O(n^2) per graph); ``criteria`` and pre-existing edges together with
-a cell; the sampler and score-step loops and ``DeviceDataset`` with a cell.  A batch without ``cell`` takes exactly the paths it took before.
+Narrower cells (crystal unit cells, several images per pair) are served on request: ``computeEdgeIndex(..., images="all")`` builds the
+list of EVERY image of every ordered pair inside the cutoff, an atom's own images included (``src == dst``, shift != 0), in the order
+source, destination, image offset (``csrc/e3k_images.h`` states the rule, its premise and the order; ``csrc/e3k_images.hip``;
+restated in torch by ``_images_rule``).  ``image_ranges`` computes, on the host in float64, how many images per axis the walk has
+to visit (``R_k = ceil(r_max (1 + 1e-3) / w_k + 1/2) - 1``, at most 7); the table stays in the batch as the per-graph field
+``_image_range`` (it collates and pads like ``pbc``) and belongs to ONE ``r_max``.  A batch that carries it gets the all-images list
+from ``computeEdgeIndex`` and ``computeEdgeIndexCapped`` without the keyword, so a model's own ``edge_index`` layer needs no change;
+the capped path trusts the table, an eager call with ``images="all"`` always recomputes it.  On a cell that passes ``check_cell`` the
+ranges are zero and the list is the minimum-image list, bit for bit.  Edge vectors, virial, stress and the CSR build work per edge and
+take this list as it is.
+NOT served: barostats on an all-images force field; training on stress; cell lists (the search stays O(n^2) per graph, O(n^2 M) with
+M images per destination); ``criteria`` and pre-existing edges together with a cell; the sampler and score-step loops and
+``DeviceDataset`` with a cell.  A batch without ``cell`` takes exactly the paths it took before, and so does a periodic batch that does
+not ask for all images (``check_cell``'s refusal of narrow cells included).
 """
 from __future__ import annotations
 
@@ -338,6 +349,63 @@ def check_cell(cell, pbc, r_max: float) -> None:
                                  f"2 r_max (1 + {PBC_MARGIN:g}) = {need:.6g}; narrower cells are not served (replicate to a supercell)")
 
 
+IMAGES_MAX_RANGE = 7      # E3K_IMAGES_MAX_RANGE of include/e3k.h: the kernel clamps to it, the host refuses beyond it
+IMAGE_MODES = ("minimum", "all")
+
+
+def image_ranges(cell, pbc, r_max: float) -> Tensor:
+    """The image range of every graph and axis for the all-images list (``csrc/e3k_images.h``), int32 ``[G, 3]`` on the host:
+    ``R_k = ceil(r_max (1 + 1e-3) / w_k + 0.5) - 1`` on a periodic axis of perpendicular width ``w_k`` (float64, as ``check_cell``
+    computes it: ``1 / |column k of cell^-1|``), 0 on a non-periodic one.  Every image inside the cutoff then has its offset from the
+    rounded image in ``[-R_k, R_k]``; a cell that passes ``check_cell`` has ``R = 0`` everywhere.  The table belongs to ONE ``r_max``.
+    Raises ``ValueError`` (naming graph and axis) for a singular or non-finite cell that has a periodic axis and for a range above
+    ``IMAGES_MAX_RANGE`` = 7 (15 images along the axis)."""
+    c, p = _cell_pbc_host(cell, pbc)
+    reach = float(r_max) * (1.0 + PBC_MARGIN)
+    if not (math.isfinite(reach) and reach > 0.0):
+        raise ValueError(f"image_ranges needs a finite r_max > 0 (got {r_max})")
+    out = torch.zeros(c.shape[0], 3, dtype=torch.int32)
+    for g in range(c.shape[0]):
+        if not bool(p[g].any()):
+            continue
+        if not bool(torch.isfinite(c[g]).all()) or float(torch.linalg.det(c[g])) == 0.0:
+            raise ValueError(f"graph {g}: the cell is singular (or not finite) but has a periodic axis")
+        width = 1.0 / torch.linalg.inv(c[g]).norm(dim=0)
+        for k in range(3):
+            if not bool(p[g, k]):
+                continue
+            x = reach / float(width[k]) + 0.5
+            r = math.ceil(x) - 1 if math.isfinite(x) else IMAGES_MAX_RANGE + 1
+            if r > IMAGES_MAX_RANGE:
+                raise ValueError(f"graph {g}, axis {'abc'[k]}: the cell's perpendicular width {float(width[k]):.6g} needs an image range "
+                                 f"of {r if math.isfinite(x) else 'more than 7'} at r_max = {float(r_max):.6g}; ranges above "
+                                 f"{IMAGES_MAX_RANGE} are not served (replicate the cell along this axis)")
+            out[g, k] = max(r, 0)
+    return out
+
+
+def _check_candidates(n_nodes: Tensor, ranges: Tensor) -> None:
+    """(nodes of a graph) x (images per destination) must stay below 2^31: the kernel counts a source's edges in an int32."""
+    m = (2 * ranges.to("cpu", torch.int64) + 1).prod(1)
+    n = n_nodes.reshape(-1).to("cpu", torch.int64)[:m.numel()]
+    bad = torch.nonzero(n * m[:n.numel()] >= 1 << 31).reshape(-1)
+    if bad.numel():
+        g = int(bad[0])
+        raise ValueError(f"graph {g}: {int(n[g])} nodes x {int(m[g])} images per destination is not below 2^31")
+
+
+def _range_operand(data, n: int, dev) -> Tensor:
+    """``_image_range`` of the batch as the kernels read it: int32 [n, 3], contiguous, on ``dev`` (kept in the batch in that form)."""
+    r = data["_image_range"]
+    if r.numel() != 3 * n:
+        raise ValueError(f"_image_range names {r.numel() // 3} graphs, the batch has {n}")
+    if r.dtype != torch.int32 or not r.is_contiguous() or r.device != dev or r.dim() != 2:
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise ValueError("_image_range must be a contiguous int32 [G, 3] tensor on the device before a capture starts")
+        r = data["_image_range"] = r.to(dev, torch.int32).reshape(n, 3).contiguous()
+    return r
+
+
 def _cell_operands(data):
     """``(cell, inv_cell, pbc)`` of a batch with ``cell`` as the kernels read them: fp32 [G, 3, 3] (contiguous), its inverse formed on
     the host in float64 and rounded to fp32, int32 [G, 3]; the last two are kept in the batch (``_inv_cell``, ``_pbc_mask``: cells
@@ -382,6 +450,72 @@ def _periodic_rule(d: Tensor, cell: Tensor, inv: Tensor, pbc: Tensor):
     v = _fma32(n[:, 2:3], cell[:, 2, :], _fma32(n[:, 1:2], cell[:, 1, :], _fma32(n[:, 0:1], cell[:, 0, :], d)))
     sq = v * v
     return n.to(torch.int32), v, torch.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])
+
+
+def _images_rule(d: Tensor, cell: Tensor, inv: Tensor, pbc: Tensor, m: Tensor):
+    """The rule of ``csrc/e3k_images.h`` on fp32 displacements ``d`` [P, 3] with each candidate's own ``cell``, ``inv`` [P, 3, 3]
+    (fp32), ``pbc`` [P, 3] and image offset ``m`` [P, 3] (integers): the image numbers ``n = base + m`` (int32 [P, 3]; ``base`` the
+    rounded image of ``_periodic_rule``), the vectors (fp32 [P, 3]) and their lengths (fp32 [P]), operation by operation."""
+    s = _fma32(d[:, 2:3], inv[:, 2, :], _fma32(d[:, 1:2], inv[:, 1, :], d[:, 0:1] * inv[:, 0, :]))
+    n = torch.where(pbc != 0, -torch.round(s), torch.zeros_like(s)) + m.to(torch.float32)
+    v = _fma32(n[:, 2:3], cell[:, 2, :], _fma32(n[:, 1:2], cell[:, 1, :], _fma32(n[:, 0:1], cell[:, 0, :], d)))
+    sq = v * v
+    return n.to(torch.int32), v, torch.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])
+
+
+def _image_candidates(n_nodes: Tensor, ranges: Tensor, device):
+    """The candidates of the all-images walk in its order -- graph, source, destination (the source itself included), then the offset
+    m with m_0 slowest and m_2 fastest, each from -R_k: (src [P], dst [P], m [P, 3], graph [P]) int64 on ``device``."""
+    n = n_nodes.reshape(-1).tolist()
+    src, dst, off, graph, start = [], [], [], [], 0
+    for g, ng in enumerate(n):
+        r = [int(x) for x in ranges[g].tolist()]
+        m = torch.cartesian_prod(*(torch.arange(-x, x + 1) for x in r)).reshape(-1, 3)
+        i, j, q = torch.meshgrid(torch.arange(ng), torch.arange(ng), torch.arange(m.shape[0]), indexing="ij")
+        src.append(i.reshape(-1) + start)
+        dst.append(j.reshape(-1) + start)
+        off.append(m[q.reshape(-1)])
+        graph.append(torch.full((i.numel(),), g, dtype=torch.int64))
+        start += ng
+    if not src:
+        z = torch.zeros(0, dtype=torch.int64, device=device)
+        return z, z, torch.zeros(0, 3, dtype=torch.int64, device=device), z
+    return tuple(torch.cat(t).to(device) for t in (src, dst, off, graph))
+
+
+def _images_graph_host(data, attrs, pos: Tensor, r_max: float, ranges: Tensor):
+    """The torch restatement of the all-images list on whichever device holds the data: every candidate, the rule, strict ``<``."""
+    cell, pbc = data["cell"], data.get("pbc")
+    pos = pos.detach().to(torch.float32)
+    n_nodes = data["_n_nodes"]
+    c64, p = _cell_pbc_host(cell, pbc)
+    if c64.shape[0] != n_nodes.numel():
+        raise ValueError(f"cell names {c64.shape[0]} graphs, the batch has {n_nodes.numel()}")
+    cell32 = torch.as_tensor(cell).detach().to(pos.device, torch.float32).reshape(-1, 3, 3)
+    inv32 = _inverse_cells(c64).to(torch.float32).to(pos.device)
+    p = p.to(pos.device)
+    src, dst, m, g = _image_candidates(n_nodes.to("cpu"), ranges, pos.device)
+    shift, _, length = _images_rule(pos[dst] - pos[src], cell32[g], inv32[g], p[g], m)
+    keep = length < torch.tensor(float(r_max), dtype=torch.float32, device=pos.device)
+    keep = torch.logical_and(keep, torch.logical_or(src != dst, (shift != 0).any(1)))
+    attrs["_n_edges"] = ("graph", "1x0e")
+    attrs["edge_cell_shift"] = ("edge", "3x0e")
+    data["_n_edges"] = torch.bincount(g[keep], minlength=n_nodes.numel()).view(-1, 1)
+    for k in _STALE:
+        data.pop(k, None)
+    return {"edge_index": torch.stack([src[keep], dst[keep]]), "edge_cell_shift": shift[keep].contiguous()}, attrs
+
+
+def _images_graph(data, attrs, pos: Tensor, r_max: float):
+    """``computeEdgeIndex(images="all")``: the ranges on the host (always recomputed: the table in the batch belongs to this
+    ``r_max`` afterwards), kept in the batch as the per-graph field ``_image_range``, then the list of either path."""
+    ranges = image_ranges(data["cell"], data.get("pbc"), r_max)
+    _check_candidates(data["_n_nodes"], ranges)
+    attrs["_image_range"] = ("graph", "3x0e")
+    data["_image_range"] = ranges.to(pos.device)
+    if pos.is_cuda:
+        return _periodic_graph_device(data, attrs, pos, r_max, images=True)
+    return _images_graph_host(data, attrs, pos, r_max, ranges)
 
 
 def _refuse_with_cell(who: str, criteria, data=None) -> None:
@@ -431,9 +565,11 @@ def _periodic_graph_host(data, attrs, pos: Tensor, r_max: float):
     return {"edge_index": edge_index, "edge_cell_shift": shift[keep].contiguous()}, attrs
 
 
-def _periodic_graph_device(data, attrs, pos: Tensor, r_max: float):
-    """HIP path: the capped pair of ``csrc/e3k_pbc.hip`` at exactly the list's size, after one host read of the count."""
-    check_cell(data["cell"], data.get("pbc"), r_max)
+def _periodic_graph_device(data, attrs, pos: Tensor, r_max: float, images: bool = False):
+    """HIP path: the capped pair of ``csrc/e3k_pbc.hip`` -- ``images``: of ``csrc/e3k_images.hip``, with the batch's ``_image_range``
+    -- at exactly the list's size, after one host read of the count."""
+    if not images:
+        check_cell(data["cell"], data.get("pbc"), r_max)
     dev = pos.device
     pos = L.f32c(pos.detach())
     n = data["_n_nodes"].reshape(-1).to(dev)
@@ -451,11 +587,13 @@ def _periodic_graph_device(data, attrs, pos: Tensor, r_max: float):
         node_ptr = torch.full((n_graphs + 2,), total, dtype=torch.int64, device=dev)
         node_ptr[0] = 0
         node_ptr[1:n_graphs + 1] = torch.cumsum(n, 0)
-        padded = [torch.cat([t, torch.zeros_like(t[:1])]).contiguous() for t in (cell, inv, mask)]      # (alive until the fill below)
+        rule = (cell, inv, mask) + ((_range_operand(data, n_graphs, dev),) if images else ())
+        padded = [torch.cat([t, torch.zeros_like(t[:1])]).contiguous() for t in rule]      # (alive until the fill below)
         geom = tuple(L.ptr(t) for t in padded)
         node_seg = _node_segment(data, pos)
         head = (L.ptr(pos), L.ptr(node_seg), L.ptr(node_ptr), total, n_graphs, float(r_max))
-        _nlist_pair("e3k_pbc_nlist_{}", head, geom, counts, passes=("count",))
+        stem = "e3k_images_{}" if images else "e3k_pbc_nlist_{}"
+        _nlist_pair(stem, head, geom, counts, passes=("count",))
     n_edge = int(counts.sum().item())          # the one host sync: the size of the output
     edge_index = torch.empty(2, n_edge, dtype=torch.int64, device=dev)
     shift = torch.empty(n_edge, 3, dtype=torch.int32, device=dev)
@@ -464,7 +602,7 @@ def _periodic_graph_device(data, attrs, pos: Tensor, r_max: float):
         offsets = torch.empty(total + 1, dtype=torch.int64, device=dev)
         state = torch.zeros(2, dtype=torch.int64, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)      # (a list of exactly its own size cannot overflow)
-        _nlist_pair("e3k_pbc_nlist_{}", head, geom, counts, (n_edge, offsets, edge_index, n_edges, None, state, flag), shift, passes=("fill",))
+        _nlist_pair(stem, head, geom, counts, (n_edge, offsets, edge_index, n_edges, None, state, flag), shift, passes=("fill",))
     data["_n_edges"] = n_edges[:n_graphs].view(-1, 1)
     return {"edge_index": edge_index, "edge_cell_shift": shift}, attrs
 
@@ -483,14 +621,30 @@ def wrap_positions(pos: Tensor, cell: Tensor, pbc, node_ptr: Tensor) -> Tensor:
     return torch.einsum("nk,nkc->nc", frac, c.to(pos.device)[g]).to(pos.dtype)
 
 
-def computeEdgeIndex(data, attrs, r_max: float = None, key: str = "pos", criteria=None):
+def computeEdgeIndex(data, attrs, r_max: float = None, key: str = "pos", criteria=None, images: str = None):
+    """``images`` (a batch with ``cell``): ``"minimum"`` -- one image per ordered pair, ``check_cell``'s width rule -- or ``"all"`` --
+    every image inside the cutoff, an atom's own included, for cells of any width (``csrc/e3k_images.h``); the ranges are computed
+    here, on the host, and stay in the batch as ``_image_range``.  Not given: ``"all"`` for a batch that already carries
+    ``_image_range`` (the table is trusted: it belongs to the ``r_max`` it was made for), else ``"minimum"``."""
+    if images is not None and images not in IMAGE_MODES:
+        raise ValueError(f"computeEdgeIndex: images must be one of {IMAGE_MODES} (got {images!r})")
     if "_nlist_state" in data:      # a padded batch of a capped loop: the fixed-size list, rewritten in place inside the capture
         return computeEdgeIndexCapped(data, attrs, r_max=r_max, key=key, criteria=criteria)
     pos = torch.as_tensor(data[key], dtype=torch.get_default_dtype())
-    if "cell" in data:      # a periodic batch: the minimum-image list and its image numbers
+    if images == "all" and "cell" not in data:
+        raise ValueError("computeEdgeIndex: images='all' needs a periodic batch (one with 'cell')")
+    if "cell" in data:      # a periodic batch: the minimum-image list (or every image) and the image numbers
         _refuse_with_cell("computeEdgeIndex", criteria, data)
         if r_max is None:
             raise ValueError("computeEdgeIndex: a periodic cell needs r_max")
+        if images == "all":
+            return _images_graph(data, attrs, pos, r_max)
+        if images is None and "_image_range" in data:
+            n_graphs = data["_n_nodes"].numel()
+            ranges = _range_operand(data, n_graphs, pos.device)
+            if pos.is_cuda:
+                return _periodic_graph_device(data, attrs, pos, r_max, images=True)
+            return _images_graph_host(data, attrs, pos, r_max, ranges)
         return (_periodic_graph_device if pos.is_cuda else _periodic_graph_host)(data, attrs, pos, r_max)
     if pos.is_cuda and criteria is None and r_max is not None:
         return _radius_graph_device(data, attrs, pos, r_max)
@@ -631,7 +785,10 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
     A batch with ``cell`` (the ghost graph's cell zero; ``_inv_cell`` / ``_pbc_mask`` already in it, as ``run/capped.CappedBucket``
     leaves them) takes the periodic builder (``csrc/e3k_pbc.hip``) and has its ``edge_cell_shift`` [e_cap, 3] int32 rewritten in place
     beside ``edge_index`` (zero on the ghost edges).  The width restriction is NOT checked here (``check_cell``: on the host, where the
-    cell enters); a criterion together with a cell is refused.
+    cell enters); a criterion together with a cell is refused.  A batch that also carries ``_image_range`` (int32 [G + 1, 3], the
+    ghost graph's row zero; ``computeEdgeIndex(images="all")`` and ``run/capped.CappedBucket`` leave it so) takes the all-images
+    builder (``csrc/e3k_images.hip``) instead: every image of every pair inside the cutoff, for cells of any width.  The table is
+    trusted -- it cannot go to the host here -- and belongs to the ``r_max`` it was made for.
 
     Not served (``computeEdgeIndex`` does both, eagerly): ``criteria`` callbacks that are arbitrary Python, edges kept from before with
     carried attributes."""
@@ -687,10 +844,19 @@ def computeEdgeIndexCapped(data, attrs, r_max: float = None, key: str = "pos", c
             raise ValueError(f"cell names {cell.shape[0]} graphs, the padded batch has {n_graphs + 1} (the ghost graph's cell is zero)")
         if shift is None or shift.dtype != torch.int32 or not shift.is_contiguous() or shift.numel() != 3 * e_cap:
             raise ValueError(f"edge_cell_shift must be a contiguous int32 tensor of {3 * e_cap} elements to be rewritten in place")
+        ranges = None
+        if "_image_range" in data:      # every image inside the cutoff: the table is trusted (made on the host for this r_max)
+            ranges = data["_image_range"]
+            L.require_cuda(ranges)
+            if ranges.dtype != torch.int32 or not ranges.is_contiguous() or ranges.numel() != 3 * (n_graphs + 1):
+                raise ValueError(f"_image_range must be a contiguous int32 tensor of {3 * (n_graphs + 1)} elements (the ghost graph's "
+                                 "row zero)")
     counts = torch.empty(total, dtype=torch.int32, device=dev)
     offsets = torch.empty(total + 1, dtype=torch.int64, device=dev)
     if periodic:
         stem, rule = "e3k_pbc_nlist_{}", (L.ptr(cell), L.ptr(inv), L.ptr(mask))
+        if ranges is not None:
+            stem, rule = "e3k_images_{}", rule + (L.ptr(ranges),)
         attrs["edge_cell_shift"] = ("edge", "3x0e")
     elif criteria is None:
         stem, rule = "e3k_nlist_{}", ()

@@ -3,7 +3,8 @@
 the model's own ``edge_index`` layer read once, and the padded batch that carries the capped builder's device cells.
 
 A periodic batch (one with ``cell``; ``data/compute_edge.py``) is served through ``run/md.ReplayedForceField`` only: the bucket then
-also carries the cell's host-made inverse and the pbc mask, and ``edge_cell_shift`` is rebuilt beside ``edge_index``.  The sampler
+also carries the cell's host-made inverse and the pbc mask -- and, for the all-images list, the image ranges (``_image_range``, a
+zero row for the ghost graph) --, and ``edge_cell_shift`` is rebuilt beside ``edge_index``.  The sampler
 and score-step loops with a cell are not served."""
 from __future__ import annotations
 
@@ -72,6 +73,8 @@ class CappedBucket:
                 raise ValueError("a periodic batch (one with 'cell') needs the 'edge_cell_shift' of its present list beside 'edge_index'")
             # (collation stores integers as int64; the builder rewrites int32 [e_cap, 3] in place)
             padded.data["edge_cell_shift"] = padded.data["edge_cell_shift"].to(torch.int32).reshape(-1, 3).contiguous()
+            if "_image_range" in padded:      # the all-images list: the table beside ``_inv_cell`` / ``_pbc_mask``, the ghost graph's row zero
+                padded.data["_image_range"] = padded.data["_image_range"].to(torch.int32).reshape(-1, 3).contiguous()
         self.n_graphs, self.n_cap, self.e_cap = len(padded) - 1, int(padded[key].shape[0]), int(padded["edge_index"].shape[1])
 
     @property

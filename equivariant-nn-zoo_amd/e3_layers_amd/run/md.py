@@ -57,7 +57,12 @@ positions in the rescaled cell and both half kicks that use those forces see for
 lag is deliberate (GROMACS couples its weak-coupling barostats the same way).  A cell that would become narrower than the list allows,
 or a pressure that is not finite, freezes that graph's step on the device and is REPORTED at the chunk's check: ``BarostatFailure``.
 
-Not served: narrower cells (replicate to a supercell), semi-isotropic and anisotropic coupling, cell degrees of freedom with momenta
+Narrower cells (crystal unit cells): ``ReplayedForceField(..., images="all")`` captures the all-images list (``csrc/e3k_images.h``: every
+image of every pair inside the cutoff, an atom's own included); ``ff.image_range`` is the table of image ranges, ``set_cell`` recomputes
+it on the host (ranges above 7 are refused before anything changes), and the integrators, FIRE, constraints, ``virial_key`` and
+``stress_key`` run as they are.  On a wide cell the ranges are zero and every output equals ``images="minimum"``'s bit for bit.
+
+Not served: a barostat on a force field with ``images="all"``, semi-isotropic and anisotropic coupling, cell degrees of freedom with momenta
 (MTK, Parrinello-Rahman), a barostat together with constraints, variable-cell FIRE (variable cells driven by the host are served
 through ``set_cell``), training on stress, the kinetic part of the stress, cell lists (the search stays O(n^2) per graph).
 """
@@ -70,7 +75,7 @@ import torch
 
 from ..backend import lib as L
 from ..backend.graph import EdgeCapacityExceeded
-from ..data.compute_edge import PBC_MARGIN, _inverse_cells, check_cell, computeEdgeIndex, computeEdgeIndexCapped, normal_draw, wrap_positions
+from ..data.compute_edge import IMAGE_MODES, PBC_MARGIN, _check_candidates, _inverse_cells, check_cell, computeEdgeIndex, image_ranges, computeEdgeIndexCapped, normal_draw, wrap_positions
 from .capped import EDGE_KEYS, PERIODIC_REBUILT_KEYS, CappedBucket
 from .graph_step import CapturedStep, bucket_capacity
 
@@ -95,7 +100,11 @@ class ReplayedForceField:
 
     def __init__(self, model, batch, r_max: float, energy_key: str = "energy", forces_key: str = "forces", edge_slack: float = 1.5,
                  key: str = "pos", warmup: int = 3, edge_multiple: int = 1024, virial_key: Optional[str] = None,
-                 stress_key: Optional[str] = None):
+                 stress_key: Optional[str] = None, images: str = "minimum"):
+        if images not in IMAGE_MODES:
+            raise ValueError(f"ReplayedForceField: images must be one of {IMAGE_MODES} (got {images!r})")
+        if images == "all" and "cell" not in batch:
+            raise ValueError("ReplayedForceField: images='all' needs a periodic batch (one with 'cell')")
         if not batch[key].is_cuda:
             raise RuntimeError("ReplayedForceField needs a device batch: there is no CPU fallback for graph replay")
         if edge_slack < 1.0:
@@ -106,14 +115,16 @@ class ReplayedForceField:
         self.model, self.r_max, self.key = model, float(r_max), key
         self.energy_key, self.forces_key = energy_key, forces_key
         self.virial_key, self.stress_key = virial_key, stress_key
+        self.images = images
         if "cell" not in batch:
             self.stress_key = None      # an open batch has no volume: ``stress`` stays None
         self._require_emitted(model, self.virial_key, self.stress_key)      # before anything is captured
         self.edge_slack, self.warmup, self.edge_multiple = float(edge_slack), warmup, int(edge_multiple)
         self.dev = batch[key].device
         self._base = batch.clone()
-        for k in EDGE_KEYS + PERIODIC_REBUILT_KEYS:
+        for k in EDGE_KEYS + PERIODIC_REBUILT_KEYS + ("_image_range",):      # (the ranges: made by every _build of images="all")
             self._base.pop(k)
+        self._base.attrs.pop("_image_range", None)
         # a periodic batch: what the builder uses (None: open boundaries) -- [G, 3, 3] fp32 and bool [G, 3]
         self.cell = self._base["cell"].detach().reshape(-1, 3, 3) if "cell" in self._base else None
         self.pbc = None if self.cell is None else (self._base["pbc"].reshape(-1, 3) != 0 if "pbc" in self._base else
@@ -131,11 +142,13 @@ class ReplayedForceField:
 
     # ---- capture ----------------------------------------------------------------------------------------------------
     def _build(self, pos, e_min: int):
-        if self.cell is not None:      # on the host, before anything is captured (construction and every grow())
+        if self.cell is not None and self.images == "minimum":      # on the host, before anything is captured (construction and every grow())
             check_cell(self.cell, self.pbc, self.r_max)
         base = self._base.clone()
         base[self.key] = pos.detach().to(torch.float32).clone()
-        new, attrs = computeEdgeIndex(base.data, base.attrs, r_max=self.r_max, key=self.key)      # eager: the sizes go to the host once
+        # eager: the sizes go to the host once.  images="all": image_ranges runs here, on the host, where check_cell runs otherwise,
+        # and leaves ``_image_range`` in the batch -- the capture below then takes the all-images builder
+        new, attrs = computeEdgeIndex(base.data, base.attrs, r_max=self.r_max, key=self.key, images=self.images if self.cell is not None else None)
         base.attrs.update(attrs)
         base.update(new)
         n, e = self.n_real, int(new["edge_index"].shape[1])
@@ -189,9 +202,15 @@ class ReplayedForceField:
         """[G, 3, 3] fp32, ``-virial / volume``: as ``virial``; None without a ``stress_key`` or without a cell."""
         return None if self.stress_key is None else self._out[len(self._extra_keys) + 1].view(-1, 3, 3)
 
+    @property
+    def image_range(self):
+        """[G, 3] int32: a view of the captured graph's image ranges (``images="all"``; ``data.image_ranges`` at this ``r_max``), else None"""
+        return self.static.data["_image_range"].view(-1, 3)[:self.n_graphs] if self.images == "all" else None
+
     def set_cell(self, cell) -> None:
-        """New cells for the captured graph, ``[G, 3, 3]`` or ``[G, 9]`` (host or device), WITHOUT capturing again: ``check_cell`` runs
-        on the host first and raises before anything changes; then the static ``cell`` and its host-made float64 inverse (rounded to
+        """New cells for the captured graph, ``[G, 3, 3]`` or ``[G, 9]`` (host or device), WITHOUT capturing again: ``check_cell`` (with
+        ``images="all"``: ``image_ranges``, whose table is overwritten in place beside the cell; a range that rises may overflow the
+        list: ``check()`` / ``grow()``) runs on the host first and raises before anything changes; then the static ``cell`` and its host-made float64 inverse (rounded to
         fp32, as at construction) are overwritten in place -- the pointers stay, the next replay rebuilds the list -- ``cell`` and
         ``volume`` follow and ``valid`` is False.  The ghost graph's rows stay zero.  The positions are the CALLER's to scale (a
         homogeneous strain moves them with the cell: ``pos @ (I + eps)``); an open force field raises ``ValueError``.  For cell scans
@@ -202,9 +221,16 @@ class ReplayedForceField:
         if new.numel() != 9 * self.n_graphs:
             raise ValueError(f"set_cell needs [{self.n_graphs}, 3, 3] (or [{self.n_graphs}, 9]), got {tuple(new.shape)}")
         new = new.reshape(-1, 3, 3).to(torch.float32)      # what the builder uses
-        check_cell(new, self.pbc, self.r_max)
+        ranges = None
+        if self.images == "all":
+            ranges = image_ranges(new, self.pbc, self.r_max)
+            _check_candidates(self._base["_n_nodes"], ranges)
+        else:
+            check_cell(new, self.pbc, self.r_max)
         inv = _inverse_cells(new.to(torch.float64)).to(torch.float32)
         static = self.static.data
+        if ranges is not None:
+            self.image_range.copy_(ranges)
         static["cell"].view(-1, 9)[:self.n_graphs].copy_(new.reshape(-1, 9))
         static["_inv_cell"].view(-1, 9)[:self.n_graphs].copy_(inv.reshape(-1, 9))
         self.cell.copy_(new)      # (a view of the base batch: a grow() captures on it)
@@ -880,6 +906,9 @@ class VelocityVerlet(_ChunkedDriver):
                                  "fixed bond lengths, and the constraint forces' virial is not formed")
             if getattr(ff, "cell", None) is None:
                 raise ValueError("a barostat needs a periodic force field: this one has no cell")
+            if getattr(ff, "images", "minimum") == "all":
+                raise ValueError("barostat= on a force field with images='all' is not served: the barostat kernel freezes a graph by one "
+                                 "minimum width, which has no meaning for per-axis image ranges")
             if not bool(torch.as_tensor(ff.pbc).all()):
                 raise ValueError("a barostat needs every axis periodic: this force field has a non-periodic axis (isotropic scaling "
                                  "of an open direction has no pressure to answer to)")

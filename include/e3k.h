@@ -1254,7 +1254,8 @@ int e3k_layer_profile_read(e3k_layer* layer, int32_t kind, float* ms, int64_t* n
  * list above and the edge vectors, under ONE restriction the host checks (data/compute_edge.check_cell): the perpendicular
  * width of every cell along each periodic axis exceeds 2 r_max (1 + 1e-3).  An ordered pair then has at most one image inside
  * the cutoff, an atom never sees its own image, and that image is the one found by rounding the fractional displacement, so
- * the list keeps one slot per ordered pair.  Narrower cells are NOT served (nothing here detects them: pairs are missed).
+ * the list keeps one slot per ordered pair.  Narrower cells are NOT served by THESE entries (nothing here detects them: pairs
+ * are missed); e3k_images_count / _fill below build the list of every image for them.
  * For source i, destination j of graph g, in fp32:
  *   d   = pos[j] - pos[i]
  *   s_k = fmaf(d_z, inv[2][k], fmaf(d_y, inv[1][k], d_x * inv[0][k]))         inv = inv_cell[g]
@@ -1286,6 +1287,31 @@ int e3k_pbc_nlist_fill(const float* pos, const int64_t* node_seg, const int64_t*
 int e3k_pbc_edge_vector_fwd(const float* pos, const int32_t* src, const int32_t* dst, const int32_t* edge_cell_shift,
                             const int64_t* node_seg, const float* cell, int32_t n_cells, int64_t N, int64_t E, float* edge_vec,
                             float* edge_len, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Periodic cells, every image inside the cutoff (csrc/e3k_images.hip; the rule itself, its premise and the order:
+ * csrc/e3k_images.h).  For cells narrower than the minimum-image section above allows (crystal unit cells): the capped list of
+ * the same builder kernel, with every image of every ordered pair of a graph whose vector is shorter than r_max, an atom's own
+ * images included (src == dst, shift != 0).  The host gives an image range per graph and axis (data/compute_edge.image_ranges:
+ * R_k = ceil(r_max (1 + 1e-3) / w_k + 0.5) - 1 on a periodic axis of perpendicular width w_k, 0 on the others; a cell the section
+ * above accepts has R = 0).  For source i, destination j (j == i included) and every offset m in prod_k [-R_k, R_k], in fp32:
+ *   d, s_k as above;  n_k = (pbc[g][k] ? -rintf(s_k) : 0) + m_k;  v from n by the fmaf chain above
+ *   kept iff sqrtf((v_x v_x + v_y v_y) + v_z v_z) < r_max  and not (j == i and n == 0)
+ * Order: source ascending, destination ascending, then m ascending with m_0 slowest and m_2 fastest, each from -R_k.  With every
+ * range zero the outputs are e3k_pbc_nlist_count / _fill's bit for bit.
+ *   image_range [G + 1, 3] int32 (the ghost graph's row: zeros).  Every entry is clamped to [0, E3K_IMAGES_MAX_RANGE] and taken as
+ *   0 where pbc is 0, so a malformed table cannot widen the walk; every other argument, output, guard and refusal is
+ *   e3k_pbc_nlist_count / _fill's, and a NULL image_range is refused (E3K_ERR_INVALID, nothing launched).  The host keeps
+ *   (nodes of a graph) x prod_k (2 R_k + 1) below 2^31.
+ * ------------------------------------------------------------------------------------------ */
+#define E3K_IMAGES_MAX_RANGE 7
+int e3k_images_count(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                     const float* cell, const float* inv_cell, const int32_t* pbc, const int32_t* image_range, int32_t* counts,
+                     void* stream);
+int e3k_images_fill(const float* pos, const int64_t* node_seg, const int64_t* node_ptr, int64_t N, int32_t G, float r_max,
+                    const float* cell, const float* inv_cell, const int32_t* pbc, const int32_t* image_range, const int32_t* counts,
+                    int64_t e_cap, int64_t* offsets, int64_t* edge_index, int32_t* edge_cell_shift, int64_t* n_edges,
+                    int64_t* edge_segment, int64_t* state, int32_t* flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Virial (csrc/e3k_virial.hip): the strain derivative of the energy from the operands of the force backward.

@@ -8,7 +8,8 @@ evaluation, the neighbour list rebuilt inside it, two integrator launches beside
     python tools/md_bench.py --fire --out profiles/md_fire.json                         (the FIRE iteration against its eager loop)
     python tools/md_bench.py --constraints --out profiles/md_constraints.json           (the SHAKE / RATTLE step against the plain step)
     python tools/md_bench.py --pbc --molecules 32 64 --out profiles/md_pbc.json         (the step in a vacuum cell against the open step)
-    python tools/md_bench.py --stress --out profiles/md_stress.json                     (virial and stress delivered against the same step without)
+    python tools/md_bench.py --images --molecules 32 64 --out profiles/md_images.json   (all images: wide cell vs minimum image; narrow cell vs supercell)
+    python tools/md_bench.py --stress --out profiles/md_stress.json                    (virial and stress delivered against the same step without)
     python tools/md_bench.py --stress --one-graph --molecules 128                       (... with the molecules as ONE graph of 2 000+ atoms)
     python tools/md_bench.py --npt --molecules 32 64 --out profiles/md_npt.json         (Langevin + scr barostat against the same step without, keys on)
     python tools/md_bench.py --npt --one-graph --molecules 128                          (... one workgroup of the barostat walks every component)
@@ -268,6 +269,96 @@ def bench_pbc(n_mol, steps, warmup, reps, dt, dev):
             "periodic_over_open_median": round(statistics.median(rows["periodic"]) / statistics.median(rows["open"]), 4)}
 
 
+def _alternate(ffs, x0, v0, steps, warmup, reps, dt):
+    """the protocol of ``bench_pbc`` for force fields that may differ in size: {name: (ms per step rows, host-busy rows)}"""
+    from e3_layers_amd.run.md import VelocityVerlet
+
+    mds = {k: VelocityVerlet(ff, torch.ones(x0[k].shape[0]), dt) for k, ff in ffs.items()}
+    rows = {k: ([], []) for k in ffs}
+    for name, md in mds.items():
+        replay_start(md, ffs[name], x0[name], v0[name])
+        md.run(warmup, check_every=warmup)
+    for _ in range(reps):
+        for name, md in mds.items():
+            replay_start(md, ffs[name], x0[name], v0[name])
+            ms, host = timed(replay_steps(md, ffs[name], steps))
+            ffs[name].check()
+            rows[name][0].append(ms / steps)
+            rows[name][1].append(1e3 * host / steps)
+    return rows, mds
+
+
+def crystal(model_batch, r_max, reps, dev, side=6.0, grid=3, jitter=0.05):
+    """A synthetic crystal for ``bench_images``: ``grid``^3 atoms on a jittered grid in a cubic cell of ``side`` (no two atoms, images
+    included, closer than side / grid - 2 sqrt(3) jitter side: 1.48 A as shipped), species drawn from ``model_batch``'s, repeated
+    ``reps`` times along every axis with the cell scaled to match.  One graph, on ``dev``, without a list."""
+    from e3_layers_amd.data.data import Batch
+
+    gen = torch.Generator().manual_seed(5)
+    kinds = model_batch["species"].reshape(-1).cpu()
+    g = torch.cartesian_prod(*(torch.arange(grid, dtype=torch.float64),) * 3)
+    frac = (g + 0.5) / grid + jitter * (2 * torch.rand(g.shape, generator=gen, dtype=torch.float64) - 1)
+    species = kinds[torch.randint(0, kinds.numel(), (g.shape[0],), generator=gen)]
+    copies = torch.cartesian_prod(*(torch.arange(reps, dtype=torch.float64),) * 3).reshape(-1, 3)
+    pos = (side * (frac[None] + copies[:, None]).reshape(-1, 3)).float()
+    attrs = {"pos": ("node", "1x1o"), "species": ("node", "1x0e"), "total_energy": ("graph", "1x0e"), "cell": ("graph", "3x1o")}
+    sample = {"pos": pos, "species": species.repeat(copies.shape[0]).reshape(-1, 1).long(), "total_energy": torch.zeros(1, 1),
+              "cell": (side * reps * torch.eye(3)).reshape(1, 9), "_n_nodes": torch.tensor([[pos.shape[0]]])}
+    return Batch.from_data_list([sample], attrs).to(dev)
+
+
+def bench_images(n_mol, steps, warmup, reps, dt, dev):
+    """The all-images builder (csrc/e3k_images.hip) in the replayed step, in the protocol of ``bench_pbc``.  (a) The wide vacuum cell
+    of ``bench_pbc`` with images="all" (every range zero: the same list, asserted) against images="minimum".  (b) One narrow cell
+    (``crystal``: 27 atoms in a 6 A cube, ranges (1, 1, 1) at the shipped r_max of 5) with images="all" against its 3 x 3 x 3
+    supercell (729 atoms, 18 A) with images="minimum": ms per step and per atom-step."""
+    from e3_layers_amd.run.md import ReplayedForceField
+
+    model, batch, r_max, x0, v0 = setup(n_mol, dev)
+    vac = batch.clone()
+    width = vacuum_cell(vac, x0, r_max, dev)
+    ffs = {"minimum": ReplayedForceField(model, vac.clone(), r_max), "all": ReplayedForceField(model, vac.clone(), r_max, images="all")}
+    if bool(ffs["all"].image_range.any()):
+        raise RuntimeError("the vacuum cell has a nonzero image range")
+    rows, mds = _alternate(ffs, {k: x0 for k in ffs}, {k: v0 for k in ffs}, steps, warmup, reps, dt)
+    lists = {}
+    for name, ff in ffs.items():      # the same list at the start
+        replay_start(mds[name], ff, x0, v0)
+        lists[name] = ff.static["edge_index"][:, :int(ff.n_edges)].clone()
+    if not torch.equal(lists["minimum"], lists["all"]):
+        raise RuntimeError("the all-images list of the vacuum cell differs from the minimum-image list")
+    med = {k: statistics.median(r[0]) for k, r in rows.items()}
+    wide = {"molecules": n_mol, "atoms": int(x0.shape[0]), "edges_at_start": int(lists["all"].shape[1]), "cell_width": round(width, 3),
+            "e_cap": {k: ff.e_cap for k, ff in ffs.items()}, "steps": steps, "reps": reps, "dt": dt,
+            "regrowths": sum(md.regrowths for md in mds.values()), "recaptures": sum(ff.recaptures for ff in ffs.values()),
+            "minimum_ms_per_step": mmm(rows["minimum"][0]), "all_ms_per_step": mmm(rows["all"][0]),
+            "minimum_host_busy_ms_per_step": mmm(rows["minimum"][1]), "all_host_busy_ms_per_step": mmm(rows["all"][1]),
+            "all_minus_minimum_us_median": round(1e3 * (med["all"] - med["minimum"]), 2),
+            "all_over_minimum_median": round(med["all"] / med["minimum"], 4)}
+    cells = {"cell": crystal(batch, r_max, 1, dev), "supercell": crystal(batch, r_max, 3, dev)}
+    ffs = {"cell": ReplayedForceField(model, cells["cell"], r_max, images="all"), "supercell": ReplayedForceField(model, cells["supercell"], r_max)}
+    xs = {k: b["pos"].clone() for k, b in cells.items()}
+    gen = torch.Generator().manual_seed(2)
+    v_cell = 0.2 * torch.randn(xs["cell"].shape, generator=gen).to(dev)
+    vs = {"cell": v_cell, "supercell": v_cell.repeat(27, 1)}      # (the supercell moves as 27 copies of the cell)
+    rows, mds = _alternate(ffs, xs, vs, steps, warmup, reps, dt)
+    for name, ff in ffs.items():
+        replay_start(mds[name], ff, xs[name], vs[name])
+    edges = {k: int(ff.n_edges) for k, ff in ffs.items()}
+    if edges["supercell"] != 27 * edges["cell"]:
+        raise RuntimeError(f"the supercell's list has {edges['supercell']} edges, the cell's {edges['cell']}")
+    atoms = {k: int(x.shape[0]) for k, x in xs.items()}
+    med = {k: statistics.median(r[0]) for k, r in rows.items()}
+    narrow = {"atoms": atoms, "edges_at_start": edges, "image_range": ffs["cell"].image_range.cpu().tolist(), "cell_side": 6.0,
+              "e_cap": {k: ff.e_cap for k, ff in ffs.items()}, "steps": steps, "reps": reps, "dt": dt,
+              "regrowths": sum(md.regrowths for md in mds.values()), "recaptures": sum(ff.recaptures for ff in ffs.values()),
+              "cell_ms_per_step": mmm(rows["cell"][0]), "supercell_ms_per_step": mmm(rows["supercell"][0]),
+              "cell_us_per_atom_step_median": round(1e3 * med["cell"] / atoms["cell"], 3),
+              "supercell_us_per_atom_step_median": round(1e3 * med["supercell"] / atoms["supercell"], 3),
+              "supercell_over_cell_ms_median": round(med["supercell"] / med["cell"], 4)}
+    return {"wide": wide, "narrow": narrow}
+
+
 def vacuum_cell(batch, x0, r_max, dev):
     """``batch`` in the cubic vacuum cell of ``bench_pbc`` (in place), and the cell's width"""
     width = float((x0.max(0).values - x0.min(0).values).max()) + 2.0 * r_max + 8.0
@@ -502,6 +593,8 @@ def main():
     ap.add_argument("--fire", action="store_true", help="the FIRE iteration against its eager loop")
     ap.add_argument("--constraints", action="store_true", help="the step with bonds to hydrogen constrained against the plain step")
     ap.add_argument("--pbc", action="store_true", help="the step in a vacuum cell (periodic builder, same edge set) against the open step")
+    ap.add_argument("--images", action="store_true", help="images='all': the wide vacuum cell against images='minimum', and a narrow cell "
+                                                          "against its 3 x 3 x 3 supercell")
     ap.add_argument("--stress", action="store_true", help="the step with virial and stress delivered against the step without (vacuum cell)")
     ap.add_argument("--one-graph", action="store_true", help="with --stress / --npt: the molecules as ONE graph (the kernels' longest walk)")
     ap.add_argument("--npt", action="store_true", help="the Langevin step with keys on and an scr barostat against the same step without it")
@@ -520,14 +613,14 @@ def main():
         from e3_layers_amd.run.md import Langevin, ReplayedForceField, VelocityVerlet
 
         model, batch, r_max, x0, v0 = setup(args.molecules[0], dev)
-        if args.pbc or args.stress or args.npt:      # the vacuum cell of bench_pbc
+        if args.pbc or args.stress or args.npt or args.images:      # the vacuum cell of bench_pbc
             vacuum_cell(batch, x0, r_max, dev)
         if args.stress or args.npt:
             from e3_layers_amd.nn import enable_virial
 
             ff = ReplayedForceField(enable_virial(model), batch, r_max, virial_key="virial", stress_key="stress")
         else:
-            ff = ReplayedForceField(model, batch, r_max)
+            ff = ReplayedForceField(model, batch, r_max, **({"images": "all"} if args.images else {}))
         if args.fire:
             make_fire(ff).run(args.trace_steps, check_every=args.trace_steps)
         else:
@@ -547,7 +640,7 @@ def main():
             md.run(args.trace_steps, check_every=args.trace_steps)
         torch.cuda.synchronize()
         print(json.dumps({"trace_steps": args.trace_steps, "molecules": args.molecules[0], "integrator": args.integrator, "fire": args.fire,
-                          "constraints": args.constraints, "pbc": args.pbc, "stress": args.stress, "npt": args.npt}))
+                          "constraints": args.constraints, "pbc": args.pbc, "stress": args.stress, "npt": args.npt, "images": args.images}))
         return
     if args.fire:
         workload = "FIRE relaxation with per-graph state on config_energy_force (as shipped), synth_qm9: replayed iteration vs the eager loop"
@@ -565,6 +658,11 @@ def main():
         workload = ("velocity-Verlet step with virial and stress delivered vs the same step without, both replayed in a cubic vacuum cell, on "
                     "config_energy_force (as shipped), synth_qm9" + (" laid out as one graph" if args.one_graph else "") + ", unit masses")
         results = [bench_stress(n, args.steps, args.warmup, args.reps, args.dt, dev, args.one_graph) for n in args.molecules]
+    elif args.images:
+        workload = ("velocity-Verlet step with the all-images periodic builder, replayed, on config_energy_force (as shipped), unit masses: "
+                    "wide = synth_qm9 in the cubic vacuum cell of --pbc, images='all' (ranges zero, identical list) vs images='minimum'; "
+                    "narrow = a 27-atom cubic cell of 6 A (ranges 1, 1, 1) with images='all' vs its 3 x 3 x 3 supercell with images='minimum'")
+        results = [bench_images(n, args.steps, args.warmup, args.reps, args.dt, dev) for n in args.molecules]
     elif args.pbc:
         workload = ("velocity-Verlet step in a cubic vacuum cell (periodic builder and edge vectors, identical edge set) vs the "
                     "open-boundary step, both replayed, on config_energy_force (as shipped), synth_qm9, unit masses")
