@@ -245,7 +245,12 @@ int e3k_tp_plan_create(const e3k_tp_group* groups, int32_t n_groups, int32_t d_i
 void e3k_tp_plan_destroy(e3k_tp_plan* plan);
 
 /* x [N,d_in] cf, sh [E,d_sh], w [E,w_numel]; src [E]; CSR by destination (dst_ptr [N+1],
- * dst_perm [E] = edge ids grouped by destination, ascending inside a group); out [N,d_mid]. */
+ * dst_perm [E] = edge ids grouped by destination, ascending inside a group); out [N,d_mid].
+ * E = 0, for every tensor-product entry point of this section: the per-edge arrays may be NULL; the calls with a per-node output
+ * (out, g_x) run and give every node the result of a node without edges -- out and a stored g_x are written as zeros, an
+ * accumulated g_x keeps the caller's zero-fill -- while the calls whose outputs are all per edge (e3k_tp_bwd_w, e3k_tp_bwd_w_ordered,
+ * e3k_tp_bwd_e_table, e3k_tp_bwd_w_dual) launch nothing, write nothing and return E3K_OK before they look at the plan: also for a
+ * plan they would otherwise refuse with E3K_ERR_UNSUPPORTED.  N = 0 returns E3K_OK likewise. */
 int e3k_tp_fwd(const e3k_tp_plan* plan, const float* x, const float* sh, const float* w, const int32_t* src,
                const int32_t* dst_ptr, const int32_t* dst_perm, int64_t N, int64_t E, float* out, void* stream);
 /* g_w [E,w_numel] written (may be NULL when only g_sh is wanted); g_sh [E,d_sh] accumulated with atomics when

@@ -25,9 +25,12 @@ import ctypes as C
 import pytest
 import torch
 
-from tests.test_gpu_tp_matrix import E3K_ERR_UNSUPPORTED, GTOL, SH9, _check_packing, _Oracle, _packed_w64
+import numpy as np
+
+from tests.test_gpu_tp_matrix import (E3K_ERR_UNSUPPORTED, GTOL, SH9, PlainRef, _check_packing, _Oracle, _packed_fields, _packed_w64, reference,
+                                      w_packed, within)
 from tests.test_gpu_tp_scalar_matrix import SENTINEL, _framed, _margins_intact
-from tests.util import rel_err
+from tests.util import record_measured, rel_err
 
 ROUTE = "tp_bwd_xw_masked_kernel"
 LEFT = "64x0e+64x0o+64x1o+64x1e+64x2e+64x2o"
@@ -204,6 +207,20 @@ def test_masked_walk_against_float64_and_the_dense_walk(dev, case):
         print(f"{case['id']} {what}: rel err {err:.3e}, on the special rows {err_r:.3e} (bound {GTOL:.0e})")
         assert err < GTOL and err_r < GTOL, f"{what}: rel err {err:.3e} / {err_r:.3e}"
     assert bool((gx[none] == 0).all()), "the row of the node without out-edges is not exactly zero"
+
+    # ---- element by element: the plain reference over the PRUNED plan's paths (the dead columns of g_mid and of the table are no
+    # operand of it, so they add nothing to M; g_w is w_live wide) and its bound gamma_k M (tests/test_gpu_tp_matrix.py)
+    assert live_col == sorted(live_col)      # (the compact columns are the live dense columns in their order)
+    plain_ref = PlainRef(pruned, s["ei"].numpy(), n, True)
+    w_d, M_d, k_w = w_packed([f.numpy() for f in _packed_fields(packed)], s["bins"].bin.cpu().numpy(), s["bins"].coef.cpu().numpy())
+    lw = live_w.numpy()
+    refs = reference(plain_ref, "bwd_xw_ptable", {"x": s["x"].double().numpy(), "sh": s["sh"].double().numpy(), "g": g_zero.double().numpy()},
+                     (np.ascontiguousarray(w_d[:, lw]), np.ascontiguousarray(M_d[:, lw]), k_w))
+    assert refs["g_w"][0].shape == (e, w_live)
+    for what, got in (("g_x", gx1), ("g_w", gw1)):
+        ratio = within(f"{case['id']} {what}", got.contiguous(), refs[what])
+        print(f"{case['id']} {what}: worst error / bound {ratio:.3f}")
+        record_measured("test_gpu_tp_masked_matrix", case=case["id"], output=what, error_over_bound=ratio)
 
 
 @pytest.mark.gpu

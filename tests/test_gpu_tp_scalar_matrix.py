@@ -20,8 +20,9 @@ import ctypes as C
 import pytest
 import torch
 
-from tests.test_gpu_tp_matrix import E3K_ERR_UNSUPPORTED, GTOL, SH9, _check_packing, _graph, _Oracle, _packed_w64
-from tests.util import rel_err
+from tests.test_gpu_tp_matrix import (E3K_ERR_UNSUPPORTED, GTOL, SH9, PlainRef, _check_packing, _graph, _Oracle, _packed_fields, _packed_w64,
+                                      reference, w_packed, within)
+from tests.util import record_measured, rel_err
 
 ROUTE = "tp_bwd_xw_scalar_kernel"
 # n = 37: below the N >= 64 work-order threshold; 203: above it and not a multiple of 8
@@ -121,6 +122,15 @@ def test_scalar_walk_against_float64(dev, case):
 
     gx1, gw1 = plain()
     check("plain", gx1, gw1)
+    # element by element: the plain reference over the plan's paths and its bound gamma_k M (tests/test_gpu_tp_matrix.py: the chain
+    # of tp_bwd_x_kernel<..., 5> on one slot per group -- yt, packed_mix * coeff, one fmaf per out-edge; the dot, * coeff)
+    plain_ref = PlainRef(plan, ei.numpy(), n, True)
+    pk = w_packed([f.numpy() for f in _packed_fields(packed)], bins.bin.cpu().numpy(), bins.coef.cpu().numpy())
+    refs = reference(plain_ref, "bwd_xw_ptable", {"x": x.double().numpy(), "sh": sh.double().numpy(), "g": g.double().numpy()}, pk)
+    for what, got in (("g_x", gx1), ("g_w", gw1)):
+        ratio = within(f"{case['id']} {what}", got, refs[what])
+        print(f"{case['id']} {what}: worst error / bound {ratio:.3f}")
+        record_measured("test_gpu_tp_scalar_matrix", case=case["id"], output=what, error_over_bound=ratio)
     gx2, gw2 = plain()
     assert torch.equal(gx1.view(torch.int32), gx2.view(torch.int32)) and torch.equal(gw1.view(torch.int32), gw2.view(torch.int32)), \
         "two runs differ"
